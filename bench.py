@@ -1,6 +1,6 @@
 """Headline benchmark: tomogram voxels/sec for (DINOv2 ViT-g/14-reg features + CryoVIT 3D-conv head forward + Dice).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one synthetic 128x512x512 tomogram (BASELINE.json configs[1]+[2] chained = the end-to-end unit of
 configs[3]) through the whole hot path on one GPU, input volume already resident in HBM.  Tomograms shard
@@ -13,11 +13,17 @@ GPU, starts N child processes (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MAS
 relays rank 0's JSON line and exits non-zero if any child fails.  Under ``python -m torch.distributed.run ... bench.py
 --gpus N`` (WORLD_SIZE already set) the process is one of the ranks and runs directly.
 
-The JSON line also carries
+A plain run builds (if needed), sets up, runs W warm-up and K timed steps and prints the JSON line: `value` voxels/s and
+`ms_per_step` (the timed region's wall time / K, MAX over ranks) plus descriptive fields.  ``--dump-outputs DIR`` then also
+writes what the last timed step computed (``dump_outputs``; inputs and weights are seeded, so equal arguments give equal inputs).
+
+With ``--full`` the same timed steps run with the dominant kernel's event hook and the board sampler on, and the JSON line
+also carries `dice`, `pred_fg_fraction`, `board` (clock / power over the timed region) and
   roofline     -- the dominant kernel (the SwiGLU w12 GEMM, 44 % of all FLOPs): algorithmic FLOPs per launch divided
                   by its average launch duration measured live with HIP events on the launch stream
   stages_ms    -- per-stage device time of ONE extra, untimed tomogram run op by op with HIP events between the launches
                   (ViT GEMMs by kind / attention / LayerNorm / head ...): configs[1] = `vit_ms`, configs[2] = `head_ms`
+  configs      -- configs[1] / configs[2] from stages_ms, the head per layer, and (N=1) configs[4] and UNet3D on one tomogram
   cpu_baseline -- the torch-CPU fp32 oracle timed on this box's host cores on a bounded sample (rank 0, N=1 only)
 """
 
@@ -424,6 +430,27 @@ class BoardSampler:
                         "(MFMA-only loops on normal(0,1) bf16 operands sustain 1.77-1.85 PFLOP/s on these boards: profiles/r03_mfma_power.txt)"}
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of each large output: 16 MB as float32
+
+
+def dump_outputs(out_dir, out: dict, feats_f16) -> None:
+    """What the timed path hands its caller in its last step, as float32 ``<out_dir>/<name>.npy``: ``dice_sums`` whole, and of the
+    two large arrays (``probs`` fp32 [128,512,512] = 134 MB, ``dino_features`` fp16 [1536,128,32,32] = 805 MB as float32) the
+    same DUMP_SAMPLE flat positions in every run (numpy PCG64, seed 0, sorted), so two builds can be compared element for element."""
+    import numpy as np
+    import torch
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"probs": out["probs"], "dino_features": feats_f16, "dice_sums": out["dice_sums"]}
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(out_dir / f"{name}.npy", flat.float().cpu().numpy())
+
+
 def measured_traffic() -> dict:
     """PMC traffic of the dominant kernel, per launch, from the committed rocprofv3 --pmc passes (collected on the GPU box with
     tools/profile_round.sh, condensed by tools/summarize_profiles.py; `rocprofv3` cannot run inside this process).  The JSON names
@@ -493,11 +520,19 @@ def parse_args(argv=None):
     ap.add_argument("--slice-batch", type=int, default=128, help="slices per ViT launch sequence (reference default 128)")
     ap.add_argument("--streams", type=int, default=1, help="tomograms in flight per GPU, one per HIP stream")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="cvx_set_option(NAME, VALUE) before the run (A/B experiments)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stages", action="store_true", help="skip the per-stage breakdown tomogram")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: dominant-kernel roofline, board clock / power, Dice, per-stage "
+                         "and per-layer breakdown, configs[4] and UNet3D, cpu_baseline (a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-stages", action="store_true", help="with --full: skip the per-stage breakdown tomogram")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the launch / barrier / MAX-over-ranks / JSON plumbing over gloo (no GPU, no kernels)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main() -> None:
@@ -589,30 +624,32 @@ def main() -> None:
 
     from cryovit_amd._lib import EPI_SWIGLU
 
-    kt = DominantKernelTimer(_lib, EPI_SWIGLU)
+    kt = DominantKernelTimer(_lib, EPI_SWIGLU) if args.full else None
     for _ in range(args.warmup):
         out = step()
     step_no[0] = 0
     sync_all()
-    board = BoardSampler(dev.index or 0)
-    board.start()
-    kt.start()
+    board = BoardSampler(dev.index or 0) if args.full else None
+    if args.full:
+        board.start()
+        kt.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
     sync_all()
     elapsed = time.perf_counter() - t0
-    kt.stop()
-    board_stats = board.stop()
-    k_ms = kt.mean_ms()
-    n_launch = kt.n
+    if args.full:
+        kt.stop()
+        board_stats = board.stop()
+        k_ms = kt.mean_ms()
+        n_launch = kt.n
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, ctxs[(args.steps - 1) % S]["f16"])
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed_max = float(t.item())
-    i, sy, sp = out["dice_sums"].cpu().tolist()
-    fg = float((out["probs"] >= 0.5).float().mean())
     voxels = D_ * H_ * W_
     per_rank = None
     if world > 1:  # every rank's own rate (its K tomograms / its own time), gathered on rank 0 for the line
@@ -622,9 +659,6 @@ def main() -> None:
 
     if rank == 0:
         value = world * args.steps * voxels / elapsed_max
-        rows = min(sb, D_) * (hp * wp + 1 + cfg.n_reg)  # valid tokens per launch
-        k_flops = 2.0 * rows * cfg.dim * 2 * cfg.ffn_hidden
-        achieved = k_flops / (k_ms * 1e-3) / 1e12
         flops_tomo = vit.flops(D_, H_, W_) + head.flops(D_, hp, wp)
         line = {
             "metric": "tomogram voxels/sec (DINO feats + 3D seg fwd)", "value": value, "unit": "voxels/s", "n_gpus": world,
@@ -637,18 +671,25 @@ def main() -> None:
                        "slice_batch": sb, "streams": args.streams, "parallelism": f"tomogram-sharded x{world}, no collectives"},
             "tflops_end_to_end": flops_tomo * world * args.steps / elapsed_max / 1e12,
             "frac_of_mfma_peak_end_to_end": flops_tomo * args.steps / elapsed_max / 1e12 / PEAK_BF16_TFLOPS,
-            "dice": 2 * i / (sy + sp + 1e-3), "pred_fg_fraction": fg,
-            "roofline": {"bound": "mfma", "kernel": "k_gemm256p_nreg<EpiSwiGLUT<LN>, FULL>: w12 GEMM 1536->8192, LayerNorm folded into the epilogue + fused SiLU gate", "achieved": achieved,
-                         "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS, **measured_traffic(),
-                         "launches_timed": n_launch, "avg_launch_ms": k_ms, "flops_per_launch": k_flops},
-            "board": board_stats,
         }
-        if board_stats.get("energy_j"):  # board energy over the timed region (median power x its wall time), this rank's GPU
-            line["board"]["joules_per_tomogram"] = board_stats["energy_j"] / args.steps
-            line["board"]["voxels_per_joule"] = args.steps * voxels / board_stats["energy_j"]
+        if args.full:
+            i, sy, sp = out["dice_sums"].cpu().tolist()
+            rows = min(sb, D_) * (hp * wp + 1 + cfg.n_reg)  # valid tokens per launch
+            k_flops = 2.0 * rows * cfg.dim * 2 * cfg.ffn_hidden
+            achieved = k_flops / (k_ms * 1e-3) / 1e12
+            line.update({
+                "dice": 2 * i / (sy + sp + 1e-3), "pred_fg_fraction": float((out["probs"] >= 0.5).float().mean()),
+                "roofline": {"bound": "mfma", "kernel": "k_gemm256p_nreg<EpiSwiGLUT<LN>, FULL>: w12 GEMM 1536->8192, LayerNorm folded into the epilogue + fused SiLU gate", "achieved": achieved,
+                             "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS, **measured_traffic(),
+                             "launches_timed": n_launch, "avg_launch_ms": k_ms, "flops_per_launch": k_flops},
+                "board": board_stats,
+            })
+            if board_stats.get("energy_j"):  # board energy over the timed region (median power x its wall time), this rank's GPU
+                line["board"]["joules_per_tomogram"] = board_stats["energy_j"] / args.steps
+                line["board"]["voxels_per_joule"] = args.steps * voxels / board_stats["energy_j"]
         if per_rank is not None:
             line["per_rank_voxels_per_s"] = per_rank
-        if not args.no_stages:
+        if args.full and not args.no_stages:
             st = stage_breakdown(vit, head, vols[0], labels, feats_cl, feats_f16, sb)
             line["stages_ms"] = st
             # algorithmic TFLOP/s of the five stages that hold 99 % of the FLOPs (same accounting as VitEngine.flops, SURVEY s.8d)
@@ -671,7 +712,7 @@ def main() -> None:
                     line["configs"].update(other_configs(dev, vols[0]))
                 except Exception as e:  # the extra configurations must never cost the headline line
                     line["configs"]["other_configs_error"] = f"{type(e).__name__}: {e}"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if world > 1:

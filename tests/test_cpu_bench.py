@@ -71,3 +71,47 @@ def test_board_sampler_without_a_device():
     b.start()
     st = b.stop()
     assert st["sclk_mhz_median"] is None and st["power_w_median"] is None and st["samples"] == 0 and st["energy_j"] is None
+
+
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_plain_run_is_the_default_and_steps_are_checked():
+    import pytest
+
+    bench = _bench_module()
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert a.steps == 3 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_fixed_sample(tmp_path):
+    """dump_outputs on host tensors: small arrays whole, large ones as the same seeded sample every time, all float32."""
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    n = bench.DUMP_SAMPLE + 12345
+    probs = torch.rand(n, generator=torch.Generator().manual_seed(1))
+    feats = torch.randn(n, generator=torch.Generator().manual_seed(2)).half()
+    out = {"probs": probs, "dice_sums": torch.tensor([1.0, 2.0, 3.0]), "logits": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, out, feats)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"probs", "dino_features", "dice_sums"}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["dice_sums"], [1.0, 2.0, 3.0])
+    idx = np.sort(np.random.default_rng(0).integers(0, n, size=bench.DUMP_SAMPLE))
+    assert np.array_equal(got["probs"], probs.numpy()[idx]) and np.array_equal(got["dino_features"], feats.float().numpy()[idx])
+    for name, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{name}.npy"))
+    assert sum(p.stat().st_size for p in (tmp_path / "a").glob("*.npy")) <= 64 << 20

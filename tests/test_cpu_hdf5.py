@@ -144,12 +144,9 @@ def test_we_read_libhdf5_file(tmp_path, hdf5lib):
 
 
 def test_read_scipy_matlab73_file():
-    """A genuine HDF5 file with a 512-byte user block shipped with scipy (MATLAB v7.3)."""
-    import scipy.io
-
-    p = Path(scipy.io.__file__).parent / "matlab" / "tests" / "data" / "testhdf5_7.4_GLNX86.mat"
-    if not p.exists():
-        pytest.skip("scipy test data not installed")
+    """A genuine HDF5 file with a 512-byte user block (MATLAB v7.3): a copy of scipy's test file
+    scipy/io/matlab/tests/data/testhdf5_7.4_GLNX86.mat (BSD-3-Clause), kept under tests/golden/."""
+    p = Path(__file__).resolve().parent / "golden" / "testhdf5_7.4_GLNX86.mat"
     with H5Reader(p) as f:
         assert f.base == 512
         keys = f.keys()

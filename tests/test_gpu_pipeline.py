@@ -373,3 +373,34 @@ def test_checkpoint_file_loader_upstream_layout(gpu, tmp_path):
         load_encoder("dinov2_vits14_reg", checkpoint=tmp_path / "broken.pth", device=gpu)
     with pytest.raises(FileNotFoundError):
         load_encoder("dinov2_vits14_reg", model_dir=tmp_path / "nowhere", device=gpu)
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(gpu, tmp_path):
+    """``bench.py --steps 1 --warmup 0 --dump-outputs DIR`` twice, each in a process of its own: the plain line carries the headline
+    fields and none of ``--full``'s, and the dumped arrays (float32, 64 MB at most) are bit-identical between the two runs."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parent.parent
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert line["unit"] == "voxels/s" and line["higher_is_better"] is True and line["dtype"] == "bf16" and line["steps"] == 1
+        assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - 128 * 512 * 512) < 1.0
+        assert not {"roofline", "board", "stages_ms", "configs", "cpu_baseline", "dice"} & set(line)
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+        assert sum(p.stat().st_size for p in d.glob("*.npy")) <= 64 << 20
+    assert set(dumps[0]) == {"probs", "dino_features", "dice_sums"}
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), name
+        assert np.array_equal(a, dumps[1][name]), name
+    probs, sums = dumps[0]["probs"], dumps[0]["dice_sums"]
+    assert probs.min() >= 0.0 and probs.max() <= 1.0 and sums[1] > 0 and sums[2] > 0 and 0 <= sums[0] <= min(sums[1], sums[2])
