@@ -19,6 +19,7 @@ DTYPE_BF16, DTYPE_F16 = 0, 1  # CVX_DTYPE_*
 DICE_BLOCKS = 4096  # CVX_DICE_BLOCKS
 GN_BLOCKS = 1024  # CVX_GN_BLOCKS
 GN_MAX_GROUPS = 512  # CVX_GN_MAX_GROUPS
+PCA_SLICE_STEP = 10  # CVX_PCA_SLICE_STEP
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -141,6 +142,11 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_float, c_void_p]),
     "cvx_vit_encode": (c_int, [C.POINTER(VitDesc), C.POINTER(VitWs), c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p]),
+    "cvx_pca_moments_scratch_bytes": (c_long, [c_int, c_int, c_int]),
+    "cvx_pca_moments_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "cvx_pca_project_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cvx_pca_colormap_scratch_bytes": (c_long, [c_int, c_int, c_int]),
+    "cvx_pca_colormap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
 }
 
 _lib = None

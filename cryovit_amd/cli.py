@@ -41,7 +41,7 @@ def features(
     tomograms: Annotated[str, Argument(help="Path to the folder or .txt file containing the tomograms to process.")],
     result_folder: Annotated[str, Argument(help="Path to the folder where the DINO features will be saved.")],
     batch_size: Annotated[int, Option(min=1, help="Batch size for DINO feature extraction.")] = 64,
-    visualize: Annotated[bool, Option("--visualize", "-v", help="Save PCA visualization of DINO features? (not built: skipped)")] = False,
+    visualize: Annotated[bool, Option("--visualize", "-v", help="Save PCA visualization of DINO features? This will increase the runtime.")] = False,
     encoder: Annotated[Optional[str], Option(help="build extension: encoder name (default dinov2_vitg14_reg)")] = None,
     checkpoint: Annotated[Optional[str], Option(help="build extension: local DINOv2 state_dict file")] = None,
     synthetic_seed: Annotated[Optional[int], Option(help="build extension: seeded random encoder weights")] = None,

@@ -6,16 +6,6 @@
 
 namespace cvx {
 
-// Keys cubic-convolution taps, A = -0.75 (PyTorch bicubic), for fractional offset t in [0,1)
-__device__ __forceinline__ void cubic_taps(float t, float (&w)[4]) {
-    const float A = -0.75f;
-    const float x0 = t + 1.0f, x1 = t, x2 = 1.0f - t, x3 = 2.0f - t;
-    w[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
-    w[1] = ((A + 2.0f) * x1 - (A + 3.0f)) * x1 * x1 + 1.0f;
-    w[2] = ((A + 2.0f) * x2 - (A + 3.0f)) * x2 * x2 + 1.0f;
-    w[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
-}
-
 // out[m][k], m = (slice*hp + ph)*wp + pw, k = py*14 + px  (k >= 196 zero).  One thread = 8 consecutive k.
 // Source coordinate as torch: s = scale*(dst+0.5)-0.5 with scale = (float)(1/0.875); taps floor(s)-1..+2 clamped
 // to the (edge-padded) image, which equals clamping to the raw image because the padding replicates the border.

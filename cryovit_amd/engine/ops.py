@@ -381,3 +381,63 @@ def fpn_level_out(lateral: torch.Tensor, coarse, out: torch.Tensor, *, slices: i
     assert out.numel() == slices * C * grid * grid and lateral.shape[0] >= slices * grid * grid
     call(dev, "cvx_fpn_level_out", _lib.load().cvx_fpn_level_out, lateral.data_ptr(), _p(coarse), slices, C, grid,
          out.data_ptr())
+
+
+def pca_selected(D: int) -> int:
+    """Slices 0, 10, 20, ... of a D-slice tomogram: the ones a PCA colour map is drawn for (CVX_PCA_SLICE_STEP)."""
+    return (D + _lib.PCA_SLICE_STEP - 1) // _lib.PCA_SLICE_STEP
+
+
+def pca_moments(feats: torch.Tensor, sums: torch.Tensor, gram: torch.Tensor, scratch=None) -> None:
+    """Column sums (fp64 [C]) and Gram matrix (fp64 [C, C]) of the fp16 features [C, D, h, w] over every tenth slice."""
+    if feats.dim() != 4 or feats.dtype != torch.float16:
+        raise _lib.CvxError(f"pca_moments: feats must be fp16 [C, D, h, w], got {feats.dtype} {tuple(feats.shape)}")
+    Cc, D, h, w = feats.shape
+    if sums.dtype != torch.float64 or gram.dtype != torch.float64 or sums.numel() != Cc or gram.numel() != Cc * Cc:
+        raise _lib.CvxError("pca_moments: sums fp64 [C], gram fp64 [C, C]")
+    lib = _lib.load()
+    need = lib.cvx_pca_moments_scratch_bytes(Cc, D, h * w)
+    check(min(need, 0), "cvx_pca_moments_scratch_bytes")
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=feats.device)
+    if scratch.dtype != torch.uint8 or scratch.numel() < need:
+        raise _lib.CvxError(f"pca_moments: scratch must be uint8 with >= {need} bytes")
+    dev = _dev_check(feats, sums, gram, scratch)
+    call(dev, "cvx_pca_moments_f16", lib.cvx_pca_moments_f16, feats.data_ptr(), Cc, D, h * w, sums.data_ptr(), gram.data_ptr(),
+         scratch.data_ptr(), scratch.numel())
+
+
+def pca_project(feats: torch.Tensor, mean: torch.Tensor, comps: torch.Tensor, proj: torch.Tensor) -> None:
+    """proj fp32 [3, D', h, w] = comps (fp32 [3, C]) . (x - mean (fp32 [C])) over the selected slices."""
+    if feats.dim() != 4 or feats.dtype != torch.float16:
+        raise _lib.CvxError(f"pca_project: feats must be fp16 [C, D, h, w], got {feats.dtype} {tuple(feats.shape)}")
+    Cc, D, h, w = feats.shape
+    if mean.dtype != torch.float32 or comps.dtype != torch.float32 or proj.dtype != torch.float32:
+        raise _lib.CvxError("pca_project: mean, comps and proj must be fp32")
+    if mean.numel() != Cc or comps.numel() != 3 * Cc or proj.numel() != 3 * pca_selected(D) * h * w:
+        raise _lib.CvxError("pca_project: mean [C], comps [3, C], proj [3, D', h, w]")
+    dev = _dev_check(feats, mean, comps, proj)
+    call(dev, "cvx_pca_project_f16", _lib.load().cvx_pca_project_f16, feats.data_ptr(), Cc, D, h * w, mean.data_ptr(),
+         comps.data_ptr(), proj.data_ptr())
+
+
+def pca_colormap(proj: torch.Tensor, data: torch.Tensor, canvas: torch.Tensor, *, x_map: int, scratch=None) -> None:
+    """canvas uint8 [D', 16h, 32w, 3]: the data slices (uint8 / fp32 [D, H, W]) next to the colour maps of proj [3, D', h, w]."""
+    if data.dim() != 3 or data.dtype not in (torch.uint8, torch.float32):
+        raise _lib.CvxError(f"pca_colormap: data must be uint8 / fp32 [D, H, W], got {data.dtype} {tuple(data.shape)}")
+    D, H, W = data.shape
+    Dp, h, w = pca_selected(D), (H + 15) // 16, (W + 15) // 16
+    if proj.dtype != torch.float32 or proj.numel() != 3 * Dp * h * w:
+        raise _lib.CvxError(f"pca_colormap: proj must be fp32 [3, {Dp}, {h}, {w}]")
+    if canvas.dtype != torch.uint8 or tuple(canvas.shape) != (Dp, 16 * h, 32 * w, 3):
+        raise _lib.CvxError(f"pca_colormap: canvas must be uint8 [{Dp}, {16 * h}, {32 * w}, 3]")
+    lib = _lib.load()
+    need = lib.cvx_pca_colormap_scratch_bytes(D, H, W)
+    check(min(need, 0), "cvx_pca_colormap_scratch_bytes")
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=proj.device)
+    if scratch.dtype != torch.uint8 or scratch.numel() < need:
+        raise _lib.CvxError(f"pca_colormap: scratch must be uint8 with >= {need} bytes")
+    dev = _dev_check(proj, data, canvas, scratch)
+    call(dev, "cvx_pca_colormap", lib.cvx_pca_colormap, proj.data_ptr(), data.data_ptr(), int(data.dtype == torch.uint8), D, H, W,
+         int(x_map), canvas.data_ptr(), scratch.data_ptr(), scratch.numel())

@@ -3,7 +3,7 @@ result, arithmetic on the HIP engine.
 
   _dino_features   l.31-64    slices -> encoder -> float16 [C, D, H/16, W/16]
   _save_data       l.109-153  output HDF5: ``data`` + ``labels/<leaf>`` gzip, ``dino_features`` contiguous fp16
-  _process_sample  l.156-205  enumerate records, per tomogram: features -> re-read source -> save
+  _process_sample  l.156-205  enumerate records, per tomogram: features -> re-read source -> save (-> PCA images)
   run_trainer      l.304-350  paths (incl. the inverted src/dst naming), model load, sample loop
 Multi-GPU: records of a sample are sharded over the ranks of a ``torch.distributed.run`` launch (run/sharding.py).
 """
@@ -23,6 +23,7 @@ from cryovit_amd.config import instantiate, samples, tomogram_exts
 from cryovit_amd.models.encoder import load_encoder
 from cryovit_amd.models.sam_encoder import load_sam_encoder
 from cryovit_amd.run.sharding import select_device, shard_records, world_info
+from cryovit_amd.visualization import dino_pca
 
 
 @torch.inference_mode()
@@ -69,21 +70,23 @@ class _PinnedRing:
             if len(lst) < 4:
                 lst.append(t)
 
-    def stream(self, device) -> torch.cuda.Stream:
+    def stream(self, device, role: str = "copy") -> torch.cuda.Stream:
         with self._lock:
-            if device not in self._streams:
-                self._streams[device] = torch.cuda.Stream(device)
-            return self._streams[device]
+            if (device, role) not in self._streams:
+                self._streams[(device, role)] = torch.cuda.Stream(device)
+            return self._streams[(device, role)]
 
 
 _ring = _PinnedRing()
 
 
 @torch.inference_mode()
-def _dino_features_async(data: torch.Tensor, model, batch_size: int):
-    """The fused path of ``_dino_features`` WITHOUT its synchronisation: returns ``(host fp16 tensor, event, release)``; the array is
-    valid once ``event.synchronize()`` returns, ``release()`` hands the pinned buffer back.  Used by ``_process_sample``'s pipeline
-    (the writer thread waits for the event), so the launch thread never blocks on the copy of the tomogram it has just issued."""
+def _dino_features_async(data: torch.Tensor, model, batch_size: int, pca: bool = False):
+    """The fused path of ``_dino_features`` WITHOUT its synchronisation: returns ``(host fp16 tensor, event, release, moments)``; the
+    array is valid once ``event.synchronize()`` returns, ``release()`` hands the pinned buffer back.  Used by ``_process_sample``'s
+    pipeline (the writer thread waits for the event), so the launch thread never blocks on the copy of the tomogram it has just
+    issued.  ``pca``: the moments of the PCA colour maps are launched right after the features (``moments``, else None; the
+    writer finishes the export with ``dino_pca.finish_export``)."""
     f16, _ = model.features_from_raw(data, batch_size, want_f16=True, want_cl=False)
     host = _ring.take(f16.shape, f16.dtype)
     cur = torch.cuda.current_stream(f16.device)
@@ -94,7 +97,8 @@ def _dino_features_async(data: torch.Tensor, model, batch_size: int):
         ev = torch.cuda.Event()
         ev.record(side)
     f16.record_stream(side)  # the caching allocator must not hand this block out again before the copy has read it
-    return host, ev, (lambda: _ring.give(host))
+    moments = dino_pca.launch_moments(f16, copy_stream=side) if pca else None
+    return host, ev, (lambda: _ring.give(host)), moments
 
 
 @torch.inference_mode()
@@ -157,20 +161,30 @@ def _process_sample(src_dir: Path, dst_dir: Path, csv_dir: Path, model, sample: 
     # Three-stage host pipeline around the GPU (the reference runs these serially, SURVEY s.8a a3): a reader thread
     # decompresses tomogram i+1 while the GPU works on i, a writer thread gzips and writes i-1 (zlib drops the GIL).
     feature_fn = _sam_features if use_sam else _dino_features
+    export = image_dir is not None and not use_sam  # PCA colour maps: DINO features only (reference l.285-287)
+    if image_dir is not None and use_sam:
+        logging.warning("export_features=True: PCA colour maps are drawn for DINO features only -- skipped for SAM features")
 
-    def save(i, features, ready=None, release=None):
+    def save(i, features, ready=None, release=None, moments=None):
         try:
             if ready is not None:
                 ready.synchronize()  # the device-to-host copy of THIS tomogram (issued on a side stream) has landed
                 features = features.numpy()
-            _save_data(io.read_all_flat(tomo_dir / mine[i]), features, mine[i], result_dir)
+            data = io.read_all_flat(tomo_dir / mine[i])
+            _save_data(data, features, mine[i], result_dir)
         finally:
             if release is not None:
                 release()
+        if moments is not None:  # moments launched with the features: eigensolve here, projection / colour on a side stream
+            dino_pca.finish_export(moments, data["data"], mine[i][:-4], Path(image_dir) / sample,
+                                   stream=_ring.stream(moments.feats.device, "pca"))
+        elif export:
+            dino_pca.export_pca(data["data"], features, mine[i][:-4], Path(image_dir) / sample, device=model_device)
         shapes = features.shape if not isinstance(features, dict) else {k: [f.shape for f in v] for k, v in features.items()}
         logging.info("[rank %d] %s/%s -> %s %s", rank, sample, mine[i], "sam_features" if use_sam else "dino_features", shapes)
         return mine[i]
 
+    model_device = getattr(model, "device", None)  # the writer threads' uploads go to the encoder's GPU, not GPU 0
     with ThreadPoolExecutor(max_workers=1) as reader, ThreadPoolExecutor(max_workers=2) as writer:
         nxt = reader.submit(dataset.__getitem__, 0) if len(dataset) else None
         pending = []
@@ -178,15 +192,14 @@ def _process_sample(src_dir: Path, dst_dir: Path, csv_dir: Path, model, sample: 
             x = nxt.result()
             nxt = reader.submit(dataset.__getitem__, i + 1) if i + 1 < len(dataset) else None
             if not use_sam and torch.is_tensor(x) and x.dim() == 3 and hasattr(model, "features_from_raw"):
-                host, ev, release = _dino_features_async(x, model, batch_size)  # no host synchronisation on the launch thread
-                pending.append(writer.submit(save, i, host, ev, release))
+                # no host synchronisation on the launch thread
+                host, ev, release, moments = _dino_features_async(x, model, batch_size, pca=export)
+                pending.append(writer.submit(save, i, host, ev, release, moments))
             else:
                 pending.append(writer.submit(save, i, feature_fn(x, model, batch_size)))
             while len(pending) > 2:  # bound the number of 400-MB feature arrays waiting to be written
                 done.append(pending.pop(0).result())
         done += [f.result() for f in pending]
-    if image_dir is not None:
-        logging.warning("export_features=True: PCA colour maps are plotting (out of scope of this build) -- skipped")
     return done
 
 
@@ -223,7 +236,8 @@ def run_trainer(cfg) -> None:
 def run_dino(train_data: list[Path], result_dir: Path, batch_size: int, use_sam: bool = False, visualize: bool = False, *,
              encoder: dict | None = None) -> None:
     """Feature extraction over a list of tomogram files of any supported format (mirror of l.211-299): one
-    ``<result_dir>/<stem>.hdf`` per input with ``data``, ``dino_features`` and the source's other datasets under ``labels/``.
+    ``<result_dir>/<stem>.hdf`` per input with ``data``, ``dino_features`` and the source's other datasets under ``labels/``;
+    ``visualize``: PCA colour maps under ``<result_dir>/../dino_images/<stem>/<stem>/`` (the reference's doubled stem).
     ``encoder`` overrides keys of the config's ``encoder`` block (name / checkpoint / synthetic_seed / device)."""
     from cryovit_amd.config import compose
     from cryovit_amd.types import FileData
@@ -240,8 +254,15 @@ def run_dino(train_data: list[Path], result_dir: Path, batch_size: int, use_sam:
     files = [FileData(tomo_path=Path(f)) for f in train_data]
     dataset = instantiate(cfg.datamodule.dataset, input_key=None, label_key=None)(files, for_dino=True, use_sam=use_sam)
     result_list = [Path(result_dir) / f"{Path(f).stem}.hdf" for f in train_data]
-    if visualize:
-        logging.warning("visualize=True: PCA colour maps are plotting (out of scope of this build) -- skipped")
+    if visualize and use_sam:
+        logging.warning("visualize=True: PCA colour maps are drawn for DINO features only -- skipped for SAM features")
+
+    def save(aux_data, features, result_path: Path):
+        _save_data(aux_data, features, result_path.name, result_path.parent)
+        if visualize and not use_sam:
+            stem = result_path.name[:-4]
+            dino_pca.export_pca(aux_data["data"], features, stem, result_path.parent.parent / "dino_images" / stem, device=device)
+
     try:
         with ThreadPoolExecutor(max_workers=2) as writer:
             pending = []
@@ -249,7 +270,7 @@ def run_dino(train_data: list[Path], result_dir: Path, batch_size: int, use_sam:
                 x = dataset[i]
                 features = feature_fn(x.data, model, cfg.batch_size)
                 result_path = result_list[i].with_suffix(".hdf")
-                pending.append(writer.submit(_save_data, x.aux_data, features, result_path.name, result_path.parent))
+                pending.append(writer.submit(save, x.aux_data, features, result_path))
                 while len(pending) > 2:
                     pending.pop(0).result()
             for f in pending:

@@ -399,6 +399,34 @@ typedef struct cvx_head_ws {                  /* device workspaces, fp16 channel
 int cvx_head_forward(const cvx_head_desc* head, const cvx_head_ws* ws, const void* feats_cl, int D, int h, int w, float* logits,
                      float* probs, const int8_t* labels, float* dice, uint8_t* mask, float mask_threshold, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * PCA colour maps of DINO features (export_features=True / `cryovit features --visualize`; the reference's
+ * cryovit/visualization/dino_pca.py with PCA-3 in place of PCA(1024) + UMAP).  feats: fp16 [C][D][hw] (the
+ * features as the encoder writes them, hw = h*w); only slices 0, 10, 20, ... (D' = ceil(D / 10), N' = D'*hw rows) are read.
+ * Everything is deterministic: fixed-order reductions, no atomics.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_PCA_SLICE_STEP 10
+
+/* bytes of device scratch cvx_pca_moments_f16 needs (fp32 split-K partials of the Gram tiles); < 0 on bad sizes */
+long cvx_pca_moments_scratch_bytes(int C, int D, int hw);
+/* sums fp64 [C] = column sums over the N' selected rows; gram fp64 [C][C] = X X^T over them (fp16 MFMA, fp32 split
+ * partials summed in fp64 in split order, exactly symmetric).  No centring: the caller forms (G - s s^T / N') / (N' - 1). */
+int cvx_pca_moments_f16(const void* feats, int C, int D, int hw, double* sums, double* gram, void* scratch, long scratch_bytes,
+                        hipStream_t stream);
+/* proj fp32 [3][N'] = comps (fp32 [3][C]) . (x - mean (fp32 [C])) for every selected row, row index = slice' * hw + pixel */
+int cvx_pca_project_f16(const void* feats, int C, int D, int hw, const float* mean, const float* comps, float* proj,
+                        hipStream_t stream);
+/* bytes of device scratch cvx_pca_colormap needs: fp32 [3][D'][2h][2w] upsampled maps + min / max partials */
+long cvx_pca_colormap_scratch_bytes(int D, int H, int W);
+/* canvas uint8 [D'][16h][2*16w][3] (h = ceil(H/16), w = ceil(W/16); 16-byte aligned), one RGB image per selected slice:
+ * black, the data slice 10*j' (data uint8 when is_u8 else fp32 [D][H][W], min-max normalised over the whole volume, truncated,
+ * flipped vertically, grey) at the origin, and at column x_map the colour map of proj (fp32 [3][D'][h][w] from
+ * cvx_pca_project_f16): bicubic x2 (A = -0.75), per-channel min-max over all D' slices, matplotlib rgb_to_hsv, s = 0.9,
+ * v = 0.75, hsv_to_rgb, (uint8)(255 * rgb), each pixel an 8x8 block, flipped vertically (x_map = W as the reference
+ * pastes it; anything past the canvas edge is dropped). */
+int cvx_pca_colormap(const float* proj, const void* data, int is_u8, int D, int H, int W, int x_map, uint8_t* canvas, void* scratch,
+                     long scratch_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
