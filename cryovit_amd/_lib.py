@@ -20,6 +20,11 @@ DICE_BLOCKS = 4096  # CVX_DICE_BLOCKS
 GN_BLOCKS = 1024  # CVX_GN_BLOCKS
 GN_MAX_GROUPS = 512  # CVX_GN_MAX_GROUPS
 PCA_SLICE_STEP = 10  # CVX_PCA_SLICE_STEP
+LABEL_I8, LABEL_U8, LABEL_I16, LABEL_U16, LABEL_I32, LABEL_F32 = range(6)  # CVX_LABEL_* dtypes
+LABEL_BITMAP_BITS = 65536  # CVX_LABEL_BITMAP_BITS
+LABEL_CENSUS_WORDS = 4 + LABEL_BITMAP_BITS // 32  # CVX_LABEL_CENSUS_WORDS
+LABEL_NONINTEGER, LABEL_WIDE = 1, 2  # CVX_LABEL_NONINTEGER / CVX_LABEL_WIDE census flags
+LABEL_MATCH, LABEL_WEIGHT = 0, 1  # CVX_LABEL_MATCH / CVX_LABEL_WEIGHT
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -147,6 +152,8 @@ SIGNATURES = {
     "cvx_pca_project_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cvx_pca_colormap_scratch_bytes": (c_long, [c_int, c_int, c_int]),
     "cvx_pca_colormap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
+    "cvx_label_census": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
+    "cvx_label_metrics": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,11 +1,12 @@
-"""``cryovit`` command line for the two script-level flows on the hot path (mirror of
-``/root/reference/src/cryovit/cli/{cli,dino_cli,infer_cli}.py``): same command names, arguments, options and defaults.
+"""``cryovit`` command line for the script-level flows (mirror of
+``/root/reference/src/cryovit/cli/{cli,dino_cli,infer_cli,eval_cli}.py``): same command names, arguments, options and defaults.
 
     python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize]
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
+    python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
 
-``train`` / ``evaluate`` (Lightning training loops) are outside the hot path and not provided.  Extra options, marked
-"build extension", replace the network fetch of the encoder weights.
+``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
+replace the network fetch of the encoder weights.
 """
 
 from __future__ import annotations
@@ -22,7 +23,20 @@ cli = typer.Typer(add_completion=False, no_args_is_help=True, pretty_exceptions_
 
 @cli.callback()
 def callback():
-    """CryoViT's command line interface (MI355X build): feature extraction and inference."""
+    """CryoViT's command line interface (MI355X build): feature extraction, inference and evaluation."""
+
+
+def _load_encoder(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]):
+    """The encoder of the "build extension" options, or None when none of them is given."""
+    ov = _encoder_overrides(encoder, checkpoint, synthetic_seed)
+    if not ov:
+        return None
+    from cryovit_amd.config import compose
+    from cryovit_amd.models.encoder import load_encoder
+
+    cfg = compose("dino_features", [])
+    return load_encoder(ov.get("name", "dinov2_vitg14_reg"), model_dir=cfg.model_dir, checkpoint=ov.get("checkpoint"),
+                        synthetic_seed=ov.get("synthetic_seed"))
 
 
 def _encoder_overrides(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]) -> dict:
@@ -78,16 +92,38 @@ def infer(
     assert tomograms_path.exists(), "Tomograms path does not exist."
     assert model_path.exists() and model_path.suffix == ".model", "Model path does not exist or is not a .model file."
     result_path.mkdir(parents=True, exist_ok=True)
-    enc = None
-    ov = _encoder_overrides(encoder, checkpoint, synthetic_seed)
-    if ov:
-        from cryovit_amd.config import compose
-        from cryovit_amd.models.encoder import load_encoder
+    run_inference(load_files_from_path(tomograms_path), model_path, result_path, threshold=threshold,
+                  encoder=_load_encoder(encoder, checkpoint, synthetic_seed))
 
-        cfg = compose("dino_features", [])
-        enc = load_encoder(ov.get("name", "dinov2_vitg14_reg"), model_dir=cfg.model_dir, checkpoint=ov.get("checkpoint"),
-                           synthetic_seed=ov.get("synthetic_seed"))
-    run_inference(load_files_from_path(tomograms_path), model_path, result_path, threshold=threshold, encoder=enc)
+
+@cli.command(name="evaluate", no_args_is_help=True)
+def evaluate(
+    test_data: Annotated[str, Argument(help="Path to the folder or .txt file containing the test tomograms.")],
+    test_labels: Annotated[str, Argument(help="Path to the folder or .txt file containing the test labels.")],
+    labels: Annotated[list[str], Option(help="List of available label names in ascending-value order.")],
+    model: Annotated[str, Argument(help="Path to the .model file containing the pre-trained model.")],
+    result_folder: Annotated[Optional[str], Option(help="Path to the directory to save the evaluation results. Evaluation metrics will be saved to a .csv file in a folder named 'results' inside the result folder.",
+                                                   show_default="the current working directory")] = None,
+    visualize: Annotated[bool, Option("--visualize", "-v", help="Save visualizations of model predictions?. This will slightly increase the runtime. Results will be saved in a folder named `predictions` inside the result folder.")] = False,
+    encoder: Annotated[Optional[str], Option(help="build extension: encode files without dino_features on the fly with this encoder")] = None,
+    checkpoint: Annotated[Optional[str], Option(help="build extension: local DINOv2 state_dict file")] = None,
+    synthetic_seed: Annotated[Optional[int], Option(help="build extension: seeded random encoder weights")] = None,
+):
+    """Evaluate a pre-trained model on a test dataset."""
+    from cryovit_amd.run.eval_model import run_evaluation
+    from cryovit_amd.utils import load_files_from_path, load_model
+
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
+    test_path, label_path, model_path = Path(test_data), Path(test_labels), Path(model)
+    result_path = Path(result_folder) if result_folder else Path.cwd()
+    assert test_path.exists(), "Test data path does not exist."
+    assert label_path.exists(), "Test labels path does not exist."
+    assert model_path.exists() and model_path.suffix == ".model", "Model path does not exist, or is not a .model file."
+    _, _, _, label_key = load_model(model_path, load_model=False)
+    assert label_key in labels, f"The label key {label_key} used to train the model is not in the provided labels."
+    result_path.mkdir(parents=True, exist_ok=True)
+    run_evaluation(load_files_from_path(test_path), load_files_from_path(label_path), labels, model_path, result_path,
+                   visualize=visualize, encoder=_load_encoder(encoder, checkpoint, synthetic_seed))
 
 
 if __name__ == "__main__":

@@ -4,14 +4,18 @@
 The reference wraps a pandas DataFrame of ``splits.csv`` (columns ``sample, tomo_name, split_id``) in a
 LightningDataModule; here the rows are plain dicts and the "dataloader" is the dataset itself with ``collate_fn`` applied
 to one tomogram at a time (evaluation batch size is 1: ``configs/datamodule/dataloader/default.yaml:7``).  Only the
-evaluation side (``test_df`` / ``predict_df`` and the ``val_df`` / ``train_df`` they are defined through) is mirrored."""
+evaluation side (``test_df`` / ``predict_df`` and the ``val_df`` / ``train_df`` they are defined through) is mirrored.
+
+``FileDataModule`` (``file_datamodule.py:14-69``) pairs user-supplied data files with label files for ``cryovit evaluate``."""
 
 from __future__ import annotations
 
 import csv
+import logging
 from pathlib import Path
 
 from cryovit_amd.datasets.tomo_dataset import collate_fn
+from cryovit_amd.types import FileData
 
 
 def _num(v):
@@ -104,4 +108,39 @@ class SingleSampleDataModule(MultiSampleDataModule):
         super().__init__(sample, split_id, split_key, test_sample, **kwargs)
 
 
-__all__ = ["BaseDataModule", "SingleSampleDataModule", "MultiSampleDataModule", "collate_fn"]
+class FileDataModule:
+    """Data files, optionally paired one to one with label files (file_datamodule.py:14-69): lists of different lengths are
+    rejected, a pair whose data or label file is missing is skipped with a warning, ``sample`` is the data file's folder name."""
+
+    def __init__(self, data_paths, dataset_fn, dataloader_fn=None, val_paths=None, data_labels=None, val_labels=None,
+                 labels: list[str] | None = None, **_):
+        self.data_files = self._combine_files_and_labels(data_paths, data_labels, labels)
+        self.val_files = self._combine_files_and_labels(val_paths, val_labels, labels) if val_paths is not None else []
+        self.dataset_fn, self.dataloader_fn = dataset_fn, dataloader_fn
+
+    @staticmethod
+    def _combine_files_and_labels(files, labels, label_keys) -> list[FileData]:
+        files = [Path(f) for f in files]
+        file_labels = [None] * len(files) if labels is None else [Path(lp) for lp in labels]
+        if len(files) != len(file_labels):
+            raise ValueError("Number of data files must match number of label files.")
+        combined = []
+        for fp, lp in zip(files, file_labels):
+            if not fp.exists() or (lp is not None and not lp.exists()):
+                logging.warning("File %s or label %s does not exist, skipping.", fp, lp)
+                continue
+            combined.append(FileData(tomo_path=fp, label_path=lp, sample=fp.parent.name, labels=label_keys))
+        return combined
+
+    def test_dataset(self):
+        if len(self.data_files) == 0:
+            raise ValueError("No testing data provided.")
+        return self.dataset_fn(self.data_files, train=False)
+
+    def predict_dataset(self):
+        if len(self.data_files) == 0:
+            raise ValueError("No prediction data provided.")
+        return self.dataset_fn(self.data_files, train=False)
+
+
+__all__ = ["BaseDataModule", "SingleSampleDataModule", "MultiSampleDataModule", "FileDataModule", "collate_fn"]

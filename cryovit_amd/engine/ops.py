@@ -441,3 +441,61 @@ def pca_colormap(proj: torch.Tensor, data: torch.Tensor, canvas: torch.Tensor, *
     dev = _dev_check(proj, data, canvas, scratch)
     call(dev, "cvx_pca_colormap", lib.cvx_pca_colormap, proj.data_ptr(), data.data_ptr(), int(data.dtype == torch.uint8), D, H, W,
          int(x_map), canvas.data_ptr(), scratch.data_ptr(), scratch.numel())
+
+
+# ---- label decode and evaluation counts (`cryovit evaluate`) ----
+
+_LABEL_DTYPES = {torch.int8: _lib.LABEL_I8, torch.uint8: _lib.LABEL_U8, torch.int16: _lib.LABEL_I16, torch.uint16: _lib.LABEL_U16,
+                 torch.int32: _lib.LABEL_I32, torch.float32: _lib.LABEL_F32}
+
+
+def _label_dtype(labels: torch.Tensor, what: str) -> int:
+    if labels.dtype not in _LABEL_DTYPES:
+        raise _lib.CvxError(f"{what}: label dtype must be one of int8, uint8, int16, uint16, int32, float32, got {labels.dtype}")
+    return _LABEL_DTYPES[labels.dtype]
+
+
+def label_census(labels: torch.Tensor, census: torch.Tensor) -> None:
+    """census int32 [LABEL_CENSUS_WORDS] = min, max, flags, 0, presence bitmap over [min, max] of the label volume (any shape,
+    file dtype); see ``label_census_values`` for the host side."""
+    dtype = _label_dtype(labels, "label_census")
+    if census.dtype != torch.int32 or census.numel() != _lib.LABEL_CENSUS_WORDS:
+        raise _lib.CvxError(f"label_census: census must be int32 [{_lib.LABEL_CENSUS_WORDS}]")
+    dev = _dev_check(labels, census)
+    call(dev, "cvx_label_census", _lib.load().cvx_label_census, labels.data_ptr(), dtype, labels.numel(), census.data_ptr())
+
+
+def label_census_values(census) -> tuple[int, int, list[int]]:
+    """(min, max, sorted distinct values) of a census copied to the host (numpy int32 / torch CPU tensor); raises ValueError on
+    the flags: float labels that are not integers, or a value range wider than the bitmap (LABEL_BITMAP_BITS values)."""
+    import numpy as np
+
+    c = np.asarray(census, dtype=np.int32)
+    lo, hi, flags = int(c[0]), int(c[1]), int(c[2])
+    if flags & _lib.LABEL_NONINTEGER:
+        raise ValueError("label volume holds float values that are not integers")
+    if flags & _lib.LABEL_WIDE:
+        raise ValueError(f"label values span more than {_lib.LABEL_BITMAP_BITS} integers")
+    if lo > hi:
+        return lo, hi, []
+    bits = np.unpackbits(c[4:].view(np.uint8), bitorder="little")[: hi - lo + 1]
+    return lo, hi, (np.flatnonzero(bits) + lo).tolist()
+
+
+def label_metrics(probs: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor, *, value: int = 0, mode: int = _lib.LABEL_MATCH,
+                  thr: float = 0.5, y_out=None) -> None:
+    """counts uint64 (or int64) [5] += sum y, sum [p >= thr], sum y [p >= thr], sum [p > thr], sum y [p > thr] over the voxels whose decoded
+    label y is > -1 (LABEL_MATCH: y = the int8 {-1, 0, 1} map of ``value`` that utils._match_label_keys_to_data makes; LABEL_WEIGHT:
+    y = int8(label)).  probs fp32 and labels (file dtype) of equal numel; y_out (optional) int8 receives y."""
+    dtype = _label_dtype(labels, "label_metrics")
+    if probs.dtype != torch.float32 or probs.numel() != labels.numel():
+        raise _lib.CvxError("label_metrics: probs must be fp32 with as many elements as labels")
+    if counts.dtype not in (torch.uint64, torch.int64) or counts.numel() != 5:
+        raise _lib.CvxError("label_metrics: counts must be uint64 / int64 [5]")
+    if y_out is not None and (y_out.dtype != torch.int8 or y_out.numel() != labels.numel()):
+        raise _lib.CvxError("label_metrics: y_out must be int8 with as many elements as labels")
+    if mode not in (_lib.LABEL_MATCH, _lib.LABEL_WEIGHT):
+        raise _lib.CvxError(f"label_metrics: unknown mode {mode}")
+    dev = _dev_check(probs, labels, counts, y_out)
+    call(dev, "cvx_label_metrics", _lib.load().cvx_label_metrics, probs.data_ptr(), labels.data_ptr(), dtype, labels.numel(), int(mode),
+         int(value), float(thr), counts.data_ptr(), _p(y_out))

@@ -7,10 +7,16 @@ What replaces ``pytorch_lightning.Trainer.test``: the loop below.  A reader thre
 GPU works on i; under ``torch.distributed.run`` the test records are sharded over the ranks (tomograms are independent, no
 data-path collective) and every rank writes the files of its own tomograms; the CSV rows are appended by rank 0 after an
 object gather so two ranks never rewrite one CSV file concurrently.
+
+``run_evaluation`` (reference l.21-91, ``cryovit evaluate``) scores a ``.model`` file on user-supplied data and label files
+(``FileDataModule``).  The label volume is read as stored and decoded on the GPU: ``cvx_label_census`` gives its distinct
+values (``np.unique`` of ``_match_label_keys_to_data``), ``cvx_label_metrics`` makes the model's label map of one value and
+counts the sums DiceMetric and F1Metric are computed from, in one pass over probabilities and labels.
 """
 
 from __future__ import annotations
 
+import dataclasses
 import logging
 import random
 from concurrent.futures import ThreadPoolExecutor
@@ -19,8 +25,11 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from cryovit_amd.config import instantiate
+from cryovit_amd import _lib
+from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
+from cryovit_amd.engine import ops
+from cryovit_amd.models.metrics import dice_from_sums
 from cryovit_amd.run.sharding import gather_rows, select_device, shard_records, world_info
 
 
@@ -105,3 +114,161 @@ def run_trainer(cfg) -> None:
 
     logging.info("Starting testing.")
     test_loop(model, datamodule.test_dataset(), callbacks)
+
+
+## For scripts: `cryovit evaluate`
+
+_F1_THRESHOLD = 0.5  # F1Metric: p_hat = p > 0.5 (metrics.py:56-93)
+
+
+def _metric_thresholds(metric_fns: dict) -> list[float]:
+    """The thresholds the model's metrics need counts at: DiceMetric ``p >= threshold``, F1Metric ``p > 0.5``."""
+    out = []
+    for m in metric_fns.values():
+        kind = type(m).__name__
+        if kind == "DiceMetric":
+            t = float(m.thresh)
+        elif kind == "F1Metric":
+            t = _F1_THRESHOLD
+        else:
+            raise NotImplementedError(f"metric {kind}: run_evaluation computes DiceMetric and F1Metric")
+        if t not in out:
+            out.append(t)
+    return out
+
+
+def metrics_from_counts(metric_fns: dict, counts: dict[float, list[int]]) -> dict[str, float]:
+    """Per-tomogram metric values from the exact counts of ``cvx_label_metrics`` at each threshold
+    ([sum y, sum p>=t, sum y p>=t, sum p>t, sum y p>t]): the formulas of DiceMetric and F1Metric."""
+    out = {}
+    for name, m in metric_fns.items():
+        if type(m).__name__ == "DiceMetric":
+            ysum, psum, inter = counts[float(m.thresh)][:3]
+            out[name] = dice_from_sums(float(inter), float(ysum), float(psum))
+        else:
+            ysum, _, _, psum, tp = counts[_F1_THRESHOLD]
+            fp, fn = psum - tp, ysum - tp
+            precision, recall = tp / (tp + fp + 1e-6), tp / (tp + fn + 1e-6)
+            out[name] = 2 * (precision * recall) / (precision + recall + 1e-6)
+    return out
+
+
+def label_plan(labels_dev: torch.Tensor, label_path: Path, label_keys: list[str], label_key: str) -> tuple[int, int]:
+    """(mode, value) that decodes ``label_key`` from this label volume the way ``load_labels`` does: the single-key HDF branch
+    keeps ``data.astype(np.int8)`` (LABEL_WEIGHT); every other branch matches names to the volume's distinct values
+    (LABEL_MATCH), which come from the census kernel.  Raises what ``_match_label_keys_to_data`` raises."""
+    from cryovit_amd.utils import match_label_values
+
+    if Path(label_path).suffix in (".h5", ".hdf", ".hdf5") and len(label_keys) == 1:
+        return _lib.LABEL_WEIGHT, 0
+    census = torch.empty(_lib.LABEL_CENSUS_WORDS, dtype=torch.int32, device=labels_dev.device)
+    ops.label_census(labels_dev, census)
+    _, _, values = ops.label_census_values(census.cpu().numpy())
+    value = match_label_values(values, label_keys)[label_key]
+    return _lib.LABEL_MATCH, int(value)
+
+
+@torch.inference_mode()
+def score_labels(probs: torch.Tensor, labels_dev: torch.Tensor, mode: int, value: int, metric_fns: dict, want_labels: bool = False):
+    """(metrics dict, decoded int8 label volume on the device or None): one ``cvx_label_metrics`` pass per distinct threshold
+    (one in the shipped configs); the decoded labels, when asked for, are written by the first pass."""
+    if probs.numel() != labels_dev.numel():
+        raise ValueError(f"label volume {tuple(labels_dev.shape)} does not match the prediction {tuple(probs.shape)}")
+    probs = probs.contiguous()
+    y = torch.empty(labels_dev.shape, dtype=torch.int8, device=labels_dev.device) if want_labels else None
+    thresholds = _metric_thresholds(metric_fns) or [_F1_THRESHOLD]  # (no metrics: still decode the labels for the writer)
+    counts = torch.zeros(len(thresholds), 5, dtype=torch.int64, device=labels_dev.device)
+    for k, t in enumerate(thresholds):
+        ops.label_metrics(probs, labels_dev, counts[k], value=value, mode=mode, thr=t, y_out=y if k == 0 else None)
+    host = counts.cpu().tolist()
+    return metrics_from_counts(metric_fns, dict(zip(thresholds, host))), y
+
+
+def _load_one(dataset, records, i: int, on_the_fly: bool, label_key: str):
+    """Host side of tomogram i: (collated batch or None, raw data [D,H,W] when the encoder runs on it, the aux ``data`` the
+    prediction writer stores, the label volume as stored in its file)."""
+    from cryovit_amd.utils import load_data, read_label_volume
+
+    raw_labels = np.ascontiguousarray(read_label_volume(records[i].label_path, key=label_key))
+    if on_the_fly:
+        raw = np.ascontiguousarray(load_data(records[i].tomo_path, key="data")[0].squeeze(0), dtype=np.float32)
+        return None, raw, raw, raw_labels
+    item = dataset[i]
+    return collate_fn([item]), None, item.aux_data["data"], raw_labels
+
+
+@torch.inference_mode()
+def _probabilities(model, batch, raw, encoder, batch_size: int) -> torch.Tensor:
+    """fp32 probabilities [D, H, W] on the model's device: the model on the collated batch, or (raw data + encoder) the
+    features straight from the encoder into the head, as ``infer_model._predict_file`` does."""
+    if batch is not None:
+        return model.forward(batch)[0]
+    vol = torch.from_numpy(raw)
+    _, cl = encoder.features_from_raw(vol, batch_size, want_f16=False, want_cl=True)
+    hp, wp, *_ = encoder.engine.geometry(vol.shape[1], vol.shape[2])
+    return model.engine().forward(cl, vol.shape[0], hp, wp)["probs"]
+
+
+def run_evaluation(test_data: list[Path], test_labels: list[Path], labels: list[str], model_path: Path, result_dir: Path,
+                   visualize: bool = True, *, encoder=None, batch_size: int = 128, device: str | None = None) -> Path:
+    """Score the ``.model`` at ``model_path`` on ``test_data`` / ``test_labels`` (paired in order; ``labels``: the label names in
+    ascending value order).  Writes ``<result_dir>/results/<name>/<sample>.csv`` (CsvWriter) and, with ``visualize``,
+    ``<result_dir>/predictions/<name>/<sample>/<file>`` (TestPredictionWriter).  Returns the directory holding the CSV files
+    (the reference returns ``results/<name>.csv``, a file its CsvWriter never writes: DESIGN.md s.7).
+
+    ``encoder`` (extension, as in ``run_inference``): CryoVIT data files without ``dino_features`` are encoded on the fly."""
+    from cryovit_amd.datamodules import FileDataModule
+    from cryovit_amd.run.infer_model import _has_key
+    from cryovit_amd.types import BatchedModelResult
+    from cryovit_amd.utils import load_model
+
+    rank, _, world = world_info()
+    device = select_device(device)
+    model, model_type, model_name, label_key = load_model(model_path, device=device)
+    assert model is not None, "Loaded model is None."
+    assert label_key in labels, f"The label key {label_key} used to train the model is not in the provided labels."
+    cfg = compose("eval_model", [f"name={model_name}", f"label_key={label_key}", f"model={model_type.value}", "additional_keys=[data]",
+                                 "datamodule=file", f"paths.results_dir={Path(result_dir)}"])  # (the writers' paths interpolate it)
+    input_key = cfg.model.input_key if cfg.model.input_key == "dino_features" else None  # else: find available data instead
+    dataset_fn = instantiate(cfg.datamodule.dataset, input_key=input_key, label_key=label_key)
+    datamodule = FileDataModule(data_paths=test_data, data_labels=test_labels, labels=list(labels), dataset_fn=dataset_fn)
+    records = datamodule.data_files
+    if not records:
+        raise ValueError("No testing data provided.")
+    # the dataset loads the model input only (records without labels); labels are read raw and decoded on the GPU
+    dataset = dataset_fn([dataclasses.replace(fd, label_path=None, labels=None) for fd in records], train=False)
+    logging.info("Setup dataset.")
+
+    callbacks = {k: instantiate(c) for k, c in cfg.callbacks.items() if visualize or k != "test_pred_writer"}
+    file_cbs = [cb for k, cb in callbacks.items() if k != "csv_writer"]
+    csv_cb = callbacks["csv_writer"]
+    mine = shard_records(records, rank, world)
+
+    def load(i):
+        on_the_fly = encoder is not None and model.input_key == "dino_features" and not _has_key(records[i].tomo_path, "dino_features")
+        return _load_one(dataset, records, i, on_the_fly, label_key)
+
+    logging.info("Starting testing.")
+    rows = []
+    with ThreadPoolExecutor(max_workers=1) as reader:
+        nxt = reader.submit(load, mine[0]) if mine else None
+        for k, i in enumerate(mine):
+            batch, raw, aux, raw_labels = nxt.result()
+            nxt = reader.submit(load, mine[k + 1]) if k + 1 < len(mine) else None
+            fd = records[i]
+            probs = _probabilities(model, batch, raw, encoder, batch_size)
+            labels_dev = torch.from_numpy(raw_labels).to(probs.device)
+            mode, value = label_plan(labels_dev, fd.label_path, list(labels), label_key)
+            metrics, y = score_labels(probs, labels_dev, mode, value, model.metric_fns, want_labels=bool(file_cbs))
+            out = BatchedModelResult(num_tomos=1, samples=[fd.sample], tomo_names=[fd.tomo_path.name], split_id=None, data=[aux],
+                                     label=[y.cpu().numpy().astype(np.float32)] if y is not None else [],
+                                     preds=[probs.float().cpu().numpy()] if file_cbs else [], losses={}, metrics=metrics, aux_data=None)
+            logging.info("[rank %d] %s/%s %s", rank, fd.sample, fd.tomo_path.name, " ".join(f"{m}={v:.4f}" for m, v in metrics.items()))
+            for cb in file_cbs:
+                cb.on_test_batch_end(None, model, out, None, k)
+            out.data, out.label, out.preds = [], [], []
+            rows.append(out)
+    for out in gather_rows(rows, world):
+        if rank == 0:
+            csv_cb.on_test_batch_end(None, model, out, None, 0)
+    return Path(csv_cb.results_dir)

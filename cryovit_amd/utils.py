@@ -4,6 +4,8 @@ SURVEY.md s.8f row N2).  Same function names, arguments, return values and error
   read_hdf / read_mrc / read_tiff   l.115-183   -> (data, FileMetadata); HDF5 without a key: the dataset with the most unique values
   load_data                          l.186-225   any supported file -> float32-normalised [C, D, H, W] + the key used
   load_labels / _match_label_keys_to_data  l.228-301
+  read_label_volume / match_label_values   the same two without np.unique / np.where: the raw label volume, and the
+                                           value-to-name matching from the volume's distinct values (``cryovit evaluate``)
   load_files_from_path               l.304-330   directory (recursive) or .txt listing
   save_model / save_model_from_weights / load_model   l.336-468
 
@@ -268,6 +270,45 @@ def load_labels(file_path, label_keys: list[str], key: str | None) -> dict[str, 
     else:
         raise ValueError(_UNSUPPORTED.format(file_path))
     return labels
+
+
+def read_label_volume(file_path, key: str | None) -> np.ndarray:
+    """The label volume of ``load_labels`` exactly as stored (file dtype), without the ``np.unique`` of ``_metadata``: HDF5 reads
+    the dataset ``key`` (a missing key logs the reference's warning and raises ``KeyError``), .mrc / .tif the whole image."""
+    file_path = Path(file_path)
+    if not file_path.exists():
+        raise FileNotFoundError(f"File {file_path} does not exist.")
+    if file_path.suffix in (".h5", ".hdf", ".hdf5"):
+        opener = (lambda p: io.h5py.File(p, "r")) if io.HAVE_H5PY else io.H5Reader
+        with opener(file_path) as fh:
+            try:
+                obj = fh[key]
+            except KeyError:
+                logging.warning("Key %s not found in file %s. Attempting to read all keys instead.", key, file_path)
+                raise KeyError(key) from None
+            return obj.read() if isinstance(obj, io.H5Dataset) else obj[()]
+    if file_path.suffix in (".mrc", ".mrcs"):
+        return _read_mrc_array(file_path)
+    if file_path.suffix in (".tiff", ".tif"):
+        return _read_tiff_array(file_path)
+    raise ValueError(_UNSUPPORTED.format(file_path))
+
+
+def match_label_values(values: list, label_keys: list[str]) -> dict[str, Any]:
+    """label name -> label value, from the sorted distinct values of a label volume: the matching rules and errors of
+    ``_match_label_keys_to_data`` (a negative minimum is not counted, an unnamed 0 is background)."""
+    nunique = len(values)
+    adjusted = nunique if not values or values[0] >= 0 else nunique - 1
+    if adjusted == len(label_keys):
+        label_values = list(values)
+    elif adjusted == len(label_keys) + 1 and 0 in values:
+        label_values = [v for v in values if v > 0]
+    else:
+        raise ValueError(f"Number of unique values in label data ({nunique}) does not match number of provided label "
+                         f"keys ({len(label_keys)}).")
+    if len(label_values) != len(label_keys):
+        raise ValueError("zip() argument 2 is " + ("shorter" if len(label_keys) < len(label_values) else "longer") + " than argument 1")
+    return dict(zip(label_keys, label_values))
 
 
 def load_files_from_path(path: Path) -> list[Path]:

@@ -427,6 +427,33 @@ long cvx_pca_colormap_scratch_bytes(int D, int H, int W);
 int cvx_pca_colormap(const float* proj, const void* data, int is_u8, int D, int H, int W, int x_map, uint8_t* canvas, void* scratch,
                      long scratch_bytes, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Label decode and evaluation counts (`cryovit evaluate`, run/eval_model.py:run_evaluation).  labels: the label volume as read
+ * from its file, one of the CVX_LABEL_* dtypes, n elements; labels / probs / y_out 16-byte aligned.  Integer results only,
+ * combined with integer atomics (exact and order-independent: two calls give the same bits).
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_LABEL_I8 0
+#define CVX_LABEL_U8 1
+#define CVX_LABEL_I16 2
+#define CVX_LABEL_U16 3
+#define CVX_LABEL_I32 4
+#define CVX_LABEL_F32 5
+#define CVX_LABEL_BITMAP_BITS 65536                            /* widest value range the census resolves */
+#define CVX_LABEL_CENSUS_WORDS (4 + CVX_LABEL_BITMAP_BITS / 32)
+#define CVX_LABEL_NONINTEGER 1                                 /* census flag: a float32 value is NaN, inf or not an integer */
+#define CVX_LABEL_WIDE 2                                       /* census flag: max - min >= CVX_LABEL_BITMAP_BITS (or outside int32) */
+#define CVX_LABEL_MATCH 0  /* y = 1 where lab == value, -1 (ignored) where lab == -1, else (value == 0 ? 1 : 0): _match_label_keys_to_data */
+#define CVX_LABEL_WEIGHT 1 /* y = int8(lab), ignored where y <= -1: the single-key HDF branch of load_labels */
+
+/* census int32 [CVX_LABEL_CENSUS_WORDS] (written whole): [0] min, [1] max, [2] flags, [3] 0, then a bitmap of
+ * CVX_LABEL_BITMAP_BITS bits, word 4 + k/32 bit k%32 set iff the value min + k occurs.  The bitmap is left empty when a flag is
+ * set.  n == 0 gives min = INT_MAX > max = INT_MIN. */
+int cvx_label_census(const void* labels, int dtype, long n, int32_t* census, hipStream_t stream);
+/* counts uint64 [5] (+=) over the voxels with y > -1 (y decoded as `mode` says with `value`): sum y, sum [p >= thr],
+ * sum y [p >= thr], sum [p > thr], sum y [p > thr]; probs fp32 [n].  y_out (nullable) int8 [n] = y of every voxel. */
+int cvx_label_metrics(const float* probs, const void* labels, int dtype, long n, int mode, int value, float thr, uint64_t* counts,
+                      int8_t* y_out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
