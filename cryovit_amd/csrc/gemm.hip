@@ -16,6 +16,15 @@
 
 namespace cvx {
 
+// convt.hip: few-channel (1,2,2) transposed convolutions without LDS / K padding
+bool convt_small_eligible(const cvx_gemm_desc& d);
+int convt_small_dispatch(const cvx_gemm_desc& d, hipStream_t st);
+// conv_halo.hip: LDS-halo kernels for the full-resolution few-channel layers
+bool conv3_halo_eligible(const cvx_conv3d_desc& d);
+int conv3_halo_dispatch(const cvx_conv3d_desc& d, hipStream_t st);
+bool conv3_march_eligible(const cvx_conv3d_desc& d);
+int conv3_march_dispatch(const cvx_conv3d_desc& d, hipStream_t st);
+
 // ------------------------------------------------------------------------------------------------
 // Epilogues.  NREG orientation: store<NV>(n0, m, v) -- v[i] is output feature n0+i of row m.
 //             MREG orientation: store<NV>(m0, n, v) -- v[i] is row m0+i of output feature n.
@@ -66,6 +75,24 @@ __device__ __forceinline__ void load_vec(float* dst, const float* src) {
 // `rowstat` at fp32 [rows][2] = (rstd, -mu * rstd), written by cvx_rowstat_finalize / cvx_split_stream.
 __device__ __forceinline__ float ln_fold(float acc, float2 rs, float cs, float b) { return fmaf(acc, rs.x, fmaf(rs.y, cs, b)); }
 
+// prep() of every epilogue with per-column constants: bias, and in the gamma slot the LayerScale gain of the residual epilogues
+// or (LN fold) the column sums
+template <int NV, class E>
+__device__ __forceinline__ void load_consts(const E& e, VecCtx<NV>& c, long n0) {
+    load_vec<NV>(c.bias, e.bias + n0);
+    if constexpr (epi_is_ln<E>::value) load_vec<NV>(c.gamma, e.bias + e.cs_off + n0);
+    else if constexpr (epi_has_preload<E>::value || epi_has_hl<E>::value) load_vec<NV>(c.gamma, e.gamma + n0);
+}
+// shifted() of the row-major bf16 outputs (EpiBF16, EpiSwiGLUT): the same epilogue for rows [m_off, ...) of the problem when A
+// is passed advanced by m_off rows (tail launches)
+template <class E>
+static E shifted_rows(const E& e, long m_off) {
+    E r = e;
+    r.out = e.out + m_off * e.ldc; r.m_valid = e.m_valid - m_off;
+    if (e.rowstat) r.rowstat = e.rowstat + 2 * m_off;
+    return r;
+}
+
 // out[m][n] = bf16 | fp16 (act(acc + bias[n]));  ACT: 0 none, 1 GELU(erf);  HALF: fp16 operands and output (the head)
 template <int ACT, bool HALF = false, bool LN = false>
 struct EpiBF16 {
@@ -75,10 +102,7 @@ struct EpiBF16 {
     const float* rowstat = nullptr; long cs_off = 0;  // LN only
     template <int NV> using Ctx = VecCtx<NV>;
     template <int NV>
-    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const {
-        load_vec<NV>(c.bias, bias + n0);
-        if constexpr (LN) load_vec<NV>(c.gamma, bias + cs_off + n0);  // (the gamma slot carries the column sums)
-    }
+    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const { load_consts<NV>(*this, c, n0); }
     template <int NV>
     __device__ __forceinline__ void store(const Ctx<NV>& c, long n0, long m, const float* acc) const {
         if (m >= m_valid) return;
@@ -92,13 +116,7 @@ struct EpiBF16 {
         }
         store_bf16_chunked<NV, HALF>(out + m * ldc + n0, v, n0, n_valid);
     }
-    // the same epilogue for rows [m_off, ...) of the problem when A is passed advanced by m_off rows (tail launches)
-    EpiBF16 shifted(long m_off) const {
-        EpiBF16 e = *this;
-        e.out = out + m_off * ldc; e.m_valid = m_valid - m_off;
-        if (rowstat) e.rowstat = rowstat + 2 * m_off;
-        return e;
-    }
+    EpiBF16 shifted(long m_off) const { return shifted_rows(*this, m_off); }
     // LDS-staged row-major store (gemm256.h): 16 accumulators -> OUT16 packed bf16 outputs of column n0 >> OUT_SHIFT
     static constexpr int OUT16 = 16, OUT_SHIFT = 0;
     __device__ __forceinline__ void produce(const Ctx<16>& c, const float* acc, uint32_t (&w)[8], float2 rs = float2{0.f, 0.f}) const {
@@ -120,10 +138,7 @@ struct EpiSwiGLUT {
     const float* rowstat = nullptr; long cs_off = 0;  // LN only (see EpiBF16)
     template <int NV> using Ctx = VecCtx<NV>;
     template <int NV>
-    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const {
-        load_vec<NV>(c.bias, bias + n0);
-        if constexpr (LN) load_vec<NV>(c.gamma, bias + cs_off + n0);
-    }
+    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const { load_consts<NV>(*this, c, n0); }
     template <int NV>
     __device__ __forceinline__ void store(const Ctx<NV>& c, long n0, long m, const float* acc) const {
         static_assert(NV == 16, "SwiGLU epilogue needs 16 contiguous features per lane");
@@ -139,12 +154,7 @@ struct EpiSwiGLUT {
         }
         store_bf16_chunked<8>(out + m * ldc + (n0 >> 1), v, 0, 1);
     }
-    EpiSwiGLUT shifted(long m_off) const {
-        EpiSwiGLUT e = *this;
-        e.out = out + m_off * ldc; e.m_valid = m_valid - m_off;
-        if (rowstat) e.rowstat = rowstat + 2 * m_off;
-        return e;
-    }
+    EpiSwiGLUT shifted(long m_off) const { return shifted_rows(*this, m_off); }
     static constexpr int OUT16 = 8, OUT_SHIFT = 1;  // 8 gated outputs per 16 accumulators, output column = n0 / 2
     // Written on register-adjacent PAIRS (accumulator elements 2i, 2i+1 of one fragment): packed adds / multiplies, two exp2,
     // two rcp and one packed convert per two outputs.  Left to the SLP vectoriser the same arithmetic came out with the pairs
@@ -170,36 +180,24 @@ struct EpiSwiGLUT {
 };
 using EpiSwiGLU = EpiSwiGLUT<false>;
 
-// residual stream update in fp32:  x[m][n] += gamma[n] * (acc + bias[n])
 // x[m][n] (+)= gamma[n] * (acc + bias[n]) on the fp32 stream.  ACC = true: read-modify-write (LayerScale + residual);
 // ACC = false: plain fp32 output (x is only written -- Hiera's projected shortcut, the FPN lateral convs)
 template <bool ACC>
 struct EpiResidT {
     static constexpr bool ACCUM = ACC;
     float* x; long ldx; const float* bias; const float* gamma; long m_valid, n_valid;
-#ifdef CVX_LN_EMIT_PROTO
-    uint16_t* emit_xb = nullptr; long emit_ldb = 0;  // timing prototype (tools/bench_ln_emit.py): bf16 copy of the updated x
-    float* emit_part = nullptr; long emit_rows = 0;  // ... and row partial sums P[4 * N tiles][emit_rows][2]
-#endif
     template <int NV> using Ctx = VecCtx<NV>;
     template <int NV>
-    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const {
-        load_vec<NV>(c.bias, bias + n0);
-        load_vec<NV>(c.gamma, gamma + n0);
-    }
-    // the residual values are PRE-LOADED for a batch of output columns before any of them is stored: issued one after
-    // the other, each load -> add -> store round trip exposed a full HBM latency (32 per lane per tile: the epilogue
-    // took as long as the whole K loop of the proj GEMM -- tools/stamp_gemm_coarse.py)
+    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const { load_consts<NV>(*this, c, n0); }
     EpiResidT shifted(long m_off) const {
         EpiResidT r = *this;
         r.x = x + m_off * ldx;
         r.m_valid = m_valid - m_off;
-#ifdef CVX_LN_EMIT_PROTO
-        if (r.emit_xb) r.emit_xb = emit_xb + m_off * emit_ldb;
-        if (r.emit_part) r.emit_part = emit_part + m_off * 2;
-#endif
         return r;
     }
+    // the residual values are PRE-LOADED for a batch of output columns before any of them is stored: issued one after
+    // the other, each load -> add -> store round trip exposed a full HBM latency (32 per lane per tile: the epilogue
+    // took as long as the whole K loop of the proj GEMM -- tools/stamp_gemm_coarse.py)
     static constexpr bool HAS_PRELOAD = true;
     template <int NV> struct Pre { float4 x[NV / 4]; };
     template <int NV>
@@ -244,10 +242,7 @@ struct EpiResidHL {
     uint16_t* xh; uint16_t* xl; long ldx; const float* bias; const float* gamma; float* part; long part_rows; long m_valid, n_valid;
     template <int NV> using Ctx = VecCtx<NV>;
     template <int NV>
-    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const {
-        load_vec<NV>(c.bias, bias + n0);
-        load_vec<NV>(c.gamma, gamma + n0);
-    }
+    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const { load_consts<NV>(*this, c, n0); }
     EpiResidHL shifted(long m_off) const {
         EpiResidHL r = *this;
         r.xh = xh + m_off * ldx; r.xl = xl + m_off * ldx; r.part = part + m_off * 2; r.m_valid = m_valid - m_off;
@@ -295,7 +290,7 @@ struct EpiPatch {
     float* x; long ldx; const float* bias; const float* pos; long ldpos; int npatch, ntp, tok0; long m_valid, n_valid;
     template <int NV> using Ctx = VecCtx<NV>;
     template <int NV>
-    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const { load_vec<NV>(c.bias, bias + n0); }
+    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const { load_consts<NV>(*this, c, n0); }
     template <int NV>
     __device__ __forceinline__ void store(const Ctx<NV>& c, long n0, long m, const float* acc) const {
         if (m >= m_valid) return;
@@ -376,7 +371,7 @@ struct EpiConvT {
     int up_z = 0;  // 1: kernel = stride = (2,2,2) (UNet3D's upconv, unet3d.py:166-170): n = ((iz*2+i)*2+j)*Cout + o, output [2D][2H][2W][Cout]
     template <int NV> using Ctx = VecCtx<NV>;
     template <int NV>
-    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const { load_vec<NV>(c.bias, bias + n0); }
+    __device__ __forceinline__ void prep(Ctx<NV>& c, long n0) const { load_consts<NV>(*this, c, n0); }
     template <int NV>
     __device__ __forceinline__ void store(const Ctx<NV>& c, long n0, long m, const float* acc) const {
         if (m >= m_valid) return;
@@ -536,8 +531,6 @@ __global__ __launch_bounds__(G256_THREADS) void k_gemm256p_mreg(const uint16_t* 
 }
 
 // tuning switches (cvx_set_option): A/B the tile kernels and pipeline schedules inside ONE process
-static std::atomic<int> g_resid_stagger{0};  // cycles between the XCDs' start offsets in the residual GEMMs ("gemm_resid_stagger")
-static std::atomic<int> g_resid_reverse{0};  // residual GEMMs walk their tile sequence from the end (A/B: "gemm_resid_reverse")
 static std::atomic<int> g_tile_group_l_host{8};  // host copy of g_tile_group_l (the persistent kernel takes it as an argument)
 static std::atomic<int> g_use_gemm256{1}, g_gemm256_variant{9}, g_gemm_stagger{0};  // 9 = persistent (gemm256p.h)  // stagger: measured no gain (tools/bench_gemm.py 5 vs 1005)
 template <class Epi> static constexpr int epilogue_cycles() { return 12000; }       // bf16 store epilogues (stamped)
@@ -560,39 +553,70 @@ __global__ __launch_bounds__(G4W_THREADS) void k_gemm4w(const uint16_t* A, long 
 }
 #endif
 
+// The one place that launches a GEMM-family kernel: dynamic-LDS limit, launch, error check.
+template <class... P, class... Args>
+static int launch_kernel(void (*k)(P...), int threads, int lds_bytes, int grid, hipStream_t st, const Args&... args) {
+    CVX_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds_bytes, st, args...);
+    return cvx_check_launch();
+}
+
+// Tile counts of an M x n_pad problem.  NREG: the features run along the tile's R side (BR), the rows along L; MREG: swapped.
+struct Tiles { int n, m; };
+struct Tile256 { static constexpr int BR = 256, BL = 256; };
+template <class Cfg, bool MREG = false>
+static Tiles tile_counts(long M, long Npad) {
+    constexpr int BN = MREG ? Cfg::BL : Cfg::BR, BM = MREG ? Cfg::BR : Cfg::BL;
+    return {(int)(Npad / BN), (int)((M + BM - 1) / BM)};
+}
+
+// plain GEMM on the small tiles (gemm_core.h)
+template <class Cfg, bool MREG = false, class Epi>
+static int launch_tile(const uint16_t* A, long lda, const uint16_t* Wt, long ldw, long M, long Npad, long Kpad, const Epi& epi,
+                       hipStream_t st) {
+    const Tiles t = tile_counts<Cfg, MREG>(M, Npad);
+    if constexpr (MREG) return launch_kernel(k_gemm_mreg<Cfg, Epi>, GEMM_THREADS, Cfg::LDS_BYTES, t.n * t.m, st, A, lda, Wt, ldw, (int)(Kpad / BK), t.n, t.m, epi);
+    else return launch_kernel(k_gemm_nreg<Cfg, Epi>, GEMM_THREADS, Cfg::LDS_BYTES, t.n * t.m, st, A, lda, Wt, ldw, (int)(Kpad / BK), t.n, t.m, epi);
+}
+
 static bool use_gemm256(long M, long Npad, long Kpad) {
     return g_use_gemm256 && Npad % 256 == 0 && Kpad % BK == 0 && Kpad / BK >= 4 && M >= 1024;
+}
+
+// CUs of the current device rounded down to a multiple of 8, so every XCD gets the same number of persistent workgroups
+// (cached per DEVICE: a process may drive several GPUs, one volume per stream each)
+static int device_cus(int* n_cu) {
+    static std::atomic<int> n_cu_of[64];
+    int dev = 0;
+    CVX_HIP(hipGetDevice(&dev));
+    *n_cu = dev >= 0 && dev < 64 ? n_cu_of[dev].load() : 0;
+    if (!*n_cu) {
+        int n = 0;
+        CVX_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        *n_cu = n >= 8 ? n / 8 * 8 : 8;
+        if (dev >= 0 && dev < 64) n_cu_of[dev] = *n_cu;
+    }
+    return 0;
 }
 
 template <class Epi, bool MREG>
 static int launch_256(const uint16_t* A, long lda, const uint16_t* Wt, long ldw, long M, long Npad, long Kpad, const Epi& epi,
                       hipStream_t st) {
-    const int tiles_n = (int)(Npad / 256), tiles_m = (int)((M + 255) / 256);
+    const Tiles t = tile_counts<Tile256>(M, Npad);
+    const int ntiles = t.n * t.m, nk = (int)(Kpad / BK);
 #ifdef CVX_ABLATION
     if (g_use_gemm256 == 2) {  // one-wave-per-SIMD tile (gemm4w.h)
         auto k4 = g_gemm256_variant == 1 ? k_gemm4w<Epi, MREG, 1> : g_gemm256_variant == 2 ? k_gemm4w<Epi, MREG, 2> : k_gemm4w<Epi, MREG, 0>;
-        CVX_HIP(hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, G4W_LDS_BYTES));
-        hipLaunchKernelGGL(k4, dim3(tiles_n * tiles_m), dim3(G4W_THREADS), G4W_LDS_BYTES, st, A, lda, Wt, ldw, (int)(Kpad / G4W_KS),
-                           tiles_n, tiles_m, epi);
-        return cvx_check_launch();
+        return launch_kernel(k4, G4W_THREADS, G4W_LDS_BYTES, ntiles, st, A, lda, Wt, ldw, (int)(Kpad / G4W_KS), t.n, t.m, epi);
     }
 #endif
     const int variant = g_gemm256_variant;
-    if constexpr ((!MREG && (epi_has_preload<Epi>::value || epi_has_produce<Epi>::value || epi_has_hl<Epi>::value)) || (MREG && epi_is_mreg<Epi>::value)) {
+    constexpr bool resid = epi_has_preload<Epi>::value || epi_has_hl<Epi>::value;
+    if constexpr ((!MREG && (resid || epi_has_produce<Epi>::value)) || (MREG && epi_is_mreg<Epi>::value)) {
         if (variant == 9 || variant == 29) {
-            // one workgroup per CU (128 KiB of LDS each), a multiple of 8 so every XCD gets the same number
-            // (per DEVICE: a process may drive several GPUs, one volume per stream each)
-            static std::atomic<int> n_cu_of[64];
-            int dev = 0;
-            CVX_HIP(hipGetDevice(&dev));
-            int n_cu = dev >= 0 && dev < 64 ? n_cu_of[dev].load() : 0;
-            if (!n_cu) {
-                int n = 0;
-                CVX_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-                n_cu = n >= 8 ? n / 8 * 8 : 8;
-                if (dev >= 0 && dev < 64) n_cu_of[dev] = n_cu;
-            }
-            const int ntiles = tiles_n * tiles_m;
+            // one workgroup per CU (128 KiB of LDS each)
+            int n_cu = 0;
+            if (int rc = device_cus(&n_cu)) return rc;
             const int grid = ntiles >= n_cu ? n_cu : (ntiles + 7) / 8 * 8;
             const bool full = M % 256 == 0 && epi.n_valid == Npad;
             void (*kp)(const uint16_t*, long, const uint16_t*, long, int, int, int, int, int, Epi);
@@ -604,11 +628,10 @@ static int launch_256(const uint16_t* A, long lda, const uint16_t* Wt, long ldw,
                 if (variant == 29) kp = k_gemm256p_nreg<Epi, true, true>;  // stamped (interior tiles only)
 #endif
             }
-            CVX_HIP(hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, G256P_LDS_BYTES));
-            hipLaunchKernelGGL(kp, dim3(grid), dim3(G256_THREADS), G256P_LDS_BYTES, st, A, lda, Wt, ldw, (int)(Kpad / BK), tiles_n, tiles_m,
-                               ((epi_has_preload<Epi>::value || epi_has_hl<Epi>::value) && g_resid_reverse ? -1 : 1) * (int)g_tile_group_l_host,
-                               ntiles > grid ? ((epi_has_preload<Epi>::value || epi_has_hl<Epi>::value) ? (int)g_resid_stagger : (int)g_gemm_stagger) : 0, epi);
-            return cvx_check_launch();
+            // The residual GEMMs start their XCDs together: a stagger shortens the epilogue to what ONE XCD's fabric port delivers
+            // and loses more at the ragged end; nor do they walk their tiles from the end (a negative group_l).
+            const int xcd_stagger = !resid && ntiles > grid ? (int)g_gemm_stagger : 0;
+            return launch_kernel(kp, G256_THREADS, G256P_LDS_BYTES, grid, st, A, lda, Wt, ldw, nk, t.n, t.m, (int)g_tile_group_l_host, xcd_stagger, epi);
         }
     }
     void (*k)(const uint16_t*, long, const uint16_t*, long, int, int, int, Epi, int);
@@ -632,13 +655,9 @@ static int launch_256(const uint16_t* A, long lda, const uint16_t* Wt, long ldw,
             default: k = k_gemm256_nreg<Epi, 0>; break;
         }
     }
-    CVX_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, G256_LDS_BYTES));
     // quarter of one tile's duration (~2800 cycles per K tile + epilogue), only when the launch has several rounds
-    const long nk = Kpad / BK;
-    const int stagger = (g_gemm_stagger && (long)tiles_n * tiles_m > 512) ? (int)((nk * 2800 + epilogue_cycles<Epi>()) / 4) : 0;
-    hipLaunchKernelGGL(k, dim3(tiles_n * tiles_m), dim3(G256_THREADS), G256_LDS_BYTES, st, A, lda, Wt, ldw, (int)nk, tiles_n, tiles_m,
-                       epi, stagger);
-    return cvx_check_launch();
+    const int stagger = (g_gemm_stagger && ntiles > 512) ? (int)(((long)nk * 2800 + epilogue_cycles<Epi>()) / 4) : 0;
+    return launch_kernel(k, G256_THREADS, G256_LDS_BYTES, ntiles, st, A, lda, Wt, ldw, nk, t.n, t.m, epi, stagger);
 }
 
 template <class E, class = void> struct epi_can_shift : std::false_type {};
@@ -646,64 +665,58 @@ template <class E> struct epi_can_shift<E, std::void_t<decltype(std::declval<con
 
 // Tail split: a 256-tile grid whose last round would keep only a few CUs busy (e.g. 3096 tiles = 12 rounds + 24 tiles for
 // the N = 1536 GEMMs of one 128-slice batch) is cut into a main launch of whole rounds and a tail launch over the remaining
-// M rows with 128x128 tiles (4x as many, quarter-size tiles: the tail costs ~0.3 of a round instead of a full one).
+// M rows with small tiles (4x or 8x as many: the tail costs ~0.3 of a round instead of a full one).
 static std::atomic<int> g_tail_split{2};  // 2: also for the residual epilogue with a short K loop (proj), which pays off since the tail runs on 64 x 128 tiles
-static std::atomic<int> g_tail_deep{1};  // cvx_set_option("gemm_tail_deep"): tails run on the multi-stage ring (0: the double-buffered tiles, for A/B)
-static std::atomic<int> g_tail_tile{1};  // tail launches: 1 = 64 x 128 tiles (twice the workgroups on the idle chip), 0 = 128 x 128
-static std::atomic<int> g_tail_max{128};  // (64 -> 128 in round 3: 281.26 -> 280.26 ms per tomogram; 0 = never: 282.89) largest last partial round (in 256 x 256 tiles) that is cut off into a tail launch ("gemm_tail_max")
-static long tail_split_rows(long M, long Npad, bool allow = true) {
+// largest last partial round (in 256 x 256 tiles) that is cut off into a tail launch
+// (64 -> 128 in round 3: 281.26 -> 280.26 ms per tomogram; never: 282.89)
+constexpr long TAIL_MAX_TILES = 128;
+static long tail_split_rows(long M, long Npad, bool allow) {
     const long tiles_n = Npad / 256, tiles_m = (M + 255) / 256, tiles = tiles_n * tiles_m, rem = tiles % 256;
-    if (!g_tail_split || !allow || tiles < 512 || rem == 0 || rem > g_tail_max) return M;
+    if (!allow || tiles < 512 || rem == 0 || rem > TAIL_MAX_TILES) return M;
     const long main_mtiles = (tiles - rem) / tiles_n;
     return main_mtiles > 0 ? main_mtiles * 256 : M;
 }
 
-template <class Cfg, class Epi>
-static int launch_nreg(const uint16_t* A, long lda, const uint16_t* Wt, long ldw, long M, long Npad, long Kpad,
-                       const Epi& epi, hipStream_t st) {
-    const int tiles_n = (int)(Npad / Cfg::BR), tiles_m = (int)((M + Cfg::BL - 1) / Cfg::BL);
-    auto k = k_gemm_nreg<Cfg, Epi>;
-    CVX_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES));
-    hipLaunchKernelGGL(k, dim3(tiles_n * tiles_m), dim3(GEMM_THREADS), Cfg::LDS_BYTES, st, A, lda, Wt, ldw,
-                       (int)(Kpad / BK), tiles_n, tiles_m, epi);
-    return cvx_check_launch();
+// The tail policy: how many rows the main 256-tile launch takes and which small tile runs the rest.
+enum class TailTile { RING_64x128, T64x128, T128x128 };
+struct TailPlan { long m_main; TailTile tile; };
+static TailPlan tail_plan(long M, long Npad, long Kpad, bool resid, bool mreg) {
+    // (the small tiles' fp32 read-modify-write epilogue is not LDS-staged: with a short K loop a tail on 128 x 128 tiles cost
+    //  more than the idle round it removes -- measured on the proj GEMM; on 64 x 128 tiles it pays off: g_tail_split == 2)
+    const int split = g_tail_split;
+    const long m_main = tail_split_rows(M, Npad, split && (!resid || Kpad >= 2048 || split == 2));
+    const long rows = M - m_main;
+    // The tail is a handful of tiles on an otherwise idle chip, one workgroup per CU at most: what it waits for is the DMA round
+    // trip of each K tile, so it gets the ring with 2-3 K tiles in flight (gemm_core.h, TileCfg STAGES; r03_tail_ring_ab.txt: 297.86
+    // ms per tomogram against 298.51 double-buffered, a 6-deep ring equal to the 4-deep one).  The residual GEMMs' tails only: 192
+    // workgroups.  For the qkv / w12 tails -- 288 / 512 workgroups of 128 x 128 -- a 128 x 256 tile on a 3-deep ring, one workgroup
+    // per CU, measured SLOWER than two double-buffered workgroups per CU: 34.5 / 36.1 us against 29.1 / 30.7; 64 x 128 tiles on a
+    // 3-deep ring, two per CU: +0.36 ms per tomogram.
+    if (resid && !mreg && (Npad / 64) * ((rows + 127) / 128) <= 256) return {m_main, TailTile::RING_64x128};
+    // 64 x 128 tiles: twice the workgroups on the idle chip (8 per 256 x 256 tile), as long as they fit in one round
+    if (rows / 256 * (Npad / 256) * 8 <= 256) return {m_main, TailTile::T64x128};
+    return {m_main, TailTile::T128x128};
 }
 
-// 256-tile launch with the tail split (NREG epilogues that can be re-based on a row offset)
-template <class Epi>
+// 256-tile launch with the tail split (epilogues that can be re-based on a row offset)
+template <class Epi, bool MREG = false>
 static int launch_256_split(const uint16_t* A, long lda, const uint16_t* Wt, long ldw, long M, long Npad, long Kpad, const Epi& epi,
                             hipStream_t st) {
     if constexpr (epi_can_shift<Epi>::value) {
-        // (the 128-tile kernel's fp32 read-modify-write epilogue is not LDS-staged: with a short K loop the tail would cost
-        //  more than the idle round it removes -- measured on the proj GEMM)
-        const long m_main = tail_split_rows(M, Npad, !(epi_has_preload<Epi>::value || epi_has_hl<Epi>::value) || Kpad >= 2048 || g_tail_split == 2);
-        if (m_main < M) {
-            int rc = launch_256<Epi, false>(A, lda, Wt, ldw, m_main, Npad, Kpad, epi, st);
-            if (rc) return rc;
-            // the tail is a handful of tiles on an otherwise idle chip, one workgroup per CU at most: what it waits for is the DMA
-            // round trip of each K tile, so it gets the ring with 2-3 K tiles in flight (gemm_core.h, TileCfg STAGES)
-            const long rows = M - m_main;
-            if (g_tail_deep) {
-                // (the residual GEMMs' tails only: 192 workgroups.  For the qkv / w12 tails -- 288 / 512 workgroups of 128 x 128 -- a
-                //  128 x 256 tile on a 3-deep ring, one workgroup per CU, measured SLOWER than two double-buffered workgroups per
-                //  CU: 34.5 / 36.1 us against 29.1 / 30.7; 64 x 128 tiles on a 3-deep ring, two per CU: +0.36 ms per tomogram)
-                if constexpr (epi_has_preload<Epi>::value || epi_has_hl<Epi>::value) {
-                    if ((Npad / 64) * ((rows + 127) / 128) <= 256) {
-                        return launch_nreg<TileCfg<64, 128, 1, 4>>(A + m_main * lda, lda, Wt, ldw, rows, Npad, Kpad, epi.shifted(m_main), st);
-                    }
-                }
-            }
-            // (before the ring: more, smaller workgroups finish sooner)
-            if (g_tail_tile == 2 && (M - m_main) / 256 * (Npad / 256) * 16 <= 1024)
-                // 64 x 64 tiles, 32 KB of LDS each: three workgroups per CU.  The tail is LATENCY-bound (one K tile of look-ahead, a
-                // K tile per DMA round trip): co-resident workgroups overlap each other's waits
-                return launch_nreg<TileCfg<64, 64, 1>>(A + m_main * lda, lda, Wt, ldw, M - m_main, Npad, Kpad, epi.shifted(m_main), st);
-            if (g_tail_tile && (M - m_main) / 256 * (Npad / 256) * 8 <= 256)  // (8 small tiles per 256 x 256 tile: one round at most)
-                return launch_nreg<TileCfg<64, 128, 1>>(A + m_main * lda, lda, Wt, ldw, M - m_main, Npad, Kpad, epi.shifted(m_main), st);
-            return launch_nreg<TileCfg<128, 128, 2>>(A + m_main * lda, lda, Wt, ldw, M - m_main, Npad, Kpad, epi.shifted(m_main), st);
+        constexpr bool resid = epi_has_preload<Epi>::value || epi_has_hl<Epi>::value;
+        const TailPlan p = tail_plan(M, Npad, Kpad, resid, MREG);
+        if (p.m_main < M) {
+            if (int rc = launch_256<Epi, MREG>(A, lda, Wt, ldw, p.m_main, Npad, Kpad, epi, st)) return rc;
+            const uint16_t* At = A + p.m_main * lda;
+            const long rows = M - p.m_main;
+            const Epi et = epi.shifted(p.m_main);
+            if constexpr (resid && !MREG)
+                if (p.tile == TailTile::RING_64x128) return launch_tile<TileCfg<64, 128, 1, 4>>(At, lda, Wt, ldw, rows, Npad, Kpad, et, st);
+            if (p.tile == TailTile::T64x128) return launch_tile<TileCfg<64, 128, 1>, MREG>(At, lda, Wt, ldw, rows, Npad, Kpad, et, st);
+            return launch_tile<TileCfg<128, 128, 2>, MREG>(At, lda, Wt, ldw, rows, Npad, Kpad, et, st);
         }
     }
-    return launch_256<Epi, false>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
+    return launch_256<Epi, MREG>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
 }
 
 template <class Epi>
@@ -711,69 +724,38 @@ static int dispatch_nreg(const uint16_t* A, long lda, const uint16_t* Wt, long l
                          const Epi& epi, hipStream_t st) {
     if (Kpad % BK) return cvx_fail("gemm: K must be padded to a multiple of 64");
     if (use_gemm256(M, Npad, Kpad)) return launch_256_split(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
-    if (Npad % 128 == 0) return launch_nreg<TileCfg<128, 128, 2>>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
-    if (Npad % 64 == 0) return launch_nreg<TileCfg<64, 256, 1>>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
+    if (Npad % 128 == 0) return launch_tile<TileCfg<128, 128, 2>>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
+    if (Npad % 64 == 0) return launch_tile<TileCfg<64, 256, 1>>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
     if constexpr (!epi_has_hl<Epi>::value) {  // (the hi/lo residual epilogue works on 64-column slots)
-        if (Npad % 32 == 0) return launch_nreg<TileCfg<32, 256, 1>>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
-        if (Npad % 16 == 0) return launch_nreg<TileCfg<16, 256, 1>>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
+        if (Npad % 32 == 0) return launch_tile<TileCfg<32, 256, 1>>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
+        if (Npad % 16 == 0) return launch_tile<TileCfg<16, 256, 1>>(A, lda, Wt, ldw, M, Npad, Kpad, epi, st);
     }
     return cvx_fail("gemm: N must be padded to a multiple of 16 (64 for the hi/lo residual epilogue)");
 }
 
 template <class Cfg, class Epi>
 static int launch_conv3(const cvx_conv3d_desc& d, const Epi& epi, hipStream_t st) {
-    const long M = (long)d.D * d.H * d.W;
-    const int tiles_n = (int)(d.n_pad / Cfg::BR), tiles_m = (int)((M + Cfg::BL - 1) / Cfg::BL);
-    auto k = k_conv3_nreg<Cfg, Epi>;
-    CVX_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES));
-    hipLaunchKernelGGL(k, dim3(tiles_n * tiles_m), dim3(GEMM_THREADS), Cfg::LDS_BYTES, st, (const uint16_t*)d.in,
-                       (const uint16_t*)d.zero_page, d.C, d.D, d.H, d.W, d.dil, (const uint16_t*)d.w, (long)d.k_pad,
-                       (int)(d.k_pad / BK), tiles_n, tiles_m, epi);
-    return cvx_check_launch();
+    const Tiles t = tile_counts<Cfg>((long)d.D * d.H * d.W, d.n_pad);
+    return launch_kernel(k_conv3_nreg<Cfg, Epi>, GEMM_THREADS, Cfg::LDS_BYTES, t.n * t.m, st, (const uint16_t*)d.in, (const uint16_t*)d.zero_page,
+                         d.C, d.D, d.H, d.W, d.dil, (const uint16_t*)d.w, (long)d.k_pad, (int)(d.k_pad / BK), t.n, t.m, epi);
 }
 
 template <class Cfg, class Epi>
 static int launch_pool2(const cvx_conv3d_desc& d, int cshift, const Epi& epi, hipStream_t st) {
     const int Do = d.D / 2, Ho = d.H / 2, Wo = d.W / 2;
-    const long M = (long)Do * Ho * Wo;
-    const int tiles_n = (int)(d.n_pad / Cfg::BR), tiles_m = (int)((M + Cfg::BL - 1) / Cfg::BL);
-    auto k = k_pool2_nreg<Cfg, Epi>;
-    CVX_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES));
-    hipLaunchKernelGGL(k, dim3(tiles_n * tiles_m), dim3(GEMM_THREADS), Cfg::LDS_BYTES, st, (const uint16_t*)d.in, (const uint16_t*)d.zero_page,
-                       cshift, Do, Ho, Wo, (const uint16_t*)d.w, (long)d.k_pad, (int)(d.k_pad / BK), tiles_n, tiles_m, epi);
-    return cvx_check_launch();
+    const Tiles t = tile_counts<Cfg>((long)Do * Ho * Wo, d.n_pad);
+    return launch_kernel(k_pool2_nreg<Cfg, Epi>, GEMM_THREADS, Cfg::LDS_BYTES, t.n * t.m, st, (const uint16_t*)d.in, (const uint16_t*)d.zero_page,
+                         cshift, Do, Ho, Wo, (const uint16_t*)d.w, (long)d.k_pad, (int)(d.k_pad / BK), t.n, t.m, epi);
 }
 
 }  // namespace cvx
 
-namespace cvx {  // convt.hip: few-channel (1,2,2) transposed convolutions without LDS / K padding
-bool convt_small_eligible(const cvx_gemm_desc& d);
-int convt_small_dispatch(const cvx_gemm_desc& d, hipStream_t st);
-}
-
 using namespace cvx;
-
-extern std::atomic<int> g_attn_variant, g_attn_xcd_remap, g_attn_mfma_prio, g_attn_half_tile;  // attention.hip
-extern std::atomic<int> g_ln_policy;                         // norm.hip
-extern std::atomic<int> g_win_attn_prefetch, g_win_attn_x32; // hiera.hip
 
 extern "C" int cvx_debug_read_gemm256(unsigned long long* out32) {
     CVX_HIP(hipMemcpyFromSymbol(out32, HIP_SYMBOL(cvx::g_gemm256_dbg), sizeof(unsigned long long) * 32));
     return 0;
 }
-#ifdef CVX_LN_EMIT_PROTO
-static uint16_t* g_emit_xb_host = nullptr;
-static long g_emit_ldb_host = 0;
-static float* g_emit_part_host = nullptr;
-static long g_emit_rows_host = 0;
-extern "C" int cvx_debug_set_emit(void* xb, long ldb, float* part, long rows) {  // timing prototype only (tools/bench_ln_emit.py)
-    g_emit_xb_host = (uint16_t*)xb;
-    g_emit_ldb_host = ldb;
-    g_emit_part_host = part;
-    g_emit_rows_host = rows;
-    return 0;
-}
-#endif
 extern "C" int cvx_debug_read_gemm256p(unsigned long long* out96) {
     CVX_HIP(hipMemcpyFromSymbol(out96, HIP_SYMBOL(cvx::g_gemm256p_dbg), sizeof(unsigned long long) * 96));
     return 0;
@@ -783,6 +765,10 @@ extern "C" int cvx_debug_read_gemm256p(unsigned long long* out96) {
 static std::atomic<int> g_conv_halo{2};
 static std::atomic<int> g_convt_small{1};  // dedicated kernel for the head's 16->8 and 32->32 transposed convolutions (0: GEMM tile)
 static std::atomic<int> g_conv_wide{1};  // 192-wide implicit-GEMM tile for C_out % 192 == 0 (0: three 64-wide tiles)
+// the other files' switches
+extern std::atomic<int> g_attn_variant, g_attn_xcd_remap, g_attn_mfma_prio, g_attn_half_tile;  // attention.hip
+extern std::atomic<int> g_ln_policy;                         // norm.hip
+extern std::atomic<int> g_win_attn_prefetch, g_win_attn_x32; // hiera.hip
 
 extern "C" int cvx_set_option(const char* name, int value) {
     if (!name) return cvx_fail("set_option: null name");
@@ -809,19 +795,6 @@ extern "C" int cvx_set_option(const char* name, int value) {
         if (!one_of({0, 1, 2})) return cvx_fail("set_option: gemm_tail_split is 0 (off), 1 (on; residual epilogues only for K >= 2048) or 2 (always)");
         g_tail_split = value;
     }
-    else if (!strcmp(name, "gemm_tail_max")) {
-        if (value < 0 || value > 255) return cvx_fail("set_option: gemm_tail_max is a tile count in [0, 255]");
-        g_tail_max = value;
-    }
-    else if (!strcmp(name, "gemm_tail_tile")) {
-        if (!one_of({0, 1, 2})) return cvx_fail("set_option: gemm_tail_tile is 0 (128 x 128), 1 (64 x 128) or 2 (64 x 64 tiles)");
-        g_tail_tile = value;
-    }
-    else if (!strcmp(name, "gemm_resid_reverse")) g_resid_reverse = value != 0;
-    else if (!strcmp(name, "gemm_resid_stagger")) {
-        if (value < 0 || value > 1000000) return cvx_fail("set_option: gemm_resid_stagger is a cycle count in [0, 1e6]");
-        g_resid_stagger = value;
-    }
     else if (!strcmp(name, "conv_halo")) {
         if (!one_of({0, 2}) && !(abl && value == 1))
             return cvx_fail("set_option: conv_halo is 0 (implicit GEMM) or 2 (z-marching ring); 1 (the round-1 tile-halo kernel) needs a -DCVX_ABLATION build");
@@ -843,7 +816,6 @@ extern "C" int cvx_set_option(const char* name, int value) {
             return cvx_fail("set_option: unknown attn_variant (ablation variants need a -DCVX_ABLATION build)");
         g_attn_variant = value;
     } else if (!strcmp(name, "attn_xcd_remap")) g_attn_xcd_remap = value != 0;
-    else if (!strcmp(name, "gemm_tail_deep")) g_tail_deep = value != 0;  // 0: double-buffered tail tiles (A/B); a 6-deep ring measured equal to the 4-deep one
     else if (!strcmp(name, "attn_mfma_prio")) g_attn_mfma_prio = value & 3;
     else if (!strcmp(name, "attn_half_tile")) g_attn_half_tile = value != 0;
     else if (!strcmp(name, "tile_group_l")) {
@@ -882,35 +854,12 @@ extern "C" int cvx_gemm_bf16(const cvx_gemm_desc* d, hipStream_t st) {
     return gemm_dispatch(d, st);
 }
 
-// V^T GEMM (MREG orientation): whole rounds on the persistent 256 tile, the rest (or a small problem) on 64 x 128 / 128 x 128 tiles
-template <class E>
-static int dispatch_vt(const cvx_gemm_desc* d, const uint16_t* A, const uint16_t* W, const E& e, hipStream_t st) {
-    using Cfg = TileCfg<128, 128, 2>;
-    auto tail128 = [&](const uint16_t* a, long m, const E& ev) {
-        const int tiles_n = (int)(d->n_pad / Cfg::BL), tiles_m = (int)((m + Cfg::BR - 1) / Cfg::BR);
-        auto k = k_gemm_mreg<Cfg, E>;
-        CVX_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES));
-        hipLaunchKernelGGL(k, dim3(tiles_n * tiles_m), dim3(GEMM_THREADS), Cfg::LDS_BYTES, st, a, d->lda, W, d->ldw,
-                           (int)(d->k_pad / BK), tiles_n, tiles_m, ev);
-        return cvx_check_launch();
-    };
-    if (use_gemm256(d->m, d->n_pad, d->k_pad)) {
-        const long m_main = tail_split_rows(d->m, d->n_pad);
-        int rc = launch_256<E, true>(A, d->lda, W, d->ldw, m_main, d->n_pad, d->k_pad, e, st);
-        if (rc || m_main == d->m) return rc;
-        if (g_tail_tile && (d->m - m_main) / 256 * (d->n_pad / 256) * 8 <= 256) {
-            using CfgS = TileCfg<64, 128, 1>;
-            const long m = d->m - m_main;
-            const int tiles_n = (int)(d->n_pad / CfgS::BL), tiles_m = (int)((m + CfgS::BR - 1) / CfgS::BR);
-            auto k = k_gemm_mreg<CfgS, E>;
-            CVX_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, CfgS::LDS_BYTES));
-            hipLaunchKernelGGL(k, dim3(tiles_n * tiles_m), dim3(GEMM_THREADS), CfgS::LDS_BYTES, st, A + m_main * d->lda, d->lda, W, d->ldw,
-                               (int)(d->k_pad / BK), tiles_n, tiles_m, e.shifted(m_main));
-            return cvx_check_launch();
-        }
-        return tail128(A + m_main * d->lda, d->m - m_main, e.shifted(m_main));
-    }
-    return tail128(A, d->m, e);
+// Runtime flags -> template arguments: lift(f, b1, b2, ...) calls f(std::bool_constant<b1>{}, std::bool_constant<b2>{}, ...)
+template <class F>
+static int lift(F&& f) { return f(); }
+template <class F, class... B>
+static int lift(F&& f, bool b, B... rest) {
+    return b ? lift([&](auto... t) { return f(std::true_type{}, t...); }, rest...) : lift([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
 }
 
 static int gemm_dispatch(const cvx_gemm_desc* d, hipStream_t st) {
@@ -919,100 +868,54 @@ static int gemm_dispatch(const cvx_gemm_desc* d, hipStream_t st) {
     if (d->m <= 0) return 0;
     if (!A || !W || !d->out || !d->bias) return cvx_fail("gemm: a, w, out and bias must be device pointers");
     if (d->dtype != CVX_DTYPE_BF16 && d->dtype != CVX_DTYPE_F16) return cvx_fail("gemm: unknown dtype");
-    if (d->dtype == CVX_DTYPE_F16 && d->epilogue != CVX_EPI_BF16 && d->epilogue != CVX_EPI_BF16_GELU && d->epilogue != CVX_EPI_CONVT)
+    const bool f16 = d->dtype == CVX_DTYPE_F16, ln = d->ln_rowstat != nullptr;
+    if (f16 && d->epilogue != CVX_EPI_BF16 && d->epilogue != CVX_EPI_BF16_GELU && d->epilogue != CVX_EPI_CONVT)
         return cvx_fail("gemm: fp16 operands are built for the plain / GELU / ConvT epilogues (the segmentation head)");
+    uint16_t* out16 = (uint16_t*)d->out;
+    const long cs_off = ln ? d->n_pad : 0;  // LN fold: bias = [b' | cs], n_pad floats apart
+    auto nreg = [&](const auto& e) { return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st); };
     switch (d->epilogue) {
-        case CVX_EPI_BF16: {
-            if (d->ln_rowstat) {
-                EpiBF16<0, false, true> e{(uint16_t*)d->out, d->ldc, d->bias, d->m, d->n, d->ln_rowstat, d->n_pad};
-                return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-            }
-            if (d->dtype == CVX_DTYPE_F16) {
-                EpiBF16<0, true> e{(uint16_t*)d->out, d->ldc, d->bias, d->m, d->n};
-                return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-            }
-            EpiBF16<0> e{(uint16_t*)d->out, d->ldc, d->bias, d->m, d->n};
-            return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-        }
-        case CVX_EPI_BF16_GELU: {
-            if (d->ln_rowstat) {
-                EpiBF16<1, false, true> e{(uint16_t*)d->out, d->ldc, d->bias, d->m, d->n, d->ln_rowstat, d->n_pad};
-                return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-            }
-            if (d->dtype == CVX_DTYPE_F16) {
-                EpiBF16<1, true> e{(uint16_t*)d->out, d->ldc, d->bias, d->m, d->n};
-                return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-            }
-            EpiBF16<1> e{(uint16_t*)d->out, d->ldc, d->bias, d->m, d->n};
-            return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-        }
-        case CVX_EPI_SWIGLU: {
+        case CVX_EPI_BF16:
+        case CVX_EPI_BF16_GELU:  // (the LN fold takes bf16 operands)
+            return lift([&](auto gelu, auto half, auto lnf) {
+                if constexpr (half() && lnf()) return -1;  // (never called: not a kernel of the library)
+                else return nreg(EpiBF16<gelu() ? 1 : 0, half(), lnf()>{out16, d->ldc, d->bias, d->m, d->n, d->ln_rowstat, cs_off});
+            }, d->epilogue == CVX_EPI_BF16_GELU, f16 && !ln, ln);
+        case CVX_EPI_SWIGLU:
             if (d->n_pad % 128) return cvx_fail("gemm: SwiGLU needs N padded to 128");
-            if (d->ln_rowstat) {
-                EpiSwiGLUT<true> e{(uint16_t*)d->out, d->ldc, d->bias, d->m, d->n, d->ln_rowstat, d->n_pad};
+            return lift([&](auto lnf) {
+                const EpiSwiGLUT<lnf()> e{out16, d->ldc, d->bias, d->m, d->n, d->ln_rowstat, cs_off};
                 if (use_gemm256(d->m, d->n_pad, d->k_pad)) return launch_256_split(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-                return launch_nreg<TileCfg<128, 128, 2>>(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-            }
-            EpiSwiGLU e{(uint16_t*)d->out, d->ldc, d->bias, d->m, d->n};
-            if (use_gemm256(d->m, d->n_pad, d->k_pad)) return launch_256_split(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-            return launch_nreg<TileCfg<128, 128, 2>>(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-        }
-        case CVX_EPI_RESID: {
-            if (!d->out || !d->bias || !d->gamma) return cvx_fail("gemm: the residual epilogue needs out, bias and gamma (LayerScale)");
-            EpiResid e{(float*)d->out, d->ldc, d->bias, d->gamma, d->m, d->n};
-#ifdef CVX_LN_EMIT_PROTO
-            if (!g_emit_xb_host) return cvx_fail("emit prototype: cvx_debug_set_emit first (the store counts of this build assume the emission)");
-            e.emit_xb = g_emit_xb_host; e.emit_ldb = g_emit_ldb_host;
-            if (!g_emit_part_host) return cvx_fail("emit prototype: the partial-sum buffer is required too");
-            e.emit_part = g_emit_part_host; e.emit_rows = g_emit_rows_host;
-#endif
-            return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-        }
-        case CVX_EPI_RESID_HL: {
-            if (!d->out || !d->out2 || !d->bias || !d->gamma || !d->stat_part)
+                return launch_tile<TileCfg<128, 128, 2>>(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
+            }, ln);
+        case CVX_EPI_RESID:
+            if (!d->gamma) return cvx_fail("gemm: the residual epilogue needs out, bias and gamma (LayerScale)");
+            return nreg(EpiResid{(float*)d->out, d->ldc, d->bias, d->gamma, d->m, d->n});
+        case CVX_EPI_RESID_HL:
+            if (!d->out2 || !d->gamma || !d->stat_part)
                 return cvx_fail("gemm: the hi/lo residual epilogue needs out (hi), out2 (lo), bias, gamma and stat_part");
             if (d->n % 64 || d->n_pad % 64 || d->n > d->n_pad || d->ldc < d->n)
                 return cvx_fail("gemm: the hi/lo residual epilogue needs N a multiple of 64 (64-column statistics slots), N <= n_pad, ldc >= N");
             if (d->stat_rows < (d->m + 255) / 256 * 256) return cvx_fail("gemm: stat_rows must cover M rounded up to 256 rows");
-            EpiResidHL e{(uint16_t*)d->out, (uint16_t*)d->out2, d->ldc, d->bias, d->gamma, d->stat_part, d->stat_rows, d->m, d->n};
-            return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-        }
-        case CVX_EPI_F32: {
-            if (!d->out || !d->bias || !d->gamma) return cvx_fail("gemm: the fp32 epilogue needs out, bias and gamma");
-            EpiF32 e{(float*)d->out, d->ldc, d->bias, d->gamma, d->m, d->n};
-            return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-        }
-        case CVX_EPI_PATCH: {
-            EpiPatch e{(float*)d->out, d->ldc, d->bias, d->pos, d->ldpos, d->npatch, d->ntp, d->tok0, d->m, d->n};
-            return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-        }
-        case CVX_EPI_VT: {
+            return nreg(EpiResidHL{out16, (uint16_t*)d->out2, d->ldc, d->bias, d->gamma, d->stat_part, d->stat_rows, d->m, d->n});
+        case CVX_EPI_F32:
+            if (!d->gamma) return cvx_fail("gemm: the fp32 epilogue needs out, bias and gamma");
+            return nreg(EpiF32{(float*)d->out, d->ldc, d->bias, d->gamma, d->m, d->n});
+        case CVX_EPI_PATCH:
+            return nreg(EpiPatch{(float*)d->out, d->ldc, d->bias, d->pos, d->ldpos, d->npatch, d->ntp, d->tok0, d->m, d->n});
+        case CVX_EPI_VT:  // MREG orientation: whole rounds on the persistent 256 tile, the rest (or a small problem) on the small tiles
             if (d->n_pad % 128 || d->k_pad % BK) return cvx_fail("gemm: V^T epilogue needs N padded to 128, K to 64");
-            if (d->ln_rowstat) {
-                EpiVTT<true> e{(uint16_t*)d->out, d->bias, d->heads, d->ntp, d->kp, d->m, d->n, 0, d->ln_rowstat, d->n_pad};
-                return dispatch_vt(d, A, W, e, st);
-            }
-            EpiVT e{(uint16_t*)d->out, d->bias, d->heads, d->ntp, d->kp, d->m, d->n};
-            return dispatch_vt(d, A, W, e, st);
-        }
-        case CVX_EPI_CONVT: {
+            return lift([&](auto lnf) {
+                const EpiVTT<lnf()> e{out16, d->bias, d->heads, d->ntp, d->kp, d->m, d->n, 0, d->ln_rowstat, cs_off};
+                if (use_gemm256(d->m, d->n_pad, d->k_pad)) return launch_256_split<EpiVTT<lnf()>, true>(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
+                return launch_tile<TileCfg<128, 128, 2>, true>(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
+            }, ln);
+        case CVX_EPI_CONVT:
             if (d->cout % 8) return cvx_fail("gemm: ConvT C_out must be a multiple of 8");
             if (g_convt_small && convt_small_eligible(*d)) return convt_small_dispatch(*d, st);
-            if (d->dtype == CVX_DTYPE_F16) {  // the head's activations are fp16
-                if (d->act) {
-                    EpiConvT<1, true> e{(uint16_t*)d->out, d->bias, d->H, d->W, d->cout, d->m, d->n, d->convt_up_z ? 1 : 0};
-                    return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-                }
-                EpiConvT<0, true> e{(uint16_t*)d->out, d->bias, d->H, d->W, d->cout, d->m, d->n, d->convt_up_z ? 1 : 0};
-                return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-            }
-            if (d->act) {
-                EpiConvT<1> e{(uint16_t*)d->out, d->bias, d->H, d->W, d->cout, d->m, d->n, d->convt_up_z ? 1 : 0};
-                return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-            }
-            EpiConvT<0> e{(uint16_t*)d->out, d->bias, d->H, d->W, d->cout, d->m, d->n, d->convt_up_z ? 1 : 0};
-            return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st);
-        }
+            return lift([&](auto gelu, auto half) {  // (fp16: the head's activations)
+                return nreg(EpiConvT<gelu() ? 1 : 0, half()>{out16, d->bias, d->H, d->W, d->cout, d->m, d->n, d->convt_up_z ? 1 : 0});
+            }, d->act != 0, f16);
         default:
             return cvx_fail("gemm: unknown epilogue");
     }
@@ -1029,13 +932,6 @@ static int conv3_dispatch(const cvx_conv3d_desc& d, hipStream_t st) {
     if (d.n_pad % 32 == 0) return launch_conv3<TileCfg<32, 256, 1>>(d, e, st);
     if (d.n_pad % 16 == 0) return launch_conv3<TileCfg<16, 256, 1>>(d, e, st);
     return cvx_fail("conv3d: C_out must be padded to a multiple of 16");
-}
-
-namespace cvx {  // conv_halo.hip: LDS-halo kernel for the full-resolution few-channel layers
-bool conv3_halo_eligible(const cvx_conv3d_desc& d);
-int conv3_halo_dispatch(const cvx_conv3d_desc& d, hipStream_t st);
-bool conv3_march_eligible(const cvx_conv3d_desc& d);
-int conv3_march_dispatch(const cvx_conv3d_desc& d, hipStream_t st);
 }
 
 template <int ACT>
