@@ -25,6 +25,8 @@ LABEL_BITMAP_BITS = 65536  # CVX_LABEL_BITMAP_BITS
 LABEL_CENSUS_WORDS = 4 + LABEL_BITMAP_BITS // 32  # CVX_LABEL_CENSUS_WORDS
 LABEL_NONINTEGER, LABEL_WIDE = 1, 2  # CVX_LABEL_NONINTEGER / CVX_LABEL_WIDE census flags
 LABEL_MATCH, LABEL_WEIGHT = 0, 1  # CVX_LABEL_MATCH / CVX_LABEL_WEIGHT
+SEG_MAX_LABELS = 8  # CVX_SEG_MAX_LABELS
+SEG_F32, SEG_U8 = 0, 1  # CVX_SEG_* label dtypes
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -154,6 +156,8 @@ SIGNATURES = {
     "cvx_pca_colormap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
     "cvx_label_census": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "cvx_label_metrics": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "cvx_seg_overlay": (c_int, [c_void_p, C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(C.c_double), c_int, c_int, c_int, c_int,
+                                C.c_double, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -499,3 +499,38 @@ def label_metrics(probs: torch.Tensor, labels: torch.Tensor, counts: torch.Tenso
     dev = _dev_check(probs, labels, counts, y_out)
     call(dev, "cvx_label_metrics", _lib.load().cvx_label_metrics, probs.data_ptr(), labels.data_ptr(), dtype, labels.numel(), int(mode),
          int(value), float(thr), counts.data_ptr(), _p(y_out))
+
+
+# ---- multi-label segmentation overlays (`visualize_results --exp_type segmentations`) ----
+
+_SEG_DTYPES = {torch.float32: _lib.SEG_F32, torch.uint8: _lib.SEG_U8}
+
+
+def seg_overlay(data: torch.Tensor, labels, colours, out: torch.Tensor, *, threshold: float = 0.5) -> None:
+    """out uint8 [D, H, 2W, 3]: the grey ``data`` (fp32 [D, H, W], clipped to [0, 1]) in the left half; in the right half the
+    colour sum of ``labels`` (up to SEG_MAX_LABELS volumes [D, H, W], each fp32 probabilities or uint8 masks, ``colours[i]`` the
+    RGB of label i as three floats) wherever a channel of the clipped sum exceeds ``threshold``, the grey data elsewhere.
+    numpy's arithmetic operation for operation (include/cryovit_hip.h), so the bytes equal the numpy form.  The inputs must
+    be finite: numpy defines no uint8 conversion of a NaN and nothing here checks for one."""
+    labels, colours = list(labels), [tuple(float(v) for v in c) for c in colours]
+    dev = _dev_check(data, out, *labels)
+    if data.dim() != 3 or data.dtype != torch.float32:
+        raise _lib.CvxError(f"seg_overlay: data must be fp32 [D, H, W], got {data.dtype} {tuple(data.shape)}")
+    if len(labels) > _lib.SEG_MAX_LABELS:
+        raise _lib.CvxError(f"seg_overlay: at most {_lib.SEG_MAX_LABELS} label volumes, got {len(labels)}")
+    if len(colours) != len(labels) or any(len(c) != 3 for c in colours):
+        raise _lib.CvxError("seg_overlay: one RGB colour (three floats) per label volume")
+    for t in labels:
+        if t.dtype not in _SEG_DTYPES:
+            raise _lib.CvxError(f"seg_overlay: label volumes must be fp32 or uint8, got {t.dtype}")
+        if t.shape != data.shape:
+            raise _lib.CvxError(f"seg_overlay: label volume {tuple(t.shape)} does not match data {tuple(data.shape)}")
+    D, H, W = data.shape
+    if out.dtype != torch.uint8 or tuple(out.shape) != (D, H, 2 * W, 3):
+        raise _lib.CvxError(f"seg_overlay: out must be uint8 [{D}, {H}, {2 * W}, 3]")
+    n = len(labels)
+    ptrs = (C.c_void_p * _lib.SEG_MAX_LABELS)(*[t.data_ptr() for t in labels])
+    dtypes = (C.c_int * _lib.SEG_MAX_LABELS)(*[_SEG_DTYPES[t.dtype] for t in labels])
+    cols = (C.c_double * (3 * _lib.SEG_MAX_LABELS))(*[v for c in colours for v in c])
+    call(dev, "cvx_seg_overlay", _lib.load().cvx_seg_overlay, data.data_ptr(), ptrs, dtypes, cols, n, D, H, W, float(threshold),
+         out.data_ptr())

@@ -454,6 +454,22 @@ int cvx_label_census(const void* labels, int dtype, long n, int32_t* census, hip
 int cvx_label_metrics(const float* probs, const void* labels, int dtype, long n, int mode, int value, float thr, uint64_t* counts,
                       int8_t* y_out, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Multi-label segmentation overlays (`python -m cryovit_amd.training.visualize_results --exp_type segmentations`; the
+ * reference's cryovit/visualization/segmentations.py).  One streaming pass, no atomics: two calls give the same bits.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_SEG_MAX_LABELS 8
+#define CVX_SEG_F32 0 /* label volume of fp32 probabilities */
+#define CVX_SEG_U8 1  /* label volume of uint8 masks */
+
+/* out uint8 [D][H][2W][3] (any alignment): left half the grey data, right half the overlay.  data fp32 [D][H][W]; labels /
+ * label_dtypes / colours are HOST arrays of n (0 <= n <= CVX_SEG_MAX_LABELS) device pointers to [D][H][W] volumes, their
+ * CVX_SEG_* dtypes and n x 3 RGB doubles.  Per voxel and channel c, as numpy evaluates it: comb = 0 (fp32); for each label in
+ * order comb = (float)((double)comb + (double)seg * colour[c]); comb = clip(comb, 0, 1); g = clip(data, 0, 1); right =
+ * comb > (float)threshold ? comb : g (per channel); left = g; bytes = (uint8)(x * 255.0f), truncated.  Inputs must be finite. */
+int cvx_seg_overlay(const float* data, const void* const* labels, const int* label_dtypes, const double* colours, int n, int D,
+                    int H, int W, double threshold, uint8_t* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
