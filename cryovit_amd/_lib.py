@@ -27,6 +27,8 @@ LABEL_NONINTEGER, LABEL_WIDE = 1, 2  # CVX_LABEL_NONINTEGER / CVX_LABEL_WIDE cen
 LABEL_MATCH, LABEL_WEIGHT = 0, 1  # CVX_LABEL_MATCH / CVX_LABEL_WEIGHT
 SEG_MAX_LABELS = 8  # CVX_SEG_MAX_LABELS
 SEG_F32, SEG_U8 = 0, 1  # CVX_SEG_* label dtypes
+COMPONENT_COLS = 10  # CVX_COMPONENT_COLS
+COMPONENT_MAX_VOXELS = 2**31 - 2  # CVX_COMPONENT_MAX_VOXELS
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -158,6 +160,9 @@ SIGNATURES = {
     "cvx_label_metrics": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "cvx_seg_overlay": (c_int, [c_void_p, C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(C.c_double), c_int, c_int, c_int, c_int,
                                 C.c_double, c_void_p, c_void_p]),
+    "cvx_components_scratch_bytes": (c_long, [c_int, c_int, c_int]),
+    "cvx_components_label": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_long, c_void_p]),
+    "cvx_components_table": (c_int, [c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,60 @@
+"""Connected instances (organelles) of a binary prediction: how many there are, how large each is and where it lies.
+
+``label_volume`` labels a mask that is already on the device (``engine.ops.label_components``: HIP union-find, exact and
+bit-reproducible); ``instance_rows`` turns the integer table into the rows people read; ``label_file`` does both for a
+prediction file that ``cryovit infer`` wrote earlier.
+"""
+
+from __future__ import annotations
+
+from pathlib import Path
+
+import numpy as np
+
+INSTANCE_COLUMNS = ["id", "voxels", "z", "y", "x", "z0", "z1", "y0", "y1", "x0", "x1"]
+
+
+def instance_rows(table) -> list[dict]:
+    """One dict per row of the int64 [K, 10] table (voxels, sum_z, sum_y, sum_x, z0, z1, y0, y1, x0, x1; a host array or a
+    tensor): ``id`` 1..K, ``voxels``, the centroid ``z, y, x`` = sum / voxels in float64, and the inclusive bounding box."""
+    if hasattr(table, "detach"):
+        table = table.detach().cpu().numpy()
+    t = np.asarray(table, dtype=np.int64).reshape(-1, 10)
+    rows = []
+    for i, (n, sz, sy, sx, z0, z1, y0, y1, x0, x1) in enumerate(t.tolist()):
+        rows.append({"id": i + 1, "voxels": n, "z": sz / n, "y": sy / n, "x": sx / n,
+                     "z0": z0, "z1": z1, "y0": y0, "y1": y1, "x0": x0, "x1": x1})
+    return rows
+
+
+def label_volume(mask, *, connectivity: int = 26, min_size: int = 0):
+    """(labels int32 [D, H, W], table int64 [K, 10]) of a uint8 device mask; both stay on the device."""
+    from cryovit_amd.engine import ops
+
+    return ops.label_components(mask, connectivity=connectivity, min_size=min_size)
+
+
+def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, result_dir=None, device=None) -> Path:
+    """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
+    datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
+    ``result_dir`` (default: the file's folder, i.e. in place).  Returns the written file."""
+    import torch
+
+    from cryovit_amd import io
+    from cryovit_amd.run import writers
+    from cryovit_amd.run.sharding import select_device
+
+    path = Path(path)
+    key = f"{label}_preds"
+    datasets = io.read_all_flat(path)
+    if key not in datasets:
+        raise KeyError(f"{path} holds no '{key}' dataset (found {sorted(datasets)})")
+    datasets.pop(f"{label}_instances", None)  # an earlier run's result is replaced
+    preds = datasets[key]
+    if preds.ndim != 3:
+        raise ValueError(f"'{key}' of {path} must be a [D, H, W] volume, got shape {preds.shape}")
+    device = select_device(device)
+    mask = torch.from_numpy(np.ascontiguousarray(preds != 0).view(np.uint8)).to(device)
+    labels, table = label_volume(mask, connectivity=connectivity, min_size=min_size)
+    return writers.write_instances(result_dir if result_dir is not None else path.parent, path.name, label, datasets,
+                                   labels.cpu().numpy(), instance_rows(table))

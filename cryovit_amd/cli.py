@@ -3,10 +3,13 @@
 
     python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize]
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
+                                    [--instances [--min-size N] [--connectivity 6|26]]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
+    python -m cryovit_amd.cli instances <predictions> --label NAME [--min-size N] [--connectivity 6|26] [--result-folder DIR]
 
 ``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
-replace the network fetch of the encoder weights.
+replace the network fetch of the encoder weights or add what the reference leaves to the user: ``instances`` (and
+``infer --instances``) labels the connected instances of a predicted mask on the GPU and tabulates their size and position.
 """
 
 from __future__ import annotations
@@ -37,6 +40,12 @@ def _load_encoder(encoder: Optional[str], checkpoint: Optional[str], synthetic_s
     cfg = compose("dino_features", [])
     return load_encoder(ov.get("name", "dinov2_vitg14_reg"), model_dir=cfg.model_dir, checkpoint=ov.get("checkpoint"),
                         synthetic_seed=ov.get("synthetic_seed"))
+
+
+def _check_connectivity(value: int) -> int:
+    if value not in (6, 26):
+        raise typer.BadParameter("connectivity must be 6 (faces) or 26 (faces, edges and corners)")
+    return value
 
 
 def _encoder_overrides(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]) -> dict:
@@ -81,6 +90,9 @@ def infer(
     encoder: Annotated[Optional[str], Option(help="build extension: encode files without dino_features on the fly with this encoder")] = None,
     checkpoint: Annotated[Optional[str], Option(help="build extension: local DINOv2 state_dict file")] = None,
     synthetic_seed: Annotated[Optional[int], Option(help="build extension: seeded random encoder weights")] = None,
+    instances: Annotated[bool, Option("--instances", help="build extension: also label the connected instances of each mask on the GPU (<label>_instances dataset and instances/<tomogram>_<label>.csv)")] = False,
+    min_size: Annotated[int, Option(min=0, help="build extension: with --instances, drop instances of fewer voxels")] = 0,
+    connectivity: Annotated[int, Option(callback=_check_connectivity, help="build extension: with --instances, 6 (faces) or 26 (faces, edges and corners)")] = 26,
 ):
     """Segment tomograms using a pre-trained model."""
     from cryovit_amd.run.infer_model import run_inference
@@ -93,7 +105,29 @@ def infer(
     assert model_path.exists() and model_path.suffix == ".model", "Model path does not exist or is not a .model file."
     result_path.mkdir(parents=True, exist_ok=True)
     run_inference(load_files_from_path(tomograms_path), model_path, result_path, threshold=threshold,
-                  encoder=_load_encoder(encoder, checkpoint, synthetic_seed))
+                  encoder=_load_encoder(encoder, checkpoint, synthetic_seed), instances=instances, min_size=min_size,
+                  connectivity=connectivity)
+
+
+@cli.command(name="instances", no_args_is_help=True)
+def instances_cmd(
+    predictions: Annotated[str, Argument(help="Path to the folder or .txt file containing prediction files written by `infer`.")],
+    label: Annotated[str, Option(help="build extension: label name; the <label>_preds dataset of every file is labelled.")],
+    min_size: Annotated[int, Option(min=0, help="build extension: drop instances of fewer voxels")] = 0,
+    connectivity: Annotated[int, Option(callback=_check_connectivity, help="build extension: 6 (faces) or 26 (faces, edges and corners)")] = 26,
+    result_folder: Annotated[Optional[str], Option(help="build extension: folder for the labelled files and instances/*.csv.",
+                                                   show_default="the folder of the predictions (files are updated in place)")] = None,
+):
+    """Label and measure the connected instances of existing predictions (build extension)."""
+    from cryovit_amd.analysis.instances import label_file
+    from cryovit_amd.utils import load_files_from_path
+
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
+    predictions_path = Path(predictions)
+    assert predictions_path.exists(), "Predictions path does not exist."
+    for f in load_files_from_path(predictions_path):
+        out = label_file(f, label, connectivity=connectivity, min_size=min_size, result_dir=result_folder)
+        logging.info("Labelled %s", out)
 
 
 @cli.command(name="evaluate", no_args_is_help=True)

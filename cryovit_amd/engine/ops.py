@@ -534,3 +534,45 @@ def seg_overlay(data: torch.Tensor, labels, colours, out: torch.Tensor, *, thres
     cols = (C.c_double * (3 * _lib.SEG_MAX_LABELS))(*[v for c in colours for v in c])
     call(dev, "cvx_seg_overlay", _lib.load().cvx_seg_overlay, data.data_ptr(), ptrs, dtypes, cols, n, D, H, W, float(threshold),
          out.data_ptr())
+
+
+# ---- connected instances of a predicted mask (`cryovit infer --instances`, `cryovit instances`) ----
+
+_components_scratch = {}
+
+
+def components_scratch(D: int, H: int, W: int, device) -> torch.Tensor:
+    """Per (shape, device) workspace of ``label_components``: K, the block counts of the scan and the union-find parents."""
+    key = (D, H, W, torch.device(device))
+    if key not in _components_scratch:
+        need = _lib.load().cvx_components_scratch_bytes(D, H, W)
+        check(min(need, 0), "cvx_components_scratch_bytes")
+        _components_scratch[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return _components_scratch[key]
+
+
+def label_components(mask: torch.Tensor, *, connectivity: int = 26, min_size: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    """(labels int32 [D, H, W], table int64 [K, 10]) of the uint8 mask [D, H, W] (nonzero = foreground), both on the device.
+    Components under ``connectivity`` 6 or 26 are numbered 1..K in ascending order of their smallest linear voxel index,
+    background is 0; components with fewer than ``min_size`` voxels become background before the numbering.  A table row
+    holds voxels, sum_z, sum_y, sum_x, z0, z1, y0, y1, x0, x1 (box inclusive).  Exact and bit-reproducible; the host waits
+    once, for K."""
+    if mask.dim() != 3 or mask.dtype != torch.uint8:
+        raise _lib.CvxError(f"label_components: mask must be uint8 [D, H, W], got {mask.dtype} {tuple(mask.shape)}")
+    if connectivity not in (6, 26):
+        raise _lib.CvxError(f"label_components: connectivity must be 6 or 26, got {connectivity}")
+    if min_size < 0:
+        raise _lib.CvxError(f"label_components: min_size must be >= 0, got {min_size}")
+    dev = _dev_check(mask)
+    D, H, W = mask.shape
+    if mask.numel() > _lib.COMPONENT_MAX_VOXELS:
+        raise _lib.CvxError(f"label_components: {D}x{H}x{W} has more than 2^31 - 2 voxels")
+    lib = _lib.load()
+    scratch = components_scratch(D, H, W, dev)
+    labels = torch.empty((D, H, W), dtype=torch.int32, device=dev)
+    call(dev, "cvx_components_label", lib.cvx_components_label, _p(mask), D, H, W, int(connectivity), int(min_size), _p(labels),
+         scratch.data_ptr(), scratch.numel())
+    k = int(scratch[:4].view(torch.int32).item())  # the one wait
+    table = torch.empty((k, _lib.COMPONENT_COLS), dtype=torch.int64, device=dev)
+    call(dev, "cvx_components_table", lib.cvx_components_table, D, H, W, k, _p(labels), _p(table), scratch.data_ptr(), scratch.numel())
+    return labels, table

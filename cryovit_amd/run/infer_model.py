@@ -11,6 +11,11 @@ sharded over the ranks (no collective on the data path; rank 0 learns the other 
 Extension (not in the reference): ``encoder=`` -- a loaded DINOv2 encoder.  The reference requires ``dino_features`` to be
 in every input file (produced by ``cryovit features``); with an encoder, files that only hold ``data`` are encoded on the
 fly and the features go to the head in HBM without a round trip through the file system.
+
+Extension (not in the reference): ``instances=True`` -- the connected instances of the mask are labelled on the device
+(``engine.ops.label_components``) while the mask is still in HBM; each file then also holds ``<label_key>_instances`` and an
+instance table is written to ``<result_dir>/instances/<tomogram stem>_<label_key>.csv``.  ``<label_key>_preds`` stays the
+unfiltered threshold mask.
 """
 
 from __future__ import annotations
@@ -23,6 +28,7 @@ import numpy as np
 import torch
 
 from cryovit_amd import io
+from cryovit_amd.analysis.instances import instance_rows, label_volume
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
 from cryovit_amd.run import writers
@@ -62,8 +68,19 @@ def _predict_file(model, dataset, idx: int, threshold: float, encoder, batch_siz
     return item.aux_data["data"], mask
 
 
+def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table) -> Path:
+    """``writers.write_segmentation`` plus the instance volume and CSV (writer thread)."""
+    datasets = {"data": raw.astype(np.float32), f"{label_key}_preds": segs.astype(np.uint8, copy=False)}
+    return writers.write_instances(result_dir, tomo_name, label_key, datasets, labels, instance_rows(table))
+
+
 def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, threshold: float = 0.5, *, encoder=None,
-                  batch_size: int = 128, device: str | None = None) -> list[Path]:
+                  batch_size: int = 128, device: str | None = None, instances: bool = False, min_size: int = 0,
+                  connectivity: int = 26) -> list[Path]:
+    if connectivity not in (6, 26):
+        raise ValueError(f"connectivity must be 6 or 26, got {connectivity}")
+    if min_size < 0:
+        raise ValueError(f"min_size must be >= 0, got {min_size}")
     rank, _, world = world_info()
     device = select_device(device)
     model, model_type, model_name, label_key = load_model(model_path, device=device)
@@ -87,8 +104,17 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
             raw, mask = _predict_file(model, dataset, i, threshold, encoder, batch_size)
             host = torch.empty(mask.shape, dtype=torch.uint8, pin_memory=True)
             host.copy_(mask, non_blocking=True)
+            if instances:
+                labels, table = label_volume(mask.contiguous(), connectivity=connectivity, min_size=min_size)
+                host_labels = torch.empty(labels.shape, dtype=torch.int32, pin_memory=True)
+                host_labels.copy_(labels, non_blocking=True)
+                host_table = table.cpu()
             torch.cuda.current_stream(mask.device).synchronize()
-            pending.append((i, writer.submit(writers.write_segmentation, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy())))
+            if instances:
+                pending.append((i, writer.submit(_write_with_instances, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),
+                                                 host_labels.numpy(), host_table.numpy())))
+            else:
+                pending.append((i, writer.submit(writers.write_segmentation, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy())))
             while len(pending) > 2:
                 j, fut = pending.pop(0)
                 paths.append((j, str(fut.result())))

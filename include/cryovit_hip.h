@@ -470,6 +470,32 @@ int cvx_label_metrics(const float* probs, const void* labels, int dtype, long n,
 int cvx_seg_overlay(const float* data, const void* const* labels, const int* label_dtypes, const double* colours, int n, int D,
                     int H, int W, double threshold, uint8_t* out, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Connected instances of a predicted mask (`cryovit infer --instances`, `cryovit instances`).  mask uint8 [D][H][W], nonzero =
+ * foreground.  Two foreground voxels belong to one component iff a chain of foreground voxels joins them, each step a
+ * neighbour under the connectivity: 6 (faces) or 26 (faces, edges, corners); no wrap-around.  Background is 0; components are
+ * numbered 1..K in ascending order of their smallest linear voxel index (z*H + y)*W + x, the order of a C-order raster scan.
+ * Components with fewer than min_size voxels become background and the others are numbered 1..K in the same order (min_size 0
+ * and 1 remove nothing).  Integers only (integer atomic add / min / max): two calls give the same bits.
+ * Two calls, because the table has K rows and K is known only after the first:
+ *   cvx_components_label   writes the int32 K to the first 4 bytes of scratch; labels is used as workspace
+ *   (the caller reads K once and allocates table int64 [K][CVX_COMPONENT_COLS])
+ *   cvx_components_table   writes labels int32 [D][H][W] and the table, from the same scratch, on the same stream
+ * A table row: voxels, sum_z, sum_y, sum_x, z0, z1, y0, y1, x0, x1 (bounding box inclusive).  An empty volume and an all-zero
+ * mask give K = 0.  Refused with an error: D*H*W > CVX_COMPONENT_MAX_VOXELS, negative extents, another connectivity, null
+ * pointers, scratch shorter than cvx_components_scratch_bytes.  labels and scratch 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_COMPONENT_COLS 10
+#define CVX_COMPONENT_MAX_VOXELS 2147483646L /* 2^31 - 2: voxel index + 1 is held in an int32 */
+
+/* bytes of device scratch for one volume; < 0 on bad extents */
+long cvx_components_scratch_bytes(int D, int H, int W);
+int cvx_components_label(const uint8_t* mask, int D, int H, int W, int connectivity, long min_size, int32_t* labels, void* scratch,
+                         long scratch_bytes, hipStream_t stream);
+/* k: the K that cvx_components_label left in scratch (ids past k are written as background rather than past the table) */
+int cvx_components_table(int D, int H, int W, long k, int32_t* labels, int64_t* table, const void* scratch, long scratch_bytes,
+                         hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
