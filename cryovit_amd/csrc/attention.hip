@@ -13,23 +13,101 @@
 #include "../../include/cryovit_hip.h"
 #include "host_util.h"
 #include <atomic>
+#include <string.h>
 
 namespace cvx {
 
 constexpr int ATT_THREADS = 256;
 constexpr int KV_TILE = 64;
 constexpr int ATT_TILE_BYTES = 64 * 128;  // 64 rows x 64 bf16
+// Launch flags (the kernels' last argument, built by attn_launch_flags).  They change speed, never results.
+constexpr int ATT_XCD_REMAP = 1;       // the query blocks of one (slice, head) share an XCD (block_coord)
+constexpr int ATT_PRIO_QK = 2;         // s_setprio 1 around the wave's S^T MFMAs (cvx_set_option "attn_mfma_prio" bit 0)
+constexpr int ATT_PRIO_PV = 4;         // ... and around its O^T MFMAs (bit 1)
+constexpr int ATT_FULL_LAST_TILE = 8;  // do NOT skip the all-padding upper half of the last key tile ("attn_half_tile" 0: A/B runs)
 
 __device__ __forceinline__ int pi_row(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
-// VARIANT: 0 = default (the O rescale is skipped when no row maximum of the wave moved), 1 = always rescale,
-//          10-13 = timing-only ablations (10: exp2 replaced by a multiply, 11: K/V tile 0 reused, no DMA / wait / barrier,
-//          12: DMA issued but no wait / barrier, 13: wait + barrier but no DMA)
-//          3 = THREE K/V^T buffers: tile j+2 is issued in iteration j and waited for with a counted vmcnt(4)
-//          8 / 9 = variant 7 with EIGHT waves per workgroup (256 query rows share every K / V^T tile: half the LDS-DMA instructions
-//          and half the L2 -> LDS bytes per query row).  Two such workgroups per CU keep four waves per SIMD, and their 2 x 48 KB of
-//          LDS have room for a THIRD tile buffer (8: two tiles of look-ahead behind a counted wait; 9: two buffers, for A/B runs) --
-//          the three-buffer form of the 4-wave kernel (variant 3) paid for its buffer with the fourth wave per SIMD.
+// How the row maximum m of p = exp2(S - m) is kept: per tile (O and l rescaled when it moves); or as an anchor subtracted INSIDE
+// the product (see k_attention) that is raised when a tile's row maxima outgrow it; or when its probability sums run away.
+enum class Softmax { RunningMax, TileMax, ProbSum };
+// What a variant number (cvx_set_option "attn_variant", the VARIANT of k_attention) selects.
+struct AttnCfg {
+    int waves = 4;  // per workgroup, 32 query rows each
+    int nbuf = 2;   // K / V^T tile buffers in LDS
+    Softmax softmax = Softmax::RunningMax;
+    bool legacy = false;  // always rescale O, idle waves of the last query block run the products (the first kernel, for A/B runs)
+    bool no_exp = false, no_sync = false, no_dma = false;  // timing-only ablations: the output is garbage
+};
+// 0 = general kernel (the O rescale is skipped when no row maximum of the wave moved), 1 = always rescale,
+// 3 = THREE K/V^T buffers: tile j+2 is issued in iteration j and waited for with a counted vmcnt(4)
+// 6 = maximum subtracted inside the product, anchor raised by the tile maxima, 7 = by the probability sums (default)
+// 8 / 9 = variant 7 with EIGHT waves per workgroup (256 query rows share every K / V^T tile: half the LDS-DMA instructions
+//         and half the L2 -> LDS bytes per query row).  Two such workgroups per CU keep four waves per SIMD, and their 2 x 48 KB of
+//         LDS have room for a THIRD tile buffer (8: two tiles of look-ahead behind a counted wait; 9: two buffers, for A/B runs) --
+//         the three-buffer form of the 4-wave kernel (variant 3) paid for its buffer with the fourth wave per SIMD.
+// 10-13 = timing-only ablations (10: exp2 replaced by a multiply, 11: K/V tile 0 reused, no DMA / wait / barrier,
+//         12: DMA issued but no wait / barrier, 13: wait + barrier but no DMA)
+// (4 / 5 are k_attention64 with 3 / 4 waves.)
+constexpr AttnCfg attn_cfg(int variant) {
+    AttnCfg c;
+    switch (variant) {
+        case 1: c.legacy = true; break;
+        case 3: c.nbuf = 3; break;
+        case 6: c.softmax = Softmax::TileMax; break;
+        case 7: c.softmax = Softmax::ProbSum; break;
+        case 8: c.softmax = Softmax::ProbSum; c.waves = 8; c.nbuf = 3; break;
+        case 9: c.softmax = Softmax::ProbSum; c.waves = 8; break;
+        case 10: c.no_exp = true; break;
+        case 11: c.no_sync = c.no_dma = true; break;
+        case 12: c.no_sync = true; break;
+        case 13: c.no_dma = true; break;
+    }
+    return c;
+}
+
+// ---- shared pieces.  s / o: the S^T / O^T accumulators of one 32-query group (lane (r, h): query r; keys / dims in registers) ----
+// XCD-aware block order: blocks b and b+8 share an XCD (private L2).  All nqb query blocks of one (slice, head) --
+// which stream the SAME K / V^T -- are placed on one XCD, back to back in its dispatch sequence, so a K/V tile is an
+// L2 miss once and an L2 hit for the other query blocks.  (Placement only changes speed, never results.)
+struct BlockCoord { int qb, slice, head; };
+__device__ __forceinline__ BlockCoord block_coord(int flags, int nqb, int heads) {
+    int qb, pair;
+    if (flags & ATT_XCD_REMAP) {
+        const int xcd = blockIdx.x & 7, w = blockIdx.x >> 3;
+        pair = (w / nqb) * 8 + xcd;
+        qb = w % nqb;
+    } else {
+        pair = blockIdx.x / nqb;
+        qb = blockIdx.x % nqb;
+    }
+    return {qb, pair / heads, pair % heads};
+}
+
+// row maximum of the tile: 32 registers, then the other half of the row's keys from lane ^ 32
+__device__ __forceinline__ float row_max(const f32x16 (&s)[2]) {
+    float m = s[0][0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) m = fmaxf(m, s[0][i]);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) m = fmaxf(m, s[1][i]);
+    return fmaxf(m, __shfl_xor(m, 32, 64));
+}
+
+// s = exp2(s) in place; psum = the lane's sum (its half of the row's keys)
+// (accumulating the sums two at a time with v_pk_add_f32 -- 16 instead of 32 adds -- measured 3 % SLOWER: 1.100 vs 1.064 ms)
+__device__ __forceinline__ void exp2_sum(f32x16 (&s)[2], float& psum) {
+    psum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float p = __builtin_amdgcn_exp2f(s[t][i]);
+            s[t][i] = p;
+            psum += p;
+        }
+}
+
 // VROW: V is NOT pre-transposed -- it sits row-major beside Q and K in one [rows][3C] buffer (columns 2C ..), written by ONE qkv GEMM
 //       with the plain row-major epilogue (no separate V^T GEMM launch, no scattered 16-B stores of a transposed epilogue, no vt buffer).
 //       The V tile is staged exactly like the K tile ([key][64 dims], same swizzle); the A operand of O^T += V^T P^T (32 dims x 16 keys,
@@ -38,31 +116,22 @@ __device__ __forceinline__ int pi_row(int r) { return (r & 0x13) | ((r & 4) << 1
 typedef short v4s_t __attribute__((ext_vector_type(4)));
 typedef short v8s_t __attribute__((ext_vector_type(8)));
 template <int VARIANT, bool VROW = false>
-__global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS) void k_attention(const uint16_t* __restrict__ qk, long ldqk,
-                                                           const uint16_t* __restrict__ vt, uint16_t* __restrict__ out,
-                                                           long ldo, int heads, int ntok, int ntp, int kp, int C, int nqb,
-                                                           int xcd_remap) {
-    constexpr int NW = (VARIANT == 8 || VARIANT == 9) ? 8 : 4;       // waves per workgroup, 32 query rows each
+__global__ __launch_bounds__(attn_cfg(VARIANT).waves * 64) void k_attention(const uint16_t* __restrict__ qk, long ldqk,
+                                                                            const uint16_t* __restrict__ vt, uint16_t* __restrict__ out,
+                                                                            long ldo, int heads, int ntok, int ntp, int kp, int C, int nqb,
+                                                                            int flags) {
+    constexpr AttnCfg cfg = attn_cfg(VARIANT);
+    constexpr int NW = cfg.waves, NBUF = cfg.nbuf;
     constexpr int NT = NW * 64, QB = NW * 32;                        // threads, query rows per workgroup
     constexpr int PPT = 512 / NT;                                    // 16-B pieces per thread and tile (K and V^T alike)
-    constexpr int NBUF = (VARIANT == 3 || VARIANT == 8) ? 3 : 2;
+    constexpr bool AUG = cfg.softmax != Softmax::RunningMax, PSUM_TRIGGER = cfg.softmax == Softmax::ProbSum;
+    constexpr bool LEGACY = cfg.legacy, ABL_NOEXP = cfg.no_exp, ABL_NOSYNC = cfg.no_sync, ABL_NODMA = cfg.no_dma;
     __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * ATT_TILE_BYTES];  // [buf][K | V^T]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // XCD-aware block order: blocks b and b+8 share an XCD (private L2).  All nqb query blocks of one (slice, head) --
-    // which stream the SAME K / V^T -- are placed on one XCD, back to back in its dispatch sequence, so a K/V tile is an
-    // L2 miss once and an L2 hit for the other query blocks.  (Placement only changes speed, never results.)
-    int qb, pair;
-    const bool prio_qk = (xcd_remap & 2) != 0, prio_pv = (xcd_remap & 4) != 0;  // s_setprio 1 around the wave's MFMA blocks (cvx_set_option "attn_mfma_prio": bit 0 S^T, bit 1 O^T)
-    if (xcd_remap & 1) {
-        const int xcd = blockIdx.x & 7, w = blockIdx.x >> 3;
-        pair = (w / nqb) * 8 + xcd;
-        qb = w % nqb;
-    } else {
-        pair = blockIdx.x / nqb;
-        qb = blockIdx.x % nqb;
-    }
-    const int slice = pair / heads, head = pair - slice * heads;
+    const bool prio_qk = (flags & ATT_PRIO_QK) != 0, prio_pv = (flags & ATT_PRIO_PV) != 0;
+    const BlockCoord bc = block_coord(flags, nqb, heads);
+    const int qb = bc.qb, slice = bc.slice, head = bc.head;
     const long row0 = (long)slice * ntp;
     const uint16_t* Qp = qk + row0 * ldqk + head * 64;
     const uint16_t* Kp = Qp + C;
@@ -72,7 +141,7 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
     const int r = lane & 31, h = lane >> 5;
     const int q0 = qb * QB + wave * 32;
     const int qrow = min(q0 + r, ntp - 1);  // rows past the slice are clamped for loads, never stored
-    const bool wave_idle = VARIANT != 1 && q0 >= ntok;  // (variant 1 keeps the old behaviour for A/B runs)
+    const bool wave_idle = !LEGACY && q0 >= ntok;
 
     // Q fragments: B operand of S^T = K Q^T.  lane (r,h) holds Q[q0+r][16*ks + 8*h + j]
     // The loads are inline asm with their own wait (below, before the key loop): left to hipcc, the waits for these four
@@ -86,14 +155,12 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
     }
     // Scores arrive in LOG2 units: the caller folds head_dim^-0.5 * log2(e) into the Q projection (one rounding, at weight
     // packing), so p = exp2(S - m) with no multiply.
-    // VARIANT 6: the running maximum is subtracted INSIDE the matrix product: a fifth
+    // Softmax::TileMax / ProbSum: the maximum is subtracted INSIDE the matrix product: a fifth
     // k-step whose K operand is the constant column e_0 and whose Q operand carries -m of the lane's query row, so
     //   S' = K Q^T - m   and   p = exp2(S')   with no per-element VALU work at all
     // as long as the row maxima of the tile stay within DEFER (log2 units) of the value subtracted.  The VALU, not the
     // matrix pipe, bounds this kernel at head_dim 64 (PMC: VALU active 73 % of SIMD cycles, MFMA 39 %); the 32 fused
     // multiply-adds per tile this removes were 15 % of its vector instructions, for 2 more MFMAs on the idle pipe.
-    constexpr bool AUG = VARIANT == 6 || VARIANT == 7 || VARIANT == 8 || VARIANT == 9;
-    constexpr bool PSUM_TRIGGER = VARIANT == 7 || VARIANT == 8 || VARIANT == 9;  // the maximum is only looked at in tile 0; later tiles watch their probability sums
     constexpr float DEFER = 3.0f;  // p <= 2^3 before a row's maximum is raised (bf16 P is floating point: same relative precision)
     bf16x8 kaug, qaug;
     [[maybe_unused]] float m_used = 0.f;  // what is currently subtracted (exactly representable in bf16)
@@ -173,18 +240,15 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
 #pragma unroll
     for (int i = 0; i < 16; ++i) { o[0][i] = 0.f; o[1][i] = 0.f; }
     float m_run = -INFINITY, l_run = 0.f;
-    const float LOG2E = 1.0f;  // (scores are already in log2 units: see the note at the Q fragments)
 
     const int nkv = (ntok + KV_TILE - 1) / KV_TILE;
-    constexpr bool SKIP_RESCALE = VARIANT != 1, ABL_NOEXP = VARIANT == 10;
-    constexpr bool ABL_NOSYNC = VARIANT == 11 || VARIANT == 12, ABL_NODMA = VARIANT == 11 || VARIANT == 13;
     issue(0, 0);
     if (NBUF == 3 && nkv > 1) issue(1, 1);
     // Q has landed (and tile 0 / 1 with it: the loop's own first wait is then a no-op); "+v" pins every use of qf below this
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3])::"memory");
     int buf = 0;  // buffer of tile j
     const char* kt = smem;
-    [[maybe_unused]] bool redo = false;  // VARIANT 7: tile j is computed again, with the row maxima (no new wait / barrier / DMA)
+    [[maybe_unused]] bool redo = false;  // ProbSum: tile j is computed again, with the row maxima (no new wait / barrier / DMA)
     for (int j = 0; j < nkv; ++j) {
         if (!PSUM_TRIGGER || !redo) {
         if (!ABL_NOSYNC || j == 0) {
@@ -217,7 +281,7 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
         const int kv0 = j * KV_TILE;
         // 1029 keys = 16 x 64 + 5: the upper 32 keys of the last tile are all padding.  Their products, S^T and O^T alike, are
         // skipped (wave-uniform): half a tile of MFMAs in 17, which at the board's power limit is time
-        const bool half_tile = !(xcd_remap & 8) && kv0 + 32 >= ntok;  // (bit 3: A/B switch, cvx_set_option "attn_half_tile" 0)
+        const bool half_tile = !(flags & ATT_FULL_LAST_TILE) && kv0 + 32 >= ntok;
         auto compute_s = [&]() {
 #pragma unroll
             for (int i = 0; i < 16; ++i) { s[0][i] = 0.f; s[1][i] = 0.f; }
@@ -244,30 +308,22 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
                     }
             }
         };
-        if constexpr (!PSUM_TRIGGER) compute_s();
+        compute_s();
 
+        // The two anchored forms (S' = S - m_used, log2 units) share the raise below and differ in what triggers it.
+        // The rows are anchored at the maximum of tile 0 whatever its sign (m_used starts at 0: a row whose scores are all far
+        // below zero must not underflow to l = 0); later the anchor only ever goes up.  It is bf16-representable, so the
+        // products of the next tiles subtract exactly what the rescale assumes; delta is exact in fp32.
+        // (The raise stays written out in both: as a lambda it changes the shipped kernel's code.)
         if constexpr (PSUM_TRIGGER) {
-            // ---- online softmax on S' = S - m_used (log2 units), VARIANT 7 ----
-            // Tile 0 anchors every row at its own maximum (16 v_max3 + one cross-half exchange, once per query block).  After that the
-            // row maximum is not computed on the common path: p = exp2(S') is floating point, so a row whose later scores exceed its
-            // anchor simply produces p > 1 -- the same relative precision in bf16 P, in the fp32 sums and in O.  What has to be
-            // prevented is overflow, and for that the probability SUM the tile computes anyway is enough: when a lane's sum passes
-            // 2^24 the whole tile is computed AGAIN (same LDS tile: no wait, barrier or DMA) in the anchored form.  Per 64-key tile
-            // this removes 16 v_max3, the exchange and the compare chain from a loop whose vector ISSUE slots, not its matrix pipe,
-            // set the pace.
+            // Trigger: tile 0, or a tile whose probability sums ran away.  After tile 0 the row maximum is not computed on the
+            // common path: p = exp2(S') is floating point, so a row whose later scores exceed its anchor simply produces p > 1 --
+            // the same relative precision in bf16 P, in the fp32 sums and in O.  What has to be prevented is overflow, and for
+            // that the probability SUM the tile computes anyway is enough.  Per 64-key tile this removes 16 v_max3, the exchange
+            // and the compare chain from a loop whose vector ISSUE slots, not its matrix pipe, set the pace.
             float psum;
-            compute_s();
             if (anchor) {
-                // tile 0, or a tile whose probability sums ran away: the rows are (re-)anchored at their maximum exactly as variant 6
-                // does in every tile.  Tile 0 takes the maximum whatever its sign (a row whose scores are all far below zero must not
-                // underflow to l = 0); later the anchor only ever goes up.  The anchor is bf16-representable so that the products of
-                // the next tiles subtract exactly what the rescale here assumes.
-                float mloc = s[0][0];
-#pragma unroll
-                for (int i = 1; i < 16; ++i) mloc = fmaxf(mloc, s[0][i]);
-#pragma unroll
-                for (int i = 0; i < 16; ++i) mloc = fmaxf(mloc, s[1][i]);
-                mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+                const float mloc = row_max(s);
                 const float m_new = (float)(__bf16)(m_used + (j == 0 ? mloc : fmaxf(mloc, 0.f)));
                 const float delta = m_new - m_used;
                 m_used = m_new;
@@ -277,18 +333,10 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { o[0][i] *= alpha; o[1][i] *= alpha; s[0][i] -= delta; s[1][i] -= delta; }
             }
-            // (accumulating the sums two at a time with v_pk_add_f32 -- 16 instead of 32 adds -- measured 3 % SLOWER: 1.100 vs 1.064 ms)
-            psum = 0.f;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float p = __builtin_amdgcn_exp2f(s[t][i]);
-                    s[t][i] = p;
-                    psum += p;
-                }
-            // some row's probabilities outgrew its anchor by 2^19 or more (or overflowed): the tile is computed again, this time
-            // with the maximum (never twice: the anchored pass is final -- variant 6's own bound, p <= 2^(half a bf16 spacing of m))
+            exp2_sum(s, psum);
+            // some row's probabilities outgrew its anchor by 2^19 or more (a lane's sum passed 2^24, or overflowed): the tile is
+            // computed AGAIN (same LDS tile: no wait, barrier or DMA), this time with the maximum (never twice: the anchored pass
+            // is final -- TileMax's own bound, p <= 2^(half a bf16 spacing of m))
             if (!anchor && __builtin_amdgcn_ballot_w64(!(psum <= 16777216.0f)) != 0) {
                 redo = true;
                 --j;
@@ -296,18 +344,9 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
             }
             l_run += psum;
         } else if constexpr (AUG) {
-            // ---- online softmax on S' = S - m_used (log2 units) ----
-            float mloc = s[0][0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) mloc = fmaxf(mloc, s[0][i]);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mloc = fmaxf(mloc, s[1][i]);
-            mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-            // tile 0 anchors every row at its own maximum, whatever its sign (m_used starts at 0: a row whose scores are all
-            // far below zero must not underflow to l = 0); later tiles only ever raise it
+            // Trigger: every tile computes its row maxima; tile 0, or a row that outgrew its anchor by DEFER
+            const float mloc = row_max(s);
             if (j == 0 || __builtin_amdgcn_ballot_w64(mloc > DEFER) != 0) {
-                // the subtracted maximum becomes the row's new maximum rounded to bf16 (the value the next tiles' products
-                // subtract must be the one used here); delta is exact in fp32
                 const float m_new = (float)(__bf16)(m_used + (j == 0 ? mloc : fmaxf(mloc, 0.f)));
                 const float delta = m_new - m_used;
                 m_used = m_new;
@@ -317,44 +356,30 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { o[0][i] *= alpha; o[1][i] *= alpha; s[0][i] -= delta; s[1][i] -= delta; }
             }
+            float psum;
+            exp2_sum(s, psum);
+            l_run += psum;
+        } else {
+            // ---- running maximum (scores already carry head_dim^-0.5 through Q) ----
+            const float m_new = fmaxf(m_run, row_max(s));
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+            m_run = m_new;
             float psum = 0.f;
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const float p = __builtin_amdgcn_exp2f(s[t][i]);
+                    const float p = ABL_NOEXP ? (s[t][i] - m_new) * 0.001f : __builtin_amdgcn_exp2f(s[t][i] - m_new);
                     s[t][i] = p;
                     psum += p;
                 }
-            l_run += psum;
-        } else {
-        // ---- online softmax (scores already carry head_dim^-0.5 through Q) ----
-        float mloc = s[0][0];
+            l_run = fmaf(l_run, alpha, psum);
+            // alpha == 1 exactly when the row maximum did not move: skip the 32-register rescale unless some lane needs it
+            if (LEGACY || __builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
 #pragma unroll
-        for (int i = 1; i < 16; ++i) mloc = fmaxf(mloc, s[0][i]);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mloc = fmaxf(mloc, s[1][i]);
-        mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-        const float m_new = fmaxf(m_run, mloc);
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * LOG2E);
-        const float mb = m_new * LOG2E;
-        m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float p = ABL_NOEXP ? fmaf(s[t][i], LOG2E, -mb) * 0.001f : __builtin_amdgcn_exp2f(fmaf(s[t][i], LOG2E, -mb));
-                s[t][i] = p;
-                psum += p;
+                for (int i = 0; i < 16; ++i) { o[0][i] *= alpha; o[1][i] *= alpha; }
             }
-        l_run = fmaf(l_run, alpha, psum);
-        // alpha == 1 exactly when the row maximum did not move: skip the 32-register rescale unless some lane needs it
-        if (!SKIP_RESCALE || __builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { o[0][i] *= alpha; o[1][i] *= alpha; }
         }
-        }  // !AUG
 
         // ---- O^T[dt] += V^T[dt] P^T : accumulator registers 8s..8s+7 of S^T[t] are k-step s of the B operand ----
         if (prio_pv) __builtin_amdgcn_s_setprio(1);
@@ -385,7 +410,6 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
         if (prio_pv) __builtin_amdgcn_s_setprio(0);
     }
 
-    // ---- normalise and store: lane (r,h) holds O[q0+r][32dt + 8g + 4h + (0..3)] in regs 4g..4g+3 ----
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
     if (q0 + r < ntok) {
@@ -411,21 +435,13 @@ __global__ __launch_bounds__((VARIANT == 8 || VARIANT == 9) ? 512 : ATT_THREADS)
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void k_attention64(const uint16_t* __restrict__ qk, long ldqk, const uint16_t* __restrict__ vt,
                                                          uint16_t* __restrict__ out, long ldo, int heads, int ntok, int ntp, int kp,
-                                                         int C, int nqb, int xcd_remap) {
+                                                         int C, int nqb, int flags) {
     constexpr int NT = NW * 64;
     __shared__ __attribute__((aligned(16))) char smem[2 * 2 * ATT_TILE_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int qb, pair;
-    if (xcd_remap & 1) {
-        const int xcd = blockIdx.x & 7, w = blockIdx.x >> 3;
-        pair = (w / nqb) * 8 + xcd;
-        qb = w % nqb;
-    } else {
-        pair = blockIdx.x / nqb;
-        qb = blockIdx.x % nqb;
-    }
-    const int slice = pair / heads, head = pair - slice * heads;
+    const BlockCoord bc = block_coord(flags, nqb, heads);
+    const int qb = bc.qb, slice = bc.slice, head = bc.head;
     const long row0 = (long)slice * ntp;
     const uint16_t* Qp = qk + row0 * ldqk + head * 64;
     const uint16_t* Kp = Qp + C;
@@ -470,7 +486,6 @@ __global__ __launch_bounds__(NW * 64) void k_attention64(const uint16_t* __restr
 #pragma unroll
         for (int i = 0; i < 16; ++i) { o[g][0][i] = 0.f; o[g][1][i] = 0.f; }
     float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
-    const float LOG2E = 1.0f;  // (scores are already in log2 units: see the note at the Q fragments)
     const int nkv = (ntok + KV_TILE - 1) / KV_TILE;
 
     issue(0, 0);
@@ -508,22 +523,15 @@ __global__ __launch_bounds__(NW * 64) void k_attention64(const uint16_t* __restr
         }
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-            float mloc = s[g][0][0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) mloc = fmaxf(mloc, s[g][0][i]);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mloc = fmaxf(mloc, s[g][1][i]);
-            mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-            const float m_new = fmaxf(m_run[g], mloc);
-            const float alpha = __builtin_amdgcn_exp2f((m_run[g] - m_new) * LOG2E);
-            const float mb = m_new * LOG2E;
+            const float m_new = fmaxf(m_run[g], row_max(s[g]));
+            const float alpha = __builtin_amdgcn_exp2f(m_run[g] - m_new);
             m_run[g] = m_new;
             float psum = 0.f;
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const float p = __builtin_amdgcn_exp2f(fmaf(s[g][t][i], LOG2E, -mb));
+                    const float p = __builtin_amdgcn_exp2f(s[g][t][i] - m_new);
                     s[g][t][i] = p;
                     psum += p;
                 }
@@ -576,11 +584,71 @@ __global__ __launch_bounds__(NW * 64) void k_attention64(const uint16_t* __restr
 
 using namespace cvx;
 
-std::atomic<int> g_attn_variant{7};     // cvx_set_option("attn_variant"); 7 = maximum subtracted inside the product, re-anchoring triggered by the probability sums (default); 6 = by the tile maxima
-std::atomic<int> g_attn_xcd_remap{1};   // cvx_set_option("attn_xcd_remap")
-std::atomic<int> g_attn_half_tile{1};   // cvx_set_option("attn_half_tile"): skip the all-padding upper half of the last key tile (0: A/B runs)
-std::atomic<int> g_attn_mfma_prio{2};   // cvx_set_option("attn_mfma_prio"): s_setprio 1 around the wave's MFMA blocks (bit 0: S^T, bit 1: O^T).  Measured per layer:
-                                        // 0: 1.028 ms, 1: 1.018, 2: 0.999 (default), 3: 1.003 -- the O^T MFMAs wait behind other waves' softmax VALU otherwise
+// ---- host side ----
+typedef void (*attn_kernel_t)(const uint16_t*, long, const uint16_t*, uint16_t*, long, int, int, int, int, int, int, int);
+struct AttnVariant {
+    int id;  // cvx_set_option("attn_variant")
+    attn_kernel_t kernel;  // the V^T form (cvx_attention_bf16)
+    int threads, rows;     // per workgroup: threads, query rows
+    bool needs_ld64;       // the lone-wave DMA offsets of the AUG kernels assume ldqk % 64 == 0 (see issue() in k_attention)
+};
+template <int V>
+static AttnVariant attn_row() {
+    constexpr AttnCfg c = attn_cfg(V);
+    return {V, k_attention<V, false>, c.waves * 64, c.waves * 32, c.softmax != Softmax::RunningMax};
+}
+// every variant of this build; cvx_set_option("attn_variant") accepts exactly these
+static const AttnVariant g_attn_variants[] = {
+    attn_row<0>(),
+    attn_row<7>(),
+#ifdef CVX_ABLATION  // earlier / rejected schedules (parity-tested on the ablation build) and timing-only ones with garbage output
+    attn_row<1>(), attn_row<3>(), attn_row<6>(),
+    attn_row<8>(),  // 8-wave workgroups, three buffers: measured 1.001 -> 1.123 ms per layer
+    attn_row<9>(),  // 8-wave workgroups, two buffers: 1.082 ms
+    attn_row<10>(), attn_row<11>(), attn_row<12>(), attn_row<13>(),
+    {4, k_attention64<3>, 192, 192, false},
+    {5, k_attention64<4>, 256, 256, false},
+#endif
+};
+static const AttnVariant* find_attn_variant(int id) {
+    for (const AttnVariant& v : g_attn_variants)
+        if (v.id == id) return &v;
+    return nullptr;
+}
+
+static std::atomic<int> g_attn_variant{7};     // 7 = maximum subtracted inside the product, re-anchoring triggered by the probability sums
+static std::atomic<int> g_attn_xcd_remap{1};
+static std::atomic<int> g_attn_half_tile{1};   // skip the all-padding upper half of the last key tile (0: A/B runs)
+static std::atomic<int> g_attn_mfma_prio{2};   // s_setprio 1 around the wave's MFMA blocks (bit 0: S^T, bit 1: O^T).  Measured per layer:
+                                               // 0: 1.028 ms, 1: 1.018, 2: 0.999 (default), 3: 1.003 -- the O^T MFMAs wait behind other waves' softmax VALU otherwise
+
+// the "attn_*" names of cvx_set_option (gemm.hip)
+int cvx_attn_set_option(const char* name, int value) {
+    if (!strcmp(name, "attn_variant")) {
+        if (!find_attn_variant(value)) return cvx_fail("set_option: unknown attn_variant (ablation variants need a -DCVX_ABLATION build)");
+        g_attn_variant = value;
+    } else if (!strcmp(name, "attn_xcd_remap")) g_attn_xcd_remap = value != 0;
+    else if (!strcmp(name, "attn_mfma_prio")) g_attn_mfma_prio = value & 3;
+    else if (!strcmp(name, "attn_half_tile")) g_attn_half_tile = value != 0;
+    else return cvx_fail("set_option: unknown option");
+    return 0;
+}
+
+static int attn_launch_flags(long pairs) {  // pairs = heads * slices: the remap deals (slice, head) pairs round the 8 XCDs
+    const int prio = g_attn_mfma_prio;
+    return (pairs % 8 == 0 && g_attn_xcd_remap ? ATT_XCD_REMAP : 0) | (prio & 1 ? ATT_PRIO_QK : 0) | (prio & 2 ? ATT_PRIO_PV : 0) |
+           (g_attn_half_tile ? 0 : ATT_FULL_LAST_TILE);
+}
+
+static int launch_attention(const AttnVariant& v, const char* grid_msg, const void* qk, long ldqk, const void* vt, void* out, long ldo,
+                            int slices, int heads, int ntok, int ntp, int kp, hipStream_t st) {
+    const int nqb = (ntok + v.rows - 1) / v.rows;
+    const long nblk = (long)nqb * heads * slices;
+    if (nblk > 0x7fffffff) return cvx_fail(grid_msg);
+    hipLaunchKernelGGL(v.kernel, dim3((unsigned)nblk), dim3(v.threads), 0, st, (const uint16_t*)qk, ldqk, (const uint16_t*)vt, (uint16_t*)out,
+                       ldo, heads, ntok, ntp, kp, heads * 64, nqb, attn_launch_flags((long)heads * slices));
+    return cvx_check_launch();
+}
 
 extern "C" int cvx_attention_qkv_bf16(const void* qkv, long ld, void* out, long ldo, int slices, int heads, int ntok, int ntp,
                                       hipStream_t st) {
@@ -588,13 +656,8 @@ extern "C" int cvx_attention_qkv_bf16(const void* qkv, long ld, void* out, long 
     if (!qkv || !out) return cvx_fail("attention_qkv: null pointer");
     if (ntp % 8 || ntp < ntok || ld % 64 || ld < 3L * heads * 64 || ldo % 4)
         return cvx_fail("attention_qkv: need ntp%8==0, ntp>=ntok, ld%64==0 (the default kernel's lone-wave DMA offsets), ld >= 3*heads*64");
-    const int nqb = (ntok + 127) / 128;
-    const long nblk = (long)nqb * heads * slices;
-    if (nblk > 0x7fffffff) return cvx_fail("attention_qkv: grid too large");
-    const int xcd_remap = (((long)heads * slices) % 8 == 0 && g_attn_xcd_remap ? 1 : 0) | ((g_attn_mfma_prio.load() & 3) << 1) | (g_attn_half_tile.load() ? 0 : 8);
-    hipLaunchKernelGGL((k_attention<7, true>), dim3((unsigned)nblk), dim3(ATT_THREADS), 0, st, (const uint16_t*)qkv, ld, (const uint16_t*)nullptr,
-                       (uint16_t*)out, ldo, heads, ntok, ntp, /*kp (unused)*/ 0, heads * 64, nqb, xcd_remap);
-    return cvx_check_launch();
+    const AttnVariant v = {7, k_attention<7, true>, ATT_THREADS, 128, true};
+    return launch_attention(v, "attention_qkv: grid too large", qkv, ld, nullptr, out, ldo, slices, heads, ntok, ntp, /*kp (unused)*/ 0, st);
 }
 
 extern "C" int cvx_attention_bf16(const void* qk, long ldqk, const void* vt, void* out, long ldo, int slices, int heads,
@@ -602,42 +665,10 @@ extern "C" int cvx_attention_bf16(const void* qk, long ldqk, const void* vt, voi
     if (slices <= 0) return 0;
     if (ntp % 8 || kp % 64 || kp < ntok || ntp < ntok || ldqk % 8 || ldo % 4)
         return cvx_fail("attention: need ntp%8==0, kp%64==0, kp>=ntok, ntp>=ntok, ldqk%8==0");
-    int variant = g_attn_variant;  // one read per call: a concurrent cvx_set_option cannot give a mixed launch
-    // Variant 6's single-wave query blocks derive the departed waves' DMA offsets by XOR-ing 64 into wave 0's own, which is the other
-    // waves' row term only while a K row's byte pitch is a multiple of 128 (ldqk % 64 == 0: every DINOv2 width).  Other leading
-    // dimensions take the general kernel (variant 0: a running maximum per tile).
-    if ((variant == 6 || variant == 7 || variant == 8 || variant == 9) && ldqk % 64 != 0) variant = 0;
-    const int rows_per_block = variant == 4 ? 192 : (variant == 5 || variant == 8 || variant == 9) ? 256 : 128;
-    const int nqb = (ntok + rows_per_block - 1) / rows_per_block;
-    const long nblk = (long)nqb * heads * slices;
-    if (nblk > 0x7fffffff) return cvx_fail("attention: grid too large");
-    const int xcd_remap = (((long)heads * slices) % 8 == 0 && g_attn_xcd_remap ? 1 : 0) | ((g_attn_mfma_prio.load() & 3) << 1) | (g_attn_half_tile.load() ? 0 : 8);
-    dim3 grid((unsigned)nblk);
-    void (*k)(const uint16_t*, long, const uint16_t*, uint16_t*, long, int, int, int, int, int, int, int);
-    switch (variant) {
-        case 7: k = k_attention<7>; break;
-#ifdef CVX_ABLATION  // earlier / rejected schedules (parity-tested on the ablation build) and timing-only ones with garbage output
-        case 8: k = k_attention<8>; break;  // 8-wave workgroups, three buffers: measured 1.001 -> 1.123 ms per layer
-        case 9: k = k_attention<9>; break;  // 8-wave workgroups, two buffers: 1.082 ms
-        case 1: k = k_attention<1>; break;
-        case 3: k = k_attention<3>; break;
-        case 6: k = k_attention<6>; break;
-        case 10: k = k_attention<10>; break;
-        case 11: k = k_attention<11>; break;
-        case 12: k = k_attention<12>; break;
-        case 13: k = k_attention<13>; break;
-#endif
-        default: k = k_attention<0>; break;
-    }
-#ifdef CVX_ABLATION
-    if (variant == 4 || variant == 5) {
-        auto k64 = variant == 4 ? k_attention64<3> : k_attention64<4>;
-        hipLaunchKernelGGL(k64, grid, dim3(rows_per_block), 0, st, (const uint16_t*)qk, ldqk, (const uint16_t*)vt, (uint16_t*)out, ldo,
-                           heads, ntok, ntp, kp, heads * 64, nqb, xcd_remap);
-        return cvx_check_launch();
-    }
-#endif
-    hipLaunchKernelGGL(k, grid, dim3((variant == 8 || variant == 9) ? 512 : ATT_THREADS), 0, st, (const uint16_t*)qk, ldqk, (const uint16_t*)vt, (uint16_t*)out, ldo, heads,
-                       ntok, ntp, kp, heads * 64, nqb, xcd_remap);
-    return cvx_check_launch();
+    const AttnVariant* v = find_attn_variant(g_attn_variant);  // one read per call: a concurrent cvx_set_option cannot give a mixed launch
+    // The single-wave query blocks of the AUG kernels derive the departed waves' DMA offsets by XOR-ing 64 into wave 0's own, which is
+    // the other waves' row term only while a K row's byte pitch is a multiple of 128 (ldqk % 64 == 0: every DINOv2 width).  Other
+    // leading dimensions take the general kernel (variant 0: a running maximum per tile).
+    if (v->needs_ld64 && ldqk % 64 != 0) v = find_attn_variant(0);
+    return launch_attention(*v, "attention: grid too large", qk, ldqk, vt, out, ldo, slices, heads, ntok, ntp, kp, st);
 }

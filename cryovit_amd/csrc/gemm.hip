@@ -766,7 +766,7 @@ static std::atomic<int> g_conv_halo{2};
 static std::atomic<int> g_convt_small{1};  // dedicated kernel for the head's 16->8 and 32->32 transposed convolutions (0: GEMM tile)
 static std::atomic<int> g_conv_wide{1};  // 192-wide implicit-GEMM tile for C_out % 192 == 0 (0: three 64-wide tiles)
 // the other files' switches
-extern std::atomic<int> g_attn_variant, g_attn_xcd_remap, g_attn_mfma_prio, g_attn_half_tile;  // attention.hip
+int cvx_attn_set_option(const char* name, int value);         // attention.hip: the "attn_*" options
 extern std::atomic<int> g_ln_policy;                         // norm.hip
 extern std::atomic<int> g_win_attn_prefetch, g_win_attn_x32; // hiera.hip
 
@@ -811,13 +811,7 @@ extern "C" int cvx_set_option(const char* name, int value) {
         if (!one_of({0, 1, 2, 3})) return cvx_fail("set_option: ln_policy is a 2-bit mask (1: cacheable loads, 2: rows walked from the end)");
         g_ln_policy = value;
     }
-    else if (!strcmp(name, "attn_variant")) {
-        if (!one_of({0, 7}) && !(abl && one_of({1, 3, 4, 5, 6, 8, 9, 10, 11, 12, 13})))
-            return cvx_fail("set_option: unknown attn_variant (ablation variants need a -DCVX_ABLATION build)");
-        g_attn_variant = value;
-    } else if (!strcmp(name, "attn_xcd_remap")) g_attn_xcd_remap = value != 0;
-    else if (!strcmp(name, "attn_mfma_prio")) g_attn_mfma_prio = value & 3;
-    else if (!strcmp(name, "attn_half_tile")) g_attn_half_tile = value != 0;
+    else if (!strncmp(name, "attn_", 5)) return cvx_attn_set_option(name, value);
     else if (!strcmp(name, "tile_group_l")) {
         if (value < 1) return cvx_fail("set_option: tile_group_l must be >= 1");
         g_tile_group_l_host = value;

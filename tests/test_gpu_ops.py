@@ -239,11 +239,12 @@ def test_layernorm(gpu, C):
 
 @pytest.fixture
 def attn_variant(request):
-    """All attention kernels kept in attention.hip are parity-tested: 0 = 32 query rows per wave (4-wave blocks),
-    3 = three K/V buffers, 4 / 5 = 64 query rows per wave in 3- / 4-wave blocks, 6 (default) = 0 with the running maximum
-    subtracted inside the QK^T product (augmented k-step) and raised only when a row outgrows it by 2^3, 7 (default) = 6 with the
-    re-anchoring triggered by the tile's probability SUMS (the maximum is only computed in tile 0; a jump beyond the range of one
-    exp2 recomputes the tile against raised anchors)."""
+    """All attention kernels kept in attention.hip that compute real output are parity-tested: 0 = 32 query rows per wave (4-wave
+    blocks), running maximum per tile (the general kernel), 3 = 0 with three K/V buffers, 4 / 5 = 64 query rows per wave in 3- /
+    4-wave blocks, 6 = 0 with the maximum subtracted inside the QK^T product (augmented k-step) and raised only when a row outgrows
+    it by 2^3, 7 (default) = 6 with the re-anchoring triggered by the tile's probability SUMS (the maximum is only computed in tile
+    0; a jump beyond the range of one exp2 recomputes the tile against raised anchors), 8 / 9 = 7 in 8-wave blocks with three / two
+    K/V buffers.  Only 0 and 7 are in the product library; the others run on the ablation build."""
     from cryovit_amd import _lib
 
     set_option_or_skip("attn_variant", request.param)
@@ -311,6 +312,44 @@ def test_attention_qkv_row_major_v(gpu, nt, slices, heads):
     out2 = torch.zeros_like(out)
     ops.attention(qk2.to(gpu), vt.to(gpu), out2, slices=slices, heads=heads, ntok=nt, ntp=ntp, kp=kp)
     assert torch.equal(out2[:M].reshape(slices, ntp, C)[:, :nt], out[:M].reshape(slices, ntp, C)[:, :nt])
+
+
+def test_attention_launch_flags_change_speed_only(gpu):
+    """attn_half_tile, attn_mfma_prio and attn_xcd_remap travel to the kernel as bits of one flag word and must not change a single
+    output bit: the skipped half tile has P exactly 0, the other two move blocks or wave priorities.  133 tokens x 8 slices x 1 head:
+    eight (slice, head) pairs (the XCD remap is active), 5 valid keys in the last key tile (the half-tile skip is active), and a
+    lone-wave last query block."""
+    from cryovit_amd import _lib
+    from cryovit_amd.engine import ops
+
+    nt, slices, heads = 133, 8, 1
+    C = heads * 64
+    ntp = ops.round_up(nt, 8)
+    M = slices * ntp
+    q, k, v = rnd(slices, nt, heads, 64, seed=24) * 1.5, rnd(slices, nt, heads, 64, seed=25), rnd(slices, nt, heads, 64, seed=26)
+    buf = torch.randn(ops.alloc_rows(M), 3 * C, generator=torch.Generator().manual_seed(27)).to(torch.bfloat16)  # junk pad rows
+    rows = buf[:M].reshape(slices, ntp, 3 * C)
+    rows[:, :nt, :C] = bf(q * 0.125 * LOG2E).reshape(slices, nt, C)
+    rows[:, :nt, C : 2 * C] = bf(k).reshape(slices, nt, C)
+    rows[:, :nt, 2 * C :] = bf(v).reshape(slices, nt, C)
+    buf = buf.to(gpu)
+
+    def run():
+        out = torch.zeros(ops.alloc_rows(M), C, dtype=torch.bfloat16, device=gpu)
+        ops.attention_qkv(buf, out, slices=slices, heads=heads, ntok=nt, ntp=ntp)
+        return out[:M].reshape(slices, ntp, C)[:, :nt].clone()
+
+    want = run()
+    defaults = {"attn_half_tile": 1, "attn_mfma_prio": 2, "attn_xcd_remap": 1}
+    try:
+        for name, values in (("attn_half_tile", (0, 1)), ("attn_mfma_prio", (0, 1, 2, 3)), ("attn_xcd_remap", (0, 1))):
+            for value in values:
+                _lib.set_option(name, value)
+                assert torch.equal(run(), want), (name, value)
+            _lib.set_option(name, defaults[name])
+    finally:
+        for name, value in defaults.items():
+            _lib.set_option(name, value)
 
 
 @pytest.mark.parametrize("pad", [8, 24, 40])
@@ -1041,8 +1080,8 @@ def test_final_norm_hl_equals_fp32_form(gpu):
 
 
 def test_variants_on_the_ablation_build(gpu):
-    """The kernel variants that were measured and rejected (GEMM schedules 1 / 5 / 6 / 7 / 8 and the 4-wave tile, attention 0-6
-    incl. the 64-rows-per-wave forms, the tile-halo convolution) are compiled into ``libcryovit_hip_ablation.so`` only; their
+    """The kernel variants that were measured and rejected (GEMM schedules 1 / 5 / 6 / 7 / 8 and the 4-wave tile, attention 3, 4, 5,
+    6, 8 and 9 -- i.e. incl. the 64-rows-per-wave and 8-wave forms -- beside the shipped 0 and 7, the tile-halo convolution) are compiled into ``libcryovit_hip_ablation.so`` only; their
     parity tests -- the parametrised cases this module skips on the product library -- run here, in a child process that loads
     that build (``CVX_ABLATION_LIB=1``)."""
     import subprocess
