@@ -56,6 +56,13 @@ template <class E> struct epi_is_f16<E, decltype((void)E::F16)> { static constex
 __device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
 __device__ __forceinline__ float bflo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bfhi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+// A value kept as a PAIR of bf16 (the folded residual stream): hi = bf16(x), lo = bf16(x - hi), 16 significant bits;
+// read back as hi + lo, exact in fp32.  Two values per word, like pack2bf.
+__device__ __forceinline__ void split_hl(float x0, float x1, uint32_t& hi, uint32_t& lo) {
+    hi = pack2bf(x0, x1);
+    lo = pack2bf(x0 - bflo(hi), x1 - bfhi(hi));
+}
+__device__ __forceinline__ float2 merge_hl(uint32_t hi, uint32_t lo) { return float2{bflo(hi) + bflo(lo), bfhi(hi) + bfhi(lo)}; }
 
 // branch-free erf (Abramowitz-Stegun 7.1.26, |err| <= 1.5e-7): keeps fused epilogues straight-line
 __device__ __forceinline__ float erf_as(float x) {
@@ -143,9 +150,11 @@ __device__ __forceinline__ void cubic_taps(float t, float (&w)[4]) {
     w[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
 }
 
+// sum over aligned groups of LANES lanes (xor butterflies below the group width); 64 = the whole wave
+template <int LANES = 64>
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = LANES / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 __device__ __forceinline__ float wave_max(float v) {

@@ -248,6 +248,7 @@ struct EpiResidHL {
         r.xh = xh + m_off * ldx; r.xl = xl + m_off * ldx; r.part = part + m_off * 2; r.m_valid = m_valid - m_off;
         return r;
     }
+    // (merge_hl / split_hl of common.h written out: through the helpers hipcc schedules the k_gemm_nreg / k_gemm256_nreg instances differently)
     // accumulator-layout form (the 128 / 64-wide tiles: tails and small problems): 16 contiguous columns n0.. of row m per lane,
     // the four lane groups of a wave cover one 64-column slot.  Every lane runs the shuffles (no early exit).
     template <int NV>
@@ -767,7 +768,6 @@ static std::atomic<int> g_convt_small{1};  // dedicated kernel for the head's 16
 static std::atomic<int> g_conv_wide{1};  // 192-wide implicit-GEMM tile for C_out % 192 == 0 (0: three 64-wide tiles)
 // the other files' switches
 int cvx_attn_set_option(const char* name, int value);         // attention.hip: the "attn_*" options
-extern std::atomic<int> g_ln_policy;                         // norm.hip
 extern std::atomic<int> g_win_attn_prefetch, g_win_attn_x32; // hiera.hip
 
 extern "C" int cvx_set_option(const char* name, int value) {
@@ -807,10 +807,6 @@ extern "C" int cvx_set_option(const char* name, int value) {
         g_win_attn_prefetch = value;
     }
     else if (!strcmp(name, "win_attn_x32")) g_win_attn_x32 = value != 0;
-    else if (!strcmp(name, "ln_policy")) {
-        if (!one_of({0, 1, 2, 3})) return cvx_fail("set_option: ln_policy is a 2-bit mask (1: cacheable loads, 2: rows walked from the end)");
-        g_ln_policy = value;
-    }
     else if (!strncmp(name, "attn_", 5)) return cvx_attn_set_option(name, value);
     else if (!strcmp(name, "tile_group_l")) {
         if (value < 1) return cvx_fail("set_option: tile_group_l must be >= 1");

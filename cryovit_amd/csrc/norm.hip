@@ -3,13 +3,9 @@
 #include "common.h"
 #include "../../include/cryovit_hip.h"
 #include "host_util.h"
-#include <atomic>
 
 namespace cvx {
 
-constexpr int LN_MAXJ = 8;  // float4 per lane: C <= 64*4*8 = 2048
-
-// One wave per row; the row lives in registers (two-pass mean / centred variance, fp32).
 // The token stream is either one fp32 array or the bf16 (hi, lo) pair of the ViT path (x = hi + lo, exact in fp32)
 struct RowF32 {
     const float* row;
@@ -20,65 +16,88 @@ struct RowHL {
     const uint16_t* hi; const uint16_t* lo;
     __device__ __forceinline__ float4 ld4(int i) const {
         const uint2 a = *(const uint2*)(hi + 4 * i), b = *(const uint2*)(lo + 4 * i);
-        return float4{bflo(a.x) + bflo(b.x), bfhi(a.x) + bfhi(b.x), bflo(a.y) + bflo(b.y), bfhi(a.y) + bfhi(b.y)};
+        const float2 p = merge_hl(a.x, b.x), q = merge_hl(a.y, b.y);
+        return float4{p.x, p.y, q.x, q.y};
     }
-    __device__ __forceinline__ float ld1(int c) const { return bf2f(hi[c]) + bf2f(lo[c]); }
+    __device__ __forceinline__ float ld1(int c) const { return merge_hl(hi[c], lo[c]).x; }  // (a lone bf16 is the low half of a word)
 };
 
-template <class Row>
-__device__ __forceinline__ void ln_row_stats(const Row& row, int C4, int lane, float4 (&v)[LN_MAXJ], float& mean,
-                                             float& rstd, int C, float eps) {
-    float s = 0.f;
+// R rows in registers with their statistics.  A row is spread over LPR lanes (64, 32 or 16: a wave holds 64 / LPR rows); lane `sub`
+// of the group holds the chunks sub + LPR * j, j < NJ, of V consecutive floats (V = 4: one float4; V = 8: two adjacent ones).
+// C <= LPR * V * NJ; the widest forms, 64 * 4 * 8 and 64 * 8 * 4, reach 2048.
+constexpr int LN_MAXJ = 8, LN_MAXJ8 = 4;
+template <int V, int NJ, int R = 1>
+struct LnRows {
+    float4 v[R][NJ][V / 4];
+    float mean[R], rstd[R];
+};
+
+__device__ __forceinline__ float sum4(const float4& a) { return (a.x + a.y) + (a.z + a.w); }
+
+// Two-pass mean / centred variance (fp32) of the rows held in registers.  ALL rows' loads are issued before the first reduction
+// (R = 2: twice the loads in flight).  A full-wave row skips the chunks past C; a 16 / 32-lane group loads zeros for them, and its
+// xor butterflies stop below the group width.  Every lane of the wave must arrive here (shuffles).
+template <int LPR, int V, int NJ, int R, class Row>
+__device__ __forceinline__ void ln_row_stats(const Row (&rows)[R], int C, float eps, int sub, LnRows<V, NJ, R>& o) {
+    constexpr int H = V / 4;
+    const int CV = C >> (V == 4 ? 2 : 3);
+    float s[R];
 #pragma unroll
-    for (int j = 0; j < LN_MAXJ; ++j) {
-        const int i = lane + 64 * j;
-        if (i < C4) {
-            v[j] = row.ld4(i);
-            s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+    for (int r = 0; r < R; ++r) {
+        s[r] = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int i = sub + LPR * j;
+            if (LPR < 64 || i < CV) {
+#pragma unroll
+                for (int h = 0; h < H; ++h) o.v[r][j][h] = i < CV ? rows[r].ld4(H * i + h) : float4{0.f, 0.f, 0.f, 0.f};
+                float c = sum4(o.v[r][j][0]);
+                if (H == 2) c += sum4(o.v[r][j][1]);  // (the two halves of a chunk are added before the chunk is accumulated)
+                s[r] += c;
+            }
         }
     }
-    mean = wave_sum(s) / (float)C;
-    float q = 0.f;
 #pragma unroll
-    for (int j = 0; j < LN_MAXJ; ++j) {
-        const int i = lane + 64 * j;
-        if (i < C4) {
-            const float a = v[j].x - mean, b = v[j].y - mean, c = v[j].z - mean, d = v[j].w - mean;
-            q += (a * a + b * b) + (c * c + d * d);
+    for (int r = 0; r < R; ++r) {
+        const float mean = wave_sum<LPR>(s[r]) / (float)C;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (sub + LPR * j < CV) {
+#pragma unroll
+                for (int h = 0; h < H; ++h) {
+                    const float4& a = o.v[r][j][h];
+                    const float a0 = a.x - mean, a1 = a.y - mean, a2 = a.z - mean, a3 = a.w - mean;
+                    q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+                }
+            }
         }
+        o.mean[r] = mean;
+        o.rstd[r] = rsqrtf(wave_sum<LPR>(q) / (float)C + eps);
     }
-    rstd = rsqrtf(wave_sum(q) / (float)C + eps);
 }
 
-// Narrow rows (C < 1024: ViT-S/B, the Hiera stages): 4 channels per lane and step keeps more of the 64 lanes busy; plain
-// loads, because these activations are small enough to still sit in the L2 / MALL when the LayerNorm reads them.
-__global__ __launch_bounds__(256) void k_layernorm_bf16_v4(const float* __restrict__ x, long ldx, const float* __restrict__ w,
-                                                        const float* __restrict__ b, uint16_t* __restrict__ out, long ldo,
-                                                        long rows, int C, float eps) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int C4 = C >> 2;
-    float4 v[LN_MAXJ];
-    float mean, rstd;
-    ln_row_stats(RowF32{x + row * ldx}, C4, lane, v, mean, rstd, C, eps);
-#pragma unroll
-    for (int j = 0; j < LN_MAXJ; ++j) {
-        const int i = lane + 64 * j;
-        if (i < C4) {
-            const float4 ww = *(const float4*)(w + 4 * i), bb = *(const float4*)(b + 4 * i);
-            uint2 o;
-            o.x = pack2bf((v[j].x - mean) * rstd * ww.x + bb.x, (v[j].y - mean) * rstd * ww.y + bb.y);
-            o.y = pack2bf((v[j].z - mean) * rstd * ww.z + bb.z, (v[j].w - mean) * rstd * ww.w + bb.w);
-            *(uint2*)(out + row * ldo + 4 * i) = o;
-        }
-    }
+// Normalise four channels and store them: bf16 (x4, x8 = one 16-B store), and, through ln_out(), fp32 and fp16
+__device__ __forceinline__ uint2 ln_bf16(const float4& v, float mean, float rstd, const float4& w, const float4& b) {
+    return uint2{pack2bf((v.x - mean) * rstd * w.x + b.x, (v.y - mean) * rstd * w.y + b.y),
+                 pack2bf((v.z - mean) * rstd * w.z + b.z, (v.w - mean) * rstd * w.w + b.w)};
+}
+__device__ __forceinline__ void ln_store_bf16(uint16_t* dst, const float4 (&v)[1], float mean, float rstd, const float4 (&w)[1],
+                                              const float4 (&b)[1]) {
+    *(uint2*)dst = ln_bf16(v[0], mean, rstd, w[0], b[0]);
+}
+__device__ __forceinline__ void ln_store_bf16(uint16_t* dst, const float4 (&v)[2], float mean, float rstd, const float4 (&w)[2],
+                                              const float4 (&b)[2]) {
+    const uint2 lo = ln_bf16(v[0], mean, rstd, w[0], b[0]), hi = ln_bf16(v[1], mean, rstd, w[1], b[1]);
+    *(uint4*)dst = uint4{lo.x, lo.y, hi.x, hi.y};
 }
 
-
-// Narrower still (C <= 384: Hiera stages 1 and 2 with 144 / 288 channels): at one row per wave only 36 / 72 of the 64 / 128 lane slots
-// carry data.  Here a row takes LPR = 16 / 32 lanes, a wave 4 / 2 rows, a lane NJ float4s (lane-strided): 75 % of the slots, and
-// four / two rows' loads in flight per wave.  Reductions stay inside the LPR-lane group (xor butterflies below LPR).
+// Rows of C < 1024 channels (ViT-S/B, the Hiera stages), 4 channels per lane and step; plain loads, because these activations are
+// small enough to still sit in the L2 / MALL when the LayerNorm reads them.
+//   <64, 8>  one row per wave: 4 channels per step keeps more of the 64 lanes busy than 8 would.
+//   <32, 3>, <16, 3>  narrower still (C <= 384 / 192: Hiera stages 1 and 2 with 288 / 144 channels): at one row per wave only
+//   72 / 36 of the 128 / 64 lane slots carry data.  Here a row takes 32 / 16 lanes and a wave 2 / 4 rows: 75 % of the slots, and
+//   two / four rows' loads in flight per wave.
 template <int LPR, int NJ>
 __global__ __launch_bounds__(256) void k_layernorm_bf16_rows(const float* __restrict__ x, long ldx, const float* __restrict__ w,
                                                              const float* __restrict__ b, uint16_t* __restrict__ out, long ldo,
@@ -87,113 +106,46 @@ __global__ __launch_bounds__(256) void k_layernorm_bf16_rows(const float* __rest
     const int lane = threadIdx.x & 63, sub = lane % LPR;
     const long row = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
     const bool live = row < rows;
+    if (RPW == 1 && !live) return;          // (a wave whose only row is dead has no shuffle to keep convergent)
     const long rr = live ? row : rows - 1;  // (the clamped duplicate is computed and not stored: keeps the shuffles convergent)
-    const int C4 = C >> 2;
-    float4 v[NJ];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int i = sub + LPR * j;
-        v[j] = i < C4 ? *(const float4*)(x + rr * ldx + 4 * i) : float4{0.f, 0.f, 0.f, 0.f};
-        s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-    }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        if (sub + LPR * j < C4) {
-            const float a0 = v[j].x - mean, a1 = v[j].y - mean, a2 = v[j].z - mean, a3 = v[j].w - mean;
-            q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-        }
-    }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    const float rstd = rsqrtf(q / (float)C + eps);
+    LnRows<4, NJ> st;
+    ln_row_stats<LPR>({RowF32{x + rr * ldx}}, C, eps, sub, st);
     if (!live) return;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int i = sub + LPR * j;
-        if (i < C4) {
-            const float4 ww = *(const float4*)(w + 4 * i), bb = *(const float4*)(b + 4 * i);
-            uint2 o2;
-            o2.x = pack2bf((v[j].x - mean) * rstd * ww.x + bb.x, (v[j].y - mean) * rstd * ww.y + bb.y);
-            o2.y = pack2bf((v[j].z - mean) * rstd * ww.z + bb.z, (v[j].w - mean) * rstd * ww.w + bb.w);
-            *(uint2*)(out + row * ldo + 4 * i) = o2;
+        if (i < (C >> 2)) {
+            const float4 ww[1] = {*(const float4*)(w + 4 * i)}, bb[1] = {*(const float4*)(b + 4 * i)};
+            ln_store_bf16(out + row * ldo + 4 * i, st.v[0][j], st.mean[0], st.rstd[0], ww, bb);
         }
     }
 }
 
-// LN_V8: 8 consecutive channels per lane and step (two adjacent 16-B loads, ONE 16-B store of 8 bf16) -- full-width stores
-// instead of the 8-B ones of the float4 mapping; LN_ROWS rows per wave keep twice the loads in flight.
-constexpr int LN_MAXJ8 = 4;   // 8-channel chunks per lane: C <= 64*8*4 = 2048
+// Wide rows (C >= 1024, C % 8 == 0): 8 consecutive channels per lane and step (two adjacent 16-B loads, ONE 16-B store of 8 bf16)
+// -- full-width stores instead of the 8-B ones of the float4 mapping; LN_ROWS rows per wave keep twice the loads in flight.
+// Cacheable loads, and the blocks walk the rows from the END of the stream (the rows the producing GEMM wrote last may still sit in
+// the Infinity Cache): measured against streaming loads and the forward walk, 17.4 -> 16.2-16.4 ms per tomogram.
 constexpr int LN_ROWS = 2;
-
-// POLICY bit 0: plain (cacheable) loads instead of streaming ones; bit 1: blocks walk the rows from the END of the stream (the rows
-// the producing GEMM wrote last may still sit in the Infinity Cache) -- A/B switches, cvx_set_option("ln_policy", v)
-template <int POLICY>
 __global__ __launch_bounds__(256) void k_layernorm_bf16(const float* __restrict__ x, long ldx, const float* __restrict__ w,
                                                         const float* __restrict__ b, uint16_t* __restrict__ out, long ldo,
                                                         long rows, int C, float eps) {
     const int lane = threadIdx.x & 63;
-    const long blk = (POLICY & 2) ? (long)gridDim.x - 1 - blockIdx.x : (long)blockIdx.x;
-    const long row0 = (blk * 4 + (threadIdx.x >> 6)) * LN_ROWS;
+    const long row0 = (((long)gridDim.x - 1 - blockIdx.x) * 4 + (threadIdx.x >> 6)) * LN_ROWS;
     if (row0 >= rows) return;
-    const int C8 = C >> 3;
-    f32x4 v[LN_ROWS][LN_MAXJ8][2];
-    float s[LN_ROWS];
+    RowF32 src[LN_ROWS];
 #pragma unroll
-    for (int r = 0; r < LN_ROWS; ++r) {
-        s[r] = 0.f;
-        const long row = row0 + r < rows ? row0 + r : rows - 1;  // the clamped duplicate is computed and not stored
-        const float* xr = x + row * ldx;
-#pragma unroll
-        for (int j = 0; j < LN_MAXJ8; ++j) {
-            const int i = lane + 64 * j;
-            if (i < C8) {
-                v[r][j][0] = (POLICY & 1) ? *(const f32x4*)(xr + 8 * i) : __builtin_nontemporal_load((const f32x4*)(xr + 8 * i));
-                v[r][j][1] = (POLICY & 1) ? *(const f32x4*)(xr + 8 * i + 4) : __builtin_nontemporal_load((const f32x4*)(xr + 8 * i + 4));
-                s[r] += ((v[r][j][0].x + v[r][j][0].y) + (v[r][j][0].z + v[r][j][0].w)) +
-                        ((v[r][j][1].x + v[r][j][1].y) + (v[r][j][1].z + v[r][j][1].w));
-            }
-        }
-    }
-    float mean[LN_ROWS], rstd[LN_ROWS];
-#pragma unroll
-    for (int r = 0; r < LN_ROWS; ++r) {
-        mean[r] = wave_sum(s[r]) / (float)C;
-        float q = 0.f;
-#pragma unroll
-        for (int j = 0; j < LN_MAXJ8; ++j) {
-            if (lane + 64 * j < C8) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const float a0 = v[r][j][h].x - mean[r], a1 = v[r][j][h].y - mean[r], a2 = v[r][j][h].z - mean[r],
-                                a3 = v[r][j][h].w - mean[r];
-                    q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-                }
-            }
-        }
-        rstd[r] = rsqrtf(wave_sum(q) / (float)C + eps);
-    }
+    for (int r = 0; r < LN_ROWS; ++r) src[r].row = x + (row0 + r < rows ? row0 + r : rows - 1) * ldx;  // the clamped duplicate is computed and not stored
+    LnRows<8, LN_MAXJ8, LN_ROWS> st;
+    ln_row_stats<64>(src, C, eps, lane, st);
 #pragma unroll
     for (int j = 0; j < LN_MAXJ8; ++j) {
         const int i = lane + 64 * j;
-        if (i < C8) {
-            const float4 w0 = *(const float4*)(w + 8 * i), w1 = *(const float4*)(w + 8 * i + 4);
-            const float4 b0 = *(const float4*)(b + 8 * i), b1 = *(const float4*)(b + 8 * i + 4);
+        if (i < (C >> 3)) {
+            const float4 ww[2] = {*(const float4*)(w + 8 * i), *(const float4*)(w + 8 * i + 4)};
+            const float4 bb[2] = {*(const float4*)(b + 8 * i), *(const float4*)(b + 8 * i + 4)};
 #pragma unroll
-            for (int r = 0; r < LN_ROWS; ++r) {
-                if (row0 + r >= rows) continue;
-                const float m = mean[r], rs = rstd[r];
-                uint4 o;
-                o.x = pack2bf((v[r][j][0].x - m) * rs * w0.x + b0.x, (v[r][j][0].y - m) * rs * w0.y + b0.y);
-                o.y = pack2bf((v[r][j][0].z - m) * rs * w0.z + b0.z, (v[r][j][0].w - m) * rs * w0.w + b0.w);
-                o.z = pack2bf((v[r][j][1].x - m) * rs * w1.x + b1.x, (v[r][j][1].y - m) * rs * w1.y + b1.y);
-                o.w = pack2bf((v[r][j][1].z - m) * rs * w1.z + b1.z, (v[r][j][1].w - m) * rs * w1.w + b1.w);
-                *(uint4*)(out + (row0 + r) * ldo + 8 * i) = o;
-            }
+            for (int r = 0; r < LN_ROWS; ++r)
+                if (row0 + r < rows) ln_store_bf16(out + (row0 + r) * ldo + 8 * i, st.v[r][j], st.mean[r], st.rstd[r], ww, bb);
         }
     }
 }
@@ -226,38 +178,24 @@ __global__ __launch_bounds__(256) void k_final_norm(const void* __restrict__ x, 
         else return RowF32{(const float*)x + (row0 + t) * ldx};
     };
 
-    // phase 1: statistics (and the channels-last fp16 copy) -- one wave per token, 16 tokens per wave
+    // phase 1: statistics, the fp32 tokens x_norm_patchtokens [slice][p][C] (the encoder-protocol output) and the channels-last
+    // fp16 copy -- one wave per token, 16 tokens per wave
     for (int t = wave; t < ntile; t += 4) {
-        float4 v[LN_MAXJ];
-        float mean, rstd;
-        ln_row_stats(row_of(t), C4, lane, v, mean, rstd, C, eps);
+        LnRows<4, LN_MAXJ> st;
+        ln_row_stats<64>({row_of(t)}, C, eps, lane, st);
+        const float mean = st.mean[0], rstd = st.rstd[0];
         if (lane == 0) { s_mean[t] = mean; s_rstd[t] = rstd; }
-        if (f32) {  // x_norm_patchtokens [slice][p][C] in fp32 (the encoder-protocol output)
-            float* orow = f32 + ((long)slice * npatch + p0 + t) * C;
+        if (!f32 && !cl) continue;
+        const long orow = ((long)slice * npatch + p0 + t) * C;
 #pragma unroll
-            for (int j = 0; j < LN_MAXJ; ++j) {
-                const int i = lane + 64 * j;
-                if (i < C4) {
-                    const float4 ww = *(const float4*)(w + 4 * i), bb = *(const float4*)(b + 4 * i);
-                    float4 o;
-                    o.x = ln_out(v[j].x, mean, rstd, ww.x, bb.x); o.y = ln_out(v[j].y, mean, rstd, ww.y, bb.y);
-                    o.z = ln_out(v[j].z, mean, rstd, ww.z, bb.z); o.w = ln_out(v[j].w, mean, rstd, ww.w, bb.w);
-                    *(float4*)(orow + 4 * i) = o;
-                }
-            }
-        }
-        if (cl) {
-            uint16_t* orow = cl + ((long)slice * npatch + p0 + t) * C;
-#pragma unroll
-            for (int j = 0; j < LN_MAXJ; ++j) {
-                const int i = lane + 64 * j;
-                if (i < C4) {
-                    const float4 ww = *(const float4*)(w + 4 * i), bb = *(const float4*)(b + 4 * i);
-                    uint2 o;
-                    o.x = pack2h(ln_out(v[j].x, mean, rstd, ww.x, bb.x), ln_out(v[j].y, mean, rstd, ww.y, bb.y));
-                    o.y = pack2h(ln_out(v[j].z, mean, rstd, ww.z, bb.z), ln_out(v[j].w, mean, rstd, ww.w, bb.w));
-                    *(uint2*)(orow + 4 * i) = o;
-                }
+        for (int j = 0; j < LN_MAXJ; ++j) {
+            const int i = lane + 64 * j;
+            if (i < C4) {
+                const float4 ww = *(const float4*)(w + 4 * i), bb = *(const float4*)(b + 4 * i), v = st.v[0][j][0];
+                const float4 o{ln_out(v.x, mean, rstd, ww.x, bb.x), ln_out(v.y, mean, rstd, ww.y, bb.y), ln_out(v.z, mean, rstd, ww.z, bb.z),
+                               ln_out(v.w, mean, rstd, ww.w, bb.w)};
+                if (f32) *(float4*)(f32 + orow + 4 * i) = o;
+                if (cl) *(uint2*)(cl + orow + 4 * i) = uint2{pack2h(o.x, o.y), pack2h(o.z, o.w)};
             }
         }
     }
@@ -462,48 +400,21 @@ __global__ __launch_bounds__(256) void k_split_stream(const float* __restrict__ 
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const int C8 = C >> 3;
-    const float* xr = x + row * ldx;
-    f32x4 v[LN_MAXJ8][2];
-    float s = 0.f;
+    LnRows<8, LN_MAXJ8> st;
+    ln_row_stats<64>({RowF32{x + row * ldx}}, C, eps, lane, st);
 #pragma unroll
     for (int j = 0; j < LN_MAXJ8; ++j) {
         const int i = lane + 64 * j;
-        if (i < C8) {
-            v[j][0] = *(const f32x4*)(xr + 8 * i);
-            v[j][1] = *(const f32x4*)(xr + 8 * i + 4);
-            s += ((v[j][0].x + v[j][0].y) + (v[j][0].z + v[j][0].w)) + ((v[j][1].x + v[j][1].y) + (v[j][1].z + v[j][1].w));
-        }
-    }
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < LN_MAXJ8; ++j) {
-        const int i = lane + 64 * j;
-        if (i < C8) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float a0 = v[j][h].x - mean, a1 = v[j][h].y - mean, a2 = v[j][h].z - mean, a3 = v[j][h].w - mean;
-                q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-            }
+        if (i < (C >> 3)) {
+            const float4 v0 = st.v[0][j][0], v1 = st.v[0][j][1];
             uint4 oh, ol;
-            uint32_t* ph = &oh.x;
-            uint32_t* pl = &ol.x;
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const float x0 = v[j][h][2 * k], x1 = v[j][h][2 * k + 1];
-                    const uint32_t hw = pack2bf(x0, x1);
-                    ph[2 * h + k] = hw;
-                    pl[2 * h + k] = pack2bf(x0 - bflo(hw), x1 - bfhi(hw));
-                }
+            split_hl(v0.x, v0.y, oh.x, ol.x); split_hl(v0.z, v0.w, oh.y, ol.y);
+            split_hl(v1.x, v1.y, oh.z, ol.z); split_hl(v1.z, v1.w, oh.w, ol.w);
             *(uint4*)(xh + row * ld + 8 * i) = oh;
             *(uint4*)(xl + row * ld + 8 * i) = ol;
         }
     }
-    const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
-    if (lane == 0) *(float2*)(rowstat + 2 * row) = float2{rstd, -mean * rstd};
+    if (lane == 0) *(float2*)(rowstat + 2 * row) = float2{st.rstd[0], -st.mean[0] * st.rstd[0]};
 }
 
 // (hi, lo) -> fp32 rows (x = hi + lo, exact): where a folded stretch of the stream hands over to kernels that take fp32 (Hiera's
@@ -516,8 +427,9 @@ __global__ __launch_bounds__(256) void k_merge_stream(const uint16_t* __restrict
     const int c = (int)(idx - row * C8) * 8;
     const uint4 a = *(const uint4*)(xh + row * ld + c), b = *(const uint4*)(xl + row * ld + c);
     float* o = x + row * ldx + c;
-    *(float4*)o = float4{bflo(a.x) + bflo(b.x), bfhi(a.x) + bfhi(b.x), bflo(a.y) + bflo(b.y), bfhi(a.y) + bfhi(b.y)};
-    *(float4*)(o + 4) = float4{bflo(a.z) + bflo(b.z), bfhi(a.z) + bfhi(b.z), bflo(a.w) + bflo(b.w), bfhi(a.w) + bfhi(b.w)};
+    const float2 p0 = merge_hl(a.x, b.x), p1 = merge_hl(a.y, b.y), p2 = merge_hl(a.z, b.z), p3 = merge_hl(a.w, b.w);
+    *(float4*)o = float4{p0.x, p0.y, p1.x, p1.y};
+    *(float4*)(o + 4) = float4{p2.x, p2.y, p3.x, p3.y};
 }
 
 // part[slot][part_rows][2] (sum, sum of squares of a row over 64 columns, written by the hi/lo residual epilogue) ->
@@ -553,34 +465,30 @@ __global__ __launch_bounds__(64) void k_rowstat_finalize(const float* __restrict
 
 using namespace cvx;
 
-std::atomic<int> g_ln_policy{3};  // cvx_set_option("ln_policy", 0..3) -- gemm.hip; 3 (cacheable loads, rows from the end) measured 17.4 -> 16.2-16.4 ms per tomogram
-
 extern "C" int cvx_layernorm_bf16(const float* x, long ldx, const float* w, const float* b, void* out, long ldo,
                                   long rows, int C, float eps, hipStream_t st) {
     if (rows <= 0) return 0;
     if (C % 4 || C > 2048 || ldx % 4 || ldo % 4) return cvx_fail("layernorm: C%4==0, C<=2048, ld%4==0 required");
-    if (C <= 192) {  // 16 lanes per row, 4 rows per wave
-        hipLaunchKernelGGL((k_layernorm_bf16_rows<16, 3>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, x, ldx, w, b, (uint16_t*)out, ldo, rows,
-                           C, eps);
+    auto launch = [&](auto kernel, long rows_per_block) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0, st, x, ldx, w, b, (uint16_t*)out,
+                           ldo, rows, C, eps);
         return cvx_check_launch();
-    }
-    if (C <= 384) {  // 32 lanes per row, 2 rows per wave
-        hipLaunchKernelGGL((k_layernorm_bf16_rows<32, 3>), dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, st, x, ldx, w, b, (uint16_t*)out, ldo, rows,
-                           C, eps);
-        return cvx_check_launch();
-    }
-    if (C < 1024 || C % 8 || ldo % 8) {
-        hipLaunchKernelGGL(k_layernorm_bf16_v4, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, ldx, w, b, (uint16_t*)out, ldo, rows, C,
-                           eps);
-        return cvx_check_launch();
-    }
-    const dim3 grid((unsigned)((rows + 4 * LN_ROWS - 1) / (4 * LN_ROWS)));
-    switch (g_ln_policy.load()) {
-        case 1: hipLaunchKernelGGL(k_layernorm_bf16<1>, grid, dim3(256), 0, st, x, ldx, w, b, (uint16_t*)out, ldo, rows, C, eps); break;
-        case 2: hipLaunchKernelGGL(k_layernorm_bf16<2>, grid, dim3(256), 0, st, x, ldx, w, b, (uint16_t*)out, ldo, rows, C, eps); break;
-        case 3: hipLaunchKernelGGL(k_layernorm_bf16<3>, grid, dim3(256), 0, st, x, ldx, w, b, (uint16_t*)out, ldo, rows, C, eps); break;
-        default: hipLaunchKernelGGL(k_layernorm_bf16<0>, grid, dim3(256), 0, st, x, ldx, w, b, (uint16_t*)out, ldo, rows, C, eps); break;
-    }
+    };
+    if (C <= 192) return launch(k_layernorm_bf16_rows<16, 3>, 16);  // 16 lanes per row, 4 rows per wave
+    if (C <= 384) return launch(k_layernorm_bf16_rows<32, 3>, 8);   // 32 lanes per row, 2 rows per wave
+    if (C < 1024 || C % 8 || ldo % 8) return launch(k_layernorm_bf16_rows<64, LN_MAXJ>, 4);
+    return launch(k_layernorm_bf16, 4 * LN_ROWS);
+}
+
+template <bool HL>
+static int final_norm_launch(const char* bad_shape, const void* x, const void* xlo, long ldx, const float* w, const float* b, float eps, int slices,
+                             int ntp, int tok0, int hp, int wp, int C, void* feats_f16, long d_total, long d0, void* feats_cl,
+                             float* tokens_f32, hipStream_t st) {
+    if (C % 4 || C > 64 * 4 * LN_MAXJ || ldx % 4) return cvx_fail(bad_shape);
+    const int npatch = hp * wp;
+    dim3 grid((npatch + FN_TOK - 1) / FN_TOK, slices);
+    hipLaunchKernelGGL(k_final_norm<HL>, grid, dim3(256), 0, st, x, xlo, ldx, w, b, eps, ntp, tok0, npatch, C, (_Float16*)feats_f16, d_total, d0,
+                       (uint16_t*)feats_cl, tokens_f32);
     return cvx_check_launch();
 }
 
@@ -588,12 +496,8 @@ extern "C" int cvx_final_norm_features(const float* x, long ldx, const float* w,
                                        int ntp, int tok0, int hp, int wp, int C, void* feats_f16, long d_total, long d0,
                                        void* feats_cl, float* tokens_f32, hipStream_t st) {
     if (slices <= 0) return 0;
-    if (C % 4 || C > 64 * 4 * LN_MAXJ || ldx % 4) return cvx_fail("final_norm: C%4==0, C<=2048, ldx%4==0 required");
-    const int npatch = hp * wp;
-    dim3 grid((npatch + FN_TOK - 1) / FN_TOK, slices);
-    hipLaunchKernelGGL(k_final_norm<false>, grid, dim3(256), 0, st, (const void*)x, (const void*)nullptr, ldx, w, b, eps, ntp, tok0, npatch, C,
-                       (_Float16*)feats_f16, d_total, d0, (uint16_t*)feats_cl, tokens_f32);
-    return cvx_check_launch();
+    return final_norm_launch<false>("final_norm: C%4==0, C<=2048, ldx%4==0 required", x, nullptr, ldx, w, b, eps, slices, ntp, tok0, hp, wp, C,
+                                    feats_f16, d_total, d0, feats_cl, tokens_f32, st);
 }
 
 extern "C" int cvx_final_norm_features_hl(const void* xh, const void* xl, long ld, const float* w, const float* b, float eps, int slices,
@@ -601,12 +505,8 @@ extern "C" int cvx_final_norm_features_hl(const void* xh, const void* xl, long l
                                           void* feats_cl, float* tokens_f32, hipStream_t st) {
     if (slices <= 0) return 0;
     if (!xh || !xl) return cvx_fail("final_norm_hl: null stream");
-    if (C % 4 || C > 64 * 4 * LN_MAXJ || ld % 4) return cvx_fail("final_norm_hl: C%4==0, C<=2048, ld%4==0 required");
-    const int npatch = hp * wp;
-    dim3 grid((npatch + FN_TOK - 1) / FN_TOK, slices);
-    hipLaunchKernelGGL(k_final_norm<true>, grid, dim3(256), 0, st, xh, xl, ld, w, b, eps, ntp, tok0, npatch, C, (_Float16*)feats_f16,
-                       d_total, d0, (uint16_t*)feats_cl, tokens_f32);
-    return cvx_check_launch();
+    return final_norm_launch<true>("final_norm_hl: C%4==0, C<=2048, ld%4==0 required", xh, xl, ld, w, b, eps, slices, ntp, tok0, hp, wp, C,
+                                   feats_f16, d_total, d0, feats_cl, tokens_f32, st);
 }
 
 extern "C" int cvx_split_stream(const float* x, long ldx, void* xh, void* xl, long ld, float* rowstat, long rows, int C, float eps,

@@ -29,7 +29,7 @@ import torch.nn.functional as F
 
 from cryovit_amd._lib import EPI_RESID_HL, EPI_BF16, EPI_BF16_GELU, EPI_F32, EPI_PATCH, EPI_RESID
 from cryovit_amd.engine import ops
-from cryovit_amd.engine.ops import alloc_rows, round_up
+from cryovit_amd.engine.ops import alloc_rows, pack_linear, round_up
 
 
 @dataclass(frozen=True)
@@ -172,27 +172,9 @@ class HieraEngine:
         cfg, dev = self.cfg, self.device
         g = lambda k: sd[k].detach().float()  # noqa: E731
 
-        def lin(wk, bk):
-            w, b = g(wk), g(bk)
-            w = w.reshape(w.shape[0], -1)
-            n_pad, k_pad = _npad(w.shape[0], w.shape[1]), round_up(w.shape[1], 64)
-            wp = torch.zeros(n_pad, k_pad, dtype=torch.bfloat16, device=dev)
-            wp[: w.shape[0], : w.shape[1]] = w.to(dev).to(torch.bfloat16)
-            bp = torch.zeros(n_pad, dtype=torch.float32, device=dev)
-            bp[: b.numel()] = b.to(dev)
-            return wp, bp
-
-        def ln_lin(wk, bk, gk, betak):
-            """A linear layer behind LayerNorm(gamma, beta), folded: W' = bf16(W * gamma), bias table [2, n_pad] = b + W beta | column
-            sums of W' (engine/vit.py::_pack)."""
-            w, b, gamma, beta = g(wk), g(bk), g(gk), g(betak)
-            n_pad, k_pad = _npad(w.shape[0], w.shape[1]), round_up(w.shape[1], 64)
-            wp = torch.zeros(n_pad, k_pad, dtype=torch.bfloat16, device=dev)
-            wp[: w.shape[0], : w.shape[1]] = (w * gamma[None, :]).to(dev).to(torch.bfloat16)
-            bc = torch.zeros(2, n_pad, dtype=torch.float32, device=dev)
-            bc[0, : w.shape[0]] = (b.double() + w.double() @ beta.double()).float().to(dev)
-            bc[1] = wp.double().sum(dim=1).float()
-            return wp, bc
+        def lin(wk, bk, ln=None):  # ln = the keys of the LayerNorm (gain, bias) folded into the layer (ops.pack_linear)
+            w = g(wk).flatten(1)
+            return pack_linear(w, g(bk), _npad(*w.shape), round_up(w.shape[1], 64), dev, ln=ln and (g(ln[0]), g(ln[1])))
 
         E, G0 = cfg.embed_dim, self.grids[0]
         self.pe_w, self.pe_b = lin("trunk.patch_embed.proj.weight", "trunk.patch_embed.proj.bias")  # K = c*49 + ky*7 + kx
@@ -214,9 +196,9 @@ class HieraEngine:
             if dim != dout:
                 blk["short"] = lin(p + "proj.weight", p + "proj.bias")
             if self.fold_ln and dout % 64 == 0:  # second half of the block (norm2 -> fc1) on the folded stream
-                blk["fc1_ln"] = ln_lin(p + "mlp.layers.0.weight", p + "mlp.layers.0.bias", p + "norm2.weight", p + "norm2.bias")
+                blk["fc1_ln"] = lin(p + "mlp.layers.0.weight", p + "mlp.layers.0.bias", ln=(p + "norm2.weight", p + "norm2.bias"))
                 if dim == dout:                  # ... and the first half (norm1 -> qkv) unless this is a stage transition
-                    blk["qkv_ln"] = ln_lin(p + "attn.qkv.weight", p + "attn.qkv.bias", p + "norm1.weight", p + "norm1.bias")
+                    blk["qkv_ln"] = lin(p + "attn.qkv.weight", p + "attn.qkv.bias", ln=(p + "norm1.weight", p + "norm1.bias"))
             self.blocks.append(blk)
         n = len(cfg.stages) - 1
         self.neck = [lin(f"neck.convs.{n - s}.conv.weight", f"neck.convs.{n - s}.conv.bias") for s in range(n + 1)]  # by stage

@@ -27,6 +27,28 @@ def alloc_rows(m: int) -> int:
     return round_up(m, ROW_PAD) + ROW_PAD
 
 
+def padded(t: torch.Tensor, shape, dtype, device) -> torch.Tensor:
+    """`t` converted to `dtype` in the leading corner of a zero tensor of `shape`, built where `t` lives and then moved to `device`."""
+    out = torch.zeros(shape, dtype=dtype, device=t.device)
+    out[tuple(slice(0, n) for n in t.shape)] = t.to(dtype)
+    return out.to(device)
+
+
+def pack_linear(w: torch.Tensor, b: torch.Tensor, n_pad: int, k_pad: int, device, ln=None):
+    """(bf16 [n_pad, k_pad] weight, fp32 bias) of a linear layer W[N][K], zero-padded, on `device`; fp32 inputs.  The bias is [n_pad].
+    With ``ln=(gamma, beta)`` the layer consumes LayerNorm(gamma, beta) and the norm is folded in: the gain goes into the weight,
+    W' = bf16(W * gamma) (ONE rounding), and the bias becomes [2, n_pad] = b' = b + W beta (fp64 matvec) | cs[n] = sum_k W'[n][k] (of the
+    ROUNDED weight: it multiplies -mean*rstd against the same products the MFMA accumulates).  Everything is computed where the
+    checkpoint lives and moved afterwards; the bf16 rounding is the same on either side and the fp64 sum of K bf16 values is exact."""
+    w = w.reshape(w.shape[0], -1)
+    if ln is None:
+        return padded(w, (n_pad, k_pad), torch.bfloat16, device), padded(b.reshape(-1), (n_pad,), torch.float32, device)
+    gamma, beta = ln
+    wq = padded(w * gamma[None, :], (n_pad, k_pad), torch.bfloat16, w.device)
+    bc = torch.stack([padded((b.double() + w.double() @ beta.double()).float(), (n_pad,), torch.float32, w.device), wq.double().sum(dim=1).float()])
+    return wq.to(device), bc.to(device)
+
+
 def norm_device(device) -> torch.device:
     """torch.device with an explicit index ("cuda" -> the active device), so it compares equal to ``tensor.device``."""
     d = torch.device(device)

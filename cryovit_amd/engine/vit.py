@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 from cryovit_amd._lib import EPI_BF16, EPI_BF16_GELU, EPI_PATCH, EPI_RESID, EPI_RESID_HL, EPI_SWIGLU, EPI_VT
 from cryovit_amd.engine import ops
-from cryovit_amd.engine.ops import alloc_rows, round_up
+from cryovit_amd.engine.ops import alloc_rows, pack_linear, padded, round_up
 
 
 @dataclass(frozen=True)
@@ -61,18 +61,6 @@ VIT_CONFIGS = {
     "dinov2_vitb14_reg": VitConfig(768, 12, 12, "mlp", 3072),
     "dinov2_vits14_reg": VitConfig(384, 12, 6, "mlp", 1536),
 }
-
-
-def _bf16_padded(w: torch.Tensor, n_pad: int, k_pad: int) -> torch.Tensor:
-    out = torch.zeros(n_pad, k_pad, dtype=torch.bfloat16, device=w.device)
-    out[: w.shape[0], : w.shape[1]] = w.to(torch.bfloat16)
-    return out
-
-
-def _f32_padded(v: torch.Tensor, n_pad: int) -> torch.Tensor:
-    out = torch.zeros(n_pad, dtype=torch.float32, device=v.device)
-    out[: v.numel()] = v.float().reshape(-1)
-    return out
 
 
 def random_state_dict(cfg: "VitConfig", seed: int, device="cpu", std: float = 0.02) -> dict:
@@ -150,10 +138,9 @@ class VitEngine:
         # patch embed: the three input channels are identical copies (vit_dataset.py:117-118) -> sum the kernel
         # over channels (exact in real arithmetic), K = 196 padded to 256
         pe = g("patch_embed.proj.weight").sum(dim=1).reshape(C, 196)
-        w["pe_w"] = up(_bf16_padded(pe, n128, 256))
-        w["pe_b"] = up(_f32_padded(g("patch_embed.proj.bias"), n128))
+        w["pe_w"], w["pe_b"] = pack_linear(pe, g("patch_embed.proj.bias"), n128, 256, dev)
         # general 3-channel kernel for the protocol entry point forward_features(x): K = 588 padded to 640
-        w["pe3_w"] = up(_bf16_padded(g("patch_embed.proj.weight").reshape(C, 588), n128, 640))
+        w["pe3_w"] = padded(g("patch_embed.proj.weight").reshape(C, 588), (n128, 640), torch.bfloat16, dev)
         w["reg"] = up(g("register_tokens").reshape(cfg.n_reg, C))
         w["norm_w"], w["norm_b"] = up(g("norm.weight")), up(g("norm.bias"))
         self.hid_pad = round_up(cfg.ffn_hidden, 64)
@@ -161,20 +148,9 @@ class VitEngine:
         # head_dim^-0.5 * log2(e) folded into the Q rows in fp32 BEFORE the bf16 rounding: the attention kernel works in log2
         # units (p = exp2(s - m), no per-score multiply; oracle/dinov2.py::forward_features_bf16_storage mirrors the rounding point)
         scale = 64**-0.5 * math.log2(math.e)
-        fold = self.fold_ln
 
-        def ln_linear(wm, bias, gamma, beta, n_pad):
-            """(packed bf16 weight, fp32 bias tensor) of a linear layer that consumes LayerNorm(gamma, beta).  fold_ln: the gain goes
-            into the weight, W' = bf16(W * gamma) (ONE rounding), and the bias tensor becomes [2, n_pad] = b' = b + W beta (fp64
-            matvec) | cs[n] = sum_k W'[n][k] (of the ROUNDED weight: it multiplies -mean*rstd against the same products the MFMA
-            accumulates)."""
-            if not fold:
-                return _bf16_padded(wm, n_pad, wm.shape[1]), _f32_padded(bias, n_pad)
-            wq = _bf16_padded(wm * gamma[None, :], n_pad, wm.shape[1])
-            bc = torch.zeros(2, n_pad, dtype=torch.float32, device=wm.device)
-            bc[0, : wm.shape[0]] = (bias.double() + wm.double() @ beta.double()).float()
-            bc[1] = wq.double().sum(dim=1).float()
-            return wq, bc
+        def folded(gamma, beta):  # pack_linear's `ln` of a linear layer behind LayerNorm(gamma, beta)
+            return (gamma, beta) if self.fold_ln else None
 
         for i in range(cfg.depth):
             p = f"blocks.{i}."
@@ -183,21 +159,20 @@ class VitEngine:
             qkv_b[:C] *= scale
             g1, b1, g2, b2 = g(p + "norm1.weight"), g(p + "norm1.bias"), g(p + "norm2.weight"), g(p + "norm2.bias")
             if self.merge_qkv:
-                qk_w, qk_b = ln_linear(qkv_w, qkv_b, g1, b1, round_up(3 * C, 128))  # all 3C rows: q (scaled) | k | v
+                qk_w, qk_b = pack_linear(qkv_w, qkv_b, round_up(3 * C, 128), C, dev, folded(g1, b1))  # all 3C rows: q (scaled) | k | v
                 v_w, v_b = qk_w[:0], qk_b[..., :0]  # (not read)
             else:
-                qk_w, qk_b = ln_linear(qkv_w[: 2 * C], qkv_b[: 2 * C], g1, b1, round_up(2 * C, 128))
-                v_w, v_b = ln_linear(qkv_w[2 * C :], qkv_b[2 * C :], g1, b1, n128)
+                qk_w, qk_b = pack_linear(qkv_w[: 2 * C], qkv_b[: 2 * C], round_up(2 * C, 128), C, dev, folded(g1, b1))
+                v_w, v_b = pack_linear(qkv_w[2 * C :], qkv_b[2 * C :], n128, C, dev, folded(g1, b1))
             blk = {
                 "ln1_w": up(g1), "ln1_b": up(b1),
-                "qk_w": up(qk_w), "qk_b": up(qk_b),
-                "v_w": up(v_w), "v_b": up(v_b),
-                "proj_w": up(_bf16_padded(g(p + "attn.proj.weight"), n128, C)),
-                "proj_b": up(_f32_padded(g(p + "attn.proj.bias"), n128)),
-                "ls1": up(_f32_padded(g(p + "ls1.gamma"), n128)),
+                "qk_w": qk_w, "qk_b": qk_b,
+                "v_w": v_w, "v_b": v_b,
+                "ls1": padded(g(p + "ls1.gamma"), (n128,), torch.float32, dev),
                 "ln2_w": up(g2), "ln2_b": up(b2),
-                "ls2": up(_f32_padded(g(p + "ls2.gamma"), n128)),
+                "ls2": padded(g(p + "ls2.gamma"), (n128,), torch.float32, dev),
             }
+            blk["proj_w"], blk["proj_b"] = pack_linear(g(p + "attn.proj.weight"), g(p + "attn.proj.bias"), n128, C, dev)
             Hd, Hp = cfg.ffn_hidden, self.hid_pad
             if cfg.ffn == "swiglu":
                 w12, b12 = g(p + "mlp.w12.weight"), g(p + "mlp.w12.bias")
@@ -207,15 +182,11 @@ class VitEngine:
                 # interleave in blocks of 8 so one lane's 16 accumulators are 8 gates + their 8 values (EpiSwiGLU)
                 inter_w = torch.stack([a_w.reshape(-1, 8, C), b_w.reshape(-1, 8, C)], dim=1).reshape(2 * Hp, C)
                 inter_b = torch.stack([a_b.reshape(-1, 8), b_b.reshape(-1, 8)], dim=1).reshape(2 * Hp)
-                f1_w, f1_b = ln_linear(inter_w, inter_b, g2, b2, 2 * Hp)
-                blk["ffn1_w"], blk["ffn1_b"] = up(f1_w), up(f1_b)
-                blk["ffn2_w"] = up(_bf16_padded(g(p + "mlp.w3.weight"), n128, Hp))
-                blk["ffn2_b"] = up(_f32_padded(g(p + "mlp.w3.bias"), n128))
+                blk["ffn1_w"], blk["ffn1_b"] = pack_linear(inter_w, inter_b, 2 * Hp, C, dev, folded(g2, b2))
+                blk["ffn2_w"], blk["ffn2_b"] = pack_linear(g(p + "mlp.w3.weight"), g(p + "mlp.w3.bias"), n128, Hp, dev)
             else:
-                f1_w, f1_b = ln_linear(g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias"), g2, b2, Hp)
-                blk["ffn1_w"], blk["ffn1_b"] = up(f1_w), up(f1_b)
-                blk["ffn2_w"] = up(_bf16_padded(g(p + "mlp.fc2.weight"), n128, Hp))
-                blk["ffn2_b"] = up(_f32_padded(g(p + "mlp.fc2.bias"), n128))
+                blk["ffn1_w"], blk["ffn1_b"] = pack_linear(g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias"), Hp, C, dev, folded(g2, b2))
+                blk["ffn2_w"], blk["ffn2_b"] = pack_linear(g(p + "mlp.fc2.weight"), g(p + "mlp.fc2.bias"), n128, Hp, dev)
             blocks.append(blk)
         self.w, self.blocks = w, blocks
 

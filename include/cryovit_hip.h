@@ -45,8 +45,8 @@ int cvx_device_arch(char* buf, int buflen);
  * no product path sets one.  Returns non-zero (cvx_last_error) for an unknown name or a value the library was not built with (the product
  * library holds the shipped kernel variants only; the rejected ones live in the -DCVX_ABLATION build).  Names: use_gemm256, gemm256_variant,
  * gemm_stagger, gemm_tail_split, tile_group_l,
- * attn_variant, attn_xcd_remap, attn_mfma_prio, attn_half_tile, win_attn_prefetch, win_attn_x32, conv_halo, conv_wide, convt_small,
- * ln_policy -- each is described where it is defined (csrc/gemm.hip, attention.hip, hiera.hip) and in DESIGN.md s.4 / s.8. */
+ * attn_variant, attn_xcd_remap, attn_mfma_prio, attn_half_tile, win_attn_prefetch, win_attn_x32, conv_halo, conv_wide, convt_small
+ * -- each is described where it is defined (csrc/gemm.hip, attention.hip, hiera.hip) and in DESIGN.md s.4 / s.8. */
 int cvx_set_option(const char* name, int value);
 /* diagnostic: per-wave cycle sums {load, load-barrier, mma, mma-barrier} x 8 waves written by gemm256 variant 20 */
 int cvx_debug_read_gemm256(unsigned long long* out32);

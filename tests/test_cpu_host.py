@@ -391,3 +391,29 @@ def test_eval_config_validation_and_exp_dir(tmp_path):
     d.mkdir(parents=True)
     cfg = setup_exp_dir(cfg)
     assert cfg.paths.exp_dir == d and cfg.ckpt_path == d / "weights.pt"
+
+
+def test_pack_linear():
+    """ops.pack_linear (the one weight packing of VitEngine and HieraEngine) against the formulas written out: zero-padded bf16(W) / b,
+    and with a LayerNorm folded in bf16(W * gamma) and the table b + W beta (fp64 matvec) | column sums of the padded ROUNDED weight."""
+    from cryovit_amd.engine.ops import pack_linear
+
+    gen = torch.Generator().manual_seed(41)
+    w, b = torch.randn(24, 40, generator=gen) * 0.05, torch.randn(24, generator=gen)
+    gamma, beta = 1 + 0.1 * torch.randn(40, generator=gen), 0.1 * torch.randn(40, generator=gen)
+    wq = torch.zeros(64, 64, dtype=torch.bfloat16)
+    wq[:24, :40] = w.to(torch.bfloat16)
+    bq = torch.zeros(64)
+    bq[:24] = b
+    got_w, got_b = pack_linear(w, b, 64, 64, "cpu")
+    assert got_w.dtype == torch.bfloat16 and got_b.dtype == torch.float32
+    assert torch.equal(got_w, wq) and torch.equal(got_b, bq)
+    wf = torch.zeros(64, 64, dtype=torch.bfloat16)
+    wf[:24, :40] = (w * gamma[None, :]).to(torch.bfloat16)
+    bc = torch.zeros(2, 64)
+    bc[0, :24] = (b.double() + w.double() @ beta.double()).float()
+    bc[1] = wf.double().sum(dim=1).float()
+    got_w, got_b = pack_linear(w, b, 64, 64, "cpu", ln=(gamma, beta))
+    assert got_w.dtype == torch.bfloat16 and got_b.dtype == torch.float32
+    assert torch.equal(got_w, wf) and torch.equal(got_b, bc)
+    assert torch.any(bc[1, :24] != 0) and torch.all(bc[1, 24:] == 0)
