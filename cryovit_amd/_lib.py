@@ -29,6 +29,10 @@ SEG_MAX_LABELS = 8  # CVX_SEG_MAX_LABELS
 SEG_F32, SEG_U8 = 0, 1  # CVX_SEG_* label dtypes
 COMPONENT_COLS = 10  # CVX_COMPONENT_COLS
 COMPONENT_MAX_VOXELS = 2**31 - 2  # CVX_COMPONENT_MAX_VOXELS
+EDT_U8, EDT_I32 = 0, 1  # CVX_EDT_* source dtypes
+EDT_SITES_ZERO, EDT_SITES_NONZERO = 0, 1  # CVX_EDT_SITES_*
+EDT_NONE = 2**31 - 1  # CVX_EDT_NONE
+DSTAT_COLS = 4  # CVX_DSTAT_COLS
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -163,6 +167,8 @@ SIGNATURES = {
     "cvx_components_scratch_bytes": (c_long, [c_int, c_int, c_int]),
     "cvx_components_label": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_long, c_void_p]),
     "cvx_components_table": (c_int, [c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "cvx_edt_squared": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_instance_distance_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

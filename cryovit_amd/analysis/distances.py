@@ -1,0 +1,85 @@
+"""What a Euclidean distance map says about each instance: how thick it is, how much surface it has, which voxel lies deepest
+inside it, how far it is from another label and over how many voxels the two touch.  All distances are in voxels.
+
+``edt_squared`` is the exact transform on the device (``engine.ops.edt_squared``, csrc/edt.hip); ``instance_morphology`` and
+``instance_contacts`` reduce it per instance (``engine.ops.instance_distance_stats``) and return the extra columns of the
+instance CSV, one dict per instance 1..k in id order.
+"""
+
+from __future__ import annotations
+
+import math
+
+MORPHOLOGY_COLUMNS = ["surface_voxels", "inscribed_d2", "inscribed_radius", "deep_z", "deep_y", "deep_x"]
+
+
+def contact_columns(name: str) -> list[str]:
+    return [f"gap_d2_{name}", f"gap_{name}", f"contact_voxels_{name}"]
+
+
+def edt_squared(mask, sites: str = "zero"):
+    """int32 device tensor of the exact squared distance to the nearest zero (``sites="zero"``) or nonzero voxel of the uint8
+    or int32 device volume ``mask``; see ``engine.ops.edt_squared``."""
+    from cryovit_amd.engine import ops
+
+    return ops.edt_squared(mask, sites=sites)
+
+
+def morphology_rows(stats, shape) -> list[dict]:
+    """Rows from the int64 [k, 4] statistics of (labels, distance to the background) at threshold 1: ``surface_voxels`` (d2 = 1:
+    a face neighbour in the background), ``inscribed_d2`` = max d2 and ``inscribed_radius`` = its root in float64, and the
+    deepest voxel ``deep_z, deep_y, deep_x`` (the first in raster order among equals).  A volume without background gives
+    0, -1, -1.0, -1, -1, -1."""
+    _, H, W = shape
+    rows = []
+    for count, _, hi, idx in _host(stats).tolist():
+        if hi < 0:
+            rows.append(dict(zip(MORPHOLOGY_COLUMNS, (0, -1, -1.0, -1, -1, -1))))
+        else:
+            rows.append(dict(zip(MORPHOLOGY_COLUMNS, (count, hi, math.sqrt(hi), idx // (H * W), idx // W % H, idx % W))))
+    return rows
+
+
+def contact_rows(stats, name: str) -> list[dict]:
+    """Rows from the int64 [k, 4] statistics of (labels, distance to the other mask) at threshold floor(radius^2):
+    ``gap_d2_<name>`` = min d2, ``gap_<name>`` = its root in float64 (0 where the two overlap) and ``contact_voxels_<name>`` = the
+    instance's voxels within the radius.  An empty other mask gives -1, -1.0, 0."""
+    rows = []
+    for count, lo, _, _ in _host(stats).tolist():
+        rows.append(dict(zip(contact_columns(name), (lo, math.sqrt(lo), count) if lo >= 0 else (-1, -1.0, 0))))
+    return rows
+
+
+def _host(stats):
+    import numpy as np
+
+    if hasattr(stats, "detach"):
+        stats = stats.detach().cpu().numpy()
+    return np.asarray(stats, dtype=np.int64).reshape(-1, 4)
+
+
+def instance_morphology(labels, k: int) -> list[dict]:
+    """The morphology columns of the instances 1..k of the int32 device volume ``labels``.  The distance map is taken on the
+    label volume, so what ``min_size`` removed counts as background."""
+    from cryovit_amd.engine import ops
+
+    d2 = ops.edt_squared(labels, sites="zero")
+    return morphology_rows(ops.instance_distance_stats(labels, d2, k, 1), labels.shape)
+
+
+def contact_threshold(radius: float) -> int:
+    """floor(radius^2): the largest squared voxel distance that still lies within ``radius``."""
+    if not radius >= 0:
+        raise ValueError(f"contact radius must be >= 0, got {radius}")
+    return int(math.floor(radius * radius))
+
+
+def instance_contacts(labels, k: int, other_mask, radius: float, name: str = "other") -> list[dict]:
+    """The contact columns of the instances 1..k of ``labels`` against the uint8 (or int32) device volume ``other_mask`` of the
+    same shape (nonzero = the other label), named after ``name``."""
+    from cryovit_amd.engine import ops
+
+    if tuple(other_mask.shape) != tuple(labels.shape):
+        raise ValueError(f"the other mask has shape {tuple(other_mask.shape)}, the instances {tuple(labels.shape)}")
+    d2 = ops.edt_squared(other_mask, sites="nonzero")
+    return contact_rows(ops.instance_distance_stats(labels, d2, k, contact_threshold(radius)), name)

@@ -2,7 +2,7 @@
 
 ``label_volume`` labels a mask that is already on the device (``engine.ops.label_components``: HIP union-find, exact and
 bit-reproducible); ``instance_rows`` turns the integer table into the rows people read; ``label_file`` does both for a
-prediction file that ``cryovit infer`` wrote earlier.
+prediction file that ``cryovit infer`` wrote earlier; ``distance_rows`` adds the columns that need a distance map.
 """
 
 from __future__ import annotations
@@ -34,10 +34,47 @@ def label_volume(mask, *, connectivity: int = 26, min_size: int = 0):
     return ops.label_components(mask, connectivity=connectivity, min_size=min_size)
 
 
-def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, result_dir=None, device=None) -> Path:
+def distance_rows(labels, k: int, *, morphology: bool = False, other_mask=None, other_name: str = "other",
+                  contact_radius: float = 1.0) -> list[dict]:
+    """The extra CSV columns of the instances 1..k of the int32 device volume ``labels`` (``analysis.distances``): the
+    morphology columns, then the contact columns against ``other_mask`` when one is given.  No option: k empty dicts."""
+    from cryovit_amd.analysis import distances
+
+    extra = [{} for _ in range(k)]
+    if morphology:
+        for e, m in zip(extra, distances.instance_morphology(labels, k)):
+            e.update(m)
+    if other_mask is not None:
+        for e, c in zip(extra, distances.instance_contacts(labels, k, other_mask, contact_radius, other_name)):
+            e.update(c)
+    return extra
+
+
+def _other_preds(path: Path, datasets: dict, name: str, distance_to_dir):
+    """``<name>_preds`` of the same file, else of ``distance_to_dir/<same stem>.hdf`` (a second ``infer`` run with another
+    model writes to another folder)."""
+    from cryovit_amd import io
+
+    key = f"{name}_preds"
+    if key in datasets:
+        return datasets[key]
+    if distance_to_dir is not None:
+        other = (Path(distance_to_dir) / path.name).with_suffix(".hdf")
+        if other.exists():
+            found = io.read_all_flat(other)
+            if key in found:
+                return found[key]
+            raise KeyError(f"{other} holds no '{key}' dataset (found {sorted(found)})")
+    raise KeyError(f"{path} holds no '{key}' dataset (found {sorted(datasets)})")
+
+
+def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, result_dir=None, device=None,
+               morphology: bool = False, distance_to: str | None = None, distance_to_dir=None, contact_radius: float = 1.0) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
-    ``result_dir`` (default: the file's folder, i.e. in place).  Returns the written file."""
+    ``result_dir`` (default: the file's folder, i.e. in place).  ``morphology`` adds the thickness / surface / deepest-voxel
+    columns, ``distance_to`` the gap and contact columns against ``<distance_to>_preds`` (of the same file, else of
+    ``distance_to_dir/<same stem>.hdf``) within ``contact_radius`` voxels.  Returns the written file."""
     import torch
 
     from cryovit_amd import io
@@ -53,8 +90,21 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     preds = datasets[key]
     if preds.ndim != 3:
         raise ValueError(f"'{key}' of {path} must be a [D, H, W] volume, got shape {preds.shape}")
+    if not contact_radius >= 0:
+        raise ValueError(f"contact_radius must be >= 0, got {contact_radius}")
+    other = None
+    if distance_to is not None:
+        other = _other_preds(path, datasets, distance_to, distance_to_dir)
+        if other.shape != preds.shape:
+            raise ValueError(f"'{distance_to}_preds' has shape {other.shape}, '{key}' of {path} has {preds.shape}")
     device = select_device(device)
     mask = torch.from_numpy(np.ascontiguousarray(preds != 0).view(np.uint8)).to(device)
     labels, table = label_volume(mask, connectivity=connectivity, min_size=min_size)
+    rows = instance_rows(table)
+    if morphology or other is not None:
+        other_mask = None if other is None else torch.from_numpy(np.ascontiguousarray(other != 0).view(np.uint8)).to(device)
+        for r, e in zip(rows, distance_rows(labels, len(rows), morphology=morphology, other_mask=other_mask,
+                                            other_name=distance_to or "other", contact_radius=contact_radius)):
+            r.update(e)
     return writers.write_instances(result_dir if result_dir is not None else path.parent, path.name, label, datasets,
-                                   labels.cpu().numpy(), instance_rows(table))
+                                   labels.cpu().numpy(), rows)

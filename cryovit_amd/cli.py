@@ -3,13 +3,16 @@
 
     python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize]
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
-                                    [--instances [--min-size N] [--connectivity 6|26]]
+                                    [--instances [--min-size N] [--connectivity 6|26] [--morphology]]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
     python -m cryovit_amd.cli instances <predictions> --label NAME [--min-size N] [--connectivity 6|26] [--result-folder DIR]
+                                        [--morphology] [--distance-to NAME [--distance-to-folder DIR] [--contact-radius R]]
 
 ``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
 replace the network fetch of the encoder weights or add what the reference leaves to the user: ``instances`` (and
-``infer --instances``) labels the connected instances of a predicted mask on the GPU and tabulates their size and position.
+``infer --instances``) labels the connected instances of a predicted mask on the GPU and tabulates their size and position;
+``--morphology`` and ``--distance-to`` add columns read from exact distance maps (surface voxels, inscribed radius, deepest voxel;
+gap and contact voxels against another label), all in voxels.
 """
 
 from __future__ import annotations
@@ -45,6 +48,12 @@ def _load_encoder(encoder: Optional[str], checkpoint: Optional[str], synthetic_s
 def _check_connectivity(value: int) -> int:
     if value not in (6, 26):
         raise typer.BadParameter("connectivity must be 6 (faces) or 26 (faces, edges and corners)")
+    return value
+
+
+def _check_contact_radius(value: float) -> float:
+    if not value >= 0:
+        raise typer.BadParameter("contact radius must be >= 0 (voxels)")
     return value
 
 
@@ -93,8 +102,11 @@ def infer(
     instances: Annotated[bool, Option("--instances", help="build extension: also label the connected instances of each mask on the GPU (<label>_instances dataset and instances/<tomogram>_<label>.csv)")] = False,
     min_size: Annotated[int, Option(min=0, help="build extension: with --instances, drop instances of fewer voxels")] = 0,
     connectivity: Annotated[int, Option(callback=_check_connectivity, help="build extension: with --instances, 6 (faces) or 26 (faces, edges and corners)")] = 26,
+    morphology: Annotated[bool, Option("--morphology", help="build extension: with --instances, add surface voxels, inscribed radius and deepest voxel per instance (exact distance map on the GPU; voxels)")] = False,
 ):
     """Segment tomograms using a pre-trained model."""
+    if morphology and not instances:
+        raise typer.BadParameter("--morphology needs --instances", param_hint="--morphology")
     from cryovit_amd.run.infer_model import run_inference
     from cryovit_amd.utils import load_files_from_path
 
@@ -106,7 +118,7 @@ def infer(
     result_path.mkdir(parents=True, exist_ok=True)
     run_inference(load_files_from_path(tomograms_path), model_path, result_path, threshold=threshold,
                   encoder=_load_encoder(encoder, checkpoint, synthetic_seed), instances=instances, min_size=min_size,
-                  connectivity=connectivity)
+                  connectivity=connectivity, morphology=morphology)
 
 
 @cli.command(name="instances", no_args_is_help=True)
@@ -117,6 +129,10 @@ def instances_cmd(
     connectivity: Annotated[int, Option(callback=_check_connectivity, help="build extension: 6 (faces) or 26 (faces, edges and corners)")] = 26,
     result_folder: Annotated[Optional[str], Option(help="build extension: folder for the labelled files and instances/*.csv.",
                                                    show_default="the folder of the predictions (files are updated in place)")] = None,
+    morphology: Annotated[bool, Option("--morphology", help="build extension: add surface voxels, inscribed radius and deepest voxel per instance (exact distance map on the GPU; voxels)")] = False,
+    distance_to: Annotated[Optional[str], Option(help="build extension: another label NAME; add the gap to <NAME>_preds and the voxels in contact with it (voxels)")] = None,
+    distance_to_folder: Annotated[Optional[str], Option(help="build extension: folder whose <same stem>.hdf holds <NAME>_preds when the prediction file itself does not")] = None,
+    contact_radius: Annotated[float, Option(callback=_check_contact_radius, help="build extension: with --distance-to, voxels within this distance of the other label count as contact (voxels, >= 0)")] = 1.0,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     from cryovit_amd.analysis.instances import label_file
@@ -126,7 +142,8 @@ def instances_cmd(
     predictions_path = Path(predictions)
     assert predictions_path.exists(), "Predictions path does not exist."
     for f in load_files_from_path(predictions_path):
-        out = label_file(f, label, connectivity=connectivity, min_size=min_size, result_dir=result_folder)
+        out = label_file(f, label, connectivity=connectivity, min_size=min_size, result_dir=result_folder, morphology=morphology,
+                         distance_to=distance_to, distance_to_dir=distance_to_folder, contact_radius=contact_radius)
         logging.info("Labelled %s", out)
 
 

@@ -1,0 +1,374 @@
+// Exact squared Euclidean distance maps of a mask or an instance volume, and the per-instance reduction over (labels, d2) that
+// `cryovit infer --morphology` and `cryovit instances --morphology / --distance-to` read: thickness, surface, deepest voxel,
+// gap to another label.  Integers only, no atomics in the transform and no workspace: two calls give the same bits.
+//
+// The transform is separable (out[v] = min over sites s of dz^2 + dy^2 + dx^2), three passes over the int32 volume:
+//   x pass   src -> out: per row, the squared distance to the nearest site of the row (kEdtNone when the row has none).  One
+//            wave per row.  The wave's ballots are 64-voxel site bitmaps: a count of leading / trailing zeros finds the nearest
+//            site inside a voxel's own bitmap, and a forward max-scan / backward min-scan over the bitmaps' last / first sites
+//            (one lane per bitmap) finds it beyond.
+//   y pass   in place, out[i] = min_j f[j] + (i - j)^2 along y (lines of H elements, stride W)
+//   z pass   the same along z (lines of D elements, stride H*W)
+// A min-plus workgroup owns a slab of 64 adjacent x (256-B row pieces: every access of either pass is a coalesced wave access)
+// times the WHOLE line, so that nothing it overwrites is still needed by another workgroup.
+//   RULE: a line of up to kLineMax = 512 elements (512 x 256 B = 128 KB of LDS) is staged in LDS once and every output is
+//   computed from there.  A longer line is done in place from global memory in two sweeps over blocks of outputs: blocks in
+//   descending order with the sources j <= i only, then in ascending order with j >= i only.  A block is computed, then
+//   (barrier) written, so a sweep only ever reads elements it has not yet written.  The second sweep reads the first one's
+//   results g1[j] = min_{k<=j} f[k] + (j-k)^2; every term it forms, f[k] + (j-k)^2 + (j-i)^2 with k <= j >= i, is at least
+//   f[k] + (i-k)^2 (one of the two steps is at least as long as |i-k|), and the terms with j = k or j = i are exactly those,
+//   so the minimum is the exact transform.
+// A thread holds kIpt = 8 consecutive outputs of one x and updates all of them per read of f[j]; (i - j)^2 is the same for a
+// whole wave (scalar).  f[j] == kEdtNone is skipped, so every sum formed is a true squared distance inside the volume, which
+// the entry point has checked to be below INT32_MAX.  The walk goes outwards from the thread's outputs and stops once the
+// squared step alone reaches the largest of the wave's current minima.
+#include "common.h"
+#include "../../include/cryovit_hip.h"
+#include "host_util.h"
+
+#include <limits.h>
+
+namespace cvx {
+
+constexpr int kEdtNone = CVX_EDT_NONE;
+constexpr int kRowThreads = 256;           // x pass: 4 waves = 4 rows per workgroup
+constexpr int kSlab = 64;                  // min-plus passes: adjacent x per workgroup = lanes of a wave
+constexpr int kIpt = 8;                    // outputs per thread
+constexpr int kJu = 8;                     // sources fetched per pruning test
+constexpr int kLineMax = 512;              // longest line staged in LDS
+constexpr int kLineWavesMax = 16;
+constexpr int kStatThreads = 256;
+constexpr int kStatRv = 16;                // voxels of one row per thread in the statistics pass
+
+__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// ---- x pass ----
+
+template <typename T, bool NONZERO>
+__global__ __launch_bounds__(kRowThreads) void k_edt_rows(const T* __restrict__ src, int* __restrict__ out, long rows, int W, int nc) {
+    extern __shared__ unsigned long long edt_row_lds[];
+    const int lane = threadIdx.x & 63, wave = wave_id();
+    // per wave: nc site bitmaps, then per bitmap the last site before it and the first site after it
+    unsigned long long* bits = edt_row_lds + (long)wave * 2 * nc;
+    int* before = (int*)(bits + nc);
+    int* after = before + nc;
+    const long row = (long)blockIdx.x * (kRowThreads / 64) + wave;
+    const bool live = row < rows;  // a wave past the last row walks the same loops (the barriers below) and touches no memory
+    const T* s = src + (live ? row : 0) * W;
+    for (int c = 0; c < nc; ++c) {
+        const int x = c * 64 + lane;
+        const bool site = live && x < W && (s[x] != 0) == NONZERO;
+        const unsigned long long b = __ballot(site);
+        if (lane == 0) bits[c] = b;
+    }
+    __syncthreads();
+    int carry = -1;  // forward: the last site of all earlier bitmaps
+    for (int base = 0; base < nc; base += 64) {
+        const int c = base + lane;
+        const unsigned long long b = c < nc ? bits[c] : 0;
+        int v = b ? c * 64 + 63 - __clzll((long long)b) : -1;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(v, o, 64);
+            if (lane >= o) v = max(v, t);
+        }
+        int excl = __shfl_up(v, 1, 64);
+        if (lane == 0) excl = -1;
+        if (c < nc) before[c] = max(excl, carry);
+        carry = max(carry, __shfl(v, 63, 64));
+    }
+    carry = INT_MAX;  // backward: the first site of all later bitmaps
+    for (int base = (nc - 1) / 64 * 64; base >= 0; base -= 64) {
+        const int c = base + lane;
+        const unsigned long long b = c < nc ? bits[c] : 0;
+        int v = b ? c * 64 + __ffsll((unsigned long long)b) - 1 : INT_MAX;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_down(v, o, 64);
+            if (lane + o < 64) v = min(v, t);
+        }
+        int excl = __shfl_down(v, 1, 64);
+        if (lane == 63) excl = INT_MAX;
+        if (c < nc) after[c] = min(excl, carry);
+        carry = min(carry, __shfl(v, 0, 64));
+    }
+    __syncthreads();
+    if (!live) return;
+    int* o = out + row * W;
+    for (int c = 0; c < nc; ++c) {
+        const int x = c * 64 + lane;
+        if (x >= W) break;
+        const unsigned long long b = bits[c];
+        const unsigned long long lo = b & (~0ull >> (63 - lane)), hi = b >> lane;
+        const int left = lo ? c * 64 + 63 - __clzll((long long)lo) : before[c];
+        const int right = hi ? x + __ffsll(hi) - 1 : after[c];
+        int d = INT_MAX;
+        if (left >= 0) d = x - left;
+        if (right != INT_MAX) d = min(d, right - x);
+        o[x] = d == INT_MAX ? kEdtNone : d * d;  // d < W, and (W-1)^2 < INT32_MAX was checked
+    }
+}
+
+// ---- y and z passes ----
+
+// best[k] = min(best[k], f(j) + (i0 + k - j)^2) for the sources j of [ja, jb), walked downwards from the thread's last output
+// and upwards from the source after it.  MODE 0: every pair; 1: pairs with j <= i only; 2: pairs with j >= i only.  i0 is the
+// same for the whole wave; lanes that are not `active` (past the row's end) hold no minimum and do not keep the walk going.
+template <int MODE, class F>
+__device__ __forceinline__ void edt_minplus(F f, bool active, int i0, int ja, int jb, int (&best)[kIpt]) {
+    auto take = [&](int j, int v) {
+        if (v == kEdtNone) return;
+#pragma unroll
+        for (int k = 0; k < kIpt; ++k) {
+            const int d = i0 + k - j;
+            if ((MODE == 1 && d < 0) || (MODE == 2 && d > 0)) continue;
+            best[k] = min(best[k], v + d * d);
+        }
+    };
+    auto widest = [&]() {
+        int m = best[0];
+#pragma unroll
+        for (int k = 1; k < kIpt; ++k) m = max(m, best[k]);
+        return m;
+    };
+    const int top = min(i0 + kIpt, jb);  // sources below top go to the downward walk
+    if (MODE != 2 || top > i0) {
+        const int stop = MODE == 2 ? max(ja, i0) : ja;
+        for (int j1 = top; j1 > stop; j1 -= kJu) {
+            const int gap = i0 - (j1 - 1);  // the step from the nearest source of this group to the nearest output
+            if (gap > 0 && !__any(active && gap * gap < widest())) break;
+            int v[kJu];
+#pragma unroll
+            for (int u = 0; u < kJu; ++u) v[u] = j1 - 1 - u >= stop ? f(j1 - 1 - u) : kEdtNone;
+#pragma unroll
+            for (int u = 0; u < kJu; ++u) take(j1 - 1 - u, v[u]);
+        }
+    }
+    if (MODE != 1) {
+        for (int j0 = max(top, ja); j0 < jb; j0 += kJu) {
+            const int gap = j0 - (i0 + kIpt - 1);
+            if (gap > 0 && !__any(active && gap * gap < widest())) break;
+            int v[kJu];
+#pragma unroll
+            for (int u = 0; u < kJu; ++u) v[u] = j0 + u < jb ? f(j0 + u) : kEdtNone;
+#pragma unroll
+            for (int u = 0; u < kJu; ++u) take(j0 + u, v[u]);
+        }
+    }
+}
+
+struct LineGeom {
+    int n;         // elements of a line
+    long stride;   // between two of them
+    long ostride;  // between two lines of one slab column
+    int W, nslab;  // row length, slabs per row
+};
+
+__device__ __forceinline__ void edt_store(int* line, const LineGeom& g, int i0, const int (&best)[kIpt]) {
+#pragma unroll
+    for (int k = 0; k < kIpt; ++k)
+        if (i0 + k < g.n) line[(long)(i0 + k) * g.stride] = best[k];
+}
+
+// lines of up to kLineMax elements: staged in LDS (g.n * kSlab ints), every wave then takes blocks of kIpt outputs
+__global__ __launch_bounds__(kLineWavesMax * 64) void k_edt_lines_lds(int* vol, LineGeom g) {
+    extern __shared__ int edt_line_lds[];
+    const int lane = threadIdx.x & 63, wave = wave_id(), waves = blockDim.x >> 6;
+    const int x = (int)(blockIdx.x % g.nslab) * kSlab + lane;
+    const bool in = x < g.W;
+    int* line = vol + (long)(blockIdx.x / g.nslab) * g.ostride + (in ? x : 0);
+    for (int j = wave; j < g.n; j += waves) edt_line_lds[j * kSlab + lane] = in ? line[(long)j * g.stride] : kEdtNone;
+    __syncthreads();
+    const int* col = edt_line_lds + lane;
+    for (int i0 = wave * kIpt; i0 < g.n; i0 += waves * kIpt) {
+        int best[kIpt];
+#pragma unroll
+        for (int k = 0; k < kIpt; ++k) best[k] = kEdtNone;
+        edt_minplus<0>([&](int j) { return col[j * kSlab]; }, in, i0, 0, g.n, best);
+        if (in) edt_store(line, g, i0, best);
+    }
+}
+
+// longer lines: two sweeps in place (the rule at the top of the file)
+__global__ __launch_bounds__(kLineWavesMax * 64) void k_edt_lines_long(int* vol, LineGeom g) {
+    const int lane = threadIdx.x & 63, wave = wave_id(), waves = blockDim.x >> 6;
+    const int x = (int)(blockIdx.x % g.nslab) * kSlab + lane;
+    const bool in = x < g.W;
+    int* line = vol + (long)(blockIdx.x / g.nslab) * g.ostride + (in ? x : 0);
+    auto f = [&](int j) { return in ? __hip_atomic_load(line + (long)j * g.stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : kEdtNone; };
+    const int per_block = waves * kIpt, blocks = (g.n + per_block - 1) / per_block;
+    for (int sweep = 0; sweep < 2; ++sweep) {
+        for (int t = 0; t < blocks; ++t) {
+            const int b = sweep == 0 ? blocks - 1 - t : t;
+            const int i0 = b * per_block + wave * kIpt;
+            int best[kIpt];
+#pragma unroll
+            for (int k = 0; k < kIpt; ++k) best[k] = kEdtNone;
+            if (i0 < g.n) {
+                if (sweep == 0) edt_minplus<1>(f, in, i0, 0, g.n, best);
+                else edt_minplus<2>(f, in, i0, 0, g.n, best);
+            }
+            __syncthreads();  // every wave has read what this block overwrites
+            if (in && i0 < g.n) edt_store(line, g, i0, best);
+        }
+        __syncthreads();  // the first sweep's results are what the second reads
+    }
+}
+
+// ---- per-instance statistics over (labels, d2) ----
+
+// table rows while the voxels are reduced: count, min d2, the key (d2 << 32 | INT32_MAX - index), unused
+__global__ __launch_bounds__(kStatThreads) void k_dstat_init(long long* __restrict__ out, long k) {
+    const long i = (long)blockIdx.x * kStatThreads + threadIdx.x;
+    if (i >= k * CVX_DSTAT_COLS) return;
+    const int c = (int)(i % CVX_DSTAT_COLS);
+    out[i] = c == 1 ? LLONG_MAX : c == 2 ? -1 : 0;
+}
+
+struct DstatRun {
+    int id;
+    long long count, lo, key;
+};
+
+__device__ __forceinline__ void dstat_flush(long long* __restrict__ out, const DstatRun& r) {
+    if (r.id == 0 || r.key < 0) return;
+    long long* row = out + (long)(r.id - 1) * CVX_DSTAT_COLS;
+    if (r.count) atomicAdd((unsigned long long*)row, (unsigned long long)r.count);
+    // entries move one way only: a plain read that shows no change is possible spares the atomic
+    if (r.lo < *(volatile long long*)(row + 1)) atomicMin(row + 1, r.lo);
+    if (r.key > *(volatile long long*)(row + 2)) atomicMax(row + 2, r.key);
+}
+
+__global__ __launch_bounds__(kStatThreads) void k_dstat_reduce(const int* __restrict__ labels, const int* __restrict__ d2, long long* __restrict__ out,
+                                                               long k, int thr, long rows, int W, int segs) {
+    const long t = (long)blockIdx.x * kStatThreads + threadIdx.x;
+    const long row = t / segs;
+    if (row >= rows) return;
+    const int x0 = (int)(t % segs) * kStatRv;
+    const int cnt = min(kStatRv, W - x0);
+    const long v0 = row * W + x0;
+    int id[kStatRv], d[kStatRv];
+    if (cnt == kStatRv && (((uintptr_t)(labels + v0) | (uintptr_t)(d2 + v0)) & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < kStatRv / 4; ++q) {
+            const int4 a = ((const int4*)(labels + v0))[q], b = ((const int4*)(d2 + v0))[q];
+            id[4 * q] = a.x; id[4 * q + 1] = a.y; id[4 * q + 2] = a.z; id[4 * q + 3] = a.w;
+            d[4 * q] = b.x; d[4 * q + 1] = b.y; d[4 * q + 2] = b.z; d[4 * q + 3] = b.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < kStatRv; ++i) {
+            id[i] = i < cnt ? labels[v0 + i] : 0;
+            d[i] = i < cnt ? d2[v0 + i] : kEdtNone;
+        }
+    }
+    DstatRun r{0, 0, 0, -1};
+#pragma unroll
+    for (int i = 0; i < kStatRv; ++i) {
+        const int c = id[i] >= 1 && id[i] <= k ? id[i] : 0;  // ids past the table are nobody's
+        if (c != r.id) {
+            dstat_flush(out, r);
+            r = DstatRun{c, 0, LLONG_MAX, -1};
+        }
+        if (c == 0 || d[i] == kEdtNone) continue;
+        r.count += d[i] <= thr;
+        r.lo = min(r.lo, (long long)d[i]);
+        r.key = max(r.key, ((long long)d[i] << 32) | (long long)(INT_MAX - (int)(v0 + i)));  // equal d2: the smaller index wins
+    }
+    dstat_flush(out, r);
+}
+
+__global__ __launch_bounds__(kStatThreads) void k_dstat_finalize(long long* __restrict__ out, long k) {
+    const long i = (long)blockIdx.x * kStatThreads + threadIdx.x;
+    if (i >= k) return;
+    long long* row = out + i * CVX_DSTAT_COLS;
+    const long long key = row[2];
+    if (key < 0) {  // no voxel of this id has a distance
+        row[0] = 0;
+        row[1] = row[2] = row[3] = -1;
+        return;
+    }
+    row[2] = key >> 32;
+    row[3] = INT_MAX - (key & 0xffffffffLL);
+}
+
+}  // namespace cvx
+
+using namespace cvx;
+
+namespace {
+
+// extents >= 0 and D*H*W <= CVX_COMPONENT_MAX_VOXELS; n = the voxel count
+bool edt_extents(int D, int H, int W, long& n) {
+    if (D < 0 || H < 0 || W < 0) return false;
+    n = (long)D * H;  // < 2^62
+    if (W && n > CVX_COMPONENT_MAX_VOXELS / W) return false;
+    n *= W;
+    return n <= CVX_COMPONENT_MAX_VOXELS;
+}
+
+template <typename T>
+int edt_launch_rows(const void* src, int sites, int* out, long rows, int W, hipStream_t st) {
+    const int nc = (W + 63) / 64;
+    const unsigned blocks = (unsigned)((rows + kRowThreads / 64 - 1) / (kRowThreads / 64));
+    const size_t lds = (size_t)(kRowThreads / 64) * nc * 16;  // <= 46 KB: W <= 46341
+    if (sites == CVX_EDT_SITES_NONZERO) hipLaunchKernelGGL((k_edt_rows<T, true>), dim3(blocks), dim3(kRowThreads), lds, st, (const T*)src, out, rows, W, nc);
+    else hipLaunchKernelGGL((k_edt_rows<T, false>), dim3(blocks), dim3(kRowThreads), lds, st, (const T*)src, out, rows, W, nc);
+    return cvx_check_launch();
+}
+
+int edt_launch_lines(int* vol, int n, long stride, long lines, long ostride, int W, hipStream_t st) {
+    if (n <= 1) return 0;  // a line of one element is its own transform
+    const LineGeom g{n, stride, ostride, W, (W + kSlab - 1) / kSlab};
+    const int waves = min(kLineWavesMax, (n + kIpt - 1) / kIpt);
+    const dim3 grid((unsigned)(lines * g.nslab));  // <= D*H*W
+    if (n <= kLineMax) {
+        const int lds = n * kSlab * (int)sizeof(int);
+        CVX_HIP(hipFuncSetAttribute((const void*)k_edt_lines_lds, hipFuncAttributeMaxDynamicSharedMemorySize, kLineMax * kSlab * (int)sizeof(int)));
+        hipLaunchKernelGGL(k_edt_lines_lds, grid, dim3(waves * 64), lds, st, vol, g);
+    } else {
+        hipLaunchKernelGGL(k_edt_lines_long, grid, dim3(waves * 64), 0, st, vol, g);
+    }
+    return cvx_check_launch();
+}
+
+}  // namespace
+
+extern "C" int cvx_edt_squared(const void* src, int src_dtype, int sites, int D, int H, int W, int32_t* out, hipStream_t st) {
+    long n;
+    if (!edt_extents(D, H, W, n)) return cvx_fail("edt_squared: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (src_dtype != CVX_EDT_U8 && src_dtype != CVX_EDT_I32) return cvx_fail("edt_squared: src_dtype must be CVX_EDT_U8 or CVX_EDT_I32");
+    if (sites != CVX_EDT_SITES_ZERO && sites != CVX_EDT_SITES_NONZERO) return cvx_fail("edt_squared: sites must be CVX_EDT_SITES_ZERO or CVX_EDT_SITES_NONZERO");
+    if (n == 0) return 0;
+    const long long far = (long long)(D - 1) * (D - 1) + (long long)(H - 1) * (H - 1) + (long long)(W - 1) * (W - 1);
+    if (far >= INT_MAX) return cvx_fail("edt_squared: the squared diagonal (D-1)^2 + (H-1)^2 + (W-1)^2 must be below INT32_MAX");
+    if (!src || !out) return cvx_fail("edt_squared: null pointer");
+    if (((uintptr_t)out & 3) || (src_dtype == CVX_EDT_I32 && ((uintptr_t)src & 3))) return cvx_fail("edt_squared: int32 volumes must be 4-B aligned");
+    int rc = src_dtype == CVX_EDT_U8 ? edt_launch_rows<uint8_t>(src, sites, out, (long)D * H, W, st)
+                                     : edt_launch_rows<int32_t>(src, sites, out, (long)D * H, W, st);
+    if (rc) return rc;
+    if ((rc = edt_launch_lines(out, H, W, D, (long)H * W, W, st))) return rc;  // y: one line per (z, x)
+    return edt_launch_lines(out, D, (long)H * W, H, W, W, st);                  // z: one line per (y, x)
+}
+
+extern "C" int cvx_instance_distance_stats(const int32_t* labels, const int32_t* d2, int D, int H, int W, long k, int threshold_d2,
+                                           int64_t* out, hipStream_t st) {
+    long n;
+    if (!edt_extents(D, H, W, n)) return cvx_fail("instance_distance_stats: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (k < 0) return cvx_fail("instance_distance_stats: k < 0");
+    if (k == 0) return 0;
+    if (!out || (n > 0 && (!labels || !d2))) return cvx_fail("instance_distance_stats: null pointer");
+    if (((uintptr_t)out & 7) || (((uintptr_t)labels | (uintptr_t)d2) & 3)) return cvx_fail("instance_distance_stats: misaligned pointer");
+    const unsigned nk = (unsigned)((k * CVX_DSTAT_COLS + kStatThreads - 1) / kStatThreads);
+    hipLaunchKernelGGL(k_dstat_init, dim3(nk), dim3(kStatThreads), 0, st, (long long*)out, k);
+    int rc = cvx_check_launch();
+    if (rc) return rc;
+    if (n > 0) {
+        const int segs = (W + kStatRv - 1) / kStatRv;
+        const unsigned nrow = (unsigned)(((long)D * H * segs + kStatThreads - 1) / kStatThreads);
+        hipLaunchKernelGGL(k_dstat_reduce, dim3(nrow), dim3(kStatThreads), 0, st, labels, d2, (long long*)out, k, threshold_d2, (long)D * H, W, segs);
+        if ((rc = cvx_check_launch())) return rc;
+    }
+    hipLaunchKernelGGL(k_dstat_finalize, dim3((unsigned)((k + kStatThreads - 1) / kStatThreads)), dim3(kStatThreads), 0, st, (long long*)out, k);
+    return cvx_check_launch();
+}

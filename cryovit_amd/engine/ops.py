@@ -598,3 +598,47 @@ def label_components(mask: torch.Tensor, *, connectivity: int = 26, min_size: in
     table = torch.empty((k, _lib.COMPONENT_COLS), dtype=torch.int64, device=dev)
     call(dev, "cvx_components_table", lib.cvx_components_table, D, H, W, k, _p(labels), _p(table), scratch.data_ptr(), scratch.numel())
     return labels, table
+
+
+# ---- exact distance maps and the per-instance reduction over them (`--morphology`, `cryovit instances --distance-to`) ----
+
+def edt_squared(src: torch.Tensor, *, sites: str = "zero") -> torch.Tensor:
+    """int32 [D, H, W]: the exact squared Euclidean distance, in voxels, from every voxel of ``src`` (uint8 mask or int32
+    instance volume, [D, H, W]) to the nearest site inside the volume: its zero voxels (``sites="zero"``: depth inside the
+    foreground, scipy's convention) or its nonzero voxels (``sites="nonzero"``).  0 on a site; ``_lib.EDT_NONE`` everywhere
+    when there is no site.  Integers only, no workspace, bit-reproducible; the host does not wait."""
+    if src.dim() != 3 or src.dtype not in (torch.uint8, torch.int32):
+        raise _lib.CvxError(f"edt_squared: src must be uint8 or int32 [D, H, W], got {src.dtype} {tuple(src.shape)}")
+    if sites not in ("zero", "nonzero"):
+        raise _lib.CvxError(f"edt_squared: sites must be 'zero' or 'nonzero', got {sites!r}")
+    dev = _dev_check(src)
+    D, H, W = src.shape
+    if src.numel() > _lib.COMPONENT_MAX_VOXELS:
+        raise _lib.CvxError(f"edt_squared: {D}x{H}x{W} has more than 2^31 - 2 voxels")
+    out = torch.empty((D, H, W), dtype=torch.int32, device=dev)
+    call(dev, "cvx_edt_squared", _lib.load().cvx_edt_squared, _p(src), _lib.EDT_U8 if src.dtype == torch.uint8 else _lib.EDT_I32,
+         _lib.EDT_SITES_ZERO if sites == "zero" else _lib.EDT_SITES_NONZERO, D, H, W, _p(out))
+    return out
+
+
+def instance_distance_stats(labels: torch.Tensor, d2: torch.Tensor, k: int, threshold_d2: int) -> torch.Tensor:
+    """int64 [k, 4] on the device.  Row id - 1, over the voxels of ``labels`` (int32 [D, H, W], ids 0..k) with that id whose
+    ``d2`` (``edt_squared``) is not ``_lib.EDT_NONE``: how many have d2 <= ``threshold_d2``, min d2, max d2, and the smallest
+    linear index of a voxel attaining the max; 0, -1, -1, -1 for an id without such a voxel.  Ids past k are ignored."""
+    for name, t in (("labels", labels), ("d2", d2)):
+        if t.dim() != 3 or t.dtype != torch.int32:
+            raise _lib.CvxError(f"instance_distance_stats: {name} must be int32 [D, H, W], got {t.dtype} {tuple(t.shape)}")
+    if labels.shape != d2.shape:
+        raise _lib.CvxError(f"instance_distance_stats: labels {tuple(labels.shape)} and d2 {tuple(d2.shape)} differ in shape")
+    if k < 0:
+        raise _lib.CvxError(f"instance_distance_stats: k must be >= 0, got {k}")
+    if threshold_d2 < 0:
+        raise _lib.CvxError(f"instance_distance_stats: threshold_d2 must be >= 0, got {threshold_d2}")
+    dev = _dev_check(labels, d2)
+    D, H, W = labels.shape
+    if labels.numel() > _lib.COMPONENT_MAX_VOXELS:
+        raise _lib.CvxError(f"instance_distance_stats: {D}x{H}x{W} has more than 2^31 - 2 voxels")
+    out = torch.empty((int(k), _lib.DSTAT_COLS), dtype=torch.int64, device=dev)
+    call(dev, "cvx_instance_distance_stats", _lib.load().cvx_instance_distance_stats, _p(labels), _p(d2), D, H, W, int(k),
+         min(int(threshold_d2), _lib.EDT_NONE - 1), _p(out))  # no distance is larger than EDT_NONE - 1
+    return out

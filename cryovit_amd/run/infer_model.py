@@ -15,7 +15,8 @@ fly and the features go to the head in HBM without a round trip through the file
 Extension (not in the reference): ``instances=True`` -- the connected instances of the mask are labelled on the device
 (``engine.ops.label_components``) while the mask is still in HBM; each file then also holds ``<label_key>_instances`` and an
 instance table is written to ``<result_dir>/instances/<tomogram stem>_<label_key>.csv``.  ``<label_key>_preds`` stays the
-unfiltered threshold mask.
+unfiltered threshold mask.  ``morphology=True`` (with ``instances``) adds per instance the surface voxels, the inscribed radius and
+the deepest voxel from an exact distance map of the labels (``analysis.distances``), also computed while they are in HBM.
 """
 
 from __future__ import annotations
@@ -28,7 +29,7 @@ import numpy as np
 import torch
 
 from cryovit_amd import io
-from cryovit_amd.analysis.instances import instance_rows, label_volume
+from cryovit_amd.analysis.instances import distance_rows, instance_rows, label_volume
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
 from cryovit_amd.run import writers
@@ -68,19 +69,24 @@ def _predict_file(model, dataset, idx: int, threshold: float, encoder, batch_siz
     return item.aux_data["data"], mask
 
 
-def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table) -> Path:
+def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, extra) -> Path:
     """``writers.write_segmentation`` plus the instance volume and CSV (writer thread)."""
     datasets = {"data": raw.astype(np.float32), f"{label_key}_preds": segs.astype(np.uint8, copy=False)}
-    return writers.write_instances(result_dir, tomo_name, label_key, datasets, labels, instance_rows(table))
+    rows = instance_rows(table)
+    for r, e in zip(rows, extra):
+        r.update(e)
+    return writers.write_instances(result_dir, tomo_name, label_key, datasets, labels, rows)
 
 
 def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, threshold: float = 0.5, *, encoder=None,
                   batch_size: int = 128, device: str | None = None, instances: bool = False, min_size: int = 0,
-                  connectivity: int = 26) -> list[Path]:
+                  connectivity: int = 26, morphology: bool = False) -> list[Path]:
     if connectivity not in (6, 26):
         raise ValueError(f"connectivity must be 6 or 26, got {connectivity}")
     if min_size < 0:
         raise ValueError(f"min_size must be >= 0, got {min_size}")
+    if morphology and not instances:
+        raise ValueError("morphology=True needs instances=True: the columns describe the labelled instances")
     rank, _, world = world_info()
     device = select_device(device)
     model, model_type, model_name, label_key = load_model(model_path, device=device)
@@ -109,10 +115,11 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 host_labels = torch.empty(labels.shape, dtype=torch.int32, pin_memory=True)
                 host_labels.copy_(labels, non_blocking=True)
                 host_table = table.cpu()
+                extra = distance_rows(labels, table.shape[0], morphology=morphology)
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:
                 pending.append((i, writer.submit(_write_with_instances, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),
-                                                 host_labels.numpy(), host_table.numpy())))
+                                                 host_labels.numpy(), host_table.numpy(), extra)))
             else:
                 pending.append((i, writer.submit(writers.write_segmentation, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy())))
             while len(pending) > 2:

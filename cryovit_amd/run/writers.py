@@ -59,7 +59,8 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
     gzip, dtypes as given) and ``<label>_instances`` = ``labels`` (uint16 while the largest id fits, else int32: a 128x512x512
     int32 volume would make the gzip of the writer thread the slowest stage of ``infer``), and the CSV
     <results_dir>/instances/<tomo stem>_<label>.csv of ``rows`` (``analysis.instance_rows``; floats written with ``repr``; no
-    instances: header only).  The file is written beside its final name and moved there, so re-writing a file from its own
+    instances: header only; keys beyond ``INSTANCE_COLUMNS``, e.g. those of ``analysis.distance_rows``, become further columns in
+    the rows' own order).  The file is written beside its final name and moved there, so re-writing a file from its own
     datasets cannot leave it half written.  Returns the .hdf path."""
     results_dir = Path(results_dir)
     out = (results_dir / tomo_name).with_suffix(".hdf")
@@ -74,7 +75,8 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
     csv_path = results_dir / "instances" / f"{out.stem}_{label_key}.csv"
     csv_path.parent.mkdir(parents=True, exist_ok=True)
     with open(csv_path, "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=INSTANCE_COLUMNS)
+        extras = [k for k in (rows[0] if rows else ()) if k not in INSTANCE_COLUMNS]  # every row carries the same keys
+        w = csv.DictWriter(f, fieldnames=INSTANCE_COLUMNS + extras)
         w.writeheader()
         for r in rows:
             w.writerow({k: repr(v) if isinstance(v, float) else v for k, v in r.items()})

@@ -496,6 +496,32 @@ int cvx_components_label(const uint8_t* mask, int D, int H, int W, int connectiv
 int cvx_components_table(int D, int H, int W, long k, int32_t* labels, int64_t* table, const void* scratch, long scratch_bytes,
                          hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Exact squared Euclidean distance maps (`--morphology`, `cryovit instances --distance-to`).  src [D][H][W] is uint8 (a mask)
+ * or int32 (an instance volume); the sites are its zero voxels (CVX_EDT_SITES_ZERO: the depth inside the foreground, the
+ * convention of scipy.ndimage.distance_transform_edt) or its nonzero voxels (CVX_EDT_SITES_NONZERO: the distance to the
+ * foreground).  out int32 [D][H][W]: out[v] = min over the site voxels s INSIDE the volume of |v - s|^2, in voxels, exact; 0 on
+ * a site; CVX_EDT_NONE everywhere when the volume holds no site.  Voxels outside the volume are never sites.  Integers only,
+ * no atomics, no workspace.  Refused with an error before any launch: null pointers, negative extents, D*H*W >
+ * CVX_COMPONENT_MAX_VOXELS, (D-1)^2 + (H-1)^2 + (W-1)^2 >= INT32_MAX, another dtype or sites value.  An empty volume succeeds.
+ *
+ * cvx_instance_distance_stats: labels int32 [D][H][W] with ids 0..k, d2 as written by cvx_edt_squared, out int64
+ * [k][CVX_DSTAT_COLS] (initialised by the call).  Row id - 1, over the voxels of that id with d2 != CVX_EDT_NONE: the number with
+ * d2 <= threshold_d2, min d2, max d2, and the smallest linear index (z*H + y)*W + x of a voxel that attains the max.  An id
+ * without such a voxel gets 0, -1, -1, -1; ids outside 1..k are ignored; k == 0 succeeds.  64-bit integer atomic add / min /
+ * max only (the argmax rides in one packed key), so the table does not depend on scheduling.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_EDT_U8 0
+#define CVX_EDT_I32 1
+#define CVX_EDT_SITES_ZERO 0
+#define CVX_EDT_SITES_NONZERO 1
+#define CVX_EDT_NONE 2147483647 /* INT32_MAX */
+#define CVX_DSTAT_COLS 4
+
+int cvx_edt_squared(const void* src, int src_dtype, int sites, int D, int H, int W, int32_t* out, hipStream_t stream);
+int cvx_instance_distance_stats(const int32_t* labels, const int32_t* d2, int D, int H, int W, long k, int threshold_d2,
+                                int64_t* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
