@@ -503,8 +503,8 @@ __global__ __launch_bounds__(G256_THREADS) void k_gemm256_nreg(const uint16_t* A
     stagger_first_round(stagger);
     int tr, tl;
     tile_coords(blockIdx.x, gridDim.x, tiles_n, tiles_m, tr, tl);
-    const int koff = VARIANT == 7 ? ((tr & 3) + (tl & 7)) % nk : 0;
-    gemm256_body<(VARIANT == 7 ? 5 : VARIANT)>(Wt, ldw, A, lda, nk, (long)tr * 256, (long)tl * 256, epi, smem, koff);
+    const int koff = g256_cfg(VARIANT).rotate_k ? ((tr & 3) + (tl & 7)) % nk : 0;
+    gemm256_body<VARIANT>(Wt, ldw, A, lda, nk, (long)tr * 256, (long)tl * 256, epi, smem, koff);
 }
 template <class Epi, int VARIANT>
 __global__ __launch_bounds__(G256_THREADS) void k_gemm256_mreg(const uint16_t* A, long lda, const uint16_t* Wt, long ldw, int nk,
@@ -534,6 +534,47 @@ __global__ __launch_bounds__(G256_THREADS) void k_gemm256p_mreg(const uint16_t* 
 // tuning switches (cvx_set_option): A/B the tile kernels and pipeline schedules inside ONE process
 static std::atomic<int> g_tile_group_l_host{8};  // host copy of g_tile_group_l (the persistent kernel takes it as an argument)
 static std::atomic<int> g_use_gemm256{1}, g_gemm256_variant{9}, g_gemm_stagger{0};  // 9 = persistent (gemm256p.h)  // stagger: measured no gain (tools/bench_gemm.py 5 vs 1005)
+// Every value cvx_set_option("gemm256_variant") accepts in this build, and the kernels it selects.
+enum class G256Launch { OneShot, Persistent, PersistentStamped };
+struct G256Variant {
+    int id;
+    G256Launch launch;  // the persistent tile (gemm256p.h) runs the epilogues it has; the others take the one-shot kernel of the row
+    int one_shot;       // VARIANT of k_gemm256_nreg (g256_cfg, gemm256.h)
+    int four_wave;      // VARIANT of k_gemm4w (g4w_cfg, gemm4w.h): use_gemm256 = 2, ablation build
+};
+constexpr G256Variant G256_VARIANTS[] = {
+    // the product
+    {0, G256Launch::OneShot, 0, 0},
+    {9, G256Launch::Persistent, 0, 0},
+#ifdef CVX_ABLATION  // measured-and-rejected schedules and the timing-only builds (stamps / garbage-output ablations): never in the product library
+    {1, G256Launch::OneShot, 1, 1},  // read-ahead;  4-wave tile: no DMA
+    {2, G256Launch::OneShot, 0, 2},  // 4-wave tile: same K tile;  the 8-wave tile has no such number and runs its schedule 0
+    {5, G256Launch::OneShot, 5, 0},
+    {6, G256Launch::OneShot, 6, 0},
+    {7, G256Launch::OneShot, 7, 0},
+    {8, G256Launch::OneShot, 8, 0},
+    {10, G256Launch::OneShot, 10, 0},
+    {11, G256Launch::OneShot, 11, 0},
+    {12, G256Launch::OneShot, 12, 0},
+    {13, G256Launch::OneShot, 13, 0},
+    {20, G256Launch::OneShot, 20, 0},
+    {21, G256Launch::OneShot, 21, 0},
+    {29, G256Launch::PersistentStamped, 0, 0},
+#endif
+};
+constexpr int G256_NVARIANTS = sizeof(G256_VARIANTS) / sizeof(G256_VARIANTS[0]);
+static const G256Variant* find_g256_variant(int id) {
+    for (const G256Variant& v : G256_VARIANTS)
+        if (v.id == id) return &v;
+    return nullptr;
+}
+// f(integral_constant<int, I>) for the row I of G256_VARIANTS with this id: the place to name a kernel instance by a row's numbers
+template <class F, int... I>
+static void with_g256_row(int id, F&& f, std::integer_sequence<int, I...>) {
+    ((G256_VARIANTS[I].id == id ? f(std::integral_constant<int, I>{}) : void()), ...);
+}
+template <class F>
+static void with_g256_row(int id, F&& f) { with_g256_row(id, f, std::make_integer_sequence<int, G256_NVARIANTS>{}); }
 template <class Epi> static constexpr int epilogue_cycles() { return 12000; }       // bf16 store epilogues (stamped)
 template <> constexpr int epilogue_cycles<EpiResid>() { return 40000; }              // fp32 read-modify-write
 template <> constexpr int epilogue_cycles<EpiF32>() { return 20000; }
@@ -607,14 +648,15 @@ static int launch_256(const uint16_t* A, long lda, const uint16_t* Wt, long ldw,
     const int ntiles = t.n * t.m, nk = (int)(Kpad / BK);
 #ifdef CVX_ABLATION
     if (g_use_gemm256 == 2) {  // one-wave-per-SIMD tile (gemm4w.h)
-        auto k4 = g_gemm256_variant == 1 ? k_gemm4w<Epi, MREG, 1> : g_gemm256_variant == 2 ? k_gemm4w<Epi, MREG, 2> : k_gemm4w<Epi, MREG, 0>;
+        void (*k4)(const uint16_t*, long, const uint16_t*, long, int, int, int, Epi) = nullptr;
+        with_g256_row(g_gemm256_variant, [&](auto row) { k4 = k_gemm4w<Epi, MREG, G256_VARIANTS[decltype(row)::value].four_wave>; });
         return launch_kernel(k4, G4W_THREADS, G4W_LDS_BYTES, ntiles, st, A, lda, Wt, ldw, (int)(Kpad / G4W_KS), t.n, t.m, epi);
     }
 #endif
-    const int variant = g_gemm256_variant;
+    const G256Variant& variant = *find_g256_variant(g_gemm256_variant);  // (cvx_set_option stores table values only)
     constexpr bool resid = epi_has_preload<Epi>::value || epi_has_hl<Epi>::value;
     if constexpr ((!MREG && (resid || epi_has_produce<Epi>::value)) || (MREG && epi_is_mreg<Epi>::value)) {
-        if (variant == 9 || variant == 29) {
+        if (variant.launch != G256Launch::OneShot) {
             // one workgroup per CU (128 KiB of LDS each)
             int n_cu = 0;
             if (int rc = device_cus(&n_cu)) return rc;
@@ -626,7 +668,7 @@ static int launch_256(const uint16_t* A, long lda, const uint16_t* Wt, long ldw,
             } else {
                 kp = full ? k_gemm256p_nreg<Epi, true> : k_gemm256p_nreg<Epi, false>;
 #ifdef CVX_ABLATION
-                if (variant == 29) kp = k_gemm256p_nreg<Epi, true, true>;  // stamped (interior tiles only)
+                if (variant.launch == G256Launch::PersistentStamped) kp = k_gemm256p_nreg<Epi, true, true>;  // stamped (interior tiles only)
 #endif
             }
             // The residual GEMMs start their XCDs together: a stagger shortens the epilogue to what ONE XCD's fabric port delivers
@@ -639,22 +681,7 @@ static int launch_256(const uint16_t* A, long lda, const uint16_t* Wt, long ldw,
     if constexpr (MREG) {
         k = k_gemm256_mreg<Epi, 0>;
     } else {
-        switch (variant) {
-#ifdef CVX_ABLATION  // the measured-and-rejected schedules and the timing-only builds (stamps / garbage-output ablations): never in the product library
-            case 1: k = k_gemm256_nreg<Epi, 1>; break;
-            case 5: k = k_gemm256_nreg<Epi, 5>; break;
-            case 6: k = k_gemm256_nreg<Epi, 6>; break;
-            case 7: k = k_gemm256_nreg<Epi, 7>; break;
-            case 8: k = k_gemm256_nreg<Epi, 8>; break;
-            case 20: k = k_gemm256_nreg<Epi, 20>; break;
-            case 21: k = k_gemm256_nreg<Epi, 21>; break;
-            case 10: k = k_gemm256_nreg<Epi, 10>; break;
-            case 11: k = k_gemm256_nreg<Epi, 11>; break;
-            case 12: k = k_gemm256_nreg<Epi, 12>; break;
-            case 13: k = k_gemm256_nreg<Epi, 13>; break;
-#endif
-            default: k = k_gemm256_nreg<Epi, 0>; break;
-        }
+        with_g256_row(variant.id, [&](auto row) { k = k_gemm256_nreg<Epi, G256_VARIANTS[decltype(row)::value].one_shot>; });
     }
     // quarter of one tile's duration (~2800 cycles per K tile + epilogue), only when the launch has several rounds
     const int stagger = (g_gemm_stagger && ntiles > 512) ? (int)(((long)nk * 2800 + epilogue_cycles<Epi>()) / 4) : 0;
@@ -784,7 +811,7 @@ extern "C" int cvx_set_option(const char* name, int value) {
         if (!one_of({0, 1}) && !(abl && value == 2)) return cvx_fail("set_option: use_gemm256 must be 0 or 1 (2, the 4-wave tile, needs a -DCVX_ABLATION build)");
         g_use_gemm256 = value;
     } else if (!strcmp(name, "gemm256_variant")) {
-        if (!one_of({0, 9}) && !(abl && one_of({1, 2, 5, 6, 7, 8, 10, 11, 12, 13, 20, 21, 29})))
+        if (!find_g256_variant(value))
             return cvx_fail("set_option: unknown gemm256_variant (ablation variants need a -DCVX_ABLATION build)");
         g_gemm256_variant = value;
     } else if (!strcmp(name, "gemm_stagger")) {

@@ -39,7 +39,8 @@ template <class E> struct epi_has_produce<E, std::enable_if_t<(E::OUT16 > 0)>> :
 template <class E, class = void> struct epi_has_preload : std::false_type {};
 template <class E> struct epi_has_preload<E, std::enable_if_t<E::HAS_PRELOAD>> : std::true_type {};
 
-// diagnostic build only (VARIANT 20): per-wave cycle sums of the four parts of a phase, block 0 -> g_gemm256_dbg
+// diagnostic builds only (G256Stamp): per-wave cycle sums of the four parts of a phase, block 0 (PerPhase), or of the
+// prologue / K loop / epilogue of one block (Coarse)
 __device__ unsigned long long g_gemm256_dbg[8 * 4];
 __device__ __forceinline__ unsigned long long stamp() {
     unsigned long long t;
@@ -72,16 +73,118 @@ __device__ __forceinline__ void stagger_first_round(int stagger_cycles) {
     while (__builtin_amdgcn_s_memtime() - t0 < want) __builtin_amdgcn_s_sleep(32);
 }
 
+// What a variant number (cvx_set_option "gemm256_variant", the template argument of gemm256_body) selects.
+enum class G256Sched {
+    FourPhase,  // four 16-MFMA phases per K tile, half-tile q read in phase rd(q) in {q-1, q}, 3-4 half-tiles in flight
+    ReadAhead,  // four phases, every half-tile read in phase q-1 (R-lo of the next K tile in phase 3), 5 half-tiles in flight
+    TwoPhase,   // two 32-MFMA phases per K tile (half the barriers), ring slots in the order R-lo, R-hi, L-lo, L-hi
+};
+enum class G256Stamp { None, PerPhase, Coarse };  // s_memtime stamps -> g_gemm256_dbg (diagnostic builds)
+struct G256Cfg {
+    bool known = true;
+    G256Sched schedule = G256Sched::FourPhase;
+    bool issue_in_mma = false;         // FourPhase: the DMA is issued from the MFMA segment instead of the load segment
+    bool rotate_k = false;             // the K tiles are walked from a per-workgroup offset (`koff`, chosen by the kernel)
+    bool staged_bf16_epilogue = true;  // bf16 outputs go through LDS into whole-row stores (false: straight from the accumulator layout)
+    // timing-only ablations: the output is garbage
+    bool no_dma = false;    // no DMA in the K loop
+    bool same_k = false;    // every DMA reads K tile 0 (L2-resident)
+    bool no_read = false;   // no fragment reads after the first K tile
+    bool no_r_dma = false;  // only the L half-tiles are DMA'd (what a weights-bypass-LDS kernel would move)
+    G256Stamp stamp = G256Stamp::None;
+};
+// 0 is the product's one-shot tile (it issues in the load segment); everything else exists in -DCVX_ABLATION builds only:
+// measured-and-rejected schedules (1, 5-8), timing-only ablations (10-13) and stamped builds (20, 21).
+constexpr G256Cfg g256_cfg(int variant) {
+    G256Cfg c;
+    switch (variant) {
+        case 0: break;
+        case 1: c.schedule = G256Sched::ReadAhead; break;
+        case 5: c.issue_in_mma = true; break;
+        case 6: c.schedule = G256Sched::TwoPhase; break;
+        case 7: c.issue_in_mma = c.rotate_k = true; break;
+        case 8: c.issue_in_mma = true; c.staged_bf16_epilogue = false; break;  // (A/B of the epilogue against 5)
+        case 10: c.no_dma = true; break;
+        case 11: c.same_k = true; break;
+        case 12: c.no_read = true; break;
+        case 13: c.no_r_dma = true; break;
+        case 20: c.stamp = G256Stamp::PerPhase; break;
+        case 21: c.issue_in_mma = true; c.stamp = G256Stamp::Coarse; break;
+        default: c.known = false; break;
+    }
+    return c;
+}
+
+// ---- pieces shared with the persistent form (gemm256p.h) ----
+// LDS-DMA source offsets: 2 x 16-B pieces per thread per half-tile; [half][piece], BYTES relative to the tile origin, K tile 0
+// (saddr-form DMA, common.h)
+__device__ __forceinline__ void g256_dma_offsets(long ldr, long ldl, uint32_t (&offR)[2][2], uint32_t (&offL)[2][2]) {
+    const int tid = threadIdx.x;  // (read here: hipcc simplifies the index arithmetic with the known range of the thread id)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int c = j * G256_THREADS + tid;
+        const int hr = c >> 3, ch = ((c & 7) ^ swz_chunk(hr)) << 3;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int tr = (hr >> 5) * 64 + half * 32 + (hr & 31);   // R tile row: wave hr>>5, rows [32*half, +32)
+            offR[half][j] = (uint32_t)(sigma_row<4>(tr) * ldr + ch) * 2u;
+            const int tl = (hr >> 6) * 128 + half * 64 + (hr & 63);  // L tile row: wave hr>>6, rows [64*half, +64)
+            offL[half][j] = (uint32_t)(tl * ldl + ch) * 2u;
+        }
+    }
+}
+// fragment read offsets inside a half-tile (k-step 0; k-step 1 = ^64): R + f*2048, f = 0,1;  L + f*2048, f = 0..3
+struct G256FragOff { int R, L; };
+__device__ __forceinline__ G256FragOff g256_frag_offsets(int wr, int wl) {
+    const int lane = threadIdx.x & 63;
+    const int sw = (lane & 15) >> 1;
+    const int fo = (lane & 15) * 128 + (((lane >> 4) ^ sw) << 4);
+    return {wr * 32 * 128 + fo, wl * 64 * 128 + fo};
+}
+__device__ __forceinline__ void g256_read_r(bf16x8 (&dst)[2][2], const char* half, int foR) {  // [frag][k-step]
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) dst[f][ks] = *(const bf16x8*)(half + ((foR + f * 2048) ^ (ks << 6)));
+}
+__device__ __forceinline__ void g256_read_l(bf16x8 (&lf)[4][2], const char* half, int foL) {
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) lf[f][ks] = *(const bf16x8*)(half + ((foL + f * 2048) ^ (ks << 6)));
+}
+// One phase: 16 MFMAs, accumulator block (a0.., b0..) += r x lf.  ZERO: the k-step-0 MFMAs start from C = 0 (the persistent
+// form's first K tile of a tile after the first: no accumulator clearing pass).
+// Issue order: the L-side fragment is the operand kept across consecutive MFMAs (b outer, a inner).  Against the order that keeps
+// the R-side fragment for four MFMAs (a outer, b inner) this is +0.3 ... +0.9 % on every ViT-g GEMM in alternating runs on one
+// board (profiles/r03_mma_order.txt); a boustrophedon order measured the same as this one.
+template <bool F16, bool ZERO = false>
+__device__ __forceinline__ void g256_mma(f32x4 (&acc)[4][8], const bf16x8 (&r)[2][2], const bf16x8 (&lf)[4][2], int a0, int b0) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+                acc[a0 + a][b0 + b] = mfma16x16x32<F16>(r[a][ks], lf[b][ks], (ZERO && ks == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[a0 + a][b0 + b]);
+    __builtin_amdgcn_s_setprio(0);
+}
+
 template <int VARIANT, class Epi>
 __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, long ldr, const uint16_t* __restrict__ Lmat,
                                              long ldl, int nk, long r0, long l0, const Epi& epi, char* smem, int koff = 0) {
+    constexpr G256Cfg cfg = g256_cfg(VARIANT);
+    static_assert(cfg.known, "gemm256_body: a variant number that g256_cfg does not know");
+    constexpr bool F16 = epi_is_f16<Epi>::value;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave & 3, wl = wave >> 2;  // waves 0-3 / 4-7 = L half 0 / 1 = the two stagger groups
     const int total = 4 * nk;
 
-    // ---- LDS-DMA source offsets: 2 x 16-B pieces per thread per half-tile ----
-    uint32_t offR[2][2], offL[2][2];  // [half][piece], BYTES relative to the tile origin, K tile 0 (saddr-form DMA, common.h)
+    // (g256_dma_offsets written out: through the helper the kernels of the no-R-DMA ablation (13) change, and choosing per variant
+    //  would be more code than the copy)
+    uint32_t offR[2][2], offL[2][2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = j * G256_THREADS + tid;
@@ -97,63 +200,68 @@ __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, 
     const uint16_t* Rb = Rmat + r0 * ldr;
     const uint16_t* Lb = Lmat + l0 * ldl;
 
-    // timing-only ablations (results are garbage): 10 = no DMA in the loop, 11 = DMA always from K tile 0 (L2-resident),
-    // 12 = no fragment reads in the loop
-    constexpr bool ABL_NO_DMA = VARIANT == 10, ABL_SAME_K = VARIANT == 11, ABL_NO_READ = VARIANT == 12;
-    constexpr bool ABL_NO_R_DMA = VARIANT == 13;  // only the L half-tiles are DMA'd (what a weights-bypass-LDS kernel would move)
+    constexpr bool TWO_PHASE = cfg.schedule == G256Sched::TwoPhase;
     auto issue = [&](int q) {  // half-tile q -> ring slot q & 7
-        // koff rotates the K order per workgroup (variant 7): workgroups that share an operand panel then request its K
-        // slabs at different times, so the later ones find the lines IN L2 instead of queueing behind the same miss
-        int kt = ABL_SAME_K ? 0 : (q >> 2) + koff;
+        // rotate_k: koff rotates the K order per workgroup; workgroups that share an operand panel then request its K slabs at
+        // different times, so the later ones find the lines IN L2 instead of queueing behind the same miss
+        int kt = cfg.same_k ? 0 : (q >> 2) + (cfg.rotate_k ? koff : 0);
         if (kt >= nk) kt -= nk;
         const int kind = q & 3;
         const uint32_t dst = lds_addr(smem) + (q & 7) * G256_HALF_BYTES + wave * 1024;
-        // slot order inside a K tile: variants 0-5: R-lo, L-lo, R-hi, L-hi;  variant 6: R-lo, R-hi, L-lo, L-hi
-        const bool isL = VARIANT == 6 ? (kind >= 2) : (kind & 1);
-        const int half = VARIANT == 6 ? (kind & 1) : (kind >> 1);
+        // slot order inside a K tile: R-lo, L-lo, R-hi, L-hi;  the two-phase schedule: R-lo, R-hi, L-lo, L-hi
+        const bool isL = TWO_PHASE ? (kind >= 2) : (kind & 1);
+        const int half = TWO_PHASE ? (kind & 1) : (kind >> 1);
         const uint16_t* src = (isL ? Lb : Rb) + kt * BK;
         const uint32_t o0 = isL ? offL[half][0] : offR[half][0];
         const uint32_t o1 = isL ? offL[half][1] : offR[half][1];
-        if (ABL_NO_R_DMA && !isL) {  // keep the vmcnt arithmetic: two cheap L2-resident pieces instead
+        if (cfg.no_r_dma && !isL) {  // keep the vmcnt arithmetic: two cheap L2-resident pieces instead
             glds16_saddr2<G256_THREADS * 16>(Lb, o0 % 128, o1 % 128, dst);
             return;
         }
         glds16_saddr2<G256_THREADS * 16>(src, o0, o1, dst);
     };
 
-    // ---- fragment read offsets inside a half-tile (k-step 0; k-step 1 = ^64) ----
+    // (g256_frag_offsets written out: through the helper hipcc no longer shares this lane arithmetic with the epilogue's, and every
+    //  one-shot kernel changes)
     const int sw = (lane & 15) >> 1;
     const int fo = (lane & 15) * 128 + (((lane >> 4) ^ sw) << 4);
-    const int foR = wr * 32 * 128 + fo;  // + f*2048, f = 0,1
-    const int foL = wl * 64 * 128 + fo;  // + f*2048, f = 0..3
-
+    const int foR = wr * 32 * 128 + fo, foL = wl * 64 * 128 + fo;
+    bf16x8 lf[4][2];  // L fragments, [frag][k-step]
+    // (the read-ahead schedule (1) and the no-read ablation (12) read under a condition; there the helpers change the kernels, so
+    //  these two keep the loops written out)
+    constexpr bool READS_WRITTEN_OUT = cfg.schedule == G256Sched::ReadAhead || cfg.no_read;
+    auto read_r = [&](bf16x8 (&dst)[2][2], const char* half) {
+        if constexpr (READS_WRITTEN_OUT) {
+#pragma unroll
+            for (int f = 0; f < 2; ++f)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) dst[f][ks] = *(const bf16x8*)(half + ((foR + f * 2048) ^ (ks << 6)));
+        } else g256_read_r(dst, half, foR);
+    };
+    auto read_l = [&](const char* half) {
+        if constexpr (READS_WRITTEN_OUT) {
+#pragma unroll
+            for (int f = 0; f < 4; ++f)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) lf[f][ks] = *(const bf16x8*)(half + ((foL + f * 2048) ^ (ks << 6)));
+        } else g256_read_l(lf, half, foL);
+    };
     f32x4 acc[4][8];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto mma = [&](const bf16x8 (&r)[2][2], int a0, int b0) { g256_mma<F16>(acc, r, lf, a0, b0); };
 
     [[maybe_unused]] unsigned long long dbg_load = 0, dbg_lbar = 0, dbg_mma = 0, dbg_mbar = 0;
-    constexpr bool STAMP = VARIANT == 20;
-    constexpr bool COARSE = VARIANT == 21;
+    constexpr bool STAMP = cfg.stamp == G256Stamp::PerPhase;
+    constexpr bool COARSE = cfg.stamp == G256Stamp::Coarse;
     [[maybe_unused]] unsigned long long c0 = 0, c1 = 0, c2 = 0;
     if constexpr (COARSE) c0 = stamp();
-    if constexpr (VARIANT == 6) {
-    // ---- variant 6: TWO phases of 32 MFMAs per K tile (half the barriers): A = (R, L-lo), B = (R, L-hi); the DMA runs
-    //      exactly one K tile ahead (R halves issued in phase A, L halves in phase B) ----
-    bf16x8 rlo[2][2], rhi[2][2], lf[4][2];
-    auto read_r = [&](bf16x8 (&dst)[2][2], const char* half) {
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) dst[f][ks] = *(const bf16x8*)(half + ((foR + f * 2048) ^ (ks << 6)));
-    };
-    auto read_l = [&](const char* half) {
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) lf[f][ks] = *(const bf16x8*)(half + ((foL + f * 2048) ^ (ks << 6)));
-    };
+    if constexpr (TWO_PHASE) {
+    // ---- two phases of 32 MFMAs per K tile (6): A = (R, L-lo), B = (R, L-hi); the DMA runs exactly one K tile ahead
+    //      (R halves issued in phase A, L halves in phase B) ----
+    bf16x8 rlo[2][2], rhi[2][2];
     auto mma32 = [&](int b0) {
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -162,7 +270,7 @@ __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, 
             for (int b = 0; b < 4; ++b)
 #pragma unroll
                 for (int a = 0; a < 4; ++a)
-                    acc[a][b0 + b] = mfma16x16x32<epi_is_f16<Epi>::value>(a < 2 ? rlo[a][ks] : rhi[a - 2][ks], lf[b][ks], acc[a][b0 + b]);
+                    acc[a][b0 + b] = mfma16x16x32<F16>(a < 2 ? rlo[a][ks] : rhi[a - 2][ks], lf[b][ks], acc[a][b0 + b]);
         __builtin_amdgcn_s_setprio(0);
     };
     for (int q = 0; q < 4; ++q) issue(q);
@@ -194,35 +302,12 @@ __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, 
         for (; t < nk; ++t) ktile(t, std::false_type{});
     }
     if (wl == 0) __builtin_amdgcn_s_barrier();
-    } else if constexpr (VARIANT == 0 || VARIANT == 4 || VARIANT == 5 || VARIANT == 8 || VARIANT >= 10) {
-    // ---- variants 0/4/5: reads at rd(q) in {q-1,q}, 3-4 half-tiles in flight (A = 5) ----
-    bf16x8 rlo[2][2], rhi[2][2], lf[4][2];  // [frag][k-step]
+    } else if constexpr (cfg.schedule == G256Sched::FourPhase) {
+    // ---- four phases, reads at rd(q) in {q-1,q}, 3-4 half-tiles in flight: the product's one-shot tile (0), which issues in
+    //      the load segment, and its issue-in-the-MFMA-segment form (5, 7, 8, 21) ----
+    bf16x8 rlo[2][2], rhi[2][2];
 
-    auto read_r = [&](bf16x8 (&dst)[2][2], const char* half) {
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) dst[f][ks] = *(const bf16x8*)(half + ((foR + f * 2048) ^ (ks << 6)));
-    };
-    auto read_l = [&](const char* half) {
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) lf[f][ks] = *(const bf16x8*)(half + ((foL + f * 2048) ^ (ks << 6)));
-    };
-    auto mma = [&](const bf16x8 (&r)[2][2], int a0, int b0) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int b = 0; b < 4; ++b)  // (B operand kept across consecutive MFMAs: gemm256p.h)
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-                    acc[a0 + a][b0 + b] = mfma16x16x32<epi_is_f16<Epi>::value>(r[a][ks], lf[b][ks], acc[a0 + a][b0 + b]);
-        __builtin_amdgcn_s_setprio(0);
-    };
-
-    // ---- prologue: half-tiles 0..A-1 in flight, 0 and 1 landed ----
+    // ---- prologue: half-tiles 0..4 in flight, 0 and 1 landed ----
 #pragma unroll
     for (int q = 0; q < 5; ++q)
         if (q < total) issue(q);
@@ -234,15 +319,18 @@ __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, 
     // one K tile.  STEADY: all four DMA issues exist -> unconditional issue + exact counted waits (no branches).
     // ISSUE_IN_MMA: the DMA is issued from the MFMA segment (in the issue gaps of the wave's own MFMAs) instead of the
     // load segment, which is the critical one (it competes for issue slots with the partner wave's MFMA stream).
-    constexpr bool ISSUE_IN_MMA = (VARIANT == 5 || VARIANT == 8 || VARIANT == 21);  // 8 = 5 with the un-staged bf16 epilogue (A/B)
+    constexpr bool ISSUE_IN_MMA = cfg.issue_in_mma;
     auto ktile = [&](int t, auto steady_tag) {
         constexpr bool STEADY = decltype(steady_tag)::value;
         const char* st = smem + (t & 1) * 4 * G256_HALF_BYTES;
         const int g = 4 * t;
         [[maybe_unused]] unsigned long long t0 = 0;
         if constexpr (STAMP) t0 = stamp();
+        auto mark = [&](unsigned long long& sum) {  // per-phase stamps: the cycles since the previous mark go to `sum`
+            if constexpr (STAMP) { const auto t1 = stamp(); sum += t1 - t0; t0 = t1; }
+        };
         auto do_issue = [&](int q) {
-            if constexpr (ABL_NO_DMA) return;
+            if constexpr (cfg.no_dma) return;
             if (STEADY || q < total) issue(q);
         };
         auto do_wait = [&](auto n_tag) {
@@ -255,55 +343,55 @@ __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, 
         using W6 = std::integral_constant<int, ISSUE_IN_MMA ? 4 : 6>;
         using W8 = std::integral_constant<int, ISSUE_IN_MMA ? 6 : 8>;
         // ---- phase 0: (R-lo, L-lo) ----
-        if (!ABL_NO_READ || t == 0) {
+        if (!cfg.no_read || t == 0) {
             read_r(rlo, st);
             read_l(st + G256_HALF_BYTES);
         }
         if constexpr (!ISSUE_IN_MMA) do_issue(g + 5);
         do_wait(W6{});
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_load += t1 - t0; t0 = t1; }
+        mark(dbg_load);
         __builtin_amdgcn_s_barrier();
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_lbar += t1 - t0; t0 = t1; }
+        mark(dbg_lbar);
         if constexpr (ISSUE_IN_MMA) do_issue(g + 5);
         mma(rlo, 0, 0);
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_mma += t1 - t0; t0 = t1; }
+        mark(dbg_mma);
         __builtin_amdgcn_s_barrier();
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_mbar += t1 - t0; t0 = t1; }
+        mark(dbg_mbar);
         // ---- phase 1: (R-hi, L-lo) ----
-        if (!ABL_NO_READ || t == 0) read_r(rhi, st + 2 * G256_HALF_BYTES);
+        if (!cfg.no_read || t == 0) read_r(rhi, st + 2 * G256_HALF_BYTES);
         if constexpr (!ISSUE_IN_MMA) do_issue(g + 6);
         do_wait(W6{});
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_load += t1 - t0; t0 = t1; }
+        mark(dbg_load);
         __builtin_amdgcn_s_barrier();
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_lbar += t1 - t0; t0 = t1; }
+        mark(dbg_lbar);
         if constexpr (ISSUE_IN_MMA) do_issue(g + 6);
         mma(rhi, 2, 0);
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_mma += t1 - t0; t0 = t1; }
+        mark(dbg_mma);
         __builtin_amdgcn_s_barrier();
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_mbar += t1 - t0; t0 = t1; }
+        mark(dbg_mbar);
         // ---- phase 2: (R-hi, L-hi) ----
-        if (!ABL_NO_READ || t == 0) read_l(st + 3 * G256_HALF_BYTES);
+        if (!cfg.no_read || t == 0) read_l(st + 3 * G256_HALF_BYTES);
         if constexpr (!ISSUE_IN_MMA) do_issue(g + 7);
         do_wait(W8{});
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_load += t1 - t0; t0 = t1; }
+        mark(dbg_load);
         __builtin_amdgcn_s_barrier();
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_lbar += t1 - t0; t0 = t1; }
+        mark(dbg_lbar);
         if constexpr (ISSUE_IN_MMA) do_issue(g + 7);
         mma(rhi, 2, 4);
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_mma += t1 - t0; t0 = t1; }
+        mark(dbg_mma);
         __builtin_amdgcn_s_barrier();
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_mbar += t1 - t0; t0 = t1; }
+        mark(dbg_mbar);
         // ---- phase 3: (R-lo, L-hi) ----
         if constexpr (!ISSUE_IN_MMA) do_issue(g + 8);
         do_wait(W6{});
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_load += t1 - t0; t0 = t1; }
+        mark(dbg_load);
         __builtin_amdgcn_s_barrier();
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_lbar += t1 - t0; t0 = t1; }
+        mark(dbg_lbar);
         if constexpr (ISSUE_IN_MMA) do_issue(g + 8);
         mma(rlo, 0, 4);
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_mma += t1 - t0; t0 = t1; }
+        mark(dbg_mma);
         __builtin_amdgcn_s_barrier();
-        if constexpr (STAMP) { const auto t1 = stamp(); dbg_mbar += t1 - t0; t0 = t1; }
+        mark(dbg_mbar);
     };
     {   // (a per-tile runtime choice between the two instantiations makes hipcc spill the accumulators: keep two loops)
         int t = 0;
@@ -313,33 +401,9 @@ __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, 
     if (wl == 0) __builtin_amdgcn_s_barrier();  // pairs with the stagger barrier of waves 4-7
 
     } else {
-    // ---- variant 1: every half-tile read in phase q-1, AHEAD-2 half-tiles in flight ----
-    constexpr int AHEAD = VARIANT == 1 ? 7 : (VARIANT == 2 ? 6 : 5);
-    bf16x8 rx[2][2], ry[2][2], lf[4][2];  // [frag][k-step]; rx / ry swap the R-lo / R-hi roles every K tile
-
-    auto read_r = [&](bf16x8 (&dst)[2][2], const char* half) {
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) dst[f][ks] = *(const bf16x8*)(half + ((foR + f * 2048) ^ (ks << 6)));
-    };
-    auto read_l = [&](const char* half) {
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) lf[f][ks] = *(const bf16x8*)(half + ((foL + f * 2048) ^ (ks << 6)));
-    };
-    auto mma = [&](const bf16x8 (&r)[2][2], int a0, int b0) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int b = 0; b < 4; ++b)  // (B operand kept across consecutive MFMAs: gemm256p.h)
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-                    acc[a0 + a][b0 + b] = mfma16x16x32<epi_is_f16<Epi>::value>(r[a][ks], lf[b][ks], acc[a0 + a][b0 + b]);
-        __builtin_amdgcn_s_setprio(0);
-    };
+    // ---- read-ahead (1): every half-tile read in phase q-1, AHEAD-2 = 5 half-tiles in flight ----
+    constexpr int AHEAD = 7;
+    bf16x8 rx[2][2], ry[2][2];  // rx / ry swap the R-lo / R-hi roles every K tile
     // end of the load segment of phase g: issue half-tile g+AHEAD, then retire (own pieces of) half-tile g+2
     auto issue_and_wait = [&](int g) {
         if (g + AHEAD < total) issue(g + AHEAD);
@@ -370,7 +434,7 @@ __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, 
         __builtin_amdgcn_s_barrier();
     };
 
-    // ---- prologue: half-tiles 0..A-1 in flight; 0 and 1 landed; R-lo(0) read ----
+    // ---- prologue: half-tiles 0..AHEAD-1 in flight; 0 and 1 landed; R-lo(0) read ----
 #pragma unroll
     for (int q = 0; q < AHEAD; ++q)
         if (q < total) issue(q);
@@ -440,7 +504,7 @@ __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, 
                 }
             }
         }
-    } else if constexpr (epi_has_produce<Epi>::value && VARIANT != 8) {
+    } else if constexpr (epi_has_produce<Epi>::value && cfg.staged_bf16_epilogue) {
         // bf16 row-major epilogues, staged through LDS like the fp32 one: in accumulator layout every 16-B store of a wave
         // instruction lands in a different half-used cache line (16 rows x 4 pieces); staged, an instruction writes whole
         // 128-B (BF16) / 64-B (SwiGLU) row segments.  Per wave: 32 rows x (ROWB + 16) bytes of the idle DMA ring.

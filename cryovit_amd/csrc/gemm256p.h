@@ -1,4 +1,6 @@
-// Persistent form of the 256x256x64 phase-pipelined bf16 GEMM tile (gemm256.h, schedule "variant 5").
+// Persistent form of the 256x256x64 phase-pipelined bf16 GEMM tile (gemm256.h): the four-phase schedule that issues its DMA in
+// the MFMA segment (as a one-shot tile: gemm256_variant 5; the product's one-shot tile, 0, issues in the load segment).
+// cvx_set_option("gemm256_variant") 9 selects this form, 29 its stamped build.
 //
 // One workgroup per CU walks a static list of output tiles; the LDS-DMA operand stream NEVER stops at a tile boundary:
 //
@@ -38,7 +40,6 @@
 
 namespace cvx {
 
-constexpr bool DIRECT8 = true;  // SwiGLU epilogue: store straight from the accumulator layout (A/B switch for tools/)
 constexpr int G256P_LDS_BYTES = G256_LDS_BYTES + 8 * 2048;  // ring + two 1-KiB constants pieces (bias, gamma) per wave
 
 // vector-memory operations ONE wave issues in the staged epilogue of one interior tile and that may still be in flight
@@ -114,18 +115,7 @@ __device__ __forceinline__ void gemm256p_body(const uint16_t* __restrict__ Rmat,
     }
 
     uint32_t offR[2][2], offL[2][2];  // [half][piece] LDS-DMA source offsets, BYTES relative to the tile origin
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int c = j * G256_THREADS + tid;
-        const int hr = c >> 3, ch = ((c & 7) ^ swz_chunk(hr)) << 3;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const int tr_ = (hr >> 5) * 64 + half * 32 + (hr & 31);
-            offR[half][j] = (uint32_t)(sigma_row<4>(tr_) * ldr + ch) * 2u;
-            const int tl_ = (hr >> 6) * 128 + half * 64 + (hr & 63);
-            offL[half][j] = (uint32_t)(tl_ * ldl + ch) * 2u;
-        }
-    }
+    g256_dma_offsets(ldr, ldl, offR, offL);
     long r0, l0;
     const uint16_t *Rc, *Lc, *Rn, *Ln;  // operand panels of the current / next tile
     // group_l < 0: this workgroup's chunk of the sequence is walked from its END (the launch then finishes where the
@@ -186,9 +176,7 @@ __device__ __forceinline__ void gemm256p_body(const uint16_t* __restrict__ Rmat,
         const uint32_t dst = lds0 + (((uint32_t)(st - smem) + slot * G256_HALF_BYTES) & (G256_LDS_BYTES - 1));
         glds16_saddr2<G256_THREADS * 16>(src, off[0], off[1], dst);
     };
-    const int sw = (lane & 15) >> 1;
-    const int fo = (lane & 15) * 128 + (((lane >> 4) ^ sw) << 4);
-    const int foR = wr * 32 * 128 + fo, foL = wl * 64 * 128 + fo;
+    const G256FragOff fo = g256_frag_offsets(wr, wl);
 
     f32x4 acc[4][8];
 #pragma unroll
@@ -196,45 +184,10 @@ __device__ __forceinline__ void gemm256p_body(const uint16_t* __restrict__ Rmat,
 #pragma unroll
         for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     bf16x8 rlo[2][2], rhi[2][2], lf[4][2];
-
-    auto read_r = [&](bf16x8 (&dst)[2][2], const char* half) {
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) dst[f][ks] = *(const bf16x8*)(half + ((foR + f * 2048) ^ (ks << 6)));
-    };
-    auto read_l = [&](const char* half) {
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) lf[f][ks] = *(const bf16x8*)(half + ((foL + f * 2048) ^ (ks << 6)));
-    };
-    // ZERO: first K tile of a tile after the first -- the k-step-0 MFMAs start from C = 0 (no accumulator clearing pass)
-    auto mma = [&](const bf16x8 (&r)[2][2], int a0, int b0, auto zero_tag) {
-        constexpr bool ZERO = decltype(zero_tag)::value;
-        __builtin_amdgcn_s_setprio(1);
-#if !defined(CVX_MMA_ORDER_AB)
-        // issue order: the L-side fragment is the operand kept across consecutive MFMAs (b outer, a inner).  Against the order that
-        // keeps the R-side fragment for four MFMAs (a outer, b inner: -DCVX_MMA_ORDER_AB) this is +0.3 ... +0.9 % on every ViT-g GEMM
-        // in alternating runs on one board (profiles/r03_mma_order.txt); a boustrophedon order measured the same as this one
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-                    acc[a0 + a][b0 + b] = mfma16x16x32<F16>(r[a][ks], lf[b][ks], (ZERO && ks == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[a0 + a][b0 + b]);
-#else
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    acc[a0 + a][b0 + b] = mfma16x16x32<F16>(r[a][ks], lf[b][ks], (ZERO && ks == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[a0 + a][b0 + b]);
-#endif
-        __builtin_amdgcn_s_setprio(0);
-    };
+    auto read_r = [&](bf16x8 (&dst)[2][2], const char* half) { g256_read_r(dst, half, fo.R); };
+    auto read_l = [&](const char* half) { g256_read_l(lf, half, fo.L); };
+    // first_tag: the first K tile of a tile after the first starts its accumulators from zero (ZERO of g256_mma)
+    auto mma = [&](const bf16x8 (&r)[2][2], int a0, int b0, auto first_tag) { g256_mma<F16, decltype(first_tag)::value>(acc, r, lf, a0, b0); };
 
     constexpr int S = FULL ? epi_stores_per_wave<Epi>() : 0;
     // One K tile.  Rk1 / Lk1: operand streams at the NEXT K tile (the next tile's K tile 0 after this tile's last one),
@@ -509,10 +462,10 @@ __device__ __forceinline__ void gemm256p_body(const uint16_t* __restrict__ Rmat,
             uint32_t loff[32 / RPI];
 #pragma unroll
             for (int i = 0; i < 32 / RPI; ++i) loff[i] = ((uint32_t)(RPI * i + srow) * ldc + (uint32_t)(spiece * 8)) * 2u;  // BYTES
-            if constexpr (O16 == 8 && DIRECT8) {
-                // 8 packed outputs = 16 B per lane: in accumulator layout a wave instruction already writes 16 rows x 64
-                // contiguous bytes (the four lane groups of a row sit side by side) -- the same shape the staged path
-                // produces, without the LDS round trip
+            if constexpr (O16 == 8) {
+                // SwiGLU: 8 packed outputs = 16 B per lane: in accumulator layout a wave instruction already writes 16 rows x 64
+                // contiguous bytes (the four lane groups of a row sit side by side) -- the shape staging would produce, without
+                // the LDS round trip.  The 64-B segments are left to the L2's write combining (no streaming stores).
                 const uint32_t doff = ((uint32_t)(lane & 15) * ldc + (uint32_t)(gq * 8)) * 2u;
 #pragma unroll
                 for (int b = 0; b < 8; ++b) {
@@ -527,7 +480,8 @@ __device__ __forceinline__ void gemm256p_body(const uint16_t* __restrict__ Rmat,
                     if (FULL || (16 * b + (lane & 15) < mleft && ow + gq * 8 < (epi.n_valid >> Epi::OUT_SHIFT)))
                         gst16_saddr(ob, doff, u32x4{w[0], w[1], w[2], w[3]});
                 }
-            } else
+            } else {
+            static_assert(O16 == 16, "the staged path packs 16 outputs per 16 accumulators");
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 char* oq = (char*)(outw + (long)(32 * q) * ldc);
@@ -541,12 +495,8 @@ __device__ __forceinline__ void gemm256p_body(const uint16_t* __restrict__ Rmat,
                     uint32_t w[O16 / 2];
                     epi.produce(ctx, v, w, row_consts(2 * q + bb));
                     char* dst = stg + (16 * bb + (lane & 15)) * PITCHB + gq * (O16 * 2);
-                    if constexpr (O16 == 16) {
-                        *(uint4*)dst = uint4{w[0], w[1], w[2], w[3]};
-                        *(uint4*)(dst + 16) = uint4{w[4], w[5], w[6], w[7]};
-                    } else {
-                        *(uint4*)dst = uint4{w[0], w[1], w[2], w[3]};
-                    }
+                    *(uint4*)dst = uint4{w[0], w[1], w[2], w[3]};
+                    *(uint4*)(dst + 16) = uint4{w[4], w[5], w[6], w[7]};
                 }
                 // (all the staged rows are read BEFORE the first store: the asm stores are ordering points for hipcc, and read /
                 //  wait / store one row at a time exposed the LDS latency 16 times per tile)
@@ -557,10 +507,11 @@ __device__ __forceinline__ void gemm256p_body(const uint16_t* __restrict__ Rmat,
                 for (int i = 0; i < 32 / RPI; ++i) {
                     const int row = RPI * i + srow;
                     if (FULL || (32 * q + row < mleft && ook)) {
-                        if constexpr (O16 == 16 && CVX_BF16_STORE_NT) gst16_saddr_nt(oq, loff[i], u32x4{d[i].x, d[i].y, d[i].z, d[i].w});
-                        else gst16_saddr(oq, loff[i], u32x4{d[i].x, d[i].y, d[i].z, d[i].w});  // 64-B segments: left to the L2's write combining
+                        if constexpr (CVX_BF16_STORE_NT) gst16_saddr_nt(oq, loff[i], u32x4{d[i].x, d[i].y, d[i].z, d[i].w});
+                        else gst16_saddr(oq, loff[i], u32x4{d[i].x, d[i].y, d[i].z, d[i].w});
                     }
                 }
+            }
             }
         }
         }  // !MREG

@@ -31,9 +31,29 @@ constexpr int G4W_LDS_BYTES = G4W_RING * G4W_SUB_BYTES;
 
 __device__ __forceinline__ int swz64(int row) { return (-(row >> 2)) & 3; }  // chunk XOR for 64-B rows
 
+// What a variant number of gemm4w_body selects: 0 = the tile, 1 / 2 = timing-only ablations whose output is garbage (they carry the
+// gemm256_variant numbers of the same two ablations of the 8-wave tile's table in gemm.hip)
+struct G4wCfg {
+    bool known = true;
+    bool no_dma = false;  // no DMA in the K loop
+    bool same_k = false;  // every DMA reads k-step 0 (L2-resident)
+};
+constexpr G4wCfg g4w_cfg(int variant) {
+    G4wCfg c;
+    switch (variant) {
+        case 0: break;
+        case 1: c.no_dma = true; break;
+        case 2: c.same_k = true; break;
+        default: c.known = false; break;
+    }
+    return c;
+}
+
 template <int VARIANT, class Epi>
 __device__ __forceinline__ void gemm4w_body(const uint16_t* __restrict__ Rmat, long ldr, const uint16_t* __restrict__ Lmat,
                                             long ldl, int nks, long r0, long l0, const Epi& epi, char* smem) {
+    constexpr G4wCfg cfg = g4w_cfg(VARIANT);
+    static_assert(cfg.known, "gemm4w_body: a variant number that g4w_cfg does not know");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wl = wave & 1;
@@ -91,14 +111,14 @@ __device__ __forceinline__ void gemm4w_body(const uint16_t* __restrict__ Rmat, l
         // sub-stage j+1 (8 pieces per wave) must have landed; j+2, j+3 may stay in flight
         // (lgkmcnt(0): this wave's ds_reads of sub-stage j, issued a whole k-step ago, are complete -> its slot may be
         //  rewritten by whoever passes the barrier first)
-        if constexpr (STEADY && VARIANT != 1) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
+        if constexpr (STEADY && !cfg.no_dma) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        const bool do_issue = VARIANT != 1 && (STEADY || j + 4 < nks), do_read = STEADY || j + 1 < nks;
+        const bool do_issue = !cfg.no_dma && (STEADY || j + 4 < nks), do_read = STEADY || j + 1 < nks;
         const uint32_t dst = lds_addr(smem) + ((j + 4) & (G4W_RING - 1)) * G4W_SUB_BYTES;
         const char* nst = smem + ((j + 1) & (G4W_RING - 1)) * G4W_SUB_BYTES;
-        const uint16_t* rs = Rb + (VARIANT == 2 ? 0 : (j + 4) * G4W_KS);  // VARIANT 1/2: timing-only ablations (no DMA / L2-resident DMA)
-        const uint16_t* ls = Lb + (VARIANT == 2 ? 0 : (j + 4) * G4W_KS);
+        const uint16_t* rs = Rb + (cfg.same_k ? 0 : (j + 4) * G4W_KS);
+        const uint16_t* ls = Lb + (cfg.same_k ? 0 : (j + 4) * G4W_KS);
         // hand interleave: per row of 8 MFMAs one LDS-DMA piece of sub-stage j+4 and two fragment reads of k-step j+1
 #pragma unroll
         for (int a = 0; a < 8; ++a) {

@@ -48,7 +48,8 @@ int cvx_device_arch(char* buf, int buflen);
  * attn_variant, attn_xcd_remap, attn_mfma_prio, attn_half_tile, win_attn_prefetch, win_attn_x32, conv_halo, conv_wide, convt_small
  * -- each is described where it is defined (csrc/gemm.hip, attention.hip, hiera.hip) and in DESIGN.md s.4 / s.8. */
 int cvx_set_option(const char* name, int value);
-/* diagnostic: per-wave cycle sums {load, load-barrier, mma, mma-barrier} x 8 waves written by gemm256 variant 20 */
+/* diagnostic: per-wave cycle sums {load, load-barrier, mma, mma-barrier} x 8 waves written by the per-phase stamped build of the
+ * one-shot 256-tile (gemm256_variant 20; 21, the coarse stamps, writes {prologue, K loop, epilogue, total} there) */
 int cvx_debug_read_gemm256(unsigned long long* out32);
 /* diagnostic: cycle stamps of the persistent tile kernel (variant 29, -DCVX_ABLATION builds only; zeros otherwise):
  * [wave group 2][tile 8][6] = K-loop start, K-loop end, epilogue start, epilogue end, next tile released, first K tile done */

@@ -754,6 +754,32 @@ def test_gemm256_bf16_and_resid(gpu, M, N, K, gemm256_variant):
     assert all(torch.equal(outs[0], o) for o in outs[1:])
 
 
+@pytest.mark.parametrize("gemm256_variant", [(1, 7), (1, 8)], indirect=True)
+@pytest.mark.parametrize("M,N,K", [(2065, 512, 256), (1300, 256, 448)])
+def test_gemm256_rotated_and_unstaged(gpu, M, N, K, gemm256_variant):
+    """The two one-shot schedules no other case selects: 7 walks the K tiles from a per-workgroup offset, 8 stores bf16 straight
+    from the accumulator layout.  References and tolerances of test_gemm256_bf16_and_resid.  K = 256 is the shortest K loop the
+    tile accepts (4 K tiles; 9 x 2 tiles with a ragged last row tile, and the offset ((tr & 3) + (tl & 7)) % 4 wraps); K = 448 is
+    an odd K-tile count (7), so the drained last two K tiles start on the other half of the LDS ring."""
+    from cryovit_amd._lib import EPI_BF16, EPI_RESID
+    from cryovit_amd.engine import ops
+
+    a, w, b, gm = rnd(M, K, seed=61), rnd(N, K, seed=62, scale=K**-0.5), rnd(N, seed=63), rnd(N, seed=64)
+    A, Wd = padded_bf16(a, ops.alloc_rows(M), K, gpu), padded_bf16(w, N, K, gpu)
+    ref = bf(a).float() @ bf(w).float().T + b
+    out = torch.full((ops.alloc_rows(M), N), 7.0, dtype=torch.bfloat16, device=gpu)
+    ops.gemm(EPI_BF16, A, Wd, out, b.to(gpu), m=M, n=N)
+    got = out[:M].float().cpu()
+    assert torch.allclose(got, ref, atol=2e-2, rtol=1e-2), float((got - ref).abs().max())
+    assert torch.all(out[M:].float() == 7.0)
+    x0 = rnd(M, N, seed=65)
+    x = torch.full((ops.alloc_rows(M), N), 3.0, device=gpu)
+    x[:M] = x0.to(gpu)
+    ops.gemm(EPI_RESID, A, Wd, x, b.to(gpu), m=M, n=N, gamma=gm.to(gpu))
+    assert torch.allclose(x[:M].cpu(), x0 + gm * ref, atol=2e-4, rtol=1e-4)
+    assert torch.all(x[M:] == 3.0)
+
+
 @pytest.mark.parametrize("gemm256_variant", [(1, 5), (1, 9)], indirect=True)
 def test_gemm256_padded_columns(gpu, gemm256_variant):
     """N not a multiple of the tile: W / bias / gamma padded to 512 rows, 400 valid output columns, the output buffers exactly
