@@ -888,6 +888,11 @@ static int gemm_dispatch(const cvx_gemm_desc* d, hipStream_t st) {
     const bool f16 = d->dtype == CVX_DTYPE_F16, ln = d->ln_rowstat != nullptr;
     if (f16 && d->epilogue != CVX_EPI_BF16 && d->epilogue != CVX_EPI_BF16_GELU && d->epilogue != CVX_EPI_CONVT)
         return cvx_fail("gemm: fp16 operands are built for the plain / GELU / ConvT epilogues (the segmentation head)");
+    // the LayerNorm fold exists for bf16 operands and these four epilogues: anything else would run without it (or, fp16, on the
+    // bf16 MFMA) and return 0
+    if (ln && f16) return cvx_fail("gemm: ln_rowstat (LayerNorm fold) needs bf16 operands");
+    if (ln && d->epilogue != CVX_EPI_BF16 && d->epilogue != CVX_EPI_BF16_GELU && d->epilogue != CVX_EPI_SWIGLU && d->epilogue != CVX_EPI_VT)
+        return cvx_fail("gemm: ln_rowstat (LayerNorm fold) is built for the BF16 / BF16_GELU / SWIGLU / VT epilogues");
     uint16_t* out16 = (uint16_t*)d->out;
     const long cs_off = ln ? d->n_pad : 0;  // LN fold: bias = [b' | cs], n_pad floats apart
     auto nreg = [&](const auto& e) { return dispatch_nreg(A, d->lda, W, d->ldw, d->m, d->n_pad, d->k_pad, e, st); };

@@ -447,7 +447,9 @@ __device__ __forceinline__ void gemm256p_body(const uint16_t* __restrict__ Rmat,
                 const uintptr_t pp = (uintptr_t)(epi.part + (((r0 >> 6) + wr) * epi.part_rows + mw) * 2);  // (wave-uniform: into SGPRs)
                 char* pbase = (char*)(((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(pp >> 32)) << 32) |
                                       (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pp));
-                gst16_saddr(pbase, (uint32_t)lane * 16u, __builtin_bit_cast(u32x4, st4));  // (rows past m_valid: allocated, never read)
+                // rows past m_valid stay as the caller left them, as on the small tiles (a lane's second row alone can be outside)
+                if (FULL || 2 * lane + 1 < mleft) gst16_saddr(pbase, (uint32_t)lane * 16u, __builtin_bit_cast(u32x4, st4));
+                else if (2 * lane < mleft) *(float2*)(pbase + lane * 16) = float2{st4[0], st4[1]};
             }
         } else {
             constexpr int O16 = Epi::OUT16, ROWB = 4 * O16 * 2, PITCHB = ROWB + 16, LPR = ROWB / 16, RPI = 64 / LPR;

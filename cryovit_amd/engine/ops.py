@@ -97,15 +97,20 @@ def gemm(epilogue: int, a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bia
     """C = A W^T with a fused epilogue.  a: bf16 [M_alloc, lda]; w: bf16 [n_pad, k_pad] (packed).  fp16 operands (both a and
     w) select the fp16 MFMA and fp16 outputs (plain / GELU / ConvT epilogues: the segmentation head).
     ln_rowstat (fp32 [rows, 2]): LayerNorm folded into the GEMM -- bias is then fp32 [2, n_pad] (b' | column sums of the packed
-    weight).  EPI_RESID_HL: out / out2 = the bf16 hi / lo halves of the residual stream, stat_part fp32 [n_pad/64, rows, 2]."""
+    weight); bf16 operands and the BF16 / BF16_GELU / SWIGLU / VT epilogues only.  EPI_RESID_HL: out / out2 = the bf16 hi / lo
+    halves of the residual stream, stat_part fp32 [n/64, rows, 2] (a larger one is accepted; slots < n/64 of rows < m are written)."""
     dev = _dev_check(a, w, out, bias, gamma, pos, ln_rowstat, out2, stat_part)
     assert a.dtype == w.dtype and a.dtype in (torch.bfloat16, torch.float16) and bias.dtype == torch.float32
+    if ln_rowstat is not None and a.dtype != torch.bfloat16:
+        raise _lib.CvxError("gemm: ln_rowstat (LayerNorm fold) needs bf16 operands")
+    if ln_rowstat is not None and epilogue not in (_lib.EPI_BF16, _lib.EPI_BF16_GELU, _lib.EPI_SWIGLU, _lib.EPI_VT):
+        raise _lib.CvxError("gemm: ln_rowstat (LayerNorm fold) is built for the BF16 / BF16_GELU / SWIGLU / VT epilogues")
     assert a.stride(-1) == 1 and w.is_contiguous() and bias.numel() >= w.shape[0] * (2 if ln_rowstat is not None else 1)
     if ln_rowstat is not None and (ln_rowstat.dtype != torch.float32 or ln_rowstat.numel() < 2 * round_up(m, ROW_PAD)):
         raise _lib.CvxError("gemm: ln_rowstat must be fp32 [rows, 2] with rows >= m rounded up to 256 (whole tiles are fetched)")
     if epilogue == _lib.EPI_RESID_HL:
         if out2 is None or stat_part is None or out.dtype != torch.bfloat16 or out2.dtype != torch.bfloat16 or stat_part.dim() != 3:
-            raise _lib.CvxError("gemm: EPI_RESID_HL needs bf16 out / out2 and stat_part fp32 [n_pad/64, rows, 2]")
+            raise _lib.CvxError("gemm: EPI_RESID_HL needs bf16 out / out2 and stat_part fp32 [n/64, rows, 2]")
         if stat_part.shape[0] * 64 < n or stat_part.shape[1] < round_up(m, 256) or out2.stride(0) != out.stride(0):
             raise _lib.CvxError("gemm: stat_part too small or hi / lo leading dimensions differ")
     d = GemmDesc()

@@ -98,9 +98,11 @@ typedef struct cvx_gemm_desc {
     /* LayerNorm folded into the GEMM (BF16, BF16_GELU, SWIGLU, VT; bf16 operands): A = bf16(x) un-normalised (the hi array), W
      * packed as bf16(W * ln_gamma), bias = fp32 [2][n_pad]: b' = b + W ln_beta, then cs[n] = sum_k W'[n][k];
      * ln_rowstat = fp32 [M][2] = (rstd, -mean * rstd) per row (cvx_rowstat_finalize / cvx_split_stream).  The epilogue then
-     * starts from  rstd * acc + (-mean * rstd) * cs[n] + b'[n]  instead of acc + bias[n].  NULL: plain epilogue. */
+     * starts from  rstd * acc + (-mean * rstd) * cs[n] + b'[n]  instead of acc + bias[n].  NULL: plain epilogue.  Non-NULL with
+     * fp16 operands or another epilogue: the call fails. */
     const float* ln_rowstat;
-    /* RESID_HL: lo array, fp32 partial row sums [n_pad / 64][stat_rows][2], stat_rows >= M rounded up to 256 */
+    /* RESID_HL: lo array, fp32 partial row sums [n / 64][stat_rows][2], stat_rows >= M rounded up to 256.  Slots < n / 64 of rows
+     * < M are written and nothing else: no slot of a padded column (n .. n_pad), no row >= M */
     void* out2; float* stat_part; long stat_rows;
 } cvx_gemm_desc;
 

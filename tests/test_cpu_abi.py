@@ -45,6 +45,32 @@ def test_argument_validation_without_gpu(lib):
         check(lib.cvx_attention_bf16(None, 8, None, None, 8, 1, 1, 10, 10, 64, None), "cvx_attention_bf16")
 
 
+def test_gemm_refuses_ln_rowstat_without_gpu(lib):
+    """cvx_gemm_bf16 turns down a LayerNorm fold it has no kernel for -- fp16 operands, or an epilogue other than BF16 / BF16_GELU /
+    SWIGLU / VT -- from the descriptor alone, before any device call (the pointers here are never dereferenced)."""
+    from cryovit_amd import _lib
+
+    def desc(epilogue, dtype, ln_rowstat):
+        d = _lib.GemmDesc()
+        d.epilogue, d.dtype, d.ln_rowstat = epilogue, dtype, ln_rowstat
+        d.a = d.w = d.out = d.bias = d.gamma = d.out2 = d.stat_part = d.pos = 16
+        d.m, d.n, d.n_pad, d.k_pad, d.lda, d.ldw, d.ldc, d.stat_rows = 256, 128, 128, 64, 64, 64, 128, 512
+        return d
+
+    import ctypes
+
+    with pytest.raises(_lib.CvxError, match="ln_rowstat.*bf16 operands"):
+        _lib.check(lib.cvx_gemm_bf16(ctypes.byref(desc(_lib.EPI_BF16, _lib.DTYPE_F16, 16)), None), "cvx_gemm_bf16")
+    with pytest.raises(_lib.CvxError, match="ln_rowstat.*bf16 operands"):
+        _lib.check(lib.cvx_gemm_bf16(ctypes.byref(desc(_lib.EPI_BF16_GELU, _lib.DTYPE_F16, 16)), None), "cvx_gemm_bf16")
+    for epi in (_lib.EPI_RESID, _lib.EPI_RESID_HL, _lib.EPI_F32, _lib.EPI_PATCH, _lib.EPI_CONVT):
+        with pytest.raises(_lib.CvxError, match="ln_rowstat.*epilogues"):
+            _lib.check(lib.cvx_gemm_bf16(ctypes.byref(desc(epi, _lib.DTYPE_BF16, 16)), None), "cvx_gemm_bf16")
+    d = desc(_lib.EPI_RESID, _lib.DTYPE_BF16, 16)
+    d.m = 0
+    assert lib.cvx_gemm_bf16(ctypes.byref(d), None) == 0  # an empty problem stays a no-op
+
+
 def test_no_cpu_fallback():
     if torch.cuda.is_available():
         pytest.skip("GPU present")

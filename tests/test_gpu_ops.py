@@ -1,6 +1,7 @@
 """Kernel-level parity: every HIP op (through the C ABI) against a torch-CPU fp32 computation of the same op on the
 same bf16-rounded operands.  Tolerances are stated per test; bf16 has 8 significand bits (rel. 2^-9 per rounding)."""
 
+import functools
 import math
 
 import numpy as np
@@ -918,38 +919,57 @@ def test_split_stream(gpu, rows, C):
     assert torch.allclose(got[:, 0], rstd, rtol=2e-6, atol=0) and torch.allclose(got[:, 1], -mu * rstd, rtol=1e-5, atol=1e-6)
 
 
-@pytest.mark.parametrize("M,N,K", [(700, 384, 256), (300, 128, 192), (2048, 1536, 512), (2311, 512, 256), (5000, 1536, 1536),
-                                   (66500, 512, 256), (66300, 512, 128)])
-def test_gemm_resid_hl(gpu, M, N, K):
-    """CVX_EPI_RESID_HL: x = hi + lo; x += gamma * (acc + bias); hi', lo' = split(x); stat_part[n/64][m] = row sums of the new x
-    over 64-column slots.  Shapes cover the 128-wide tiles (M < 1024), the persistent 256 tile with interior tiles only (2048),
-    with a ragged last M tile (2311), 120 tiles on the persistent kernel (5000 x 1536) and the main + tail split (66500 / 66300 x 512:
-    520 tiles = 2 whole rounds of 256 x 256 tiles + the last 964 / 764 rows on the 64 x 128 tile's 4-deep ring, with a ragged last
-    tile; K = 128 is fewer K tiles than the ring has stages)."""
-    from cryovit_amd._lib import EPI_RESID_HL
-    from cryovit_amd.engine import ops
-
+@functools.lru_cache(maxsize=1)
+def _resid_hl_operands(M, N, K):
+    """CPU operands of one hi/lo residual GEMM and its float64 result, built once per shape (never written to)."""
     a, w, b, g = rnd(M, K, seed=311), rnd(N, K, seed=312, scale=K**-0.5), rnd(N, seed=313), rnd(N, seed=314)
     x0 = rnd(M, N, seed=315, scale=2.0)
     x0[:, 3] *= 100.0
     hi0, lo0 = _split(x0)
+    ref = (hi0.float() + lo0.float()).double() + g.double() * (bf(a).double() @ bf(w).double().T + b.double())
+    return a, w, b, g, hi0, lo0, ref
+
+
+def _check_resid_hl(gpu, M, N, K, n_pad=None):
+    """One CVX_EPI_RESID_HL GEMM against float64, its statistics slots and cvx_rowstat_finalize on them.  With ``n_pad`` the weight,
+    bias and gamma are packed to n_pad > N rows / entries whose padding is NOT zero, the hi / lo arrays stay exactly N wide (a store
+    to a column >= N would land in the next row) and stat_part gets n_pad / 64 slots: the slots of padded columns and every row >= M
+    must still hold the NaN they were filled with."""
+    from cryovit_amd._lib import EPI_RESID_HL
+    from cryovit_amd.engine import ops
+
+    a, w, b, g, hi0, lo0, ref = _resid_hl_operands(M, N, K)
+    ragged = n_pad is not None
+    n_pad = n_pad if ragged else N
+    if n_pad > N:
+        w = torch.cat([w, rnd(n_pad - N, K, seed=316, scale=K**-0.5)])
+        b, g = torch.cat([b, torch.full((n_pad - N,), 3.0)]), torch.cat([g, torch.full((n_pad - N,), 2.0)])
     R = ops.alloc_rows(M)
     xh = torch.full((R, N), 7.0, dtype=torch.bfloat16, device=gpu)
     xl = torch.full((R, N), 7.0, dtype=torch.bfloat16, device=gpu)
     xh[:M], xl[:M] = hi0.to(gpu), lo0.to(gpu)
-    part = torch.full((N // 64, R, 2), float("nan"), device=gpu)
-    ops.gemm(EPI_RESID_HL, padded_bf16(a, R, K, gpu), padded_bf16(w, N, K, gpu), xh, b.to(gpu), m=M, n=N, gamma=g.to(gpu), out2=xl, stat_part=part)
-    ref = (hi0.float() + lo0.float()).double() + g.double() * (bf(a).double() @ bf(w).double().T + b.double())
+    part = torch.full((n_pad // 64, R, 2), float("nan"), device=gpu)
+    ops.gemm(EPI_RESID_HL, padded_bf16(a, R, K, gpu), padded_bf16(w, n_pad, K, gpu), xh, b.to(gpu), m=M, n=N, gamma=g.to(gpu), out2=xl, stat_part=part)
     got_h, got_l = xh[:M].float().cpu(), xl[:M].float().cpu()
     got = (got_h + got_l).double()
     # the pair carries 16+ significant bits; the fp32 accumulation order of the MFMA differs from the CPU's
     assert torch.allclose(got, ref, atol=2e-4, rtol=3e-5), float((got - ref).abs().max())
-    # hi = bf16(x); re-rounding hi + lo can only differ where lo itself was rounded up to exactly half an ulp of hi (a tie)
-    assert float((got_h != bf(got_h + got_l).float()).float().mean()) <= 5e-3, "hi is not bf16(hi + lo)"  # (measured: 1e-3)
+    # hi = bf16(x); re-rounding hi + lo can only differ where lo itself was rounded up to exactly half an ulp of hi (a tie).
+    # Expected rate 2^-10 = 9.8e-4: the remainder x - hi is spread evenly over [0, h], h = half an ulp of hi, and bf16 values just
+    # below h are h * 2^-8 apart, so bf16(x - hi) reaches h for the top 2^-9 of them; hi + lo is then halfway between hi and its
+    # neighbour and round-to-nearest-even leaves hi for the half of the cases in which hi's last bit is odd.
+    assert float((got_h != bf(got_h + got_l).float()).float().mean()) <= 5e-3, "hi is not bf16(hi + lo)"
+    s = got_h + got_l  # exact in fp32: x has 24 significant bits, hi the first 8 of them
+    moved = got_h != bf(s).float()
+    print(f"resid_hl M={M} N={N} n_pad={n_pad} K={K}: hi != bf16(hi + lo) at {float(moved.float().mean()):.3e} of the positions")
+    assert bool(((s.view(torch.int32) & 0xFFFF) == 0x8000)[moved].all()), "hi != bf16(hi + lo) where hi + lo is not a tie between two bf16 values"
     assert float((got_l.abs() - got_h.abs() * 2.0**-8).max()) <= 0, "lo is not the rounding remainder of hi"
     assert torch.all(xh[M:].float() == 7.0) and torch.all(xl[M:].float() == 7.0), "rows beyond M were written"
-    p = part[:, :M].cpu().double()
+    p = part[: N // 64, :M].cpu().double()
     assert torch.isfinite(p).all()
+    if ragged:
+        assert bool(torch.isnan(part[N // 64 :]).all()), "a statistics slot of padded columns was written"
+        assert bool(torch.isnan(part[: N // 64, M:]).all()), "statistics of rows beyond M were written"
     gs = got.reshape(M, N // 64, 64)
     s_ref, q_ref = gs.sum(-1).t(), (gs * gs).sum(-1).t()
     scale = gs.abs().sum(-1).t()
@@ -964,12 +984,45 @@ def test_gemm_resid_hl(gpu, M, N, K):
     assert torch.allclose(r[:, 0], rstd, rtol=2e-4) and torch.allclose(r[:, 1], -mu * rstd, rtol=2e-3, atol=2e-4)
 
 
-def _ln_fold_pack(w, bias, gamma, beta, n_pad, dev):
-    """bf16(W * gamma) and [2, n_pad] = (b + W beta | column sums of the rounded weight): VitEngine._pack's ln_linear."""
-    wq = torch.zeros(n_pad, w.shape[1], dtype=torch.bfloat16)
-    wq[: w.shape[0]] = bf(w * gamma[None, :])
+@pytest.mark.parametrize("M,N,K", [(700, 384, 256), (300, 128, 192), (2048, 1536, 512), (2311, 512, 256), (5000, 1536, 1536),
+                                   (66500, 512, 256), (66300, 512, 128)])
+def test_gemm_resid_hl(gpu, M, N, K):
+    """CVX_EPI_RESID_HL: x = hi + lo; x += gamma * (acc + bias); hi', lo' = split(x); stat_part[n/64][m] = row sums of the new x
+    over 64-column slots.  Shapes cover the 128-wide tiles (M < 1024), the persistent 256 tile with interior tiles only (2048),
+    with a ragged last M tile (2311), 120 tiles on the persistent kernel (5000 x 1536) and the main + tail split (66500 / 66300 x 512:
+    520 tiles = 2 whole rounds of 256 x 256 tiles + the last 964 / 764 rows on the 64 x 128 tile's 4-deep ring, with a ragged last
+    tile; K = 128 is fewer K tiles than the ring has stages)."""
+    _check_resid_hl(gpu, M, N, K)
+
+
+@pytest.mark.parametrize("gemm256_variant", [(1, 9), (1, 5)], indirect=True)
+@pytest.mark.parametrize("M,N,n_pad,K", [(700, 192, 192, 576), (1500, 320, 320, 320), (1300, 576, 768, 576), (2311, 1152, 1280, 256),
+                                         (66500, 576, 768, 256)])
+def test_gemm256_resid_hl_ragged_widths(gpu, M, N, n_pad, K, gemm256_variant):
+    """The hi/lo residual GEMM at the widths the Hiera encoder packs (engine/hiera.py _npad), where n_pad is no multiple of 128 or
+    N < n_pad; the checks of test_gemm_resid_hl plus untouched statistics slots (_check_resid_hl).  By dispatch_nreg / tail_plan:
+    (700, 192) -- M < 1024, n_pad % 128 == 64: TileCfg<64,256,1>, three column tiles, ragged last row tile;
+    (1500, 320) -- n_pad % 256 != 0 keeps M >= 1024 off the 256 tile: TileCfg<64,256,1>, five column tiles;
+    (1300, 576 -> 768) -- 3 x 6 tiles of 256 x 256 with padded columns and ragged M: the persistent kernel's predicated form (the one-shot
+      kernel for variant 5); in the last column tile one of the four wave columns is inside N, 9 of 12 statistics slots exist;
+    (2311, 1152 -> 1280) -- 5 x 10 tiles, two valid wave columns in the last column tile, K = 256: the shortest K loop the tile takes;
+    (66500, 576 -> 768) -- 3 x 260 = 780 tiles = 3 whole rounds of 256 + 12, and 12 <= TAIL_MAX_TILES: the main launch takes
+      (780 - 12) / 3 = 256 row tiles = 65536 rows (all rows inside, padded columns: predicated form), the other 964 rows are a residual
+      NREG tail of (768 / 64) x ceil(964 / 128) = 96 <= 256 workgroups, i.e. TailTile::RING_64x128 = TileCfg<64,128,1,4> with n_valid < Npad."""
+    _check_resid_hl(gpu, M, N, K, n_pad=n_pad)
+
+
+def _ln_fold_pack(w, bias, gamma, beta, n_pad, dev, k_pad=None, fill_pad=False):
+    """bf16(W * gamma) and [2, n_pad] = (b + W beta | column sums of the rounded weight): VitEngine._pack's ln_linear.  k_pad: zero
+    columns behind K, as ops.pack_linear leaves them; fill_pad: the rows / entries N .. n_pad hold values instead of zeros."""
+    N, K = w.shape
+    wq = torch.zeros(n_pad, k_pad or K, dtype=torch.bfloat16)
+    wq[:N, :K] = bf(w * gamma[None, :])
     bc = torch.zeros(2, n_pad)
-    bc[0, : w.shape[0]] = (bias.double() + w.double() @ beta.double()).float()
+    bc[0, :N] = (bias.double() + w.double() @ beta.double()).float()
+    if fill_pad and n_pad > N:
+        wq[N:, :K] = bf(rnd(n_pad - N, K, seed=329, scale=K**-0.5))
+        bc[0, N:] = 3.0
     bc[1] = wq.double().sum(1).float()
     return wq.to(dev), bc.to(dev)
 
@@ -1012,6 +1065,109 @@ def test_gemm_bf16_ln_fold(gpu, M, N, K, gelu):
     # vs the un-folded fp32 computation: the A operand is bf16(x) with a 40x outlier channel (error ~ 2^-9 * 60 * |w| per product)
     assert float((got - full).abs().mean()) <= 2e-2 and float((got - full).abs().max()) <= 0.35, (float((got - full).abs().mean()), float((got - full).abs().max()))
     assert torch.all(out[M:].float() == 7.0), "rows beyond M were written"
+
+
+@pytest.mark.parametrize("M,N,n_pad,K,k_pad,gelu", [(700, 432, 448, 144, 192, False), (700, 576, 640, 144, 192, True),
+                                                     (1300, 448, 512, 256, 256, False), (2311, 1728, 1792, 576, 576, False)])
+def test_gemm_bf16_ln_fold_ragged_widths(gpu, M, N, n_pad, K, k_pad, gelu):
+    """test_gemm_bf16_ln_fold at the widths engine/hiera.py packs: N < n_pad with n_pad no multiple of 128, and K < k_pad.  By dispatch_nreg:
+    (700, 432 -> 448, K 144 -> 192) -- n_pad % 128 == 64: EpiBF16<0, false, true> on TileCfg<64,256,1>, K zero-padded;
+    (700, 576 -> 640, K 144 -> 192, GELU) -- TileCfg<128,128,2> with a ragged last column tile, K zero-padded;
+    (1300, 448 -> 512, K 256) -- 2 x 6 tiles on the persistent 256 tile, predicated form (n_valid != Npad, ragged M), shortest K loop;
+    (2311, 1728 -> 1792, K 576) -- Hiera-L stage 3's qkv: 7 x 10 tiles on the persistent tile, predicated form.
+    The hi array and the weight are k_pad wide with zeros behind K (HieraEngine's buffers), the row constants and the reference
+    LayerNorm run over K columns; the padded weight rows, b' and column sums are not zero, `bc` is [2, n_pad] (b' and cs sit n_pad
+    floats apart) and the output is exactly N wide, so a padded column that is stored lands in the next row.
+    The un-folded fp32 band of test_gemm_bf16_ln_fold holds unchanged at K = 144: the folded arithmetic itself, in fp32 on the CPU
+    before the bf16 store, is within mean 2.2e-3 / max 2.5e-2 (432 x 144) and 1.2e-3 / 2.4e-2 (576 x 144, GELU) of it, as at the
+    other widths (2.1e-3 / 2.1e-2 at 448 x 256, 2.2e-3 / 2.4e-2 at 1728 x 576)."""
+    from cryovit_amd._lib import EPI_BF16, EPI_BF16_GELU
+    from cryovit_amd.engine import ops
+
+    x = rnd(M, K, seed=321, scale=1.5) + 0.3
+    x[:, 7] *= 40.0
+    w, bias = rnd(N, K, seed=322, scale=K**-0.5), rnd(N, seed=323)
+    gamma, beta = torch.exp(rnd(K, seed=324) * 0.5), rnd(K, seed=325, scale=0.2)
+    R = ops.alloc_rows(M)
+    xd = torch.zeros(R, k_pad, device=gpu)
+    xd[:M, :K] = x.to(gpu)
+    xh, xl, rs = torch.zeros(R, k_pad, dtype=torch.bfloat16, device=gpu), torch.zeros(R, k_pad, dtype=torch.bfloat16, device=gpu), torch.zeros(R, 2, device=gpu)
+    ops.split_stream(xd, xh, xl, rs, rows=M, Cdim=K, eps=1e-6)
+    assert torch.equal(xh[:M, :K].cpu(), bf(x)) and torch.all(xh[:, K:] == 0), "split_stream wrote the K padding of hi"
+    wq, bc = _ln_fold_pack(w, bias, gamma, beta, n_pad, gpu, k_pad=k_pad, fill_pad=True)
+    out = torch.full((R, N), 7.0, dtype=torch.bfloat16, device=gpu)
+    ops.gemm(EPI_BF16_GELU if gelu else EPI_BF16, xh, wq, out, bc, m=M, n=N, ln_rowstat=rs)
+    ref = _ln_ref(x, w, bias, gamma, beta, rs, M)
+    full = F.linear(F.layer_norm(x, (K,), gamma, beta, 1e-6), w, bias)
+    if gelu:
+        ref, full = F.gelu(ref), F.gelu(full)
+    got = out[:M].float().cpu()
+    assert torch.allclose(got, ref, atol=3e-2, rtol=1e-2), float((got - ref).abs().max())
+    err = (got - full).abs()
+    print(f"ln fold M={M} N={N} K={K}: vs fp32 LayerNorm -> Linear mean {float(err.mean()):.3e} max {float(err.max()):.3e}")
+    assert float(err.mean()) <= 2e-2 and float(err.max()) <= 0.35, (float(err.mean()), float(err.max()))
+    assert torch.all(out[M:].float() == 7.0), "rows beyond M were written"
+
+
+def _refused_ln_cases(gpu):
+    """(name, epilogue, dtype, out dtype, ops.gemm keywords) of every GEMM the library has no LayerNorm fold for; each is a valid call once
+    ln_rowstat is left out.  M = 256 rows, N = 128, K = 64."""
+    from cryovit_amd import _lib
+
+    N = 128
+    ones, pos = torch.ones(N, device=gpu), torch.zeros(1 + 64, N, device=gpu)
+    return [("fp16 operands", _lib.EPI_BF16, torch.float16, torch.float16, {}),
+            ("RESID", _lib.EPI_RESID, torch.bfloat16, torch.float32, dict(gamma=ones)),
+            ("RESID_HL", _lib.EPI_RESID_HL, torch.bfloat16, torch.bfloat16, dict(gamma=ones, out2=True, stat_part=True)),
+            ("F32", _lib.EPI_F32, torch.bfloat16, torch.float32, dict(gamma=ones)),
+            ("PATCH", _lib.EPI_PATCH, torch.bfloat16, torch.float32, dict(pos=pos, npatch=64, ntp=64, tok0=0)),
+            ("CONVT", _lib.EPI_CONVT, torch.bfloat16, torch.bfloat16, dict(H=16, W=16, cout=32, act=1, ldc=32))]  # 1 x 16 x 16 voxels -> [1][32][32][32]
+
+
+def test_gemm_refuses_ln_rowstat_it_has_no_kernel_for(gpu):
+    """ln_rowstat with fp16 operands, or on an epilogue without the LayerNorm fold (RESID, RESID_HL, F32, PATCH, CONVT), used to return 0
+    with an un-normalised product (fp16: the bf16 MFMA on fp16 bits).  Both ops.gemm and cvx_gemm_bf16 itself (a hand-filled
+    descriptor) now fail with a message and leave the outputs as they were; the same call without ln_rowstat runs."""
+    import ctypes
+
+    from cryovit_amd import _lib
+    from cryovit_amd.engine import ops
+
+    M, N, K = 256, 128, 64
+    R = ops.alloc_rows(M)
+    rs = torch.zeros(R, 2, device=gpu)
+    bc = torch.zeros(2, N, device=gpu)
+    lib = _lib.load()
+    for name, epi, dtype, out_dtype, kw in _refused_ln_cases(gpu):
+        a, w = rnd(R, K, seed=361).to(dtype).to(gpu), rnd(N, K, seed=362, scale=K**-0.5).to(dtype).to(gpu)
+        out = torch.full((R, N), 7.0, dtype=out_dtype, device=gpu)
+        kw = dict(kw)
+        if kw.get("out2"):
+            kw["out2"] = torch.full((R, N), 7.0, dtype=torch.bfloat16, device=gpu)
+            kw["stat_part"] = torch.full((N // 64, R, 2), float("nan"), device=gpu)
+        with pytest.raises(_lib.CvxError, match="ln_rowstat"):
+            ops.gemm(epi, a, w, out, bc, m=M, n=N, ln_rowstat=rs, **kw)
+        d = _lib.GemmDesc()
+        d.epilogue, d.dtype = epi, _lib.DTYPE_F16 if dtype == torch.float16 else _lib.DTYPE_BF16
+        d.a, d.lda, d.w, d.ldw = a.data_ptr(), K, w.data_ptr(), K
+        d.m, d.n, d.n_pad, d.k_pad = M, N, N, K
+        d.out, d.ldc, d.bias, d.ln_rowstat = out.data_ptr(), kw.get("ldc", N), bc.data_ptr(), rs.data_ptr()
+        d.gamma = kw["gamma"].data_ptr() if "gamma" in kw else None
+        if "pos" in kw:
+            d.pos, d.ldpos, d.npatch, d.ntp, d.tok0 = kw["pos"].data_ptr(), N, kw["npatch"], kw["ntp"], kw["tok0"]
+        if "out2" in kw:
+            d.out2, d.stat_part, d.stat_rows = kw["out2"].data_ptr(), kw["stat_part"].data_ptr(), R
+        d.H, d.W, d.cout, d.act = kw.get("H", 0), kw.get("W", 0), kw.get("cout", 0), kw.get("act", 0)
+        with torch.cuda.device(out.device):
+            rc = lib.cvx_gemm_bf16(ctypes.byref(d), torch.cuda.current_stream(out.device).cuda_stream)
+        assert rc != 0 and b"ln_rowstat" in lib.cvx_last_error(), (name, rc, lib.cvx_last_error())
+        torch.cuda.synchronize()
+        assert torch.all(out.float() == 7.0), f"{name}: a refused call wrote the output"
+        if "out2" in kw:
+            assert torch.all(kw["out2"].float() == 7.0) and bool(torch.isnan(kw["stat_part"]).all()), f"{name}: a refused call wrote lo / the statistics"
+        ops.gemm(epi, a, w, out, bc, m=M, n=N, **kw)  # (what was refused is ln_rowstat, nothing else of the call)
+        torch.cuda.synchronize()
+        assert not torch.all(out[:M].float() == 7.0), name
 
 
 @pytest.mark.parametrize("M", [500, 2560, 2311])
