@@ -169,6 +169,12 @@ SIGNATURES = {
     "cvx_components_table": (c_int, [c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "cvx_edt_squared": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_instance_distance_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p]),
+    "cvx_split_core_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_split_init": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_void_p, c_void_p, c_void_p]),
+    "cvx_split_rounds": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_split_first": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
+    "cvx_split_relabel": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
 }
 
 _lib = None

@@ -2,7 +2,8 @@
 
 ``label_volume`` labels a mask that is already on the device (``engine.ops.label_components``: HIP union-find, exact and
 bit-reproducible); ``instance_rows`` turns the integer table into the rows people read; ``label_file`` does both for a
-prediction file that ``cryovit infer`` wrote earlier; ``distance_rows`` adds the columns that need a distance map.
+prediction file that ``cryovit infer`` wrote earlier; ``distance_rows`` adds the columns that need a distance map;
+``split_volume`` cuts instances that touch over a neck into pieces (``engine.ops.split_instances``).
 """
 
 from __future__ import annotations
@@ -32,6 +33,22 @@ def label_volume(mask, *, connectivity: int = 26, min_size: int = 0):
     from cryovit_amd.engine import ops
 
     return ops.label_components(mask, connectivity=connectivity, min_size=min_size)
+
+
+def split_volume(labels, k: int, *, radius: float, min_core: int = 0, connectivity: int = 26):
+    """(labels' int32 [D, H, W], table' int64 [K', 10], component int64 [K']) of the instances 1..k of the int32 device volume
+    ``labels`` split at their necks: cores deeper than ``radius`` voxels (at least ``min_core`` voxels each) grown back inside
+    their instance; ``component`` is the input id of every piece.  All on the device."""
+    from cryovit_amd.engine import ops
+
+    return ops.split_instances(labels, k, radius=radius, min_core=min_core, connectivity=connectivity)
+
+
+def component_rows(component, extra: list[dict]) -> list[dict]:
+    """``extra`` (``distance_rows``) with the key ``component`` in front: the CSV column right after the standard ones."""
+    if hasattr(component, "detach"):
+        component = component.detach().cpu().numpy()
+    return [{"component": c, **e} for c, e in zip(np.asarray(component, dtype=np.int64).tolist(), extra)]
 
 
 def distance_rows(labels, k: int, *, morphology: bool = False, other_mask=None, other_name: str = "other",
@@ -69,12 +86,16 @@ def _other_preds(path: Path, datasets: dict, name: str, distance_to_dir):
 
 
 def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, result_dir=None, device=None,
-               morphology: bool = False, distance_to: str | None = None, distance_to_dir=None, contact_radius: float = 1.0) -> Path:
+               morphology: bool = False, distance_to: str | None = None, distance_to_dir=None, contact_radius: float = 1.0,
+               split_radius: float | None = None, split_min_core: int = 0) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  ``morphology`` adds the thickness / surface / deepest-voxel
     columns, ``distance_to`` the gap and contact columns against ``<distance_to>_preds`` (of the same file, else of
-    ``distance_to_dir/<same stem>.hdf``) within ``contact_radius`` voxels.  Returns the written file."""
+    ``distance_to_dir/<same stem>.hdf``) within ``contact_radius`` voxels.  ``split_radius`` splits the labelled instances at
+    their necks first (``split_volume``, cores of at least ``split_min_core`` voxels): the volume, the rows and the distance
+    columns are then those of the pieces, and every row carries ``component``, the id the piece had before.  Returns the
+    written file."""
     import torch
 
     from cryovit_amd import io
@@ -92,6 +113,10 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
         raise ValueError(f"'{key}' of {path} must be a [D, H, W] volume, got shape {preds.shape}")
     if not contact_radius >= 0:
         raise ValueError(f"contact_radius must be >= 0, got {contact_radius}")
+    if split_radius is not None and not split_radius >= 0:
+        raise ValueError(f"split_radius must be >= 0, got {split_radius}")
+    if split_min_core < 0:
+        raise ValueError(f"split_min_core must be >= 0, got {split_min_core}")
     other = None
     if distance_to is not None:
         other = _other_preds(path, datasets, distance_to, distance_to_dir)
@@ -100,11 +125,16 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     device = select_device(device)
     mask = torch.from_numpy(np.ascontiguousarray(preds != 0).view(np.uint8)).to(device)
     labels, table = label_volume(mask, connectivity=connectivity, min_size=min_size)
+    component = None
+    if split_radius is not None:
+        labels, table, component = split_volume(labels, int(table.shape[0]), radius=split_radius, min_core=split_min_core,
+                                                connectivity=connectivity)
     rows = instance_rows(table)
-    if morphology or other is not None:
+    if morphology or other is not None or component is not None:
         other_mask = None if other is None else torch.from_numpy(np.ascontiguousarray(other != 0).view(np.uint8)).to(device)
-        for r, e in zip(rows, distance_rows(labels, len(rows), morphology=morphology, other_mask=other_mask,
-                                            other_name=distance_to or "other", contact_radius=contact_radius)):
+        extra = distance_rows(labels, len(rows), morphology=morphology, other_mask=other_mask, other_name=distance_to or "other",
+                              contact_radius=contact_radius)
+        for r, e in zip(rows, extra if component is None else component_rows(component, extra)):
             r.update(e)
     return writers.write_instances(result_dir if result_dir is not None else path.parent, path.name, label, datasets,
                                    labels.cpu().numpy(), rows)

@@ -3,16 +3,20 @@
 
     python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize]
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
-                                    [--instances [--min-size N] [--connectivity 6|26] [--morphology]]
+                                    [--instances [--min-size N] [--connectivity 6|26] [--morphology]
+                                     [--split-radius R [--split-min-core N]]]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
     python -m cryovit_amd.cli instances <predictions> --label NAME [--min-size N] [--connectivity 6|26] [--result-folder DIR]
                                         [--morphology] [--distance-to NAME [--distance-to-folder DIR] [--contact-radius R]]
+                                        [--split-radius R [--split-min-core N]]
 
 ``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
 replace the network fetch of the encoder weights or add what the reference leaves to the user: ``instances`` (and
 ``infer --instances``) labels the connected instances of a predicted mask on the GPU and tabulates their size and position;
 ``--morphology`` and ``--distance-to`` add columns read from exact distance maps (surface voxels, inscribed radius, deepest voxel;
-gap and contact voxels against another label), all in voxels.
+gap and contact voxels against another label), all in voxels.  ``--split-radius R`` splits instances that touch over a neck
+before they are measured: cores deeper than R voxels (of at least ``--split-min-core`` voxels) are grown back inside their
+instance, and the CSV gains ``component``, the id a piece had before the split.
 """
 
 from __future__ import annotations
@@ -55,6 +59,17 @@ def _check_contact_radius(value: float) -> float:
     if not value >= 0:
         raise typer.BadParameter("contact radius must be >= 0 (voxels)")
     return value
+
+
+def _check_split_radius(value: Optional[float]) -> Optional[float]:
+    if value is not None and not value >= 0:
+        raise typer.BadParameter("split radius must be >= 0 (voxels)")
+    return value
+
+
+_SPLIT_RADIUS_HELP = ("split instances that touch over a neck: cores deeper than this many voxels are grown back inside their "
+                      "instance; the CSV gains the column component (voxels, >= 0)")
+_SPLIT_MIN_CORE_HELP = "with --split-radius, ignore cores of fewer voxels"
 
 
 def _encoder_overrides(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]) -> dict:
@@ -103,10 +118,14 @@ def infer(
     min_size: Annotated[int, Option(min=0, help="build extension: with --instances, drop instances of fewer voxels")] = 0,
     connectivity: Annotated[int, Option(callback=_check_connectivity, help="build extension: with --instances, 6 (faces) or 26 (faces, edges and corners)")] = 26,
     morphology: Annotated[bool, Option("--morphology", help="build extension: with --instances, add surface voxels, inscribed radius and deepest voxel per instance (exact distance map on the GPU; voxels)")] = False,
+    split_radius: Annotated[Optional[float], Option(callback=_check_split_radius, help="build extension: with --instances, " + _SPLIT_RADIUS_HELP)] = None,
+    split_min_core: Annotated[int, Option(min=0, help="build extension: " + _SPLIT_MIN_CORE_HELP)] = 0,
 ):
     """Segment tomograms using a pre-trained model."""
     if morphology and not instances:
         raise typer.BadParameter("--morphology needs --instances", param_hint="--morphology")
+    if split_radius is not None and not instances:
+        raise typer.BadParameter("--split-radius needs --instances", param_hint="--split-radius")
     from cryovit_amd.run.infer_model import run_inference
     from cryovit_amd.utils import load_files_from_path
 
@@ -118,7 +137,7 @@ def infer(
     result_path.mkdir(parents=True, exist_ok=True)
     run_inference(load_files_from_path(tomograms_path), model_path, result_path, threshold=threshold,
                   encoder=_load_encoder(encoder, checkpoint, synthetic_seed), instances=instances, min_size=min_size,
-                  connectivity=connectivity, morphology=morphology)
+                  connectivity=connectivity, morphology=morphology, split_radius=split_radius, split_min_core=split_min_core)
 
 
 @cli.command(name="instances", no_args_is_help=True)
@@ -133,6 +152,8 @@ def instances_cmd(
     distance_to: Annotated[Optional[str], Option(help="build extension: another label NAME; add the gap to <NAME>_preds and the voxels in contact with it (voxels)")] = None,
     distance_to_folder: Annotated[Optional[str], Option(help="build extension: folder whose <same stem>.hdf holds <NAME>_preds when the prediction file itself does not")] = None,
     contact_radius: Annotated[float, Option(callback=_check_contact_radius, help="build extension: with --distance-to, voxels within this distance of the other label count as contact (voxels, >= 0)")] = 1.0,
+    split_radius: Annotated[Optional[float], Option(callback=_check_split_radius, help="build extension: " + _SPLIT_RADIUS_HELP)] = None,
+    split_min_core: Annotated[int, Option(min=0, help="build extension: " + _SPLIT_MIN_CORE_HELP)] = 0,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     from cryovit_amd.analysis.instances import label_file
@@ -143,7 +164,8 @@ def instances_cmd(
     assert predictions_path.exists(), "Predictions path does not exist."
     for f in load_files_from_path(predictions_path):
         out = label_file(f, label, connectivity=connectivity, min_size=min_size, result_dir=result_folder, morphology=morphology,
-                         distance_to=distance_to, distance_to_dir=distance_to_folder, contact_radius=contact_radius)
+                         distance_to=distance_to, distance_to_dir=distance_to_folder, contact_radius=contact_radius,
+                         split_radius=split_radius, split_min_core=split_min_core)
         logging.info("Labelled %s", out)
 
 

@@ -13,27 +13,16 @@
 //   6. relabel+table labels = id, and the table rows by integer atomic add / min / max (exact and commutative)
 // Only the backward half of the neighbourhood (3 of 6, 13 of 26) is visited: the relation is symmetric.
 // Every sum is an integer, so the labels and the table are bit-identical from run to run.
-#include "common.h"
-#include "../../include/cryovit_hip.h"
+#include "voxel_rows.h"
 #include "host_util.h"
 
 #include <limits.h>
 
 namespace cvx {
 
-constexpr int kCclThreads = 256;
-constexpr int TZ = 4, TY = 8, TX = 64;  // tile: one wave reads 64 B of one mask row; 2048 labels = 8 KB of LDS
-constexpr int kTileVox = TZ * TY * TX;
-constexpr int kPerThread = kTileVox / kCclThreads;
-constexpr int RV = 16;                        // voxels of one row per thread in the run-combining passes
 constexpr int kChunk = kCclThreads * RV;      // voxels per block in the compaction passes
 constexpr int kScanThreads = 1024;
 constexpr int kDead = INT_MIN;                // parent[] of a root that min_size removed
-
-struct Dims {
-    int D, H, W;
-    int tx, ty;  // tiles along x and y
-};
 
 __device__ __forceinline__ int ld_lds(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ int ld_dev(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -82,13 +71,6 @@ __device__ __forceinline__ constexpr bool backward(int dz, int dy, int dx) {
     const bool before = dz < 0 || (dz == 0 && (dy < 0 || (dy == 0 && dx < 0)));
     const int steps = (dz != 0) + (dy != 0) + (dx != 0);
     return before && (CONN == 26 || steps == 1);
-}
-
-__device__ __forceinline__ void tile_origin(const Dims& d, int& z0, int& y0, int& x0) {
-    const int b = blockIdx.x;
-    x0 = (b % d.tx) * TX;
-    y0 = (b / d.tx % d.ty) * TY;
-    z0 = (b / d.tx / d.ty) * TZ;
 }
 
 // 1. tile pass: parent[v] = (smallest voxel index of v's component within its tile) + 1, 0 for background
@@ -178,42 +160,6 @@ __global__ __launch_bounds__(kCclThreads) void k_ccl_flatten(int* __restrict__ p
     const int p = ld_dev(parent + v);
     if (p == 0 || p == (int)v + 1) return;
     st_dev(parent + v, dev_find(parent, p - 1) + 1);
-}
-
-// v[0..cnt) = p[0..cnt): 16-B accesses for a full, 16-B aligned group, element accesses otherwise
-__device__ __forceinline__ void row_load(const int* __restrict__ p, int cnt, int (&v)[RV]) {
-    if (cnt == RV && ((uintptr_t)p & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < RV / 4; ++q) {
-            const int4 f = ((const int4*)p)[q];
-            v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < RV; ++i) v[i] = i < cnt ? p[i] : 0;
-    }
-}
-__device__ __forceinline__ void row_store(int* __restrict__ p, int cnt, const int (&v)[RV]) {
-    if (cnt == RV && ((uintptr_t)p & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < RV / 4; ++q) ((int4*)p)[q] = int4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
-    } else {
-#pragma unroll
-        for (int i = 0; i < RV; ++i)
-            if (i < cnt) p[i] = v[i];
-    }
-}
-
-// thread -> RV voxels of one row: (z, y, x0 .. x0 + cnt); false past the volume
-__device__ __forceinline__ bool row_piece(const Dims& d, int segs, int& z, int& y, int& x0, int& cnt) {
-    const long t = (long)blockIdx.x * kCclThreads + threadIdx.x;
-    const long row = t / segs;
-    if (row >= (long)d.D * d.H) return false;
-    x0 = (int)(t % segs) * RV;
-    y = (int)(row % d.H);
-    z = (int)(row / d.H);
-    cnt = min(RV, d.W - x0);
-    return true;
 }
 
 // 4. count[root] += voxels (count = the zeroed label volume, which nothing else uses yet); one add per run of a root along x
@@ -336,29 +282,7 @@ __global__ __launch_bounds__(kCclThreads) void k_ccl_table_init(long long* __res
     const long i = (long)blockIdx.x * kCclThreads + threadIdx.x;
     if (i >= k * CVX_COMPONENT_COLS) return;
     const int c = (int)(i % CVX_COMPONENT_COLS);
-    table[i] = c < 4 ? 0 : c == 4 ? d.D : c == 6 ? d.H : c == 8 ? d.W : -1;
-}
-
-// min / max into a table entry; the plain read first skips the atomic when it cannot change anything (entries move one way
-// only, so a stale read errs towards issuing the atomic)
-__device__ __forceinline__ void table_min(long long* p, long long v) {
-    if (v < *(volatile long long*)p) atomicMin(p, v);
-}
-__device__ __forceinline__ void table_max(long long* p, long long v) {
-    if (v > *(volatile long long*)p) atomicMax(p, v);
-}
-
-__device__ __forceinline__ void table_add_run(long long* __restrict__ table, int id, int z, int y, int xa, int xb) {
-    long long* row = table + (long)(id - 1) * CVX_COMPONENT_COLS;
-    const unsigned long long m = (unsigned long long)(xb - xa + 1);
-    auto* u = (unsigned long long*)row;
-    atomicAdd(u + 0, m);
-    atomicAdd(u + 1, m * (unsigned long long)z);
-    atomicAdd(u + 2, m * (unsigned long long)y);
-    atomicAdd(u + 3, m * (unsigned long long)(xa + xb) / 2);  // xa + ... + xb
-    table_min(row + 4, z); table_max(row + 5, z);
-    table_min(row + 6, y); table_max(row + 7, y);
-    table_min(row + 8, xa); table_max(row + 9, xb);
+    table[i] = table_empty(c, d);
 }
 
 // 6. labels[v] = id of v's root (0: background or removed), and the table from runs of one id along x
@@ -380,17 +304,7 @@ __global__ __launch_bounds__(kCclThreads) void k_ccl_relabel(const int* __restri
         id[i] = last_id;
     }
     row_store(labels + v0, cnt, id);
-    int cur = 0, xa = 0;
-#pragma unroll
-    for (int i = 0; i < RV; ++i) {
-        const int c = i < cnt ? id[i] : 0;
-        if (c != cur) {
-            if (cur) table_add_run(table, cur, z, y, xa, x0 + i - 1);
-            cur = c;
-            xa = x0 + i;
-        }
-    }
-    if (cur) table_add_run(table, cur, z, y, xa, x0 + cnt - 1);
+    table_add_piece(table, id, z, y, x0, cnt);
 }
 
 }  // namespace cvx
@@ -417,8 +331,6 @@ bool ccl_layout(int D, int H, int W, CclLayout& L) {
     L.bytes = L.off_parent + (L.n * 4 + 15) / 16 * 16;
     return true;
 }
-
-Dims ccl_dims(int D, int H, int W) { return Dims{D, H, W, (W + TX - 1) / TX, (H + TY - 1) / TY}; }
 
 }  // namespace
 

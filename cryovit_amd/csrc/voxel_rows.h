@@ -1,0 +1,108 @@
+// Pieces shared by the passes that walk an int32 [D][H][W] volume in 16-voxel row pieces and build the per-instance table
+// (components.hip: relabel + table; split.hip: renumber + table): the piece a thread owns, its 16-B loads / stores, and the
+// integer add / min / max into a table row.  Device code only; every includer compiles its own copy.
+#pragma once
+#include "common.h"
+#include "../../include/cryovit_hip.h"
+
+namespace cvx {
+
+constexpr int kCclThreads = 256;
+constexpr int TZ = 4, TY = 8, TX = 64;  // tile: one wave reads 64 B of one mask row; 2048 labels = 8 KB of LDS
+constexpr int kTileVox = TZ * TY * TX;
+constexpr int kPerThread = kTileVox / kCclThreads;
+constexpr int RV = 16;                  // voxels of one row per thread in the run-combining passes
+
+struct Dims {
+    int D, H, W;
+    int tx, ty;  // tiles along x and y
+};
+
+inline Dims ccl_dims(int D, int H, int W) { return Dims{D, H, W, (W + TX - 1) / TX, (H + TY - 1) / TY}; }
+
+__device__ __forceinline__ void tile_origin(const Dims& d, int& z0, int& y0, int& x0) {
+    const int b = blockIdx.x;
+    x0 = (b % d.tx) * TX;
+    y0 = (b / d.tx % d.ty) * TY;
+    z0 = (b / d.tx / d.ty) * TZ;
+}
+
+// v[0..cnt) = p[0..cnt): 16-B accesses for a full, 16-B aligned group, element accesses otherwise
+__device__ __forceinline__ void row_load(const int* __restrict__ p, int cnt, int (&v)[RV]) {
+    if (cnt == RV && ((uintptr_t)p & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < RV / 4; ++q) {
+            const int4 f = ((const int4*)p)[q];
+            v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < RV; ++i) v[i] = i < cnt ? p[i] : 0;
+    }
+}
+__device__ __forceinline__ void row_store(int* __restrict__ p, int cnt, const int (&v)[RV]) {
+    if (cnt == RV && ((uintptr_t)p & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < RV / 4; ++q) ((int4*)p)[q] = int4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < RV; ++i)
+            if (i < cnt) p[i] = v[i];
+    }
+}
+
+// thread -> RV voxels of one row: (z, y, x0 .. x0 + cnt); false past the volume
+__device__ __forceinline__ bool row_piece(const Dims& d, int segs, int& z, int& y, int& x0, int& cnt) {
+    const long t = (long)blockIdx.x * kCclThreads + threadIdx.x;
+    const long row = t / segs;
+    if (row >= (long)d.D * d.H) return false;
+    x0 = (int)(t % segs) * RV;
+    y = (int)(row % d.H);
+    z = (int)(row / d.H);
+    cnt = min(RV, d.W - x0);
+    return true;
+}
+
+// the value a table entry starts from: counts and sums 0, lower bounds past the volume, upper bounds -1 (the empty box)
+__device__ __forceinline__ long long table_empty(int col, const Dims& d) {
+    return col < 4 ? 0 : col == 4 ? d.D : col == 6 ? d.H : col == 8 ? d.W : -1;
+}
+
+// min / max into a table entry; the plain read first skips the atomic when it cannot change anything (entries move one way
+// only, so a stale read errs towards issuing the atomic)
+__device__ __forceinline__ void table_min(long long* p, long long v) {
+    if (v < *(volatile long long*)p) atomicMin(p, v);
+}
+__device__ __forceinline__ void table_max(long long* p, long long v) {
+    if (v > *(volatile long long*)p) atomicMax(p, v);
+}
+
+__device__ __forceinline__ void table_add_run(long long* __restrict__ table, int id, int z, int y, int xa, int xb) {
+    long long* row = table + (long)(id - 1) * CVX_COMPONENT_COLS;
+    const unsigned long long m = (unsigned long long)(xb - xa + 1);
+    auto* u = (unsigned long long*)row;
+    atomicAdd(u + 0, m);
+    atomicAdd(u + 1, m * (unsigned long long)z);
+    atomicAdd(u + 2, m * (unsigned long long)y);
+    atomicAdd(u + 3, m * (unsigned long long)(xa + xb) / 2);  // xa + ... + xb
+    table_min(row + 4, z); table_max(row + 5, z);
+    table_min(row + 6, y); table_max(row + 7, y);
+    table_min(row + 8, xa); table_max(row + 9, xb);
+}
+
+// the table rows of the runs of one id along a thread's row piece (id 0 = background)
+__device__ __forceinline__ void table_add_piece(long long* __restrict__ table, const int (&id)[RV], int z, int y, int x0, int cnt) {
+    int cur = 0, xa = 0;
+#pragma unroll
+    for (int i = 0; i < RV; ++i) {
+        const int c = i < cnt ? id[i] : 0;
+        if (c != cur) {
+            if (cur) table_add_run(table, cur, z, y, xa, x0 + i - 1);
+            cur = c;
+            xa = x0 + i;
+        }
+    }
+    if (cur) table_add_run(table, cur, z, y, xa, x0 + cnt - 1);
+}
+
+}  // namespace cvx

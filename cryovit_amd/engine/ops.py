@@ -647,3 +647,131 @@ def instance_distance_stats(labels: torch.Tensor, d2: torch.Tensor, k: int, thre
     call(dev, "cvx_instance_distance_stats", _lib.load().cvx_instance_distance_stats, _p(labels), _p(d2), D, H, W, int(k),
          min(int(threshold_d2), _lib.EDT_NONE - 1), _p(out))  # no distance is larger than EDT_NONE - 1
     return out
+
+
+# ---- touching instances split at their necks (`--split-radius`): erosion cores, geodesic regrowth ----
+
+SPLIT_ROUND_BATCH = 4  # regrowth rounds launched per read of their "changed" flags
+
+
+def _volume_check(what: str, name: str, t, dtype) -> None:
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != dtype:
+        got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise _lib.CvxError(f"{what}: {name} must be {str(dtype).removeprefix('torch.')} [D, H, W], got {got}")
+
+
+def _split_volume_check(what: str, **volumes) -> tuple[torch.device, int, int, int]:
+    """Dtype, rank, common shape, size and device of the volumes of one split stage: (device, D, H, W)."""
+    shape = None
+    for name, (t, dtype) in volumes.items():
+        _volume_check(what, name, t, dtype)
+        if shape is not None and tuple(t.shape) != shape:
+            raise _lib.CvxError(f"{what}: {name} {tuple(t.shape)} differs in shape from {shape}")
+        shape = tuple(t.shape)
+    if shape[0] * shape[1] * shape[2] > _lib.COMPONENT_MAX_VOXELS:
+        raise _lib.CvxError(f"{what}: {shape[0]}x{shape[1]}x{shape[2]} has more than 2^31 - 2 voxels")
+    dev = _dev_check(*(t for t, _ in volumes.values()))
+    return dev, *shape
+
+
+def split_core_mask(d2: torch.Tensor, threshold_d2: int) -> torch.Tensor:
+    """uint8 [D, H, W]: 1 where ``d2`` (``edt_squared``) is a distance above ``threshold_d2``: the voxels deeper than the radius."""
+    if threshold_d2 < 0:
+        raise _lib.CvxError(f"split_core_mask: threshold_d2 must be >= 0, got {threshold_d2}")
+    dev, D, H, W = _split_volume_check("split_core_mask", d2=(d2, torch.int32))
+    mask = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
+    call(dev, "cvx_split_core_mask", _lib.load().cvx_split_core_mask, _p(d2), D, H, W, min(int(threshold_d2), _lib.EDT_NONE), _p(mask))
+    return mask
+
+
+def split_init(labels: torch.Tensor, k: int, cores: torch.Tensor | None, m: int) -> torch.Tensor:
+    """int64 [D, H, W] regrowth keys (steps << 32 | seed id, as unsigned) of the instances 1..k: a voxel of a core 1..m starts at
+    (0, core id), every voxel of an instance without a core voxel at (0, m + its id), all else at all-ones."""
+    vols = {"labels": (labels, torch.int32)} | ({"cores": (cores, torch.int32)} if cores is not None else {})
+    dev, D, H, W = _split_volume_check("split_init", **vols)
+    if k < 0 or m < 0 or (m > 0 and cores is None):
+        raise _lib.CvxError(f"split_init: need k >= 0 and m >= 0 (with cores), got k = {k}, m = {m}")
+    keys = torch.empty((D, H, W), dtype=torch.int64, device=dev)
+    has_core = torch.empty(int(k) + 1, dtype=torch.int32, device=dev)
+    call(dev, "cvx_split_init", _lib.load().cvx_split_init, _p(labels), _p(cores), D, H, W, int(k), int(m), _p(has_core), _p(keys))
+    return keys
+
+
+def split_regrow(labels: torch.Tensor, keys: torch.Tensor, *, connectivity: int = 26, max_rounds: int = 4096) -> int:
+    """Lowers ``keys`` (``split_init``) in place to the fixpoint key[v] = min over the neighbours n of v with v's label of
+    key[n] + one step, and returns the number of rounds launched up to and including the one that changed nothing (which proves
+    the fixpoint).  The host reads the rounds' flags once per ``SPLIT_ROUND_BATCH`` rounds.  Raises when ``max_rounds`` rounds
+    did not reach it: ``keys`` is then not an assignment."""
+    if connectivity not in (6, 26):
+        raise _lib.CvxError(f"split_regrow: connectivity must be 6 or 26, got {connectivity}")
+    if max_rounds < 1:
+        raise _lib.CvxError(f"split_regrow: max_rounds must be >= 1, got {max_rounds}")
+    dev, D, H, W = _split_volume_check("split_regrow", labels=(labels, torch.int32), keys=(keys, torch.int64))
+    lib = _lib.load()
+    changed = torch.empty(SPLIT_ROUND_BATCH, dtype=torch.int32, device=dev)
+    done = 0
+    while done < max_rounds:
+        batch = min(SPLIT_ROUND_BATCH, max_rounds - done)
+        call(dev, "cvx_split_rounds", lib.cvx_split_rounds, _p(labels), _p(keys), D, H, W, int(connectivity), batch, _p(changed))
+        flags = changed[:batch].tolist()  # the wait
+        if 0 in flags:
+            return done + flags.index(0) + 1
+        done += batch
+    raise _lib.CvxError(f"split_regrow: no fixpoint after max_rounds = {max_rounds} rounds")
+
+
+def split_renumber(labels: torch.Tensor, keys: torch.Tensor, seeds: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(labels' int32 [D, H, W], table' int64 [K', 10], component int64 [K']) from the regrown ``keys`` with seed ids 1..seeds: the
+    pieces numbered 1..K' in ascending order of their smallest linear voxel index, their table (columns of ``label_components``)
+    and the input id each lies in.  The host waits once, for K'."""
+    dev, D, H, W = _split_volume_check("split_renumber", labels=(labels, torch.int32), keys=(keys, torch.int64))
+    if seeds < 0:
+        raise _lib.CvxError(f"split_renumber: seeds must be >= 0, got {seeds}")
+    lib = _lib.load()
+    first = torch.empty(int(seeds) + 1, dtype=torch.int32, device=dev)
+    call(dev, "cvx_split_first", lib.cvx_split_first, _p(labels), _p(keys), D, H, W, int(seeds), _p(first))
+    # the minima of the seeds that own a voxel are distinct, so their order is exact; seeds that own none sort behind them
+    order = torch.sort(first[1:]).indices
+    rank = torch.zeros(int(seeds) + 1, dtype=torch.int32, device=dev)
+    rank[order + 1] = torch.arange(1, int(seeds) + 1, dtype=torch.int32, device=dev)
+    kp = int((first[1:] != 2**31 - 1).sum().item())  # the one wait
+    out = torch.empty((D, H, W), dtype=torch.int32, device=dev)
+    table = torch.empty((kp, _lib.COMPONENT_COLS), dtype=torch.int64, device=dev)
+    component = torch.empty(kp, dtype=torch.int64, device=dev)
+    call(dev, "cvx_split_relabel", lib.cvx_split_relabel, _p(labels), _p(keys), _p(rank), D, H, W, int(seeds), kp, _p(out), _p(table),
+         _p(component))
+    return out, table, component
+
+
+def split_instances(labels: torch.Tensor, k: int, *, radius: float, min_core: int = 0, connectivity: int = 26,
+                    max_rounds: int = 4096) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(labels' int32 [D, H, W], table' int64 [K', 10], component int64 [K']): the instances 1..k of ``labels`` (int32 [D, H, W] as
+    ``label_components`` returns it: two ids never share a face) split at their necks.  The voxels deeper than ``radius`` inside
+    the foreground (``edt_squared`` > floor(radius^2)) are labelled under ``connectivity`` into cores, those under ``min_core``
+    voxels dropped; an instance that keeps no core is its own seed.  Every voxel then goes to the seed it reaches in the fewest
+    steps between neighbours of its own instance, the smaller seed id among equals; the pieces are numbered 1..K' in ascending
+    order of their smallest voxel index, ``table'`` has the columns of ``label_components`` and ``component`` the input id of
+    every piece.  floor(radius^2) == 0 erodes nothing and returns the input labels and their table.  A volume without
+    background has no distance map, hence no core: identity as well.  Exact and bit-reproducible; raises when ``max_rounds``
+    regrowth rounds do not reach the fixpoint."""
+    _volume_check("split_instances", "labels", labels, torch.int32)
+    if k < 0:
+        raise _lib.CvxError(f"split_instances: k must be >= 0, got {k}")
+    if not radius >= 0 or radius * radius >= _lib.EDT_NONE:
+        raise _lib.CvxError(f"split_instances: radius must be >= 0 (and its square below 2^31 - 1), got {radius}")
+    if min_core < 0:
+        raise _lib.CvxError(f"split_instances: min_core must be >= 0, got {min_core}")
+    if connectivity not in (6, 26):
+        raise _lib.CvxError(f"split_instances: connectivity must be 6 or 26, got {connectivity}")
+    if max_rounds < 1:
+        raise _lib.CvxError(f"split_instances: max_rounds must be >= 1, got {max_rounds}")
+    _split_volume_check("split_instances", labels=(labels, torch.int32))  # the device, before anything is launched
+    thr = int(radius * radius)  # floor: the square is >= 0
+    cores, m = None, 0
+    if thr > 0 and k > 0 and labels.numel() > 0:
+        cores, core_table = label_components(split_core_mask(edt_squared(labels, sites="zero"), thr), connectivity=connectivity,
+                                             min_size=min_core)
+        m = int(core_table.shape[0])
+    keys = split_init(labels, k, cores if m > 0 else None, m)
+    split_regrow(labels, keys, connectivity=connectivity, max_rounds=max_rounds)
+    return split_renumber(labels, keys, m + int(k))

@@ -17,6 +17,9 @@ Extension (not in the reference): ``instances=True`` -- the connected instances 
 instance table is written to ``<result_dir>/instances/<tomogram stem>_<label_key>.csv``.  ``<label_key>_preds`` stays the
 unfiltered threshold mask.  ``morphology=True`` (with ``instances``) adds per instance the surface voxels, the inscribed radius and
 the deepest voxel from an exact distance map of the labels (``analysis.distances``), also computed while they are in HBM.
+``split_radius=R`` (with ``instances``) first splits instances that touch over a neck (``analysis.instances.split_volume``: cores
+deeper than R voxels, of at least ``split_min_core`` voxels, grown back inside their instance); volume, rows and morphology are
+then those of the pieces and the CSV carries ``component``, the id a piece had before the split.
 """
 
 from __future__ import annotations
@@ -29,7 +32,7 @@ import numpy as np
 import torch
 
 from cryovit_amd import io
-from cryovit_amd.analysis.instances import distance_rows, instance_rows, label_volume
+from cryovit_amd.analysis.instances import component_rows, distance_rows, instance_rows, label_volume, split_volume
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
 from cryovit_amd.run import writers
@@ -80,13 +83,20 @@ def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs,
 
 def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, threshold: float = 0.5, *, encoder=None,
                   batch_size: int = 128, device: str | None = None, instances: bool = False, min_size: int = 0,
-                  connectivity: int = 26, morphology: bool = False) -> list[Path]:
+                  connectivity: int = 26, morphology: bool = False, split_radius: float | None = None,
+                  split_min_core: int = 0) -> list[Path]:
     if connectivity not in (6, 26):
         raise ValueError(f"connectivity must be 6 or 26, got {connectivity}")
     if min_size < 0:
         raise ValueError(f"min_size must be >= 0, got {min_size}")
     if morphology and not instances:
         raise ValueError("morphology=True needs instances=True: the columns describe the labelled instances")
+    if split_radius is not None and not instances:
+        raise ValueError("split_radius needs instances=True: it splits the labelled instances")
+    if split_radius is not None and not split_radius >= 0:
+        raise ValueError(f"split_radius must be >= 0, got {split_radius}")
+    if split_min_core < 0:
+        raise ValueError(f"split_min_core must be >= 0, got {split_min_core}")
     rank, _, world = world_info()
     device = select_device(device)
     model, model_type, model_name, label_key = load_model(model_path, device=device)
@@ -112,10 +122,16 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
             host.copy_(mask, non_blocking=True)
             if instances:
                 labels, table = label_volume(mask.contiguous(), connectivity=connectivity, min_size=min_size)
+                component = None
+                if split_radius is not None:
+                    labels, table, component = split_volume(labels, table.shape[0], radius=split_radius, min_core=split_min_core,
+                                                            connectivity=connectivity)
                 host_labels = torch.empty(labels.shape, dtype=torch.int32, pin_memory=True)
                 host_labels.copy_(labels, non_blocking=True)
                 host_table = table.cpu()
                 extra = distance_rows(labels, table.shape[0], morphology=morphology)
+                if component is not None:
+                    extra = component_rows(component, extra)
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:
                 pending.append((i, writer.submit(_write_with_instances, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),

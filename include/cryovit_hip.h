@@ -525,6 +525,45 @@ int cvx_edt_squared(const void* src, int src_dtype, int sites, int D, int H, int
 int cvx_instance_distance_stats(const int32_t* labels, const int32_t* d2, int D, int H, int W, long k, int threshold_d2,
                                 int64_t* out, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Touching instances split at their necks (`infer --instances --split-radius`, `cryovit instances --split-radius`).  labels
+ * int32 [D][H][W] with ids 0..k as cvx_components_table writes them (two ids never share a face).  The caller erodes: d2 =
+ * cvx_edt_squared(labels, CVX_EDT_I32, CVX_EDT_SITES_ZERO), cvx_split_core_mask marks d2 > threshold_d2 (= floor(radius^2)) with
+ * d2 != CVX_EDT_NONE, and cvx_components_label / _table number that mask's components 1..m: the cores.  A threshold of 0 erodes
+ * nothing: the caller then passes no cores (m = 0), and every instance is its own seed.  A volume without background has d2 =
+ * CVX_EDT_NONE everywhere, hence no core either: the split is the identity.
+ *   cvx_split_init     keys uint64 [D][H][W] = steps << 32 | seed id: a voxel of core c starts at (0, c); every voxel of an
+ *                      instance i that holds no core voxel at (0, m + i); all else at all-ones.  has_core int32 [k + 1] is
+ *                      workspace (cores may be null when m = 0).
+ *   cvx_split_rounds   `rounds` launches of the regrowth kernel: a step joins two neighbours (connectivity 6 or 26) that carry
+ *                      the SAME non-zero label, and every round lowers keys towards the fixpoint key[v] = min over such
+ *                      neighbours n of key[n] + (1 << 32), i.e. the pair (fewest steps to a seed, smallest seed id among those).
+ *                      changed int32 [rounds] is cleared by the call; round r sets changed[r] = 1 iff it lowered a key.  A round
+ *                      that lowered nothing proves the fixpoint (and so does every round after it); the caller launches until
+ *                      it sees one.  No workgroup waits for another; keys only ever decrease, each written by one aligned 8-byte
+ *                      store.
+ *   cvx_split_first    first int32 [seeds + 1] (seeds = m + k): per seed id the smallest linear index of a voxel whose key
+ *                      names it, INT32_MAX for a seed that owns none (and in entry 0).  The caller ranks these: rank int32
+ *                      [seeds + 1], 1..kp for the kp seeds that own a voxel in ascending order of `first`, anything else for
+ *                      the rest.
+ *   cvx_split_relabel  labels_out int32 [D][H][W] = rank of the voxel's seed (0 for background), table int64
+ *                      [kp][CVX_COMPONENT_COLS] with the columns of cvx_components_table, component int64 [kp] = the input id
+ *                      each piece lies in.  Ranks outside 1..kp are written as background rather than past the table.
+ * Every piece is connected and lies inside one input instance.  Integers only (integer atomic add / min / max, plain stores of
+ * equal values): two calls give the same bits.  Refused with an error before any launch: null pointers, negative extents, D*H*W >
+ * CVX_COMPONENT_MAX_VOXELS, another connectivity, k, m, seeds or kp out of range, misaligned arrays (int32: 4 bytes; keys, table,
+ * component: 8 bytes).  An empty volume succeeds.
+ * ------------------------------------------------------------------------------------------------- */
+int cvx_split_core_mask(const int32_t* d2, int D, int H, int W, int threshold_d2, uint8_t* mask, hipStream_t stream);
+int cvx_split_init(const int32_t* labels, const int32_t* cores, int D, int H, int W, long k, long m, int32_t* has_core,
+                   uint64_t* keys, hipStream_t stream);
+int cvx_split_rounds(const int32_t* labels, uint64_t* keys, int D, int H, int W, int connectivity, int rounds, int32_t* changed,
+                     hipStream_t stream);
+int cvx_split_first(const int32_t* labels, const uint64_t* keys, int D, int H, int W, long seeds, int32_t* first,
+                    hipStream_t stream);
+int cvx_split_relabel(const int32_t* labels, const uint64_t* keys, const int32_t* rank, int D, int H, int W, long seeds, long kp,
+                      int32_t* labels_out, int64_t* table, int64_t* component, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

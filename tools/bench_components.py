@@ -32,13 +32,14 @@ sys.path.insert(0, str(ROOT))
 STEP_LIMIT_S = {"ellipsoids": 240, "salt": 240, "infer": 420}
 
 
-def ellipsoid_mask(shape, count: int = 200, seed: int = 0) -> np.ndarray:
+def ellipsoid_mask(shape, count: int = 200, seed: int = 0, grow: float = 1.0) -> np.ndarray:
+    """``count`` random ellipsoids; ``grow`` scales their radii (tools/bench_split.py enlarges them until neighbours touch)."""
     rng = np.random.default_rng(seed)
     D, H, W = shape
     m = np.zeros(shape, np.uint8)
     for _ in range(count):
         c = rng.uniform((0, 0, 0), shape)
-        r = rng.uniform((3, 8, 8), (max(4, D / 8), max(9, H / 16), max(9, W / 16)))
+        r = grow * rng.uniform((3, 8, 8), (max(4, D / 8), max(9, H / 16), max(9, W / 16)))
         lo = np.maximum(np.floor(c - r).astype(int), 0)
         hi = np.minimum(np.ceil(c + r).astype(int) + 1, shape)
         z, y, x = np.ogrid[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
