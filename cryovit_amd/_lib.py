@@ -33,6 +33,8 @@ EDT_U8, EDT_I32 = 0, 1  # CVX_EDT_* source dtypes
 EDT_SITES_ZERO, EDT_SITES_NONZERO = 0, 1  # CVX_EDT_SITES_*
 EDT_NONE = 2**31 - 1  # CVX_EDT_NONE
 DSTAT_COLS = 4  # CVX_DSTAT_COLS
+PAIR_COLS = 5  # CVX_PAIR_COLS
+PAIR_MAX_CAPACITY = 2**31  # CVX_PAIR_MAX_CAPACITY
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -169,6 +171,11 @@ SIGNATURES = {
     "cvx_components_table": (c_int, [c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "cvx_edt_squared": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_instance_distance_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p]),
+    "cvx_nearest_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "cvx_nearest_instance": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cvx_instance_pair_contacts": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p,
+                                           c_void_p]),
+    "cvx_instance_pair_rows": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p]),
     "cvx_split_core_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_split_init": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_void_p, c_void_p, c_void_p]),
     "cvx_split_rounds": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -1,5 +1,7 @@
 """Quantification of predictions after the model has run: connected instances of a predicted mask, what
-its distance maps say about them, and the split of instances that touch over a neck."""
+its distance maps say about them, the split of instances that touch over a neck, and which instance of one label touches
+which of another."""
 
 from cryovit_amd.analysis.instances import INSTANCE_COLUMNS, instance_rows, label_file, label_volume, split_volume  # noqa: F401
-from cryovit_amd.analysis.distances import edt_squared, instance_contacts, instance_morphology  # noqa: F401
+from cryovit_amd.analysis.distances import (  # noqa: F401
+    PAIR_COLUMNS, edt_squared, instance_contacts, instance_morphology, instance_pair_contacts, pair_rows, partner_rows)

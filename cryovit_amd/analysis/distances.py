@@ -4,6 +4,10 @@ inside it, how far it is from another label and over how many voxels the two tou
 ``edt_squared`` is the exact transform on the device (``engine.ops.edt_squared``, csrc/edt.hip); ``instance_morphology`` and
 ``instance_contacts`` reduce it per instance (``engine.ops.instance_distance_stats``) and return the extra columns of the
 instance CSV, one dict per instance 1..k in id order.
+
+``instance_pair_contacts`` says which instance touches which instance of another label: the nearest-instance map of the other
+label (``engine.ops.nearest_instance``, csrc/nearest.hip) reduced per pair (``engine.ops.instance_pair_contacts``) into one
+row per pair, and ``partner_rows`` counts the partners of every instance for the instance CSV.
 """
 
 from __future__ import annotations
@@ -11,6 +15,7 @@ from __future__ import annotations
 import math
 
 MORPHOLOGY_COLUMNS = ["surface_voxels", "inscribed_d2", "inscribed_radius", "deep_z", "deep_y", "deep_x"]
+PAIR_COLUMNS = ["id", "other_id", "contact_voxels", "gap_d2", "gap", "at_z", "at_y", "at_x"]
 
 
 def contact_columns(name: str) -> list[str]:
@@ -83,3 +88,39 @@ def instance_contacts(labels, k: int, other_mask, radius: float, name: str = "ot
         raise ValueError(f"the other mask has shape {tuple(other_mask.shape)}, the instances {tuple(labels.shape)}")
     d2 = ops.edt_squared(other_mask, sites="nonzero")
     return contact_rows(ops.instance_distance_stats(labels, d2, k, contact_threshold(radius)), name)
+
+
+def pair_rows(table, shape) -> list[dict]:
+    """Rows (``PAIR_COLUMNS``) from the int64 [P, 5] pair table ``a, b, contact_voxels, gap_d2, at`` of volumes of ``shape``:
+    ``id`` = a, ``other_id`` = b, ``gap`` = the root of ``gap_d2`` in float64 (0 where the two overlap) and ``at_z, at_y, at_x`` =
+    the first voxel of a in raster order that lies at that gap from b."""
+    import numpy as np
+
+    _, H, W = shape
+    if hasattr(table, "detach"):
+        table = table.detach().cpu().numpy()
+    rows = []
+    for a, b, count, d2, at in np.asarray(table, dtype=np.int64).reshape(-1, 5).tolist():
+        rows.append(dict(zip(PAIR_COLUMNS, (a, b, count, d2, math.sqrt(d2), at // (H * W), at // W % H, at % W))))
+    return rows
+
+
+def partner_rows(pairs: list[dict], k: int, name: str) -> list[dict]:
+    """Per instance 1..k ``{"partners_<name>": n}``: the number of distinct other ids among the ``pair_rows`` of that instance."""
+    partners = [set() for _ in range(k)]
+    for r in pairs:
+        if 1 <= r["id"] <= k:
+            partners[r["id"] - 1].add(r["other_id"])
+    return [{f"partners_{name}": len(p)} for p in partners]
+
+
+def instance_pair_contacts(labels, k: int, other_labels, other_k: int, radius: float) -> list[dict]:
+    """The ``pair_rows`` of the instances 1..k of the int32 device volume ``labels`` against the instances 1..other_k of the int32
+    device volume ``other_labels`` of the same shape: one row per pair (a, b) such that b is the nearest other instance (the
+    smallest id among equals) of at least one voxel of a within ``radius`` voxels, in (a, b) order."""
+    from cryovit_amd.engine import ops
+
+    if tuple(other_labels.shape) != tuple(labels.shape):
+        raise ValueError(f"the other instances have shape {tuple(other_labels.shape)}, the instances {tuple(labels.shape)}")
+    d2, nearest = ops.nearest_instance(other_labels, other_k)
+    return pair_rows(ops.instance_pair_contacts(labels, k, nearest, d2, contact_threshold(radius)), labels.shape)

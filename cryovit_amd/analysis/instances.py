@@ -3,11 +3,13 @@
 ``label_volume`` labels a mask that is already on the device (``engine.ops.label_components``: HIP union-find, exact and
 bit-reproducible); ``instance_rows`` turns the integer table into the rows people read; ``label_file`` does both for a
 prediction file that ``cryovit infer`` wrote earlier; ``distance_rows`` adds the columns that need a distance map;
-``split_volume`` cuts instances that touch over a neck into pieces (``engine.ops.split_instances``).
+``split_volume`` cuts instances that touch over a neck into pieces (``engine.ops.split_instances``); ``contacts_with`` of
+``label_file`` pairs the instances with those of another label (``analysis.distances.instance_pair_contacts``).
 """
 
 from __future__ import annotations
 
+import logging
 from pathlib import Path
 
 import numpy as np
@@ -85,17 +87,40 @@ def _other_preds(path: Path, datasets: dict, name: str, distance_to_dir):
     raise KeyError(f"{path} holds no '{key}' dataset (found {sorted(datasets)})")
 
 
+def _other_instances(path: Path, datasets: dict, name: str, distance_to_dir):
+    """(volume, fresh) of the other label of ``contacts_with``: ``<name>_instances`` of the same file, else of
+    ``distance_to_dir/<same stem>.hdf`` (fresh = False: the ids are those of that label's own CSV); failing both, ``<name>_preds``
+    as ``_other_preds`` finds it (fresh = True: the caller labels it)."""
+    from cryovit_amd import io
+
+    key = f"{name}_instances"
+    if key in datasets:
+        return datasets[key], False
+    if distance_to_dir is not None:
+        other = (Path(distance_to_dir) / path.name).with_suffix(".hdf")
+        if other.exists():
+            found = io.read_all_flat(other)
+            if key in found:
+                return found[key], False
+    return _other_preds(path, datasets, name, distance_to_dir), True
+
+
 def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, result_dir=None, device=None,
                morphology: bool = False, distance_to: str | None = None, distance_to_dir=None, contact_radius: float = 1.0,
-               split_radius: float | None = None, split_min_core: int = 0) -> Path:
+               split_radius: float | None = None, split_min_core: int = 0, contacts_with: str | None = None) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  ``morphology`` adds the thickness / surface / deepest-voxel
     columns, ``distance_to`` the gap and contact columns against ``<distance_to>_preds`` (of the same file, else of
     ``distance_to_dir/<same stem>.hdf``) within ``contact_radius`` voxels.  ``split_radius`` splits the labelled instances at
     their necks first (``split_volume``, cores of at least ``split_min_core`` voxels): the volume, the rows and the distance
-    columns are then those of the pieces, and every row carries ``component``, the id the piece had before.  Returns the
-    written file."""
+    columns are then those of the pieces, and every row carries ``component``, the id the piece had before.
+    ``contacts_with`` names another label whose instances (``<contacts_with>_instances`` of the same file, else of
+    ``distance_to_dir/<same stem>.hdf``: the ids of that label's own CSV; failing both, ``<contacts_with>_preds`` labelled afresh
+    under ``connectivity`` with no ``min_size``) are paired with this label's: ``contacts/<stem>_<label>_<contacts_with>.csv``
+    under ``result_dir`` gets one row per pair of an instance and the other instance nearest to some of its voxels within
+    ``contact_radius`` voxels (``analysis.distances.PAIR_COLUMNS``), and every instance row gains ``partners_<contacts_with>``,
+    the number of such partners, after the ``distance_to`` columns.  Returns the written file."""
     import torch
 
     from cryovit_amd import io
@@ -122,6 +147,14 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
         other = _other_preds(path, datasets, distance_to, distance_to_dir)
         if other.shape != preds.shape:
             raise ValueError(f"'{distance_to}_preds' has shape {other.shape}, '{key}' of {path} has {preds.shape}")
+    partner, fresh = None, False
+    if contacts_with is not None:
+        if contacts_with == label:
+            raise ValueError(f"contacts_with must name another label than '{label}'")
+        partner, fresh = _other_instances(path, datasets, contacts_with, distance_to_dir)
+        if partner.shape != preds.shape:
+            raise ValueError(f"'{contacts_with}_{'preds' if fresh else 'instances'}' has shape {partner.shape}, '{key}' of {path} has "
+                             f"{preds.shape}")
     device = select_device(device)
     mask = torch.from_numpy(np.ascontiguousarray(preds != 0).view(np.uint8)).to(device)
     labels, table = label_volume(mask, connectivity=connectivity, min_size=min_size)
@@ -136,5 +169,21 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
                               contact_radius=contact_radius)
         for r, e in zip(rows, extra if component is None else component_rows(component, extra)):
             r.update(e)
-    return writers.write_instances(result_dir if result_dir is not None else path.parent, path.name, label, datasets,
-                                   labels.cpu().numpy(), rows)
+    result_dir = result_dir if result_dir is not None else path.parent
+    if partner is not None:
+        from cryovit_amd.analysis import distances
+
+        if fresh:
+            partner_labels, partner_table = label_volume(torch.from_numpy(np.ascontiguousarray(partner != 0).view(np.uint8)).to(device),
+                                                         connectivity=connectivity, min_size=0)
+            partner_k = int(partner_table.shape[0])
+            logging.info("%s holds no '%s_instances': the other ids come from a fresh labelling of '%s_preds' (connectivity %d)",
+                         path, contacts_with, contacts_with, connectivity)
+        else:
+            partner_labels = torch.from_numpy(np.ascontiguousarray(partner, dtype=np.int32)).to(device)
+            partner_k = int(partner.max()) if partner.size else 0
+        pairs = distances.instance_pair_contacts(labels, len(rows), partner_labels, partner_k, contact_radius)
+        for r, e in zip(rows, distances.partner_rows(pairs, len(rows), contacts_with)):
+            r.update(e)
+        writers.write_contacts(result_dir, path.name, label, contacts_with, pairs)
+    return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows)

@@ -7,7 +7,8 @@
                                      [--split-radius R [--split-min-core N]]]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
     python -m cryovit_amd.cli instances <predictions> --label NAME [--min-size N] [--connectivity 6|26] [--result-folder DIR]
-                                        [--morphology] [--distance-to NAME [--distance-to-folder DIR] [--contact-radius R]]
+                                        [--morphology] [--distance-to NAME] [--contacts-with NAME]
+                                        [--distance-to-folder DIR] [--contact-radius R]
                                         [--split-radius R [--split-min-core N]]
 
 ``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
@@ -16,7 +17,9 @@ replace the network fetch of the encoder weights or add what the reference leave
 ``--morphology`` and ``--distance-to`` add columns read from exact distance maps (surface voxels, inscribed radius, deepest voxel;
 gap and contact voxels against another label), all in voxels.  ``--split-radius R`` splits instances that touch over a neck
 before they are measured: cores deeper than R voxels (of at least ``--split-min-core`` voxels) are grown back inside their
-instance, and the CSV gains ``component``, the id a piece had before the split.
+instance, and the CSV gains ``component``, the id a piece had before the split.  ``--contacts-with NAME`` says which instance
+touches which: every instance gains ``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance,
+nearest instance of NAME within ``--contact-radius``) the voxels in contact, the narrowest gap and where it is.
 """
 
 from __future__ import annotations
@@ -150,8 +153,9 @@ def instances_cmd(
                                                    show_default="the folder of the predictions (files are updated in place)")] = None,
     morphology: Annotated[bool, Option("--morphology", help="build extension: add surface voxels, inscribed radius and deepest voxel per instance (exact distance map on the GPU; voxels)")] = False,
     distance_to: Annotated[Optional[str], Option(help="build extension: another label NAME; add the gap to <NAME>_preds and the voxels in contact with it (voxels)")] = None,
-    distance_to_folder: Annotated[Optional[str], Option(help="build extension: folder whose <same stem>.hdf holds <NAME>_preds when the prediction file itself does not")] = None,
-    contact_radius: Annotated[float, Option(callback=_check_contact_radius, help="build extension: with --distance-to, voxels within this distance of the other label count as contact (voxels, >= 0)")] = 1.0,
+    distance_to_folder: Annotated[Optional[str], Option(help="build extension: folder whose <same stem>.hdf holds <NAME>_preds (for --contacts-with also <NAME>_instances) when the prediction file itself does not; serves --distance-to and --contacts-with")] = None,
+    contact_radius: Annotated[float, Option(callback=_check_contact_radius, help="build extension: with --distance-to or --contacts-with, voxels within this distance of the other label count as contact (voxels, >= 0)")] = 1.0,
+    contacts_with: Annotated[Optional[str], Option(help="build extension: another label NAME; write contacts/<tomo>_<label>_<NAME>.csv, one row per pair of an instance and the instance of NAME nearest to some of its voxels within --contact-radius (voxels in contact, gap, where), and add partners_<NAME> per instance")] = None,
     split_radius: Annotated[Optional[float], Option(callback=_check_split_radius, help="build extension: " + _SPLIT_RADIUS_HELP)] = None,
     split_min_core: Annotated[int, Option(min=0, help="build extension: " + _SPLIT_MIN_CORE_HELP)] = 0,
 ):
@@ -165,7 +169,7 @@ def instances_cmd(
     for f in load_files_from_path(predictions_path):
         out = label_file(f, label, connectivity=connectivity, min_size=min_size, result_dir=result_folder, morphology=morphology,
                          distance_to=distance_to, distance_to_dir=distance_to_folder, contact_radius=contact_radius,
-                         split_radius=split_radius, split_min_core=split_min_core)
+                         split_radius=split_radius, split_min_core=split_min_core, contacts_with=contacts_with)
         logging.info("Labelled %s", out)
 
 

@@ -21,87 +21,34 @@
 // A thread holds kIpt = 8 consecutive outputs of one x and updates all of them per read of f[j]; (i - j)^2 is the same for a
 // whole wave (scalar).  f[j] == kEdtNone is skipped, so every sum formed is a true squared distance inside the volume, which
 // the entry point has checked to be below INT32_MAX.  The walk goes outwards from the thread's outputs and stops once the
-// squared step alone reaches the largest of the wave's current minima.
-#include "common.h"
-#include "../../include/cryovit_hip.h"
+// squared step alone reaches the largest of the wave's current minima.  The site bitmaps and the walk are in edt_pieces.h, which
+// nearest.hip shares.
+#include "edt_pieces.h"
 #include "host_util.h"
 
 #include <limits.h>
 
 namespace cvx {
 
-constexpr int kEdtNone = CVX_EDT_NONE;
-constexpr int kRowThreads = 256;           // x pass: 4 waves = 4 rows per workgroup
-constexpr int kSlab = 64;                  // min-plus passes: adjacent x per workgroup = lanes of a wave
-constexpr int kIpt = 8;                    // outputs per thread
-constexpr int kJu = 8;                     // sources fetched per pruning test
 constexpr int kLineMax = 512;              // longest line staged in LDS
-constexpr int kLineWavesMax = 16;
-constexpr int kStatThreads = 256;
-constexpr int kStatRv = 16;                // voxels of one row per thread in the statistics pass
-
-__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // ---- x pass ----
 
 template <typename T, bool NONZERO>
 __global__ __launch_bounds__(kRowThreads) void k_edt_rows(const T* __restrict__ src, int* __restrict__ out, long rows, int W, int nc) {
     extern __shared__ unsigned long long edt_row_lds[];
-    const int lane = threadIdx.x & 63, wave = wave_id();
-    // per wave: nc site bitmaps, then per bitmap the last site before it and the first site after it
-    unsigned long long* bits = edt_row_lds + (long)wave * 2 * nc;
-    int* before = (int*)(bits + nc);
-    int* after = before + nc;
-    const long row = (long)blockIdx.x * (kRowThreads / 64) + wave;
-    const bool live = row < rows;  // a wave past the last row walks the same loops (the barriers below) and touches no memory
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * (kRowThreads / 64) + wave_id();
+    const bool live = row < rows;  // a wave past the last row walks the same loops (their barriers) and touches no memory
     const T* s = src + (live ? row : 0) * W;
-    for (int c = 0; c < nc; ++c) {
-        const int x = c * 64 + lane;
-        const bool site = live && x < W && (s[x] != 0) == NONZERO;
-        const unsigned long long b = __ballot(site);
-        if (lane == 0) bits[c] = b;
-    }
-    __syncthreads();
-    int carry = -1;  // forward: the last site of all earlier bitmaps
-    for (int base = 0; base < nc; base += 64) {
-        const int c = base + lane;
-        const unsigned long long b = c < nc ? bits[c] : 0;
-        int v = b ? c * 64 + 63 - __clzll((long long)b) : -1;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(v, o, 64);
-            if (lane >= o) v = max(v, t);
-        }
-        int excl = __shfl_up(v, 1, 64);
-        if (lane == 0) excl = -1;
-        if (c < nc) before[c] = max(excl, carry);
-        carry = max(carry, __shfl(v, 63, 64));
-    }
-    carry = INT_MAX;  // backward: the first site of all later bitmaps
-    for (int base = (nc - 1) / 64 * 64; base >= 0; base -= 64) {
-        const int c = base + lane;
-        const unsigned long long b = c < nc ? bits[c] : 0;
-        int v = b ? c * 64 + __ffsll((unsigned long long)b) - 1 : INT_MAX;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_down(v, o, 64);
-            if (lane + o < 64) v = min(v, t);
-        }
-        int excl = __shfl_down(v, 1, 64);
-        if (lane == 63) excl = INT_MAX;
-        if (c < nc) after[c] = min(excl, carry);
-        carry = min(carry, __shfl(v, 0, 64));
-    }
-    __syncthreads();
+    const RowSites sites = edt_row_sites(edt_row_lds, nc, [&](int x) { return live && x < W && (s[x] != 0) == NONZERO; });
     if (!live) return;
     int* o = out + row * W;
     for (int c = 0; c < nc; ++c) {
         const int x = c * 64 + lane;
         if (x >= W) break;
-        const unsigned long long b = bits[c];
-        const unsigned long long lo = b & (~0ull >> (63 - lane)), hi = b >> lane;
-        const int left = lo ? c * 64 + 63 - __clzll((long long)lo) : before[c];
-        const int right = hi ? x + __ffsll(hi) - 1 : after[c];
+        int left, right;
+        edt_row_sides(sites, c, lane, left, right);
         int d = INT_MAX;
         if (left >= 0) d = x - left;
         if (right != INT_MAX) d = min(d, right - x);
@@ -110,59 +57,6 @@ __global__ __launch_bounds__(kRowThreads) void k_edt_rows(const T* __restrict__ 
 }
 
 // ---- y and z passes ----
-
-// best[k] = min(best[k], f(j) + (i0 + k - j)^2) for the sources j of [ja, jb), walked downwards from the thread's last output
-// and upwards from the source after it.  MODE 0: every pair; 1: pairs with j <= i only; 2: pairs with j >= i only.  i0 is the
-// same for the whole wave; lanes that are not `active` (past the row's end) hold no minimum and do not keep the walk going.
-template <int MODE, class F>
-__device__ __forceinline__ void edt_minplus(F f, bool active, int i0, int ja, int jb, int (&best)[kIpt]) {
-    auto take = [&](int j, int v) {
-        if (v == kEdtNone) return;
-#pragma unroll
-        for (int k = 0; k < kIpt; ++k) {
-            const int d = i0 + k - j;
-            if ((MODE == 1 && d < 0) || (MODE == 2 && d > 0)) continue;
-            best[k] = min(best[k], v + d * d);
-        }
-    };
-    auto widest = [&]() {
-        int m = best[0];
-#pragma unroll
-        for (int k = 1; k < kIpt; ++k) m = max(m, best[k]);
-        return m;
-    };
-    const int top = min(i0 + kIpt, jb);  // sources below top go to the downward walk
-    if (MODE != 2 || top > i0) {
-        const int stop = MODE == 2 ? max(ja, i0) : ja;
-        for (int j1 = top; j1 > stop; j1 -= kJu) {
-            const int gap = i0 - (j1 - 1);  // the step from the nearest source of this group to the nearest output
-            if (gap > 0 && !__any(active && gap * gap < widest())) break;
-            int v[kJu];
-#pragma unroll
-            for (int u = 0; u < kJu; ++u) v[u] = j1 - 1 - u >= stop ? f(j1 - 1 - u) : kEdtNone;
-#pragma unroll
-            for (int u = 0; u < kJu; ++u) take(j1 - 1 - u, v[u]);
-        }
-    }
-    if (MODE != 1) {
-        for (int j0 = max(top, ja); j0 < jb; j0 += kJu) {
-            const int gap = j0 - (i0 + kIpt - 1);
-            if (gap > 0 && !__any(active && gap * gap < widest())) break;
-            int v[kJu];
-#pragma unroll
-            for (int u = 0; u < kJu; ++u) v[u] = j0 + u < jb ? f(j0 + u) : kEdtNone;
-#pragma unroll
-            for (int u = 0; u < kJu; ++u) take(j0 + u, v[u]);
-        }
-    }
-}
-
-struct LineGeom {
-    int n;         // elements of a line
-    long stride;   // between two of them
-    long ostride;  // between two lines of one slab column
-    int W, nslab;  // row length, slabs per row
-};
 
 __device__ __forceinline__ void edt_store(int* line, const LineGeom& g, int i0, const int (&best)[kIpt]) {
 #pragma unroll
@@ -184,7 +78,7 @@ __global__ __launch_bounds__(kLineWavesMax * 64) void k_edt_lines_lds(int* vol, 
         int best[kIpt];
 #pragma unroll
         for (int k = 0; k < kIpt; ++k) best[k] = kEdtNone;
-        edt_minplus<0>([&](int j) { return col[j * kSlab]; }, in, i0, 0, g.n, best);
+        edt_minplus<EdtDistance, 0>([&](int j) { return col[j * kSlab]; }, in, i0, 0, g.n, best);
         if (in) edt_store(line, g, i0, best);
     }
 }
@@ -205,8 +99,8 @@ __global__ __launch_bounds__(kLineWavesMax * 64) void k_edt_lines_long(int* vol,
 #pragma unroll
             for (int k = 0; k < kIpt; ++k) best[k] = kEdtNone;
             if (i0 < g.n) {
-                if (sweep == 0) edt_minplus<1>(f, in, i0, 0, g.n, best);
-                else edt_minplus<2>(f, in, i0, 0, g.n, best);
+                if (sweep == 0) edt_minplus<EdtDistance, 1>(f, in, i0, 0, g.n, best);
+                else edt_minplus<EdtDistance, 2>(f, in, i0, 0, g.n, best);
             }
             __syncthreads();  // every wave has read what this block overwrites
             if (in && i0 < g.n) edt_store(line, g, i0, best);
@@ -298,20 +192,11 @@ using namespace cvx;
 
 namespace {
 
-// extents >= 0 and D*H*W <= CVX_COMPONENT_MAX_VOXELS; n = the voxel count
-bool edt_extents(int D, int H, int W, long& n) {
-    if (D < 0 || H < 0 || W < 0) return false;
-    n = (long)D * H;  // < 2^62
-    if (W && n > CVX_COMPONENT_MAX_VOXELS / W) return false;
-    n *= W;
-    return n <= CVX_COMPONENT_MAX_VOXELS;
-}
-
 template <typename T>
 int edt_launch_rows(const void* src, int sites, int* out, long rows, int W, hipStream_t st) {
     const int nc = (W + 63) / 64;
     const unsigned blocks = (unsigned)((rows + kRowThreads / 64 - 1) / (kRowThreads / 64));
-    const size_t lds = (size_t)(kRowThreads / 64) * nc * 16;  // <= 46 KB: W <= 46341
+    const size_t lds = edt_row_lds_bytes(nc);
     if (sites == CVX_EDT_SITES_NONZERO) hipLaunchKernelGGL((k_edt_rows<T, true>), dim3(blocks), dim3(kRowThreads), lds, st, (const T*)src, out, rows, W, nc);
     else hipLaunchKernelGGL((k_edt_rows<T, false>), dim3(blocks), dim3(kRowThreads), lds, st, (const T*)src, out, rows, W, nc);
     return cvx_check_launch();

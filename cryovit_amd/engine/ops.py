@@ -775,3 +775,61 @@ def split_instances(labels: torch.Tensor, k: int, *, radius: float, min_core: in
     keys = split_init(labels, k, cores if m > 0 else None, m)
     split_regrow(labels, keys, connectivity=connectivity, max_rounds=max_rounds)
     return split_renumber(labels, keys, m + int(k))
+
+
+# ---- nearest-instance maps and the pair table over them (`cryovit instances --contacts-with`) ----
+
+PAIR_CAPACITY = 1 << 12  # slots of the first pair table; it doubles for as long as a pair finds no slot
+
+
+def nearest_instance(labels: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(d2, nearest), both int32 [D, H, W]: for every voxel the exact squared distance to the nearest site of ``labels`` (int32
+    [D, H, W]; a site is a voxel with a value in 1..k, other values are nobody's) and the id of that site, the smallest id
+    among sites at that distance; on a site its own id.  ``d2`` is what ``edt_squared(labels, sites="nonzero")`` gives when every
+    nonzero value lies in 1..k; without a site it is ``_lib.EDT_NONE`` everywhere and ``nearest`` is 0.  Integers only, no
+    atomics, bit-reproducible; 8 bytes of workspace per voxel for the duration of the call; the host does not wait."""
+    _volume_check("nearest_instance", "labels", labels, torch.int32)
+    if k < 0:
+        raise _lib.CvxError(f"nearest_instance: k must be >= 0, got {k}")
+    dev, D, H, W = _split_volume_check("nearest_instance", labels=(labels, torch.int32))
+    d2 = torch.empty((D, H, W), dtype=torch.int32, device=dev)
+    nearest = torch.empty((D, H, W), dtype=torch.int32, device=dev)
+    workspace = torch.empty((D, H, W), dtype=torch.int64, device=dev)
+    call(dev, "cvx_nearest_instance", _lib.load().cvx_nearest_instance, _p(labels), int(k), D, H, W, _p(d2), _p(nearest), _p(workspace))
+    return d2, nearest
+
+
+def instance_pair_contacts(labels_a: torch.Tensor, ka: int, nearest_b: torch.Tensor, d2_b: torch.Tensor, threshold_d2: int,
+                           capacity: int | None = None) -> torch.Tensor:
+    """int64 [P, 5] on the device, one row ``a, b, contact_voxels, gap_d2, at`` per pair of an instance a of ``labels_a`` (int32
+    [D, H, W], ids 1..ka; other values are nobody's) and an instance b of the other label that is the NEAREST one
+    (``nearest_b``, ``d2_b`` = ``nearest_instance`` of the other label's volume) to at least one voxel of a within
+    ``threshold_d2``: how many voxels of a have b nearest within the threshold, the smallest ``d2_b`` among them and the smallest
+    linear index of a voxel attaining it.  Rows are sorted by (a, b).  The pairs are collected in a hash table of ``capacity``
+    slots (rounded up to a power of two; default ``PAIR_CAPACITY``) that doubles and starts over while a pair finds no slot; the
+    rows depend on neither that nor scheduling.  The host waits once per table, for the overflow flag and P."""
+    dev, D, H, W = _split_volume_check("instance_pair_contacts", labels_a=(labels_a, torch.int32), nearest_b=(nearest_b, torch.int32),
+                                       d2_b=(d2_b, torch.int32))
+    if ka < 0:
+        raise _lib.CvxError(f"instance_pair_contacts: ka must be >= 0, got {ka}")
+    if threshold_d2 < 0:
+        raise _lib.CvxError(f"instance_pair_contacts: threshold_d2 must be >= 0, got {threshold_d2}")
+    if capacity is not None and not 1 <= capacity <= _lib.PAIR_MAX_CAPACITY:
+        raise _lib.CvxError(f"instance_pair_contacts: capacity must lie in 1..2^31, got {capacity}")
+    lib = _lib.load()
+    cap = 1 << (int(capacity if capacity is not None else PAIR_CAPACITY) - 1).bit_length()
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    while True:
+        table = torch.empty((3, cap), dtype=torch.int64, device=dev)
+        call(dev, "cvx_instance_pair_contacts", lib.cvx_instance_pair_contacts, _p(labels_a), int(ka), _p(nearest_b), _p(d2_b),
+             min(int(threshold_d2), _lib.EDT_NONE - 1), D, H, W, _p(table), cap, _p(status))  # no distance is larger than EDT_NONE - 1
+        overflow, p = status.tolist()  # the wait
+        if not overflow:
+            break
+        if cap >= _lib.PAIR_MAX_CAPACITY:  # at most 31 doublings; more slots than voxels cannot overflow
+            raise _lib.CvxError(f"instance_pair_contacts: the pair table overflowed at {cap} slots")
+        cap *= 2
+    rows = torch.empty((p, _lib.PAIR_COLS), dtype=torch.int64, device=dev)
+    order = torch.sort(table[0]).indices  # the keys a << 32 | b are distinct; empty slots hold INT64_MAX and sort last
+    call(dev, "cvx_instance_pair_rows", lib.cvx_instance_pair_rows, _p(table), cap, _p(order), p, _p(rows))
+    return rows

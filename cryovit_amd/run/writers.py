@@ -7,6 +7,8 @@
                          at <results_dir>/<tomo stem>.hdf
   write_instances        (not in the reference) the prediction file with ``<label>_instances`` added (uint16 up to 65535
                          instances, int32 beyond; gzip) and <results_dir>/instances/<tomo stem>_<label>.csv, one row per instance
+  write_contacts         (not in the reference) <results_dir>/contacts/<tomo stem>_<label>_<other>.csv, one row per pair of an
+                         instance of <label> and an instance of <other> in contact
   update_metrics_csv     CsvWriter l.112-206:           <results_dir>/<sample>[_<split>].csv, columns sample, tomo_name,
                          <metrics...>[, split_id]; an existing row for the same tomogram is replaced
 """
@@ -81,6 +83,22 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
         for r in rows:
             w.writerow({k: repr(v) if isinstance(v, float) else v for k, v in r.items()})
     return out
+
+
+PAIR_COLUMNS = ["id", "other_id", "contact_voxels", "gap_d2", "gap", "at_z", "at_y", "at_x"]
+
+
+def write_contacts(results_dir, tomo_name: str, label_key: str, other_name: str, rows: list[dict]) -> Path:
+    """The CSV <results_dir>/contacts/<tomo stem>_<label>_<other>.csv of ``rows`` (``analysis.distances.pair_rows``: columns
+    ``PAIR_COLUMNS``; floats written with ``repr``; no pairs: header only).  Returns its path."""
+    path = Path(results_dir) / "contacts" / f"{Path(tomo_name).stem}_{label_key}_{other_name}.csv"
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=PAIR_COLUMNS)
+        w.writeheader()
+        for r in rows:
+            w.writerow({k: repr(v) if isinstance(v, float) else v for k, v in r.items()})
+    return path
 
 
 def update_metrics_csv(results_dir, sample: str, tomo_name: str, metrics: dict[str, float], split_id=None) -> Path:

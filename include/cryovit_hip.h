@@ -526,6 +526,40 @@ int cvx_instance_distance_stats(const int32_t* labels, const int32_t* d2, int D,
                                 int64_t* out, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Nearest-instance maps and pairwise contacts between the instances of two labels (`cryovit instances --contacts-with`).
+ *
+ * cvx_nearest_instance: labels int32 [D][H][W]; a voxel is a site iff its value lies in 1..k (other values are nobody's, as
+ * in cvx_instance_distance_stats).  d2_out int32 [D][H][W] = min over the sites s of |v - s|^2: bit for bit what
+ * cvx_edt_squared(CVX_EDT_SITES_NONZERO) gives when every nonzero value lies in 1..k.  nearest_out int32 [D][H][W] = the
+ * smallest id among the sites that attain it; on a site its own id.  Without a site: CVX_EDT_NONE and 0 everywhere.
+ * workspace: cvx_nearest_workspace_bytes(D, H, W) = 8 * D*H*W bytes, 8-byte aligned: the keys d2 << 32 | id between the passes;
+ * its contents after the call mean nothing.  Integers only, no atomics.  Refused with an error before any launch: what
+ * cvx_edt_squared refuses (null pointers, negative extents, D*H*W > CVX_COMPONENT_MAX_VOXELS, the squared diagonal >= INT32_MAX)
+ * and k < 0.  An empty volume succeeds.
+ *
+ * cvx_instance_pair_contacts: over the voxels v with a = labels_a[v] in 1..ka, b = nearest_b[v] != 0 and 0 <= d2_b[v] <=
+ * threshold_d2 (nearest_b, d2_b as cvx_nearest_instance wrote them for the other label), every pair (a, b) accumulates
+ * contact_voxels = their number, gap_d2 = the smallest d2_b among them and `at` = the smallest linear index of a voxel that
+ * attains it.  The pairs land in an open-addressed table of `capacity` slots (a power of two in 1..CVX_PAIR_MAX_CAPACITY):
+ * table int64 [3][capacity] = per slot the key a << 32 | b (INT64_MAX: empty), the count, and gap_d2 << 32 | at; status int64
+ * [2] = {1 if some pair found no slot (the table is then void: repeat with a larger one), P = the claimed slots}.  Both are
+ * initialised by the call and stay on the device.  Integer atomic add / min / max only; no part of a table that did not
+ * overflow, other than which slot a pair sits in, depends on capacity or scheduling.
+ * cvx_instance_pair_rows: rows int64 [p][CVX_PAIR_COLS] = a, b, contact_voxels, gap_d2, at of the slots order[0..p): the
+ * caller sorts the table's keys ascending (empty slots sort last) and passes the first P slot indices, which gives the rows in
+ * (a, b) order.  An index that names no claimed slot gives -1, -1, 0, -1, -1.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_PAIR_COLS 5
+#define CVX_PAIR_MAX_CAPACITY 2147483648L /* 2^31: more slots than voxels */
+
+long cvx_nearest_workspace_bytes(int D, int H, int W); /* < 0 on bad extents */
+int cvx_nearest_instance(const int32_t* labels, long k, int D, int H, int W, int32_t* d2_out, int32_t* nearest_out, void* workspace,
+                         hipStream_t stream);
+int cvx_instance_pair_contacts(const int32_t* labels_a, long ka, const int32_t* nearest_b, const int32_t* d2_b, int threshold_d2,
+                               int D, int H, int W, int64_t* table, long capacity, int64_t* status, hipStream_t stream);
+int cvx_instance_pair_rows(const int64_t* table, long capacity, const int64_t* order, long p, int64_t* rows, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Touching instances split at their necks (`infer --instances --split-radius`, `cryovit instances --split-radius`).  labels
  * int32 [D][H][W] with ids 0..k as cvx_components_table writes them (two ids never share a face).  The caller erodes: d2 =
  * cvx_edt_squared(labels, CVX_EDT_I32, CVX_EDT_SITES_ZERO), cvx_split_core_mask marks d2 > threshold_d2 (= floor(radius^2)) with
