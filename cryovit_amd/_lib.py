@@ -35,6 +35,7 @@ EDT_NONE = 2**31 - 1  # CVX_EDT_NONE
 DSTAT_COLS = 4  # CVX_DSTAT_COLS
 PAIR_COLS = 5  # CVX_PAIR_COLS
 PAIR_MAX_CAPACITY = 2**31  # CVX_PAIR_MAX_CAPACITY
+SHAPE_COLS = 24  # CVX_SHAPE_COLS
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -171,6 +172,7 @@ SIGNATURES = {
     "cvx_components_table": (c_int, [c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "cvx_edt_squared": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_instance_distance_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p]),
+    "cvx_instance_shape_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p]),
     "cvx_nearest_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     "cvx_nearest_instance": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cvx_instance_pair_contacts": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p,

@@ -4,7 +4,8 @@
 bit-reproducible); ``instance_rows`` turns the integer table into the rows people read; ``label_file`` does both for a
 prediction file that ``cryovit infer`` wrote earlier; ``distance_rows`` adds the columns that need a distance map;
 ``split_volume`` cuts instances that touch over a neck into pieces (``engine.ops.split_instances``); ``contacts_with`` of
-``label_file`` pairs the instances with those of another label (``analysis.distances.instance_pair_contacts``).
+``label_file`` pairs the instances with those of another label (``analysis.distances.instance_pair_contacts``); ``shape`` of
+``label_file`` adds surface area, Euler number and principal axes per instance (``analysis.shape.instance_shape``).
 """
 
 from __future__ import annotations
@@ -107,7 +108,8 @@ def _other_instances(path: Path, datasets: dict, name: str, distance_to_dir):
 
 def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, result_dir=None, device=None,
                morphology: bool = False, distance_to: str | None = None, distance_to_dir=None, contact_radius: float = 1.0,
-               split_radius: float | None = None, split_min_core: int = 0, contacts_with: str | None = None) -> Path:
+               split_radius: float | None = None, split_min_core: int = 0, contacts_with: str | None = None,
+               shape: bool = False) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  ``morphology`` adds the thickness / surface / deepest-voxel
@@ -120,7 +122,9 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     under ``connectivity`` with no ``min_size``) are paired with this label's: ``contacts/<stem>_<label>_<contacts_with>.csv``
     under ``result_dir`` gets one row per pair of an instance and the other instance nearest to some of its voxels within
     ``contact_radius`` voxels (``analysis.distances.PAIR_COLUMNS``), and every instance row gains ``partners_<contacts_with>``,
-    the number of such partners, after the ``distance_to`` columns.  Returns the written file."""
+    the number of such partners, after the ``distance_to`` columns.  ``shape`` adds ``analysis.shape.SHAPE_COLUMNS`` (surface area,
+    sphericity, Euler number under ``connectivity``, principal axes and direction; of the pieces after a split) as the last
+    columns of every row.  Returns the written file."""
     import torch
 
     from cryovit_amd import io
@@ -186,4 +190,9 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
         for r, e in zip(rows, distances.partner_rows(pairs, len(rows), contacts_with)):
             r.update(e)
         writers.write_contacts(result_dir, path.name, label, contacts_with, pairs)
+    if shape:
+        from cryovit_amd.analysis.shape import instance_shape
+
+        for r, e in zip(rows, instance_shape(labels, len(rows), connectivity)):
+            r.update(e)
     return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows)

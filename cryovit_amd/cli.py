@@ -3,13 +3,13 @@
 
     python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize]
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
-                                    [--instances [--min-size N] [--connectivity 6|26] [--morphology]
+                                    [--instances [--min-size N] [--connectivity 6|26] [--morphology] [--shape]
                                      [--split-radius R [--split-min-core N]]]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
     python -m cryovit_amd.cli instances <predictions> --label NAME [--min-size N] [--connectivity 6|26] [--result-folder DIR]
                                         [--morphology] [--distance-to NAME] [--contacts-with NAME]
                                         [--distance-to-folder DIR] [--contact-radius R]
-                                        [--split-radius R [--split-min-core N]]
+                                        [--split-radius R [--split-min-core N]] [--shape]
 
 ``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
 replace the network fetch of the encoder weights or add what the reference leaves to the user: ``instances`` (and
@@ -19,7 +19,10 @@ gap and contact voxels against another label), all in voxels.  ``--split-radius 
 before they are measured: cores deeper than R voxels (of at least ``--split-min-core`` voxels) are grown back inside their
 instance, and the CSV gains ``component``, the id a piece had before the split.  ``--contacts-with NAME`` says which instance
 touches which: every instance gains ``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance,
-nearest instance of NAME within ``--contact-radius``) the voxels in contact, the narrowest gap and where it is.
+nearest instance of NAME within ``--contact-radius``) the voxels in contact, the narrowest gap and where it is.  ``--shape`` adds,
+as the last columns, what shape every instance (after ``--split-radius``: every piece) has: surface area (discrete Crofton
+estimate over 13 directions), sphericity, Euler number under ``--connectivity``, the three principal-axis lengths, elongation
+and the direction of the major axis, all in voxels.
 """
 
 from __future__ import annotations
@@ -73,6 +76,8 @@ def _check_split_radius(value: Optional[float]) -> Optional[float]:
 _SPLIT_RADIUS_HELP = ("split instances that touch over a neck: cores deeper than this many voxels are grown back inside their "
                       "instance; the CSV gains the column component (voxels, >= 0)")
 _SPLIT_MIN_CORE_HELP = "with --split-radius, ignore cores of fewer voxels"
+_SHAPE_HELP = ("add surface area (Crofton estimate over 13 directions), sphericity, Euler number (under --connectivity), principal-axis "
+               "lengths, elongation and major-axis direction per instance as the last CSV columns (voxels; with infer: needs --instances)")
 
 
 def _encoder_overrides(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]) -> dict:
@@ -123,10 +128,13 @@ def infer(
     morphology: Annotated[bool, Option("--morphology", help="build extension: with --instances, add surface voxels, inscribed radius and deepest voxel per instance (exact distance map on the GPU; voxels)")] = False,
     split_radius: Annotated[Optional[float], Option(callback=_check_split_radius, help="build extension: with --instances, " + _SPLIT_RADIUS_HELP)] = None,
     split_min_core: Annotated[int, Option(min=0, help="build extension: " + _SPLIT_MIN_CORE_HELP)] = 0,
+    shape: Annotated[bool, Option("--shape", help="build extension: " + _SHAPE_HELP)] = False,
 ):
     """Segment tomograms using a pre-trained model."""
     if morphology and not instances:
         raise typer.BadParameter("--morphology needs --instances", param_hint="--morphology")
+    if shape and not instances:
+        raise typer.BadParameter("--shape needs --instances", param_hint="--shape")
     if split_radius is not None and not instances:
         raise typer.BadParameter("--split-radius needs --instances", param_hint="--split-radius")
     from cryovit_amd.run.infer_model import run_inference
@@ -140,7 +148,8 @@ def infer(
     result_path.mkdir(parents=True, exist_ok=True)
     run_inference(load_files_from_path(tomograms_path), model_path, result_path, threshold=threshold,
                   encoder=_load_encoder(encoder, checkpoint, synthetic_seed), instances=instances, min_size=min_size,
-                  connectivity=connectivity, morphology=morphology, split_radius=split_radius, split_min_core=split_min_core)
+                  connectivity=connectivity, morphology=morphology, split_radius=split_radius, split_min_core=split_min_core,
+                  shape=shape)
 
 
 @cli.command(name="instances", no_args_is_help=True)
@@ -158,6 +167,7 @@ def instances_cmd(
     contacts_with: Annotated[Optional[str], Option(help="build extension: another label NAME; write contacts/<tomo>_<label>_<NAME>.csv, one row per pair of an instance and the instance of NAME nearest to some of its voxels within --contact-radius (voxels in contact, gap, where), and add partners_<NAME> per instance")] = None,
     split_radius: Annotated[Optional[float], Option(callback=_check_split_radius, help="build extension: " + _SPLIT_RADIUS_HELP)] = None,
     split_min_core: Annotated[int, Option(min=0, help="build extension: " + _SPLIT_MIN_CORE_HELP)] = 0,
+    shape: Annotated[bool, Option("--shape", help="build extension: " + _SHAPE_HELP)] = False,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     from cryovit_amd.analysis.instances import label_file
@@ -169,7 +179,7 @@ def instances_cmd(
     for f in load_files_from_path(predictions_path):
         out = label_file(f, label, connectivity=connectivity, min_size=min_size, result_dir=result_folder, morphology=morphology,
                          distance_to=distance_to, distance_to_dir=distance_to_folder, contact_radius=contact_radius,
-                         split_radius=split_radius, split_min_core=split_min_core, contacts_with=contacts_with)
+                         split_radius=split_radius, split_min_core=split_min_core, contacts_with=contacts_with, shape=shape)
         logging.info("Labelled %s", out)
 
 

@@ -1,6 +1,7 @@
 // Pieces shared by the passes that walk an int32 [D][H][W] volume in 16-voxel row pieces and build the per-instance table
 // (components.hip: relabel + table; split.hip: renumber + table): the piece a thread owns, its 16-B loads / stores, and the
-// integer add / min / max into a table row.  Device code only; every includer compiles its own copy.
+// integer add / min / max into a table row; and, for the passes that read a voxel's 3x3x3 neighbourhood (shape.hip), a tile's
+// ids with their one-voxel halo in LDS and the sum over a wave.  Device code only; every includer compiles its own copy.
 #pragma once
 #include "common.h"
 #include "../../include/cryovit_hip.h"
@@ -103,6 +104,32 @@ __device__ __forceinline__ void table_add_piece(long long* __restrict__ table, c
         }
     }
     if (cur) table_add_run(table, cur, z, y, xa, x0 + cnt - 1);
+}
+
+// ---- a tile with its one-voxel halo in LDS (shape.hip; any pass that reads a voxel's 3x3x3 neighbourhood) ----
+
+constexpr int kHaloZ = TZ + 2, kHaloY = TY + 2, kHaloX = TX + 2;
+constexpr int kHaloCells = kHaloZ * kHaloY * kHaloX;  // 3960 int32 = 15.5 KB
+
+// the LDS cell of the tile's own voxel (z, y, x), 0 <= z < TZ etc.; a neighbour is at + (dz * kHaloY + dy) * kHaloX + dx
+__device__ __forceinline__ int halo_cell(int z, int y, int x) { return ((z + 1) * kHaloY + y + 1) * kHaloX + x + 1; }
+
+// ids[kHaloCells] = the labels of the tile at (z0, y0, x0) and of the voxels around it; a value outside 1..k and a cell outside
+// the volume read 0 (nobody's).  Global reads stay inside the volume.  The caller synchronises before it reads ids.
+__device__ __forceinline__ void tile_load_ids(const int* __restrict__ labels, const Dims& d, int z0, int y0, int x0, int k, int* ids) {
+    for (int c = threadIdx.x; c < kHaloCells; c += kCclThreads) {
+        const int x = x0 - 1 + c % kHaloX, y = y0 - 1 + c / kHaloX % kHaloY, z = z0 - 1 + c / (kHaloX * kHaloY);
+        const bool in = (unsigned)x < (unsigned)d.W && (unsigned)y < (unsigned)d.H && (unsigned)z < (unsigned)d.D;
+        const int l = in ? labels[((long)z * d.H + y) * d.W + x] : 0;
+        ids[c] = l >= 1 && l <= k ? l : 0;
+    }
+}
+
+// the sum of v over the 64 lanes of a wave, in every lane (all lanes call it)
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
 }
 
 }  // namespace cvx

@@ -649,6 +649,28 @@ def instance_distance_stats(labels: torch.Tensor, d2: torch.Tensor, k: int, thre
     return out
 
 
+
+def instance_shape_stats(labels: torch.Tensor, k: int, *, connectivity: int = 26) -> torch.Tensor:
+    """int64 [k, 24] on the device, the integer sums behind the shape columns (csrc/shape.hip).  Row id - 1, over the voxels of
+    ``labels`` (int32 [D, H, W]) with that id in 1..k, everything else counting as outside: voxels; sum of z, y, x; sum of zz,
+    yy, xx, zy, zx, yx; the Euler number under ``connectivity`` (6 or 26); and the 13 crossing counts N_d = #{v : v + d outside}
+    over the directions d lexicographically after (0,0,0), in that order.  Ids past k are ignored.  Integers only,
+    bit-reproducible; the host does not wait."""
+    if labels.dim() != 3 or labels.dtype != torch.int32:
+        raise _lib.CvxError(f"instance_shape_stats: labels must be int32 [D, H, W], got {labels.dtype} {tuple(labels.shape)}")
+    if k < 0:
+        raise _lib.CvxError(f"instance_shape_stats: k must be >= 0, got {k}")
+    if connectivity not in (6, 26):
+        raise _lib.CvxError(f"instance_shape_stats: connectivity must be 6 or 26, got {connectivity}")
+    dev = _dev_check(labels)
+    D, H, W = labels.shape
+    if labels.numel() > _lib.COMPONENT_MAX_VOXELS:
+        raise _lib.CvxError(f"instance_shape_stats: {D}x{H}x{W} has more than 2^31 - 2 voxels")
+    out = torch.empty((int(k), _lib.SHAPE_COLS), dtype=torch.int64, device=dev)
+    call(dev, "cvx_instance_shape_stats", _lib.load().cvx_instance_shape_stats, _p(labels), D, H, W, int(k), int(connectivity), _p(out))
+    return out
+
+
 # ---- touching instances split at their necks (`--split-radius`): erosion cores, geodesic regrowth ----
 
 SPLIT_ROUND_BATCH = 4  # regrowth rounds launched per read of their "changed" flags

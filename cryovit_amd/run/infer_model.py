@@ -19,7 +19,9 @@ unfiltered threshold mask.  ``morphology=True`` (with ``instances``) adds per in
 the deepest voxel from an exact distance map of the labels (``analysis.distances``), also computed while they are in HBM.
 ``split_radius=R`` (with ``instances``) first splits instances that touch over a neck (``analysis.instances.split_volume``: cores
 deeper than R voxels, of at least ``split_min_core`` voxels, grown back inside their instance); volume, rows and morphology are
-then those of the pieces and the CSV carries ``component``, the id a piece had before the split.
+then those of the pieces and the CSV carries ``component``, the id a piece had before the split.  ``shape=True`` (with
+``instances``) adds surface area, sphericity, Euler number (under ``connectivity``), principal axes and direction per instance
+(``analysis.shape``; of the pieces after a split) as the last columns of the CSV.
 """
 
 from __future__ import annotations
@@ -33,6 +35,7 @@ import torch
 
 from cryovit_amd import io
 from cryovit_amd.analysis.instances import component_rows, distance_rows, instance_rows, label_volume, split_volume
+from cryovit_amd.analysis.shape import instance_shape
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
 from cryovit_amd.run import writers
@@ -84,13 +87,15 @@ def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs,
 def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, threshold: float = 0.5, *, encoder=None,
                   batch_size: int = 128, device: str | None = None, instances: bool = False, min_size: int = 0,
                   connectivity: int = 26, morphology: bool = False, split_radius: float | None = None,
-                  split_min_core: int = 0) -> list[Path]:
+                  split_min_core: int = 0, shape: bool = False) -> list[Path]:
     if connectivity not in (6, 26):
         raise ValueError(f"connectivity must be 6 or 26, got {connectivity}")
     if min_size < 0:
         raise ValueError(f"min_size must be >= 0, got {min_size}")
     if morphology and not instances:
         raise ValueError("morphology=True needs instances=True: the columns describe the labelled instances")
+    if shape and not instances:
+        raise ValueError("shape=True needs instances=True: the columns describe the labelled instances")
     if split_radius is not None and not instances:
         raise ValueError("split_radius needs instances=True: it splits the labelled instances")
     if split_radius is not None and not split_radius >= 0:
@@ -132,6 +137,9 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 extra = distance_rows(labels, table.shape[0], morphology=morphology)
                 if component is not None:
                     extra = component_rows(component, extra)
+                if shape:
+                    for e, s in zip(extra, instance_shape(labels, table.shape[0], connectivity)):
+                        e.update(s)
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:
                 pending.append((i, writer.submit(_write_with_instances, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),

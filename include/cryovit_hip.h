@@ -560,6 +560,40 @@ int cvx_instance_pair_contacts(const int32_t* labels_a, long ka, const int32_t* 
 int cvx_instance_pair_rows(const int64_t* table, long capacity, const int64_t* order, long p, int64_t* rows, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Per-instance shape (`infer --instances --shape`, `cryovit instances --shape`): the integer sums from which the surface area
+ * (discrete Crofton estimate), the Euler number and the principal axes of every instance follow.
+ *
+ * labels int32 [D][H][W]; voxel v belongs to instance i iff labels[v] == i with i in 1..k; ids outside 1..k belong to nobody, as
+ * in cvx_instance_distance_stats.  For a given i everything that is not i counts as outside: background, other ids (split pieces
+ * touch each other) and positions beyond the volume.  out int64 [k][CVX_SHAPE_COLS], initialised by the call.  Row i - 1:
+ *    0       voxels n
+ *    1..3    sum of z, y, x over the voxels
+ *    4..9    sum of zz, yy, xx, zy, zx, yx
+ *   10       Euler number of the instance under `connectivity` (6 or 26)
+ *   11..23   N[0..12], the crossing counts N_d = #{v in i : v + d not in i} over the 13 directions d = (dz, dy, dx) that are
+ *            lexicographically greater than (0,0,0), in lexicographic order: (0,0,1), (0,1,-1), (0,1,0), (0,1,1), (1,-1,-1), ...,
+ *            (1,1,1).  The opposite direction gives the same number and is not stored.
+ *
+ * The Euler number is a sum over the voxels of i of a function of the 26 "same id" bits of the voxel's neighbourhood:
+ *   connectivity 6    chi = #voxels - #face-adjacent pairs + #full 2x2 squares - #full 2x2x2 cubes: the cubical complex on the
+ *                     voxel centres, which has the homotopy type of the 6-connected instance.  Every such cell is counted at its
+ *                     raster-first voxel, which sees the rest of it at offsets >= 0.
+ *   connectivity 26   chi = #lattice corners - #lattice edges + #lattice faces - #voxels of the union of the closed unit cubes
+ *                     of i (cubes that share a face, an edge or a corner are joined: 26-connectivity).  A cell counts when any
+ *                     voxel around it (8 around a corner, 4 around an edge, 2 at a face) belongs to i, and it is counted at the
+ *                     raster-first voxel OF i among those, so that a foreign voxel in front does not lose it.
+ *
+ * Integers only (64-bit integer atomic adds): two calls give the same bits.  Every sum fits in int64: extents are at most 32768
+ * and n <= D*H*W <= CVX_COMPONENT_MAX_VOXELS < 2^31, so a first moment is below 2^31 * 2^15 = 2^46, a second moment below 2^31 *
+ * 2^30 = 2^61, a crossing count at most n, and the Euler number, to which a voxel adds between -13 and +13, below 2^35 in magnitude.
+ * Refused with an error before any launch: null pointers, negative extents, an extent above 32768, D*H*W >
+ * CVX_COMPONENT_MAX_VOXELS, k < 0, a connectivity other than 6 or 26, misaligned arrays (labels: 4 bytes, out: 8 bytes).  k == 0
+ * and an empty volume succeed.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_SHAPE_COLS 24
+int cvx_instance_shape_stats(const int32_t* labels, int D, int H, int W, long k, int connectivity, int64_t* out, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Touching instances split at their necks (`infer --instances --split-radius`, `cryovit instances --split-radius`).  labels
  * int32 [D][H][W] with ids 0..k as cvx_components_table writes them (two ids never share a face).  The caller erodes: d2 =
  * cvx_edt_squared(labels, CVX_EDT_I32, CVX_EDT_SITES_ZERO), cvx_split_core_mask marks d2 > threshold_d2 (= floor(radius^2)) with
