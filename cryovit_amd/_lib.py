@@ -36,6 +36,7 @@ DSTAT_COLS = 4  # CVX_DSTAT_COLS
 PAIR_COLS = 5  # CVX_PAIR_COLS
 PAIR_MAX_CAPACITY = 2**31  # CVX_PAIR_MAX_CAPACITY
 SHAPE_COLS = 24  # CVX_SHAPE_COLS
+SKELETON_COLS = 8  # CVX_SKELETON_COLS
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -184,6 +185,9 @@ SIGNATURES = {
     "cvx_split_first": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
     "cvx_split_relabel": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
+    "cvx_skeleton_init": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
+    "cvx_skeleton_cycles": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_skeleton_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
 }
 
 _lib = None

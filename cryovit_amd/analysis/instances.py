@@ -5,7 +5,8 @@ bit-reproducible); ``instance_rows`` turns the integer table into the rows peopl
 prediction file that ``cryovit infer`` wrote earlier; ``distance_rows`` adds the columns that need a distance map;
 ``split_volume`` cuts instances that touch over a neck into pieces (``engine.ops.split_instances``); ``contacts_with`` of
 ``label_file`` pairs the instances with those of another label (``analysis.distances.instance_pair_contacts``); ``shape`` of
-``label_file`` adds surface area, Euler number and principal axes per instance (``analysis.shape.instance_shape``).
+``label_file`` adds surface area, Euler number and principal axes per instance (``analysis.shape.instance_shape``); ``skeleton`` of
+``label_file`` thins every instance to its centreline and adds its length, ends and branches (``analysis.skeleton``).
 """
 
 from __future__ import annotations
@@ -109,7 +110,7 @@ def _other_instances(path: Path, datasets: dict, name: str, distance_to_dir):
 def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, result_dir=None, device=None,
                morphology: bool = False, distance_to: str | None = None, distance_to_dir=None, contact_radius: float = 1.0,
                split_radius: float | None = None, split_min_core: int = 0, contacts_with: str | None = None,
-               shape: bool = False) -> Path:
+               shape: bool = False, skeleton: bool = False, skeleton_end_radius: float = 2.0) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  ``morphology`` adds the thickness / surface / deepest-voxel
@@ -124,7 +125,12 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     ``contact_radius`` voxels (``analysis.distances.PAIR_COLUMNS``), and every instance row gains ``partners_<contacts_with>``,
     the number of such partners, after the ``distance_to`` columns.  ``shape`` adds ``analysis.shape.SHAPE_COLUMNS`` (surface area,
     sphericity, Euler number under ``connectivity``, principal axes and direction; of the pieces after a split) as the last
-    columns of every row.  Returns the written file."""
+    columns of every row.  ``skeleton`` thins every instance (after a split: every piece) to its centreline
+    (``analysis.skeleton.skeleton_volume``; a line's end is kept from ``skeleton_end_radius`` voxels of depth on), writes it as
+    ``<label>_skeleton`` (int32, every voxel with its instance's id) beside ``<label>_instances`` and adds
+    ``analysis.skeleton.SKELETON_COLUMNS`` after the shape columns.  Like ``<label>_instances``, a ``<label>_skeleton`` that an
+    earlier run left in the file is not written back, with or without ``skeleton``: it would carry the ids of that run's
+    labelling.  Returns the written file."""
     import torch
 
     from cryovit_amd import io
@@ -137,6 +143,7 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     if key not in datasets:
         raise KeyError(f"{path} holds no '{key}' dataset (found {sorted(datasets)})")
     datasets.pop(f"{label}_instances", None)  # an earlier run's result is replaced
+    datasets.pop(f"{label}_skeleton", None)  # and so is its skeleton, whose ids would be stale, whether or not a new one is made
     preds = datasets[key]
     if preds.ndim != 3:
         raise ValueError(f"'{key}' of {path} must be a [D, H, W] volume, got shape {preds.shape}")
@@ -146,6 +153,8 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
         raise ValueError(f"split_radius must be >= 0, got {split_radius}")
     if split_min_core < 0:
         raise ValueError(f"split_min_core must be >= 0, got {split_min_core}")
+    if not skeleton_end_radius >= 0:
+        raise ValueError(f"skeleton_end_radius must be >= 0, got {skeleton_end_radius}")
     other = None
     if distance_to is not None:
         other = _other_preds(path, datasets, distance_to, distance_to_dir)
@@ -195,4 +204,12 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
 
         for r, e in zip(rows, instance_shape(labels, len(rows), connectivity)):
             r.update(e)
-    return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows)
+    lines = None
+    if skeleton:
+        from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
+
+        lines, line_table = skeleton_volume(labels, len(rows), skeleton_end_radius)
+        for r, e in zip(rows, skeleton_rows(line_table)):
+            r.update(e)
+        lines = lines.cpu().numpy()
+    return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows, skeleton=lines)

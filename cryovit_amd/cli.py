@@ -4,12 +4,13 @@
     python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize]
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
                                     [--instances [--min-size N] [--connectivity 6|26] [--morphology] [--shape]
-                                     [--split-radius R [--split-min-core N]]]
+                                     [--split-radius R [--split-min-core N]] [--skeleton [--skeleton-end-radius R]]]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
     python -m cryovit_amd.cli instances <predictions> --label NAME [--min-size N] [--connectivity 6|26] [--result-folder DIR]
                                         [--morphology] [--distance-to NAME] [--contacts-with NAME]
                                         [--distance-to-folder DIR] [--contact-radius R]
                                         [--split-radius R [--split-min-core N]] [--shape]
+                                        [--skeleton [--skeleton-end-radius R]]
 
 ``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
 replace the network fetch of the encoder weights or add what the reference leaves to the user: ``instances`` (and
@@ -22,7 +23,10 @@ touches which: every instance gains ``partners_<NAME>``, and ``contacts/<tomo>_<
 nearest instance of NAME within ``--contact-radius``) the voxels in contact, the narrowest gap and where it is.  ``--shape`` adds,
 as the last columns, what shape every instance (after ``--split-radius``: every piece) has: surface area (discrete Crofton
 estimate over 13 directions), sphericity, Euler number under ``--connectivity``, the three principal-axis lengths, elongation
-and the direction of the major axis, all in voxels.
+and the direction of the major axis, all in voxels.  ``--skeleton`` thins every instance (piece) on the GPU to its centreline,
+writes it as ``<label>_skeleton`` and adds, after the shape columns, the centreline's voxels, length, ends, branch voxels and
+RMS radius; ``--skeleton-end-radius R`` is the depth from which a line's end is kept (1: every surface bump keeps a spur; larger:
+spurs go, and structures thinner than R everywhere shrink to a point or a ring).
 """
 
 from __future__ import annotations
@@ -73,11 +77,22 @@ def _check_split_radius(value: Optional[float]) -> Optional[float]:
     return value
 
 
+def _check_skeleton_end_radius(value: float) -> float:
+    if not value >= 0:
+        raise typer.BadParameter("skeleton end radius must be >= 0 (voxels)")
+    return value
+
+
 _SPLIT_RADIUS_HELP = ("split instances that touch over a neck: cores deeper than this many voxels are grown back inside their "
                       "instance; the CSV gains the column component (voxels, >= 0)")
 _SPLIT_MIN_CORE_HELP = "with --split-radius, ignore cores of fewer voxels"
 _SHAPE_HELP = ("add surface area (Crofton estimate over 13 directions), sphericity, Euler number (under --connectivity), principal-axis "
                "lengths, elongation and major-axis direction per instance as the last CSV columns (voxels; with infer: needs --instances)")
+_SKELETON_HELP = ("thin every instance to its centreline on the GPU: write it as <label>_skeleton and add skeleton_voxels, "
+                  "skeleton_length, skeleton_ends, skeleton_branches and skeleton_rms_radius after the shape columns (voxels; with "
+                  "infer: needs --instances)")
+_SKELETON_END_RADIUS_HELP = ("with --skeleton, keep a line's end once it lies this deep inside the instance: 1 keeps a spur per "
+                             "surface bump, larger values drop them; structures thinner than this shrink to a point or a ring (voxels, >= 0)")
 
 
 def _encoder_overrides(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]) -> dict:
@@ -129,12 +144,16 @@ def infer(
     split_radius: Annotated[Optional[float], Option(callback=_check_split_radius, help="build extension: with --instances, " + _SPLIT_RADIUS_HELP)] = None,
     split_min_core: Annotated[int, Option(min=0, help="build extension: " + _SPLIT_MIN_CORE_HELP)] = 0,
     shape: Annotated[bool, Option("--shape", help="build extension: " + _SHAPE_HELP)] = False,
+    skeleton: Annotated[bool, Option("--skeleton", help="build extension: " + _SKELETON_HELP)] = False,
+    skeleton_end_radius: Annotated[float, Option(callback=_check_skeleton_end_radius, help="build extension: " + _SKELETON_END_RADIUS_HELP)] = 2.0,
 ):
     """Segment tomograms using a pre-trained model."""
     if morphology and not instances:
         raise typer.BadParameter("--morphology needs --instances", param_hint="--morphology")
     if shape and not instances:
         raise typer.BadParameter("--shape needs --instances", param_hint="--shape")
+    if skeleton and not instances:
+        raise typer.BadParameter("--skeleton needs --instances", param_hint="--skeleton")
     if split_radius is not None and not instances:
         raise typer.BadParameter("--split-radius needs --instances", param_hint="--split-radius")
     from cryovit_amd.run.infer_model import run_inference
@@ -149,7 +168,7 @@ def infer(
     run_inference(load_files_from_path(tomograms_path), model_path, result_path, threshold=threshold,
                   encoder=_load_encoder(encoder, checkpoint, synthetic_seed), instances=instances, min_size=min_size,
                   connectivity=connectivity, morphology=morphology, split_radius=split_radius, split_min_core=split_min_core,
-                  shape=shape)
+                  shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius)
 
 
 @cli.command(name="instances", no_args_is_help=True)
@@ -168,6 +187,8 @@ def instances_cmd(
     split_radius: Annotated[Optional[float], Option(callback=_check_split_radius, help="build extension: " + _SPLIT_RADIUS_HELP)] = None,
     split_min_core: Annotated[int, Option(min=0, help="build extension: " + _SPLIT_MIN_CORE_HELP)] = 0,
     shape: Annotated[bool, Option("--shape", help="build extension: " + _SHAPE_HELP)] = False,
+    skeleton: Annotated[bool, Option("--skeleton", help="build extension: " + _SKELETON_HELP)] = False,
+    skeleton_end_radius: Annotated[float, Option(callback=_check_skeleton_end_radius, help="build extension: " + _SKELETON_END_RADIUS_HELP)] = 2.0,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     from cryovit_amd.analysis.instances import label_file
@@ -179,7 +200,8 @@ def instances_cmd(
     for f in load_files_from_path(predictions_path):
         out = label_file(f, label, connectivity=connectivity, min_size=min_size, result_dir=result_folder, morphology=morphology,
                          distance_to=distance_to, distance_to_dir=distance_to_folder, contact_radius=contact_radius,
-                         split_radius=split_radius, split_min_core=split_min_core, contacts_with=contacts_with, shape=shape)
+                         split_radius=split_radius, split_min_core=split_min_core, contacts_with=contacts_with, shape=shape,
+                         skeleton=skeleton, skeleton_end_radius=skeleton_end_radius)
         logging.info("Labelled %s", out)
 
 

@@ -10,6 +10,7 @@ one call are rejected.
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -855,3 +856,117 @@ def instance_pair_contacts(labels_a: torch.Tensor, ka: int, nearest_b: torch.Ten
     order = torch.sort(table[0]).indices  # the keys a << 32 | b are distinct; empty slots hold INT64_MAX and sort last
     call(dev, "cvx_instance_pair_rows", lib.cvx_instance_pair_rows, _p(table), cap, _p(order), p, _p(rows))
     return rows
+
+
+# ---- centreline skeletons of instances (`--skeleton`): thinning in the order of the distance map, and the table of the result ----
+
+SKELETON_CYCLE_BATCH = 4  # thinning cycles launched per read of their "changed" flags
+
+
+def skeleton_init(labels: torch.Tensor, k: int) -> torch.Tensor:
+    """int32 [D, H, W]: ``labels`` (int32 [D, H, W]) with ids outside 1..k set to 0, the volume the thinning starts from."""
+    dev, D, H, W = _split_volume_check("skeleton_init", labels=(labels, torch.int32))
+    if k < 0:
+        raise _lib.CvxError(f"skeleton_init: k must be >= 0, got {k}")
+    alive = torch.empty((D, H, W), dtype=torch.int32, device=dev)
+    call(dev, "cvx_skeleton_init", _lib.load().cvx_skeleton_init, _p(labels), D, H, W, int(k), _p(alive))
+    return alive
+
+
+def skeleton_cycles(alive: torch.Tensor, d2: torch.Tensor, k: int, level_d2: int, end_d2: int, cycles: int,
+                    changed: torch.Tensor | None = None) -> torch.Tensor:
+    """Runs ``cycles`` thinning cycles (8 subfield passes each, csrc/skeleton.hip) on ``alive`` (int32 [D, H, W], ``skeleton_init``)
+    in place: an alive voxel with ``d2`` (int32 [D, H, W], another tensor than ``alive``) at most ``level_d2`` (and not
+    ``_lib.EDT_NONE``) is deleted when it is a (26,6) simple point of its own id and no protected end (exactly one neighbour and
+    d2 >= ``end_d2``).  Returns int32 [cycles] on the device (``changed[:cycles]`` when one of at least that length is given):
+    entry c is nonzero iff cycle c deleted a voxel.  The host does not wait."""
+    dev, D, H, W = _split_volume_check("skeleton_cycles", alive=(alive, torch.int32), d2=(d2, torch.int32))
+    if k < 0:
+        raise _lib.CvxError(f"skeleton_cycles: k must be >= 0, got {k}")
+    if level_d2 < 0 or end_d2 < 1 or cycles < 1:
+        raise _lib.CvxError(f"skeleton_cycles: need level_d2 >= 0, end_d2 >= 1 and cycles >= 1, got {level_d2}, {end_d2}, {cycles}")
+    if alive.data_ptr() == d2.data_ptr() and alive.numel() > 0:
+        raise _lib.CvxError("skeleton_cycles: alive and d2 must be different tensors")
+    if changed is None:
+        changed = torch.empty(int(cycles), dtype=torch.int32, device=dev)
+    elif changed.dim() != 1 or changed.dtype != torch.int32 or changed.numel() < cycles or _dev_check(changed) != dev:
+        raise _lib.CvxError(f"skeleton_cycles: changed must be int32 [>= {cycles}] on the device of the volumes")
+    call(dev, "cvx_skeleton_cycles", _lib.load().cvx_skeleton_cycles, _p(alive), _p(d2), D, H, W, int(k),
+         min(int(level_d2), _lib.EDT_NONE - 1), min(int(end_d2), _lib.EDT_NONE), int(cycles), _p(changed))  # no distance is larger
+    return changed[:cycles]
+
+
+def skeleton_stats(alive: torch.Tensor, d2: torch.Tensor, k: int) -> torch.Tensor:
+    """int64 [k, 8] on the device.  Row id - 1 over the voxels of ``alive`` (int32 [D, H, W]) with that id in 1..k: voxels; voxels
+    with exactly one same-id neighbour among the 26 (ends); with three or more (branch voxels); with none; the links (unordered
+    26-adjacent same-id pairs) by a face, an edge and a corner step; the sum of ``d2`` over the voxels (``_lib.EDT_NONE`` adds 0).
+    Integers only, bit-reproducible; the host does not wait."""
+    dev, D, H, W = _split_volume_check("skeleton_stats", alive=(alive, torch.int32), d2=(d2, torch.int32))
+    if k < 0:
+        raise _lib.CvxError(f"skeleton_stats: k must be >= 0, got {k}")
+    out = torch.empty((int(k), _lib.SKELETON_COLS), dtype=torch.int64, device=dev)
+    call(dev, "cvx_skeleton_stats", _lib.load().cvx_skeleton_stats, _p(alive), _p(d2), D, H, W, int(k), _p(out))
+    return out
+
+
+def skeleton_levels(alive: torch.Tensor, d2: torch.Tensor) -> int:
+    """Lmax: the smallest L with L*L >= the largest ``d2`` that is not ``_lib.EDT_NONE`` over the nonzero voxels of ``alive``; 0
+    when there is no such voxel or none above 0.  The host waits once, for that maximum."""
+    if alive.numel() == 0:
+        return 0
+    top = int(torch.where((alive != 0) & (d2 != _lib.EDT_NONE), d2, torch.zeros_like(d2)).max().item())
+    return 0 if top <= 0 else math.isqrt(top - 1) + 1
+
+
+def skeleton_thin_level(alive: torch.Tensor, d2: torch.Tensor, k: int, level: int, end_d2: int, *, max_cycles: int = 4096,
+                        batch: int | None = None) -> int:
+    """Thins ``alive`` in place at ``level`` (candidates: d2 <= level^2) to the fixpoint and returns the number of cycles up to and
+    including the first that deleted nothing.  Cycles are launched ``batch`` (default ``SKELETON_CYCLE_BATCH``) at a time, their
+    flags read once per batch (the last batch before ``max_cycles`` may be shorter); cycles after the fixpoint change nothing.
+    Raises when ``max_cycles`` cycles did not reach it."""
+    batch = SKELETON_CYCLE_BATCH if batch is None else batch
+    if max_cycles < 1 or batch < 1 or level < 1:
+        raise _lib.CvxError(f"skeleton_thin_level: need max_cycles, batch and level >= 1, got {max_cycles}, {batch}, {level}")
+    if k < 0 or end_d2 < 1:
+        raise _lib.CvxError(f"skeleton_thin_level: need k >= 0 and end_d2 >= 1, got {k}, {end_d2}")
+    dev, *_ = _split_volume_check("skeleton_thin_level", alive=(alive, torch.int32), d2=(d2, torch.int32))  # before anything is launched
+    changed = torch.empty(batch, dtype=torch.int32, device=dev)
+    done = 0
+    while done < max_cycles:
+        now = min(batch, max_cycles - done)
+        flags = skeleton_cycles(alive, d2, k, level * level, end_d2, now, changed).tolist()  # the wait
+        if 0 in flags:
+            return done + flags.index(0) + 1
+        done += now
+    raise _lib.CvxError(f"skeleton_thin_level: level {level} has no fixpoint after max_cycles = {max_cycles} cycles")
+
+
+def skeletonize_instances(labels: torch.Tensor, k: int, *, d2: torch.Tensor | None = None, end_radius: float = 2.0,
+                          max_cycles: int = 4096) -> tuple[torch.Tensor, torch.Tensor]:
+    """(skeleton int32 [D, H, W], table int64 [k, 8]) of the instances 1..k of ``labels`` (int32 [D, H, W]): every instance thinned
+    to a one-voxel-wide centreline that keeps its own id and, per id, the instance's 26-connected components, handles and cavities.
+    Voxels go in the order of ``d2`` (default ``edt_squared(labels, sites="zero")``: shallow first, which keeps the line centred):
+    for L = 1..Lmax the voxels with d2 <= L*L that are simple points and no protected ends are deleted, subfield by subfield,
+    until a cycle deletes nothing (csrc/skeleton.hip).  A line's end is protected once it is at least ``end_radius`` deep
+    (end_d2 = max(1, floor(end_radius^2))): 1 keeps the spur of every surface bump, larger values let ends shallower than that
+    erode, so a bump's spur goes while the centreline of a tube thicker than that keeps its ends; a structure thinner than that
+    everywhere shrinks to its topological core (a point, a ring).  ``table`` is ``skeleton_stats`` of the result.  With k == 0, an
+    empty volume or no background (no distance) nothing is thinned.  After a split the pieces share faces, which ``d2`` to the
+    background does not see: topology stays exact, the line near a cut face is not centred.  Exact and bit-reproducible; raises
+    when a level has no fixpoint within ``max_cycles`` cycles."""
+    vols = {"labels": (labels, torch.int32)} | ({"d2": (d2, torch.int32)} if d2 is not None else {})
+    _split_volume_check("skeletonize_instances", **vols)
+    if k < 0:
+        raise _lib.CvxError(f"skeletonize_instances: k must be >= 0, got {k}")
+    if not end_radius >= 0 or end_radius * end_radius >= _lib.EDT_NONE:
+        raise _lib.CvxError(f"skeletonize_instances: end_radius must be >= 0 (and its square below 2^31 - 1), got {end_radius}")
+    if max_cycles < 1:
+        raise _lib.CvxError(f"skeletonize_instances: max_cycles must be >= 1, got {max_cycles}")
+    end_d2 = max(1, int(end_radius * end_radius))  # floor: the square is >= 0
+    if d2 is None:
+        d2 = edt_squared(labels, sites="zero")
+    alive = skeleton_init(labels, k)
+    if k > 0:
+        for level in range(1, skeleton_levels(alive, d2) + 1):
+            skeleton_thin_level(alive, d2, k, level, end_d2, max_cycles=max_cycles)
+    return alive, skeleton_stats(alive, d2, k)

@@ -21,7 +21,10 @@ the deepest voxel from an exact distance map of the labels (``analysis.distances
 deeper than R voxels, of at least ``split_min_core`` voxels, grown back inside their instance); volume, rows and morphology are
 then those of the pieces and the CSV carries ``component``, the id a piece had before the split.  ``shape=True`` (with
 ``instances``) adds surface area, sphericity, Euler number (under ``connectivity``), principal axes and direction per instance
-(``analysis.shape``; of the pieces after a split) as the last columns of the CSV.
+(``analysis.shape``; of the pieces after a split) as the last columns of the CSV.  ``skeleton=True`` (with ``instances``) thins
+every instance (piece) to its centreline while the labels are in HBM (``analysis.skeleton``): the file gains ``<label_key>_skeleton``
+and the CSV, after the shape columns, the centreline's voxels, length, ends, branches and RMS radius; ``skeleton_end_radius`` is
+the depth from which a line's end is kept.
 """
 
 from __future__ import annotations
@@ -36,6 +39,7 @@ import torch
 from cryovit_amd import io
 from cryovit_amd.analysis.instances import component_rows, distance_rows, instance_rows, label_volume, split_volume
 from cryovit_amd.analysis.shape import instance_shape
+from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
 from cryovit_amd.run import writers
@@ -75,19 +79,20 @@ def _predict_file(model, dataset, idx: int, threshold: float, encoder, batch_siz
     return item.aux_data["data"], mask
 
 
-def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, extra) -> Path:
+def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, extra, skeleton=None) -> Path:
     """``writers.write_segmentation`` plus the instance volume and CSV (writer thread)."""
     datasets = {"data": raw.astype(np.float32), f"{label_key}_preds": segs.astype(np.uint8, copy=False)}
     rows = instance_rows(table)
     for r, e in zip(rows, extra):
         r.update(e)
-    return writers.write_instances(result_dir, tomo_name, label_key, datasets, labels, rows)
+    return writers.write_instances(result_dir, tomo_name, label_key, datasets, labels, rows, skeleton=skeleton)
 
 
 def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, threshold: float = 0.5, *, encoder=None,
                   batch_size: int = 128, device: str | None = None, instances: bool = False, min_size: int = 0,
                   connectivity: int = 26, morphology: bool = False, split_radius: float | None = None,
-                  split_min_core: int = 0, shape: bool = False) -> list[Path]:
+                  split_min_core: int = 0, shape: bool = False, skeleton: bool = False,
+                  skeleton_end_radius: float = 2.0) -> list[Path]:
     if connectivity not in (6, 26):
         raise ValueError(f"connectivity must be 6 or 26, got {connectivity}")
     if min_size < 0:
@@ -96,6 +101,10 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
         raise ValueError("morphology=True needs instances=True: the columns describe the labelled instances")
     if shape and not instances:
         raise ValueError("shape=True needs instances=True: the columns describe the labelled instances")
+    if skeleton and not instances:
+        raise ValueError("skeleton=True needs instances=True: the centrelines are those of the labelled instances")
+    if not skeleton_end_radius >= 0:
+        raise ValueError(f"skeleton_end_radius must be >= 0, got {skeleton_end_radius}")
     if split_radius is not None and not instances:
         raise ValueError("split_radius needs instances=True: it splits the labelled instances")
     if split_radius is not None and not split_radius >= 0:
@@ -140,10 +149,18 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 if shape:
                     for e, s in zip(extra, instance_shape(labels, table.shape[0], connectivity)):
                         e.update(s)
+                host_lines = None
+                if skeleton:
+                    lines, line_table = skeleton_volume(labels, table.shape[0], skeleton_end_radius)
+                    host_lines = torch.empty(lines.shape, dtype=torch.int32, pin_memory=True)
+                    host_lines.copy_(lines, non_blocking=True)
+                    for e, s in zip(extra, skeleton_rows(line_table)):
+                        e.update(s)
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:
                 pending.append((i, writer.submit(_write_with_instances, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),
-                                                 host_labels.numpy(), host_table.numpy(), extra)))
+                                                 host_labels.numpy(), host_table.numpy(), extra,
+                                                 None if host_lines is None else host_lines.numpy())))
             else:
                 pending.append((i, writer.submit(writers.write_segmentation, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy())))
             while len(pending) > 2:

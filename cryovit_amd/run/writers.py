@@ -6,7 +6,8 @@
   write_prediction       PredictionWriter l.61-109:     ``data`` fp32 gzip, ``<label>_preds`` uint8 (preds >= threshold) gzip
                          at <results_dir>/<tomo stem>.hdf
   write_instances        (not in the reference) the prediction file with ``<label>_instances`` added (uint16 up to 65535
-                         instances, int32 beyond; gzip) and <results_dir>/instances/<tomo stem>_<label>.csv, one row per instance
+                         instances, int32 beyond; gzip), with a skeleton also ``<label>_skeleton`` (int32 ids; gzip), and
+                         <results_dir>/instances/<tomo stem>_<label>.csv, one row per instance
   write_contacts         (not in the reference) <results_dir>/contacts/<tomo stem>_<label>_<other>.csv, one row per pair of an
                          instance of <label> and an instance of <other> in contact
   update_metrics_csv     CsvWriter l.112-206:           <results_dir>/<sample>[_<split>].csv, columns sample, tomo_name,
@@ -56,13 +57,14 @@ INSTANCE_COLUMNS = ["id", "voxels", "z", "y", "x", "z0", "z1", "y0", "y1", "x0",
 
 
 def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[str, np.ndarray], labels: np.ndarray,
-                    rows: list[dict]) -> Path:
+                    rows: list[dict], skeleton: np.ndarray | None = None) -> Path:
     """The prediction file <results_dir>/<tomo stem>.hdf with every array of ``datasets`` (``data``, ``<label>_preds``, ...:
     gzip, dtypes as given) and ``<label>_instances`` = ``labels`` (uint16 while the largest id fits, else int32: a 128x512x512
     int32 volume would make the gzip of the writer thread the slowest stage of ``infer``), and the CSV
     <results_dir>/instances/<tomo stem>_<label>.csv of ``rows`` (``analysis.instance_rows``; floats written with ``repr``; no
     instances: header only; keys beyond ``INSTANCE_COLUMNS``, e.g. those of ``analysis.distance_rows``, become further columns in
-    the rows' own order).  The file is written beside its final name and moved there, so re-writing a file from its own
+    the rows' own order).  ``skeleton`` (the instances' centrelines, every voxel with its instance's id) is written as
+    ``<label>_skeleton`` in int32 beside ``<label>_instances``: it is nearly all zeros and gzips to little.  The file is written beside its final name and moved there, so re-writing a file from its own
     datasets cannot leave it half written.  Returns the .hdf path."""
     results_dir = Path(results_dir)
     out = (results_dir / tomo_name).with_suffix(".hdf")
@@ -73,6 +75,8 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
             fh.create_dataset(name, arr, compression="gzip")
         fh.create_dataset(f"{label_key}_instances", labels.astype(np.uint16 if largest <= 65535 else np.int32, copy=False),
                           compression="gzip")
+        if skeleton is not None:
+            fh.create_dataset(f"{label_key}_skeleton", skeleton.astype(np.int32, copy=False), compression="gzip")
     os.replace(tmp, out)
     csv_path = results_dir / "instances" / f"{out.stem}_{label_key}.csv"
     csv_path.parent.mkdir(parents=True, exist_ok=True)

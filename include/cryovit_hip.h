@@ -632,6 +632,45 @@ int cvx_split_first(const int32_t* labels, const uint64_t* keys, int D, int H, i
 int cvx_split_relabel(const int32_t* labels, const uint64_t* keys, const int32_t* rank, int D, int H, int W, long seeds, long kp,
                       int32_t* labels_out, int64_t* table, int64_t* component, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Centreline skeletons of instances (`infer --instances --skeleton`, `cryovit instances --skeleton`): topology-preserving
+ * thinning in the order of a priority volume, and the per-instance table of the result.  Integers only, bit-reproducible.
+ *
+ * labels int32 [D][H][W]; ids outside 1..k and positions outside the volume are nobody's; for an instance everything that is
+ * not its own id is outside.  d2 int32 [D][H][W] is the priority (in the product cvx_edt_squared(labels, CVX_EDT_I32,
+ * CVX_EDT_SITES_ZERO)); it must not overlap alive.  For an alive voxel v with id i, its mask m has bit (dz+1)*9 + (dy+1)*3 +
+ * (dx+1) set for each of the 26 neighbours that is alive with id i (the bit order of cvx_instance_shape_stats).
+ *   simple          (a) the set bits of m are non-empty and form one 26-connected set, and (b) the unset positions of v's
+ *                   18-neighbourhood that are face neighbours of v are non-empty and lie in one set connected through face steps
+ *                   within the unset 18-neighbourhood positions: the classical (26,6) simple point.
+ *   protected end   m has exactly one set bit and d2[v] >= end_d2.
+ *   candidate       alive, d2[v] <= level_d2 and d2[v] != CVX_EDT_NONE.
+ *   cycle           for subfield s = 0..7 in order: every candidate with ((z&1)<<2 | (y&1)<<1 | (x&1)) == s that is simple and no
+ *                   protected end is deleted, all of them at once (one launch).  Two voxels of one subfield are never
+ *                   26-adjacent and a decision reads the 26 neighbours only, so the launch updates alive in place and equals
+ *                   deleting the same voxels one after another; a cycle after one that deleted nothing deletes nothing.
+ * The caller finds Lmax, the smallest L with L*L >= the largest d2 != CVX_EDT_NONE over the alive voxels, and for L = 1..Lmax
+ * repeats cycles with level_d2 = L*L until one deletes nothing.  What remains has, per id, the 26-components, handles and
+ * cavities of the instance.
+ *   cvx_skeleton_init    alive = labels with ids outside 1..k set to 0.
+ *   cvx_skeleton_cycles  `cycles` cycles (8 launches each).  changed int32 [cycles] is cleared by the call; cycle c sets
+ *                        changed[c] non-zero iff it deleted a voxel.
+ *   cvx_skeleton_stats   table int64 [k][CVX_SKELETON_COLS], initialised by the call.  Row id - 1 over the alive voxels of that
+ *                        id: 0 voxels; 1 voxels with exactly one alive same-id neighbour (of 26); 2 with three or more; 3 with
+ *                        none; 4, 5, 6 links by a face, an edge, a corner step (a link is an unordered pair of 26-adjacent alive
+ *                        voxels of the id, counted at its raster-first voxel: over the 13 directions after (0,0,0)); 7 the sum
+ *                        of d2 over the voxels, CVX_EDT_NONE entries adding 0.  A count is at most 13 * D*H*W < 2^35 and the
+ *                        sum of d2 below 2^31 * 2^31.
+ * Refused with an error before any launch: null pointers, negative extents, an extent above 32768, D*H*W >
+ * CVX_COMPONENT_MAX_VOXELS, k < 0, misaligned arrays (int32: 4 bytes, table: 8 bytes); by cvx_skeleton_cycles also end_d2 < 1,
+ * level_d2 < 0 and cycles < 1.  k == 0 and an empty volume succeed.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_SKELETON_COLS 8
+int cvx_skeleton_init(const int32_t* labels, int D, int H, int W, long k, int32_t* alive, hipStream_t stream);
+int cvx_skeleton_cycles(int32_t* alive, const int32_t* d2, int D, int H, int W, long k, int level_d2, int end_d2, int cycles,
+                        int32_t* changed, hipStream_t stream);
+int cvx_skeleton_stats(const int32_t* alive, const int32_t* d2, int D, int H, int W, long k, int64_t* table, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
