@@ -37,6 +37,7 @@ PAIR_COLS = 5  # CVX_PAIR_COLS
 PAIR_MAX_CAPACITY = 2**31  # CVX_PAIR_MAX_CAPACITY
 SHAPE_COLS = 24  # CVX_SHAPE_COLS
 SKELETON_COLS = 8  # CVX_SKELETON_COLS
+THICKNESS_COLS = 5  # CVX_THICKNESS_COLS
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -188,6 +189,9 @@ SIGNATURES = {
     "cvx_skeleton_init": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
     "cvx_skeleton_cycles": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_skeleton_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
+    "cvx_local_thickness_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "cvx_local_thickness_squared": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
+    "cvx_instance_thickness_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -6,7 +6,8 @@ prediction file that ``cryovit infer`` wrote earlier; ``distance_rows`` adds the
 ``split_volume`` cuts instances that touch over a neck into pieces (``engine.ops.split_instances``); ``contacts_with`` of
 ``label_file`` pairs the instances with those of another label (``analysis.distances.instance_pair_contacts``); ``shape`` of
 ``label_file`` adds surface area, Euler number and principal axes per instance (``analysis.shape.instance_shape``); ``skeleton`` of
-``label_file`` thins every instance to its centreline and adds its length, ends and branches (``analysis.skeleton``).
+``label_file`` thins every instance to its centreline and adds its length, ends and branches (``analysis.skeleton``); ``thickness`` of
+``label_file`` maps the local thickness and adds its mean, spread, minimum and maximum per instance (``analysis.thickness``).
 """
 
 from __future__ import annotations
@@ -110,7 +111,8 @@ def _other_instances(path: Path, datasets: dict, name: str, distance_to_dir):
 def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, result_dir=None, device=None,
                morphology: bool = False, distance_to: str | None = None, distance_to_dir=None, contact_radius: float = 1.0,
                split_radius: float | None = None, split_min_core: int = 0, contacts_with: str | None = None,
-               shape: bool = False, skeleton: bool = False, skeleton_end_radius: float = 2.0) -> Path:
+               shape: bool = False, skeleton: bool = False, skeleton_end_radius: float = 2.0,
+               thickness: bool = False) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  ``morphology`` adds the thickness / surface / deepest-voxel
@@ -130,7 +132,11 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     ``<label>_skeleton`` (int32, every voxel with its instance's id) beside ``<label>_instances`` and adds
     ``analysis.skeleton.SKELETON_COLUMNS`` after the shape columns.  Like ``<label>_instances``, a ``<label>_skeleton`` that an
     earlier run left in the file is not written back, with or without ``skeleton``: it would carry the ids of that run's
-    labelling.  Returns the written file."""
+    labelling.  ``thickness`` maps the local thickness of the labelled volume (``analysis.thickness``: at every voxel the diameter of
+    the largest ball inside the structure that contains it; after a split, of the union of touching pieces), writes it as
+    ``<label>_thickness`` (float32, voxels) beside ``<label>_instances`` and adds ``analysis.thickness.THICKNESS_COLUMNS`` as the last
+    columns, after the skeleton columns; with ``skeleton`` the two share one distance map.  An earlier run's ``<label>_thickness``
+    is not written back either.  Returns the written file."""
     import torch
 
     from cryovit_amd import io
@@ -144,6 +150,7 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
         raise KeyError(f"{path} holds no '{key}' dataset (found {sorted(datasets)})")
     datasets.pop(f"{label}_instances", None)  # an earlier run's result is replaced
     datasets.pop(f"{label}_skeleton", None)  # and so is its skeleton, whose ids would be stale, whether or not a new one is made
+    datasets.pop(f"{label}_thickness", None)  # the thickness map belongs to the mask as that run filtered and labelled it
     preds = datasets[key]
     if preds.ndim != 3:
         raise ValueError(f"'{key}' of {path} must be a [D, H, W] volume, got shape {preds.shape}")
@@ -204,12 +211,24 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
 
         for r, e in zip(rows, instance_shape(labels, len(rows), connectivity)):
             r.update(e)
-    lines = None
+    lines, d2 = None, None
+    if skeleton and thickness:  # one distance map for both
+        from cryovit_amd.analysis.distances import edt_squared
+
+        d2 = edt_squared(labels)
     if skeleton:
         from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
 
-        lines, line_table = skeleton_volume(labels, len(rows), skeleton_end_radius)
+        lines, line_table = skeleton_volume(labels, len(rows), skeleton_end_radius, d2)
         for r, e in zip(rows, skeleton_rows(line_table)):
             r.update(e)
         lines = lines.cpu().numpy()
-    return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows, skeleton=lines)
+    if not thickness:
+        return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows, skeleton=lines)
+    from cryovit_amd.analysis.thickness import thickness_map, thickness_rows, thickness_volume
+
+    t2, thick_table = thickness_volume(labels, len(rows), d2)
+    for r, e in zip(rows, thickness_rows(thick_table)):
+        r.update(e)
+    return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows, skeleton=lines,
+                                   thickness=thickness_map(t2))

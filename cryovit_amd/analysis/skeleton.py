@@ -63,12 +63,12 @@ def skeleton_rows(table) -> list[dict]:
     return rows
 
 
-def skeleton_volume(labels, k: int, end_radius: float = 2.0):
+def skeleton_volume(labels, k: int, end_radius: float = 2.0, d2=None):
     """(skeleton int32 [D, H, W], table int64 [k, 8]) of the instances 1..k of the int32 device volume ``labels``; both stay on the
-    device."""
+    device.  ``d2``: the distance map ``engine.ops.edt_squared(labels, sites="zero")`` when the caller already has it."""
     from cryovit_amd.engine import ops
 
-    return ops.skeletonize_instances(labels, k, end_radius=end_radius)
+    return ops.skeletonize_instances(labels, k, d2=d2, end_radius=end_radius)
 
 
 def instance_skeleton(labels, k: int, end_radius: float = 2.0) -> list[dict]:

@@ -93,6 +93,12 @@ _SKELETON_HELP = ("thin every instance to its centreline on the GPU: write it as
                   "infer: needs --instances)")
 _SKELETON_END_RADIUS_HELP = ("with --skeleton, keep a line's end once it lies this deep inside the instance: 1 keeps a spur per "
                              "surface bump, larger values drop them; structures thinner than this shrink to a point or a ring (voxels, >= 0)")
+_THICKNESS_HELP = ("map the local thickness on the GPU (at every voxel the diameter of the largest ball inside the structure that "
+                   "contains it, as Fiji's Local Thickness): write it as <label>_thickness and add thickness_mean, thickness_std, "
+                   "thickness_min and thickness_max as the last CSV columns.  The values are diameters between voxel centres of the "
+                   "background, so a slab of n voxels reads about n + 1 (the discrete bias of Fiji's Local Thickness); for an instance "
+                   "that touches no other, thickness_max equals 2 * inscribed_radius; touching pieces after --split-radius are "
+                   "measured as their union (voxels; with infer: needs --instances)")
 
 
 def _encoder_overrides(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]) -> dict:
@@ -146,6 +152,7 @@ def infer(
     shape: Annotated[bool, Option("--shape", help="build extension: " + _SHAPE_HELP)] = False,
     skeleton: Annotated[bool, Option("--skeleton", help="build extension: " + _SKELETON_HELP)] = False,
     skeleton_end_radius: Annotated[float, Option(callback=_check_skeleton_end_radius, help="build extension: " + _SKELETON_END_RADIUS_HELP)] = 2.0,
+    thickness: Annotated[bool, Option("--thickness", help="build extension: " + _THICKNESS_HELP)] = False,
 ):
     """Segment tomograms using a pre-trained model."""
     if morphology and not instances:
@@ -156,6 +163,8 @@ def infer(
         raise typer.BadParameter("--skeleton needs --instances", param_hint="--skeleton")
     if split_radius is not None and not instances:
         raise typer.BadParameter("--split-radius needs --instances", param_hint="--split-radius")
+    if thickness and not instances:
+        raise typer.BadParameter("--thickness needs --instances", param_hint="--thickness")
     from cryovit_amd.run.infer_model import run_inference
     from cryovit_amd.utils import load_files_from_path
 
@@ -168,7 +177,7 @@ def infer(
     run_inference(load_files_from_path(tomograms_path), model_path, result_path, threshold=threshold,
                   encoder=_load_encoder(encoder, checkpoint, synthetic_seed), instances=instances, min_size=min_size,
                   connectivity=connectivity, morphology=morphology, split_radius=split_radius, split_min_core=split_min_core,
-                  shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius)
+                  shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius, thickness=thickness)
 
 
 @cli.command(name="instances", no_args_is_help=True)
@@ -189,6 +198,7 @@ def instances_cmd(
     shape: Annotated[bool, Option("--shape", help="build extension: " + _SHAPE_HELP)] = False,
     skeleton: Annotated[bool, Option("--skeleton", help="build extension: " + _SKELETON_HELP)] = False,
     skeleton_end_radius: Annotated[float, Option(callback=_check_skeleton_end_radius, help="build extension: " + _SKELETON_END_RADIUS_HELP)] = 2.0,
+    thickness: Annotated[bool, Option("--thickness", help="build extension: " + _THICKNESS_HELP)] = False,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     from cryovit_amd.analysis.instances import label_file
@@ -201,7 +211,7 @@ def instances_cmd(
         out = label_file(f, label, connectivity=connectivity, min_size=min_size, result_dir=result_folder, morphology=morphology,
                          distance_to=distance_to, distance_to_dir=distance_to_folder, contact_radius=contact_radius,
                          split_radius=split_radius, split_min_core=split_min_core, contacts_with=contacts_with, shape=shape,
-                         skeleton=skeleton, skeleton_end_radius=skeleton_end_radius)
+                         skeleton=skeleton, skeleton_end_radius=skeleton_end_radius, thickness=thickness)
         logging.info("Labelled %s", out)
 
 

@@ -970,3 +970,48 @@ def skeletonize_instances(labels: torch.Tensor, k: int, *, d2: torch.Tensor | No
         for level in range(1, skeleton_levels(alive, d2) + 1):
             skeleton_thin_level(alive, d2, k, level, end_d2, max_cycles=max_cycles)
     return alive, skeleton_stats(alive, d2, k)
+
+
+# ---- local thickness (`--thickness`): the largest inscribed ball through every voxel, and the per-instance table over it ----
+
+def local_thickness_squared(d2: torch.Tensor) -> torch.Tensor:
+    """int32 [D, H, W]: the squared local-thickness radius of ``d2`` (int32 [D, H, W], non-negative; ``edt_squared(src, sites="zero")``
+    in the product, but any values are taken as they are).  0 where ``d2`` is 0; elsewhere the largest ``d2[c]`` over the voxels c
+    with ``d2[c] > 0`` whose open ball ``|p - c|^2 < d2[c]`` holds the voxel, so never below ``d2``.  Balls are clipped by the
+    volume.  If any ``d2`` is ``_lib.EDT_NONE`` every nonzero voxel gets ``_lib.EDT_NONE``.  Integers only, bit-reproducible
+    (csrc/thickness.hip); 4 bytes of workspace per 4x8x64 tile for the duration of the call; the host does not wait."""
+    dev, D, H, W = _split_volume_check("local_thickness_squared", d2=(d2, torch.int32))
+    lib = _lib.load()
+    t2 = torch.empty((D, H, W), dtype=torch.int32, device=dev)
+    workspace = torch.empty(max(int(lib.cvx_local_thickness_workspace_bytes(D, H, W)), 4) // 4, dtype=torch.int32, device=dev)
+    call(dev, "cvx_local_thickness_squared", lib.cvx_local_thickness_squared, _p(d2), D, H, W, _p(t2), _p(workspace),
+         workspace.numel() * 4)
+    return t2
+
+
+def instance_thickness_stats(labels: torch.Tensor, t2: torch.Tensor, k: int) -> torch.Tensor:
+    """int64 [k, 5] on the device.  Row id - 1, over the voxels of ``labels`` (int32 [D, H, W]) with that id in 1..k whose ``t2``
+    (``local_thickness_squared``) is neither 0 nor ``_lib.EDT_NONE``: voxels; the sum of t2; the sum of r_fx = floor(sqrt(t2 * 2^16)),
+    the exact integer root (256 times the radius, rounded down); min t2; max t2.  0, 0, 0, -1, -1 for an id without such a voxel.
+    Ids past k are ignored.  Integers only, bit-reproducible; the host does not wait."""
+    dev, D, H, W = _split_volume_check("instance_thickness_stats", labels=(labels, torch.int32), t2=(t2, torch.int32))
+    if k < 0:
+        raise _lib.CvxError(f"instance_thickness_stats: k must be >= 0, got {k}")
+    out = torch.empty((int(k), _lib.THICKNESS_COLS), dtype=torch.int64, device=dev)
+    call(dev, "cvx_instance_thickness_stats", _lib.load().cvx_instance_thickness_stats, _p(labels), _p(t2), D, H, W, int(k), _p(out))
+    return out
+
+
+def instance_thickness(labels: torch.Tensor, k: int, *, d2: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(t2 int32 [D, H, W], table int64 [k, 5]) of the instances 1..k of ``labels`` (int32 [D, H, W]): ``local_thickness_squared`` of
+    ``d2`` (default ``edt_squared(labels, sites="zero")``, the depth inside the foreground) and ``instance_thickness_stats`` over it.
+    Ids play no part in the map: after a split the pieces share faces, which ``d2`` to the background does not see, so a ball
+    centred in one piece may cover voxels of its neighbour and the map of two touching pieces is the map of their union."""
+    vols = {"labels": (labels, torch.int32)} | ({"d2": (d2, torch.int32)} if d2 is not None else {})
+    _split_volume_check("instance_thickness", **vols)
+    if k < 0:
+        raise _lib.CvxError(f"instance_thickness: k must be >= 0, got {k}")
+    if d2 is None:
+        d2 = edt_squared(labels, sites="zero")
+    t2 = local_thickness_squared(d2)
+    return t2, instance_thickness_stats(labels, t2, k)

@@ -24,7 +24,10 @@ then those of the pieces and the CSV carries ``component``, the id a piece had b
 (``analysis.shape``; of the pieces after a split) as the last columns of the CSV.  ``skeleton=True`` (with ``instances``) thins
 every instance (piece) to its centreline while the labels are in HBM (``analysis.skeleton``): the file gains ``<label_key>_skeleton``
 and the CSV, after the shape columns, the centreline's voxels, length, ends, branches and RMS radius; ``skeleton_end_radius`` is
-the depth from which a line's end is kept.
+the depth from which a line's end is kept.  ``thickness=True`` (with ``instances``) maps the local thickness of the labelled volume
+(``analysis.thickness``: at every voxel the diameter of the largest inscribed ball that contains it): the file gains
+``<label_key>_thickness`` (float32, voxels) and the CSV, as its last columns, the mean, spread, minimum and maximum per instance; with
+``skeleton`` the two share one distance map.
 """
 
 from __future__ import annotations
@@ -37,9 +40,11 @@ import numpy as np
 import torch
 
 from cryovit_amd import io
+from cryovit_amd.analysis.distances import edt_squared
 from cryovit_amd.analysis.instances import component_rows, distance_rows, instance_rows, label_volume, split_volume
 from cryovit_amd.analysis.shape import instance_shape
 from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
+from cryovit_amd.analysis.thickness import thickness_map, thickness_rows, thickness_volume
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
 from cryovit_amd.run import writers
@@ -79,20 +84,23 @@ def _predict_file(model, dataset, idx: int, threshold: float, encoder, batch_siz
     return item.aux_data["data"], mask
 
 
-def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, extra, skeleton=None) -> Path:
+def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, extra, skeleton=None, thickness=None) -> Path:
     """``writers.write_segmentation`` plus the instance volume and CSV (writer thread)."""
     datasets = {"data": raw.astype(np.float32), f"{label_key}_preds": segs.astype(np.uint8, copy=False)}
     rows = instance_rows(table)
     for r, e in zip(rows, extra):
         r.update(e)
-    return writers.write_instances(result_dir, tomo_name, label_key, datasets, labels, rows, skeleton=skeleton)
+    if thickness is None:
+        return writers.write_instances(result_dir, tomo_name, label_key, datasets, labels, rows, skeleton=skeleton)
+    return writers.write_instances(result_dir, tomo_name, label_key, datasets, labels, rows, skeleton=skeleton,
+                                   thickness=thickness_map(thickness))  # the root is taken on the writer thread
 
 
 def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, threshold: float = 0.5, *, encoder=None,
                   batch_size: int = 128, device: str | None = None, instances: bool = False, min_size: int = 0,
                   connectivity: int = 26, morphology: bool = False, split_radius: float | None = None,
                   split_min_core: int = 0, shape: bool = False, skeleton: bool = False,
-                  skeleton_end_radius: float = 2.0) -> list[Path]:
+                  skeleton_end_radius: float = 2.0, thickness: bool = False) -> list[Path]:
     if connectivity not in (6, 26):
         raise ValueError(f"connectivity must be 6 or 26, got {connectivity}")
     if min_size < 0:
@@ -103,6 +111,8 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
         raise ValueError("shape=True needs instances=True: the columns describe the labelled instances")
     if skeleton and not instances:
         raise ValueError("skeleton=True needs instances=True: the centrelines are those of the labelled instances")
+    if thickness and not instances:
+        raise ValueError("thickness=True needs instances=True: the map is that of the labelled instances")
     if not skeleton_end_radius >= 0:
         raise ValueError(f"skeleton_end_radius must be >= 0, got {skeleton_end_radius}")
     if split_radius is not None and not instances:
@@ -149,18 +159,27 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 if shape:
                     for e, s in zip(extra, instance_shape(labels, table.shape[0], connectivity)):
                         e.update(s)
-                host_lines = None
+                host_lines, host_t2, d2 = None, None, None
+                if skeleton and thickness:  # one distance map for both
+                    d2 = edt_squared(labels)
                 if skeleton:
-                    lines, line_table = skeleton_volume(labels, table.shape[0], skeleton_end_radius)
+                    lines, line_table = skeleton_volume(labels, table.shape[0], skeleton_end_radius, d2)
                     host_lines = torch.empty(lines.shape, dtype=torch.int32, pin_memory=True)
                     host_lines.copy_(lines, non_blocking=True)
                     for e, s in zip(extra, skeleton_rows(line_table)):
+                        e.update(s)
+                if thickness:
+                    t2, thick_table = thickness_volume(labels, table.shape[0], d2)
+                    host_t2 = torch.empty(t2.shape, dtype=torch.int32, pin_memory=True)
+                    host_t2.copy_(t2, non_blocking=True)
+                    for e, s in zip(extra, thickness_rows(thick_table)):
                         e.update(s)
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:
                 pending.append((i, writer.submit(_write_with_instances, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),
                                                  host_labels.numpy(), host_table.numpy(), extra,
-                                                 None if host_lines is None else host_lines.numpy())))
+                                                 None if host_lines is None else host_lines.numpy(),
+                                                 None if host_t2 is None else host_t2.numpy())))
             else:
                 pending.append((i, writer.submit(writers.write_segmentation, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy())))
             while len(pending) > 2:

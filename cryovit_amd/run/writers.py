@@ -6,7 +6,8 @@
   write_prediction       PredictionWriter l.61-109:     ``data`` fp32 gzip, ``<label>_preds`` uint8 (preds >= threshold) gzip
                          at <results_dir>/<tomo stem>.hdf
   write_instances        (not in the reference) the prediction file with ``<label>_instances`` added (uint16 up to 65535
-                         instances, int32 beyond; gzip), with a skeleton also ``<label>_skeleton`` (int32 ids; gzip), and
+                         instances, int32 beyond; gzip), with a skeleton also ``<label>_skeleton`` (int32 ids; gzip), with a
+                         thickness map also ``<label>_thickness`` (float32, voxels; gzip), and
                          <results_dir>/instances/<tomo stem>_<label>.csv, one row per instance
   write_contacts         (not in the reference) <results_dir>/contacts/<tomo stem>_<label>_<other>.csv, one row per pair of an
                          instance of <label> and an instance of <other> in contact
@@ -57,14 +58,16 @@ INSTANCE_COLUMNS = ["id", "voxels", "z", "y", "x", "z0", "z1", "y0", "y1", "x0",
 
 
 def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[str, np.ndarray], labels: np.ndarray,
-                    rows: list[dict], skeleton: np.ndarray | None = None) -> Path:
+                    rows: list[dict], skeleton: np.ndarray | None = None, thickness: np.ndarray | None = None) -> Path:
     """The prediction file <results_dir>/<tomo stem>.hdf with every array of ``datasets`` (``data``, ``<label>_preds``, ...:
     gzip, dtypes as given) and ``<label>_instances`` = ``labels`` (uint16 while the largest id fits, else int32: a 128x512x512
     int32 volume would make the gzip of the writer thread the slowest stage of ``infer``), and the CSV
     <results_dir>/instances/<tomo stem>_<label>.csv of ``rows`` (``analysis.instance_rows``; floats written with ``repr``; no
     instances: header only; keys beyond ``INSTANCE_COLUMNS``, e.g. those of ``analysis.distance_rows``, become further columns in
     the rows' own order).  ``skeleton`` (the instances' centrelines, every voxel with its instance's id) is written as
-    ``<label>_skeleton`` in int32 beside ``<label>_instances``: it is nearly all zeros and gzips to little.  The file is written beside its final name and moved there, so re-writing a file from its own
+    ``<label>_skeleton`` in int32 beside ``<label>_instances``: it is nearly all zeros and gzips to little.  ``thickness``
+    (``analysis.thickness.thickness_map``: the local thickness in voxels, 0 on the background, inf without any background) is written
+    as ``<label>_thickness`` in float32 after them.  The file is written beside its final name and moved there, so re-writing a file from its own
     datasets cannot leave it half written.  Returns the .hdf path."""
     results_dir = Path(results_dir)
     out = (results_dir / tomo_name).with_suffix(".hdf")
@@ -77,6 +80,8 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
                           compression="gzip")
         if skeleton is not None:
             fh.create_dataset(f"{label_key}_skeleton", skeleton.astype(np.int32, copy=False), compression="gzip")
+        if thickness is not None:
+            fh.create_dataset(f"{label_key}_thickness", thickness.astype(np.float32, copy=False), compression="gzip")
     os.replace(tmp, out)
     csv_path = results_dir / "instances" / f"{out.stem}_{label_key}.csv"
     csv_path.parent.mkdir(parents=True, exist_ok=True)

@@ -671,6 +671,35 @@ int cvx_skeleton_cycles(int32_t* alive, const int32_t* d2, int D, int H, int W, 
                         int32_t* changed, hipStream_t stream);
 int cvx_skeleton_stats(const int32_t* alive, const int32_t* d2, int D, int H, int W, long k, int64_t* table, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Local thickness (`infer --instances --thickness`, `cryovit instances --thickness`): at every voxel the largest ball that fits
+ * inside the structure and holds the voxel (Hildebrand & Ruegsegger), as its squared radius, and the per-instance table over it.
+ * Integers only, bit-reproducible.
+ *
+ * d2 int32 [D][H][W], non-negative (in the product cvx_edt_squared(labels, CVX_EDT_I32, CVX_EDT_SITES_ZERO), but any values
+ * are taken as they are).  t2 int32 [D][H][W], another array than d2:
+ *   t2[p] = 0                                                             where d2[p] == 0,
+ *   t2[p] = max { d2[c] : d2[c] > 0 and |p - c|^2 < d2[c] } over all voxels c of the volume   elsewhere.
+ * The ball is open and c = p qualifies, so t2 >= d2.  Balls are clipped by the volume; its border is no site.  If any d2 is
+ * CVX_EDT_NONE every nonzero voxel gets CVX_EDT_NONE.  Ids play no part: after a split, pieces that share a face are measured
+ * as their union.
+ *   cvx_local_thickness_workspace_bytes  4 bytes per 4x8x64 tile of the volume plus 4; < 0 on bad extents.
+ *   cvx_local_thickness_squared          workspace: that many bytes, 4-byte aligned; its contents after the call mean nothing.
+ *   cvx_instance_thickness_stats         table int64 [k][CVX_THICKNESS_COLS], initialised by the call.  Row id - 1 over the voxels
+ *                                        with that id in 1..k whose t2 is neither 0 nor CVX_EDT_NONE: 0 voxels; 1 the sum of t2;
+ *                                        2 the sum of r_fx = floor(sqrt(t2 * 2^16)), the exact integer root; 3 min t2; 4 max t2.
+ *                                        An id without such a voxel: 0, 0, 0, -1, -1.  Sums stay below 2^31 * 2^31.
+ * Refused with an error before any launch: negative extents, an extent above 32768, D*H*W > CVX_COMPONENT_MAX_VOXELS, k < 0,
+ * null pointers, misaligned arrays (int32: 4 bytes, table: 8 bytes), a workspace shorter than
+ * cvx_local_thickness_workspace_bytes, d2 == t2.  k == 0 and an empty volume succeed.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_THICKNESS_COLS 5
+long cvx_local_thickness_workspace_bytes(int D, int H, int W);
+int cvx_local_thickness_squared(const int32_t* d2, int D, int H, int W, int32_t* t2, void* workspace, long workspace_bytes,
+                                hipStream_t stream);
+int cvx_instance_thickness_stats(const int32_t* labels, const int32_t* t2, int D, int H, int W, long k, int64_t* table,
+                                 hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
