@@ -38,6 +38,8 @@ PAIR_MAX_CAPACITY = 2**31  # CVX_PAIR_MAX_CAPACITY
 SHAPE_COLS = 24  # CVX_SHAPE_COLS
 SKELETON_COLS = 8  # CVX_SKELETON_COLS
 THICKNESS_COLS = 5  # CVX_THICKNESS_COLS
+MESH_COLS = 3  # CVX_MESH_COLS
+MESH_FACTOR_MAX = 131072  # CVX_MESH_FACTOR_MAX
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -192,6 +194,12 @@ SIGNATURES = {
     "cvx_local_thickness_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     "cvx_local_thickness_squared": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
     "cvx_instance_thickness_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
+    "cvx_mesh_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "cvx_mesh_count": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
+    "cvx_mesh_emit": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cvx_mesh_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_long, c_long, c_void_p, c_void_p]),
+    "cvx_mesh_smooth_workspace_bytes": (c_long, [c_long]),
+    "cvx_mesh_smooth_step": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_long, c_void_p]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 """Quantification of predictions after the model has run: connected instances of a predicted mask, what
 its distance maps say about them, the split of instances that touch over a neck, which instance of one label touches
 which of another, the shape of each instance (surface area, Euler number, principal axes), its centreline (length, ends, branches)
-and its local thickness (mean, spread, min, max)."""
+its local thickness (mean, spread, min, max) and the surface mesh of the mask (PLY / STL; triangles, area, volume)."""
 
 from cryovit_amd.analysis.instances import INSTANCE_COLUMNS, instance_rows, label_file, label_volume, split_volume  # noqa: F401
 from cryovit_amd.analysis.distances import (  # noqa: F401
@@ -9,3 +9,4 @@ from cryovit_amd.analysis.distances import (  # noqa: F401
 from cryovit_amd.analysis.shape import SHAPE_COLUMNS, instance_shape, shape_rows  # noqa: F401
 from cryovit_amd.analysis.skeleton import SKELETON_COLUMNS, instance_skeleton, skeleton_rows, skeleton_volume  # noqa: F401
 from cryovit_amd.analysis.thickness import THICKNESS_COLUMNS, instance_thickness, thickness_rows, thickness_volume  # noqa: F401
+from cryovit_amd.analysis.mesh import MESH_COLUMNS, instance_mesh, mesh_arrays, mesh_rows, write_mesh, write_ply, write_stl  # noqa: F401

@@ -7,7 +7,9 @@ prediction file that ``cryovit infer`` wrote earlier; ``distance_rows`` adds the
 ``label_file`` pairs the instances with those of another label (``analysis.distances.instance_pair_contacts``); ``shape`` of
 ``label_file`` adds surface area, Euler number and principal axes per instance (``analysis.shape.instance_shape``); ``skeleton`` of
 ``label_file`` thins every instance to its centreline and adds its length, ends and branches (``analysis.skeleton``); ``thickness`` of
-``label_file`` maps the local thickness and adds its mean, spread, minimum and maximum per instance (``analysis.thickness``).
+``label_file`` maps the local thickness and adds its mean, spread, minimum and maximum per instance (``analysis.thickness``); ``mesh`` of
+``label_file`` writes the surface of the labelled mask as a triangle mesh and adds its triangles, area and volume per instance
+(``analysis.mesh``).
 """
 
 from __future__ import annotations
@@ -112,7 +114,7 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
                morphology: bool = False, distance_to: str | None = None, distance_to_dir=None, contact_radius: float = 1.0,
                split_radius: float | None = None, split_min_core: int = 0, contacts_with: str | None = None,
                shape: bool = False, skeleton: bool = False, skeleton_end_radius: float = 2.0,
-               thickness: bool = False) -> Path:
+               thickness: bool = False, mesh: bool = False, mesh_smooth: int = 0, mesh_format: str = "ply") -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  ``morphology`` adds the thickness / surface / deepest-voxel
@@ -136,7 +138,10 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     the largest ball inside the structure that contains it; after a split, of the union of touching pieces), writes it as
     ``<label>_thickness`` (float32, voxels) beside ``<label>_instances`` and adds ``analysis.thickness.THICKNESS_COLUMNS`` as the last
     columns, after the skeleton columns; with ``skeleton`` the two share one distance map.  An earlier run's ``<label>_thickness``
-    is not written back either.  Returns the written file."""
+    is not written back either.  ``mesh`` writes the surface of the labelled mask as ``meshes/<stem>_<label>.<mesh_format>`` (``ply`` or
+    ``stl``) under ``result_dir`` (``analysis.mesh``: one closed, oriented triangle mesh of ``labels > 0`` with the volume's border taken
+    as background; touching pieces are meshed as their union), after ``mesh_smooth`` pairs of Taubin steps, and adds
+    ``analysis.mesh.MESH_COLUMNS`` as the last columns, after the thickness columns.  Returns the written file."""
     import torch
 
     from cryovit_amd import io
@@ -162,6 +167,10 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
         raise ValueError(f"split_min_core must be >= 0, got {split_min_core}")
     if not skeleton_end_radius >= 0:
         raise ValueError(f"skeleton_end_radius must be >= 0, got {skeleton_end_radius}")
+    if mesh_smooth < 0:
+        raise ValueError(f"mesh_smooth must be >= 0, got {mesh_smooth}")
+    if mesh_format not in ("ply", "stl"):
+        raise ValueError(f"mesh_format must be 'ply' or 'stl', got {mesh_format!r}")
     other = None
     if distance_to is not None:
         other = _other_preds(path, datasets, distance_to, distance_to_dir)
@@ -223,12 +232,19 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
         for r, e in zip(rows, skeleton_rows(line_table)):
             r.update(e)
         lines = lines.cpu().numpy()
-    if not thickness:
-        return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows, skeleton=lines)
-    from cryovit_amd.analysis.thickness import thickness_map, thickness_rows, thickness_volume
+    more = {}
+    if thickness:
+        from cryovit_amd.analysis.thickness import thickness_map, thickness_rows, thickness_volume
 
-    t2, thick_table = thickness_volume(labels, len(rows), d2)
-    for r, e in zip(rows, thickness_rows(thick_table)):
-        r.update(e)
-    return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows, skeleton=lines,
-                                   thickness=thickness_map(t2))
+        t2, thick_table = thickness_volume(labels, len(rows), d2)
+        for r, e in zip(rows, thickness_rows(thick_table)):
+            r.update(e)
+        more["thickness"] = thickness_map(t2)
+    if mesh:
+        from cryovit_amd.analysis.mesh import mesh_arrays, mesh_rows
+
+        vertices, triangles, ids, mesh_table = mesh_arrays(labels, len(rows), mesh_smooth)
+        for r, e in zip(rows, mesh_rows(mesh_table)):
+            r.update(e)
+        writers.write_mesh(result_dir, path.name, label, vertices.cpu().numpy(), triangles.cpu().numpy(), ids.cpu().numpy(), mesh_format)
+    return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows, skeleton=lines, **more)

@@ -1015,3 +1015,78 @@ def instance_thickness(labels: torch.Tensor, k: int, *, d2: torch.Tensor | None 
         d2 = edt_squared(labels, sites="zero")
     t2 = local_thickness_squared(d2)
     return t2, instance_thickness_stats(labels, t2, k)
+
+
+# ---- surface mesh (`--mesh`): marching tetrahedra on the Kuhn decomposition, the per-instance table and Taubin smoothing ----
+
+def _mesh_check(what: str, vertices, triangles, ids=None) -> tuple[torch.device, int, int]:
+    """Dtype, shape and device of a mesh's arrays: (device, V, T)."""
+    for name, t, cols in (("vertices", vertices, 3), ("triangles", triangles, 3), ("ids", ids, None)):
+        if name == "ids" and t is None:
+            continue
+        want = 1 if cols is None else 2
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != want or (cols is not None and t.shape[1] != cols):
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise _lib.CvxError(f"{what}: {name} must be int32 {'[T]' if cols is None else '[N, 3]'}, got {got}")
+    if ids is not None and ids.shape[0] != triangles.shape[0]:
+        raise _lib.CvxError(f"{what}: {ids.shape[0]} ids for {triangles.shape[0]} triangles")
+    dev = _dev_check(vertices, triangles, ids)
+    return dev, vertices.shape[0], triangles.shape[0]
+
+
+def mesh_surface(labels: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(vertices int32 [V, 3], triangles int32 [T, 3], ids int32 [T]) on the device: the closed, consistently oriented surface of
+    ``labels > 0`` (int32 [D, H, W]) by marching tetrahedra on the Kuhn decomposition, the volume taken as surrounded by background.
+    Vertices are edge midpoints in z, y, x order and units of 1/256 voxel; a triangle's id is the label of its tet's first foreground
+    corner; orders, winding and the 14-connectivity are laid down in include/cryovit_hip.h.  Integers only, bit-reproducible
+    (csrc/mesh.hip).  The host waits once, for V and T, to size the outputs; more than 2^31 - 1 of either is refused."""
+    dev, D, H, W = _split_volume_check("mesh_surface", labels=(labels, torch.int32))
+    lib = _lib.load()
+    workspace = torch.empty((int(lib.cvx_mesh_workspace_bytes(D, H, W)) + 15) // 16 * 4, dtype=torch.int32, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    call(dev, "cvx_mesh_count", lib.cvx_mesh_count, _p(labels), D, H, W, _p(workspace), workspace.numel() * 4, _p(totals))
+    V, T = totals.tolist()
+    if V >= 2**31 or T >= 2**31:
+        raise _lib.CvxError(f"mesh_surface: {V} vertices and {T} triangles do not fit int32 indices")
+    vertices = torch.empty((V, 3), dtype=torch.int32, device=dev)
+    triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    ids = torch.empty((T,), dtype=torch.int32, device=dev)
+    call(dev, "cvx_mesh_emit", lib.cvx_mesh_emit, _p(labels), D, H, W, _p(workspace), workspace.numel() * 4, V, T, _p(vertices),
+         _p(triangles), _p(ids))
+    return vertices, triangles, ids
+
+
+def mesh_stats(vertices: torch.Tensor, triangles: torch.Tensor, ids: torch.Tensor, k: int) -> torch.Tensor:
+    """int64 [k, 3] on the device.  Row id - 1 over the triangles with that id in 1..k: triangles; the sum of floor(sqrt(|n|^2)) with
+    n = (p1 - p0) x (p2 - p0) in the vertices' units (area = c1 / 2 / 65536 voxel^2); the sum of det(p0, p1, p2) modulo 2^64
+    (volume = c2 / 6 / 256^3 voxel^3).  Of whatever vertex array is passed, raw or smoothed.  Integers only, bit-reproducible; the
+    host does not wait."""
+    dev, V, T = _mesh_check("mesh_stats", vertices, triangles, ids)
+    if k < 0:
+        raise _lib.CvxError(f"mesh_stats: k must be >= 0, got {k}")
+    out = torch.empty((int(k), _lib.MESH_COLS), dtype=torch.int64, device=dev)
+    call(dev, "cvx_mesh_stats", _lib.load().cvx_mesh_stats, _p(vertices), _p(triangles), _p(ids), V, T, int(k), _p(out))
+    return out
+
+
+def mesh_smooth(vertices: torch.Tensor, triangles: torch.Tensor, iterations: int, lam: float = 0.5, mu: float = -0.53) -> torch.Tensor:
+    """int32 [V, 3]: ``vertices`` after ``iterations`` pairs of a ``lam`` step and a ``mu`` step of integer Taubin smoothing (0: a
+    copy).  One step is x' = x + floor((S - n x) c / (n 65536)) per axis in int64 with c = round(factor * 65536), S and n the sum and
+    count of a vertex's neighbours over the directed edges of ``triangles``; topology and triangle order do not change.  The sums
+    are integer atomics, so two runs give the same bytes.  The host does not wait."""
+    dev, V, T = _mesh_check("mesh_smooth", vertices, triangles)
+    if iterations < 0:
+        raise _lib.CvxError(f"mesh_smooth: iterations must be >= 0, got {iterations}")
+    cs = [int(round(f * 65536)) for f in (lam, mu)]
+    if any(abs(c) > _lib.MESH_FACTOR_MAX for c in cs):
+        raise _lib.CvxError(f"mesh_smooth: lam and mu must lie in [-2, 2], got {lam} and {mu}")
+    out = vertices.clone()
+    if iterations == 0 or V == 0:
+        return out
+    lib = _lib.load()
+    workspace = torch.empty(int(lib.cvx_mesh_smooth_workspace_bytes(V)) // 8, dtype=torch.int64, device=dev)
+    for _ in range(iterations):
+        for c in cs:
+            call(dev, "cvx_mesh_smooth_step", lib.cvx_mesh_smooth_step, _p(out), _p(out), _p(triangles), V, T, c, _p(workspace),
+                 workspace.numel() * 8)
+    return out

@@ -27,7 +27,9 @@ and the CSV, after the shape columns, the centreline's voxels, length, ends, bra
 the depth from which a line's end is kept.  ``thickness=True`` (with ``instances``) maps the local thickness of the labelled volume
 (``analysis.thickness``: at every voxel the diameter of the largest inscribed ball that contains it): the file gains
 ``<label_key>_thickness`` (float32, voxels) and the CSV, as its last columns, the mean, spread, minimum and maximum per instance; with
-``skeleton`` the two share one distance map.
+``skeleton`` the two share one distance map.  ``mesh=True`` (with ``instances``) builds the surface mesh of the labelled mask on the
+device (``analysis.mesh``), after ``mesh_smooth`` pairs of Taubin steps: ``meshes/<tomo stem>_<label_key>.<mesh_format>`` is written on
+the writer thread and the CSV gains the triangles, area and volume per instance as its last columns.
 """
 
 from __future__ import annotations
@@ -42,6 +44,7 @@ import torch
 from cryovit_amd import io
 from cryovit_amd.analysis.distances import edt_squared
 from cryovit_amd.analysis.instances import component_rows, distance_rows, instance_rows, label_volume, split_volume
+from cryovit_amd.analysis.mesh import mesh_arrays, mesh_rows
 from cryovit_amd.analysis.shape import instance_shape
 from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
 from cryovit_amd.analysis.thickness import thickness_map, thickness_rows, thickness_volume
@@ -84,8 +87,12 @@ def _predict_file(model, dataset, idx: int, threshold: float, encoder, batch_siz
     return item.aux_data["data"], mask
 
 
-def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, extra, skeleton=None, thickness=None) -> Path:
-    """``writers.write_segmentation`` plus the instance volume and CSV (writer thread)."""
+def _write_with_instances(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, extra, skeleton=None, thickness=None,
+                          mesh=None) -> Path:
+    """``writers.write_segmentation`` plus the instance volume and CSV (writer thread); ``mesh``: (vertices, triangles, ids, format)
+    of the surface, written as ``meshes/<tomo stem>_<label>.<format>``."""
+    if mesh is not None:
+        writers.write_mesh(result_dir, tomo_name, label_key, *mesh)  # the conversion to float32 voxels is done on the writer thread
     datasets = {"data": raw.astype(np.float32), f"{label_key}_preds": segs.astype(np.uint8, copy=False)}
     rows = instance_rows(table)
     for r, e in zip(rows, extra):
@@ -100,7 +107,8 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                   batch_size: int = 128, device: str | None = None, instances: bool = False, min_size: int = 0,
                   connectivity: int = 26, morphology: bool = False, split_radius: float | None = None,
                   split_min_core: int = 0, shape: bool = False, skeleton: bool = False,
-                  skeleton_end_radius: float = 2.0, thickness: bool = False) -> list[Path]:
+                  skeleton_end_radius: float = 2.0, thickness: bool = False, mesh: bool = False, mesh_smooth: int = 0,
+                  mesh_format: str = "ply") -> list[Path]:
     if connectivity not in (6, 26):
         raise ValueError(f"connectivity must be 6 or 26, got {connectivity}")
     if min_size < 0:
@@ -113,6 +121,12 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
         raise ValueError("skeleton=True needs instances=True: the centrelines are those of the labelled instances")
     if thickness and not instances:
         raise ValueError("thickness=True needs instances=True: the map is that of the labelled instances")
+    if mesh and not instances:
+        raise ValueError("mesh=True needs instances=True: the surface is that of the labelled instances")
+    if mesh_smooth < 0:
+        raise ValueError(f"mesh_smooth must be >= 0, got {mesh_smooth}")
+    if mesh_format not in ("ply", "stl"):
+        raise ValueError(f"mesh_format must be 'ply' or 'stl', got {mesh_format!r}")
     if not skeleton_end_radius >= 0:
         raise ValueError(f"skeleton_end_radius must be >= 0, got {skeleton_end_radius}")
     if split_radius is not None and not instances:
@@ -159,7 +173,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 if shape:
                     for e, s in zip(extra, instance_shape(labels, table.shape[0], connectivity)):
                         e.update(s)
-                host_lines, host_t2, d2 = None, None, None
+                host_lines, host_t2, host_mesh, d2 = None, None, None, None
                 if skeleton and thickness:  # one distance map for both
                     d2 = edt_squared(labels)
                 if skeleton:
@@ -174,12 +188,20 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                     host_t2.copy_(t2, non_blocking=True)
                     for e, s in zip(extra, thickness_rows(thick_table)):
                         e.update(s)
+                if mesh:
+                    *arrays, mesh_table = mesh_arrays(labels, table.shape[0], mesh_smooth)
+                    host_mesh = [torch.empty(a.shape, dtype=torch.int32, pin_memory=True) for a in arrays]
+                    for h, a in zip(host_mesh, arrays):
+                        h.copy_(a, non_blocking=True)
+                    for e, s in zip(extra, mesh_rows(mesh_table)):
+                        e.update(s)
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:
                 pending.append((i, writer.submit(_write_with_instances, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),
                                                  host_labels.numpy(), host_table.numpy(), extra,
                                                  None if host_lines is None else host_lines.numpy(),
-                                                 None if host_t2 is None else host_t2.numpy())))
+                                                 None if host_t2 is None else host_t2.numpy(),
+                                                 None if host_mesh is None else (*(h.numpy() for h in host_mesh), mesh_format))))
             else:
                 pending.append((i, writer.submit(writers.write_segmentation, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy())))
             while len(pending) > 2:

@@ -9,7 +9,8 @@
                          instances, int32 beyond; gzip), with a skeleton also ``<label>_skeleton`` (int32 ids; gzip), with a
                          thickness map also ``<label>_thickness`` (float32, voxels; gzip), and
                          <results_dir>/instances/<tomo stem>_<label>.csv, one row per instance
-  write_contacts         (not in the reference) <results_dir>/contacts/<tomo stem>_<label>_<other>.csv, one row per pair of an
+  write_mesh             (not in the reference) <results_dir>/meshes/<tomo stem>_<label>.ply or .stl, the surface of the labelled mask
+  write_contacts        (not in the reference) <results_dir>/contacts/<tomo stem>_<label>_<other>.csv, one row per pair of an
                          instance of <label> and an instance of <other> in contact
   update_metrics_csv     CsvWriter l.112-206:           <results_dir>/<sample>[_<split>].csv, columns sample, tomo_name,
                          <metrics...>[, split_id]; an existing row for the same tomogram is replaced
@@ -92,6 +93,16 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
         for r in rows:
             w.writerow({k: repr(v) if isinstance(v, float) else v for k, v in r.items()})
     return out
+
+
+def write_mesh(results_dir, tomo_name: str, label_key: str, vertices: np.ndarray, triangles: np.ndarray, ids: np.ndarray,
+               fmt: str = "ply") -> Path:
+    """The surface mesh <results_dir>/meshes/<tomo stem>_<label>.<fmt> (``analysis.mesh.write_ply`` / ``write_stl``: binary PLY with
+    shared vertices and an ``instance`` per face, or binary STL with the id in the attribute word) of the arrays of
+    ``engine.ops.mesh_surface`` on the host.  Written beside its final name and moved there.  Returns its path."""
+    from cryovit_amd.analysis.mesh import write_mesh as write
+
+    return write(Path(results_dir) / "meshes" / f"{Path(tomo_name).stem}_{label_key}.{fmt}", vertices, triangles, ids, fmt)
 
 
 PAIR_COLUMNS = ["id", "other_id", "contact_voxels", "gap_d2", "gap", "at_z", "at_y", "at_x"]

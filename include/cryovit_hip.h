@@ -700,6 +700,57 @@ int cvx_local_thickness_squared(const int32_t* d2, int D, int H, int W, int32_t*
 int cvx_instance_thickness_stats(const int32_t* labels, const int32_t* t2, int D, int H, int W, long k, int64_t* table,
                                  hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Surface mesh (`infer --instances --mesh`, `cryovit instances --mesh`): one watertight, consistently oriented, indexed triangle
+ * mesh of the mask labels > 0, by marching tetrahedra on the Kuhn decomposition; per-instance triangles, area and volume; integer
+ * Taubin smoothing.  Integers only, bit-reproducible.
+ *
+ * Lattice.  The volume is treated as surrounded by one layer of background, so every surface closes (unlike cvx_edt_squared, where
+ *   the border is no site).  A cell is the cube between 8 neighbouring voxel centres of the padded lattice: (D+1)(H+1)(W+1) cells,
+ *   raster order z, y, x.  Each cell is cut into the 6 Kuhn tetrahedra: the paths from its corner (0,0,0) to (1,1,1) that add the
+ *   three unit steps in the axis orders (z,y,x), (z,x,y), (y,z,x), (y,x,z), (x,z,y), (x,y,z) = tet 0..5.  Neighbouring cells agree on
+ *   their common face, so there is no ambiguous case.  The connectivity this implies is 14 for foreground and background alike: the
+ *   6 face neighbours, the face diagonals (0,1,1), (1,0,1), (1,1,0) and the body diagonal (1,1,1), each with its opposite.
+ * Vertices.  One at the midpoint of every lattice edge of the decomposition whose ends differ in labels > 0; the edge types of a
+ *   lower end are 0..6 = the offsets z, y, x, zy, zx, yx, zyx.  int32 [V][3] in z, y, x order, in units of 1/256 voxel: (a + b) * 128
+ *   for the ends a, b in unpadded voxel coordinates (so -128 occurs).  Ordered by (raster index of the lower end, edge type).
+ * Triangles.  int32 [T][3], ordered by (cell, tet, triangle 0 / 1).  A tet with 1 or 3 foreground corners gives one triangle: the
+ *   edges from the single corner to the others (or from the others to it) in the order of the path.  A tet with foreground corners
+ *   a < b and background corners c < d (positions along the path) gives the quad (ac, ad, bd, bc) as (ac, ad, bd) and (ac, bd, bc).
+ *   Where the normal (p1 - p0) x (p2 - p0) of a triangle so listed does not point from foreground to background, p1 and p2 are
+ *   exchanged.  ids int32 [T]: the label of the tet's first foreground corner along the path; ids otherwise play no part, so
+ *   instances that share a face are meshed as their union and the plane between them carries no triangle.
+ *
+ *   cvx_mesh_workspace_bytes   8 bytes per 64 cells of a cell row (two int32 per row segment: 0.125 bytes per voxel) + 16; < 0 on
+ *                              bad extents.
+ *   cvx_mesh_count             totals int64 [2] in device memory = V, T; the workspace (16-byte aligned) keeps what cvx_mesh_emit needs.
+ *   cvx_mesh_emit              the same labels and workspace, after cvx_mesh_count on the same stream; vertices [V][3], triangles [T][3],
+ *                              ids [T] of exactly the counted sizes (with other V, T nothing is written).
+ *   cvx_mesh_stats             table int64 [k][CVX_MESH_COLS], initialised by the call, row id - 1 over the triangles with that id in
+ *                              1..k, of whatever vertex array is passed (coordinates within +-2^24): 0 triangles; 1 the sum of
+ *                              floor(sqrt(|n|^2)), n = (p1 - p0) x (p2 - p0) (area = c1 / 2 / 65536 voxel^2); 2 the sum of
+ *                              det(p0, p1, p2) modulo 2^64 (volume = c2 / 6 / 256^3 voxel^3, meaningful for an instance whose shell its
+ *                              own triangles close).  A triangle with an index outside [0, V) is ignored.
+ *   cvx_mesh_smooth_step       moved = x + floor((S - n x) c / (n 65536)) per vertex and axis in int64, S and n the sum and count of
+ *                              the b of every directed edge a -> b (a triangle (a, b, c) gives a -> b, b -> c, c -> a; on a closed
+ *                              oriented manifold that is every neighbour once); c = factor * 65536, |c| <= CVX_MESH_FACTOR_MAX; a
+ *                              vertex without a neighbour stays; moved may be vertices.  Workspace: cvx_mesh_smooth_workspace_bytes
+ *                              (32 bytes per vertex), 8-byte aligned.
+ * Refused with an error before any launch: negative extents, an extent above 32768, D*H*W > CVX_COMPONENT_MAX_VOXELS, k < 0,
+ * V or T negative or >= 2^31, null pointers, misaligned arrays, a short workspace.  An empty volume (V = T = 0) and k == 0 succeed.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_MESH_COLS 3
+#define CVX_MESH_FACTOR_MAX 131072
+long cvx_mesh_workspace_bytes(int D, int H, int W);
+int cvx_mesh_count(const int32_t* labels, int D, int H, int W, void* workspace, long workspace_bytes, int64_t* totals, hipStream_t stream);
+int cvx_mesh_emit(const int32_t* labels, int D, int H, int W, const void* workspace, long workspace_bytes, long V, long T,
+                  int32_t* vertices, int32_t* triangles, int32_t* ids, hipStream_t stream);
+int cvx_mesh_stats(const int32_t* vertices, const int32_t* triangles, const int32_t* ids, long V, long T, long k, int64_t* table,
+                   hipStream_t stream);
+long cvx_mesh_smooth_workspace_bytes(long V);
+int cvx_mesh_smooth_step(const int32_t* vertices, int32_t* moved, const int32_t* triangles, long V, long T, int c, void* workspace,
+                         long workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
