@@ -3,7 +3,8 @@ its distance maps say about them, the split of instances that touch over a neck,
 which of another, the shape of each instance (surface area, Euler number, principal axes), its centreline (length, ends, branches)
 its local thickness (mean, spread, min, max) and the surface mesh of the mask (PLY / STL; triangles, area, volume)."""
 
-from cryovit_amd.analysis.instances import INSTANCE_COLUMNS, instance_rows, label_file, label_volume, split_volume  # noqa: F401
+from cryovit_amd.analysis.instances import (  # noqa: F401
+    INSTANCE_COLUMNS, InstanceOptions, instance_rows, label_and_split, label_file, label_volume, measure, split_volume)
 from cryovit_amd.analysis.distances import (  # noqa: F401
     PAIR_COLUMNS, edt_squared, instance_contacts, instance_morphology, instance_pair_contacts, pair_rows, partner_rows)
 from cryovit_amd.analysis.shape import SHAPE_COLUMNS, instance_shape, shape_rows  # noqa: F401

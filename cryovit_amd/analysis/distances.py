@@ -14,6 +14,8 @@ from __future__ import annotations
 
 import math
 
+from cryovit_amd.analysis._tables import host_table
+
 MORPHOLOGY_COLUMNS = ["surface_voxels", "inscribed_d2", "inscribed_radius", "deep_z", "deep_y", "deep_x"]
 PAIR_COLUMNS = ["id", "other_id", "contact_voxels", "gap_d2", "gap", "at_z", "at_y", "at_x"]
 
@@ -37,7 +39,7 @@ def morphology_rows(stats, shape) -> list[dict]:
     0, -1, -1.0, -1, -1, -1."""
     _, H, W = shape
     rows = []
-    for count, _, hi, idx in _host(stats).tolist():
+    for count, _, hi, idx in host_table(stats, 4).tolist():
         if hi < 0:
             rows.append(dict(zip(MORPHOLOGY_COLUMNS, (0, -1, -1.0, -1, -1, -1))))
         else:
@@ -50,17 +52,9 @@ def contact_rows(stats, name: str) -> list[dict]:
     ``gap_d2_<name>`` = min d2, ``gap_<name>`` = its root in float64 (0 where the two overlap) and ``contact_voxels_<name>`` = the
     instance's voxels within the radius.  An empty other mask gives -1, -1.0, 0."""
     rows = []
-    for count, lo, _, _ in _host(stats).tolist():
+    for count, lo, _, _ in host_table(stats, 4).tolist():
         rows.append(dict(zip(contact_columns(name), (lo, math.sqrt(lo), count) if lo >= 0 else (-1, -1.0, 0))))
     return rows
-
-
-def _host(stats):
-    import numpy as np
-
-    if hasattr(stats, "detach"):
-        stats = stats.detach().cpu().numpy()
-    return np.asarray(stats, dtype=np.int64).reshape(-1, 4)
 
 
 def instance_morphology(labels, k: int) -> list[dict]:
@@ -94,13 +88,9 @@ def pair_rows(table, shape) -> list[dict]:
     """Rows (``PAIR_COLUMNS``) from the int64 [P, 5] pair table ``a, b, contact_voxels, gap_d2, at`` of volumes of ``shape``:
     ``id`` = a, ``other_id`` = b, ``gap`` = the root of ``gap_d2`` in float64 (0 where the two overlap) and ``at_z, at_y, at_x`` =
     the first voxel of a in raster order that lies at that gap from b."""
-    import numpy as np
-
     _, H, W = shape
-    if hasattr(table, "detach"):
-        table = table.detach().cpu().numpy()
     rows = []
-    for a, b, count, d2, at in np.asarray(table, dtype=np.int64).reshape(-1, 5).tolist():
+    for a, b, count, d2, at in host_table(table, 5).tolist():
         rows.append(dict(zip(PAIR_COLUMNS, (a, b, count, d2, math.sqrt(d2), at // (H * W), at // W % H, at % W))))
     return rows
 

@@ -1,35 +1,131 @@
-"""Connected instances (organelles) of a binary prediction: how many there are, how large each is and where it lies.
+"""Connected instances (organelles) of a binary prediction: how many there are, how large each is and where it lies, and
+the one pipeline that measures them for both ``cryovit infer --instances`` and ``cryovit instances``.
 
-``label_volume`` labels a mask that is already on the device (``engine.ops.label_components``: HIP union-find, exact and
-bit-reproducible); ``instance_rows`` turns the integer table into the rows people read; ``label_file`` does both for a
-prediction file that ``cryovit infer`` wrote earlier; ``distance_rows`` adds the columns that need a distance map;
-``split_volume`` cuts instances that touch over a neck into pieces (``engine.ops.split_instances``); ``contacts_with`` of
-``label_file`` pairs the instances with those of another label (``analysis.distances.instance_pair_contacts``); ``shape`` of
-``label_file`` adds surface area, Euler number and principal axes per instance (``analysis.shape.instance_shape``); ``skeleton`` of
-``label_file`` thins every instance to its centreline and adds its length, ends and branches (``analysis.skeleton``); ``thickness`` of
-``label_file`` maps the local thickness and adds its mean, spread, minimum and maximum per instance (``analysis.thickness``); ``mesh`` of
-``label_file`` writes the surface of the labelled mask as a triangle mesh and adds its triangles, area and volume per instance
-(``analysis.mesh``).
+``InstanceOptions`` says what every option computes and writes.  ``label_and_split`` labels a mask that is on the device
+(``label_volume``: ``engine.ops.label_components``, HIP union-find, exact and bit-reproducible) and splits touching instances at
+their necks (``split_volume``); ``measure`` adds everything the options ask for, in one column order; ``run.writers.write_measured``
+writes the result.  ``label_file`` runs the three on a prediction file that ``cryovit infer`` wrote earlier, ``run_inference`` on the
+mask while it is still in HBM.  ``instance_rows`` turns the integer table into the rows people read.
 """
 
 from __future__ import annotations
 
 import logging
+from dataclasses import dataclass, field, replace
 from pathlib import Path
+from typing import Any, Callable, ClassVar
 
 import numpy as np
 
+from cryovit_amd.analysis import distances
+from cryovit_amd.analysis._tables import host_table
+from cryovit_amd.analysis.mesh import MESH_FORMATS, mesh_arrays, mesh_rows
+from cryovit_amd.analysis.shape import instance_shape
+from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
+from cryovit_amd.analysis.thickness import thickness_rows, thickness_volume
+
 INSTANCE_COLUMNS = ["id", "voxels", "z", "y", "x", "z0", "z1", "y0", "y1", "x0", "x1"]
+
+
+@dataclass(frozen=True)
+class InstanceOptions:
+    """What is measured of the instances of one label, for ``label_file`` and ``run_inference(instances=True)`` alike.  Every
+    measurement adds its columns to ``instances/<tomo stem>_<label>.csv`` after ``INSTANCE_COLUMNS``, in the order of this list;
+    all lengths are in voxels.
+
+    ``connectivity``  6 (faces) or 26 (faces, edges and corners): what counts as one instance, and the Euler number of ``shape``.
+    ``min_size``      instances of fewer voxels become background before the numbering; ``<label>_preds`` stays unfiltered.
+    ``split_radius``  split instances that touch over a neck before anything is measured (``split_volume``): cores deeper than this
+                      many voxels, of at least ``split_min_core`` voxels each, are grown back inside their instance.  The volume, the
+                      rows and every later column are then those of the pieces, and the first extra column is ``component``, the
+                      id a piece had before.
+    ``morphology``    ``analysis.distances.MORPHOLOGY_COLUMNS``: surface voxels, inscribed radius and deepest voxel, from an exact
+                      distance map of the labels (its own: it is not the one ``skeleton`` and ``thickness`` share).
+    ``contact_radius``  of ``label_file`` alone: voxels within this distance of the other label count as contact, for ``distance_to``
+                      (the gap and contact columns ``analysis.distances.contact_columns``) and ``contacts_with``
+                      (``partners_<name>``, and ``contacts/<tomo stem>_<label>_<name>.csv`` with ``analysis.distances.PAIR_COLUMNS``).
+    ``shape``         ``analysis.shape.SHAPE_COLUMNS``: surface area, sphericity, Euler number, principal axes and direction.
+    ``skeleton``      thin every instance (piece) to its centreline (``analysis.skeleton``; a line's end is kept from
+                      ``skeleton_end_radius`` voxels of depth on): the dataset ``<label>_skeleton`` (int32, every voxel with its
+                      instance's id) beside ``<label>_instances``, and ``analysis.skeleton.SKELETON_COLUMNS``.
+    ``thickness``     the local thickness of the labelled volume (``analysis.thickness``: at every voxel the diameter of the largest
+                      ball inside the structure that contains it; after a split, of the union of touching pieces): the dataset
+                      ``<label>_thickness`` (float32) and ``analysis.thickness.THICKNESS_COLUMNS``.  With ``skeleton`` the two share
+                      one distance map; alone, each computes its own.
+    ``mesh``          the surface of the labelled mask as one closed, oriented triangle mesh (``analysis.mesh``: ``labels > 0`` with the
+                      volume's border taken as background; touching pieces are meshed as their union), after ``mesh_smooth`` pairs of
+                      Taubin steps: ``meshes/<tomo stem>_<label>.<mesh_format>`` (``ply`` or ``stl``) and ``analysis.mesh.MESH_COLUMNS``.
+
+    ``<label>_instances``, ``<label>_skeleton`` and ``<label>_thickness`` of an earlier run are never written back: they belong to
+    that run's labelling."""
+
+    connectivity: int = 26
+    min_size: int = 0
+    morphology: bool = False
+    split_radius: float | None = None
+    split_min_core: int = 0
+    shape: bool = False
+    skeleton: bool = False
+    skeleton_end_radius: float = 2.0
+    thickness: bool = False
+    mesh: bool = False
+    mesh_smooth: int = 0
+    mesh_format: str = "ply"
+    contact_radius: float = 1.0
+
+    MEASUREMENTS: ClassVar[tuple[str, ...]] = ("morphology", "shape", "skeleton", "thickness", "mesh")  # the on / off fields
+
+    def validate(self) -> "InstanceOptions":
+        """Raises ``ValueError`` for the first value out of range; returns the record."""
+        if self.connectivity not in (6, 26):
+            raise ValueError(f"connectivity must be 6 or 26, got {self.connectivity}")
+        if self.min_size < 0:
+            raise ValueError(f"min_size must be >= 0, got {self.min_size}")
+        if not self.contact_radius >= 0:
+            raise ValueError(f"contact_radius must be >= 0, got {self.contact_radius}")
+        if self.split_radius is not None and not self.split_radius >= 0:
+            raise ValueError(f"split_radius must be >= 0, got {self.split_radius}")
+        if self.split_min_core < 0:
+            raise ValueError(f"split_min_core must be >= 0, got {self.split_min_core}")
+        if not self.skeleton_end_radius >= 0:
+            raise ValueError(f"skeleton_end_radius must be >= 0, got {self.skeleton_end_radius}")
+        if self.mesh_smooth < 0:
+            raise ValueError(f"mesh_smooth must be >= 0, got {self.mesh_smooth}")
+        if self.mesh_format not in MESH_FORMATS:
+            raise ValueError(f"mesh_format must be 'ply' or 'stl', got {self.mesh_format!r}")
+        return self
+
+
+@dataclass
+class Measured:
+    """What ``measure`` found, on the device, or after ``arrays(fn)`` wherever ``fn`` puts it: ``extra``, per instance the columns
+    beyond ``INSTANCE_COLUMNS`` in their CSV order; ``pairs``, the rows of the pair-contact CSV (``contacts_with``); ``skeleton``
+    (int32 [D, H, W]); ``t2`` (int32 [D, H, W], the squared local radius: ``analysis.thickness.thickness_map`` takes the root);
+    ``mesh`` = (vertices, triangles, ids), int32."""
+
+    extra: list[dict] = field(default_factory=list)
+    pairs: list[dict] | None = None
+    skeleton: Any = None
+    t2: Any = None
+    mesh: tuple | None = None
+
+    def arrays(self, fn: Callable) -> "Measured":
+        """This record with ``fn`` applied to every volume and mesh array it holds."""
+        return replace(self, skeleton=None if self.skeleton is None else fn(self.skeleton), t2=None if self.t2 is None else fn(self.t2),
+                       mesh=None if self.mesh is None else tuple(fn(a) for a in self.mesh))
+
+
+def merge_columns(rows: list[dict], more: list[dict]) -> None:
+    """Every dict of ``more`` appended to the row of the same instance: its keys become that row's next columns."""
+    for r, m in zip(rows, more):
+        r.update(m)
 
 
 def instance_rows(table) -> list[dict]:
     """One dict per row of the int64 [K, 10] table (voxels, sum_z, sum_y, sum_x, z0, z1, y0, y1, x0, x1; a host array or a
     tensor): ``id`` 1..K, ``voxels``, the centroid ``z, y, x`` = sum / voxels in float64, and the inclusive bounding box."""
-    if hasattr(table, "detach"):
-        table = table.detach().cpu().numpy()
-    t = np.asarray(table, dtype=np.int64).reshape(-1, 10)
     rows = []
-    for i, (n, sz, sy, sx, z0, z1, y0, y1, x0, x1) in enumerate(t.tolist()):
+    for i, (n, sz, sy, sx, z0, z1, y0, y1, x0, x1) in enumerate(host_table(table, 10).tolist()):
         rows.append({"id": i + 1, "voxels": n, "z": sz / n, "y": sy / n, "x": sx / n,
                      "z0": z0, "z1": z1, "y0": y0, "y1": y1, "x0": x0, "x1": x1})
     return rows
@@ -52,26 +148,51 @@ def split_volume(labels, k: int, *, radius: float, min_core: int = 0, connectivi
 
 
 def component_rows(component, extra: list[dict]) -> list[dict]:
-    """``extra`` (``distance_rows``) with the key ``component`` in front: the CSV column right after the standard ones."""
-    if hasattr(component, "detach"):
-        component = component.detach().cpu().numpy()
-    return [{"component": c, **e} for c, e in zip(np.asarray(component, dtype=np.int64).tolist(), extra)]
+    """``extra`` with the key ``component`` in front: the CSV column right after the standard ones."""
+    return [{"component": c, **e} for c, e in zip(host_table(component, 0).tolist(), extra)]
 
 
-def distance_rows(labels, k: int, *, morphology: bool = False, other_mask=None, other_name: str = "other",
-                  contact_radius: float = 1.0) -> list[dict]:
-    """The extra CSV columns of the instances 1..k of the int32 device volume ``labels`` (``analysis.distances``): the
-    morphology columns, then the contact columns against ``other_mask`` when one is given.  No option: k empty dicts."""
-    from cryovit_amd.analysis import distances
+def label_and_split(mask, opts: InstanceOptions):
+    """(labels, table, component or None) of a uint8 device mask: ``label_volume``, then ``split_volume`` where ``opts.split_radius``
+    is set.  All on the device."""
+    labels, table = label_volume(mask, connectivity=opts.connectivity, min_size=opts.min_size)
+    if opts.split_radius is None:
+        return labels, table, None
+    return split_volume(labels, int(table.shape[0]), radius=opts.split_radius, min_core=opts.split_min_core, connectivity=opts.connectivity)
 
-    extra = [{} for _ in range(k)]
-    if morphology:
-        for e, m in zip(extra, distances.instance_morphology(labels, k)):
-            e.update(m)
+
+def measure(labels, k: int, component, opts: InstanceOptions, *, other_mask=None, other_name: str | None = None,
+            partner: Callable | None = None, partner_name: str | None = None) -> Measured:
+    """Everything ``opts`` asks for of the instances 1..k of the int32 device volume ``labels`` (``component``: that of
+    ``label_and_split``), in the order of the CSV columns.  ``other_mask``: the uint8 device mask of the label ``other_name``, for the
+    gap and contact columns.  ``partner``: called when its turn comes, returns (int32 device volume, count) of the instances of the
+    label ``partner_name``, for the pair contacts."""
+    out = Measured(extra=[{} for _ in range(k)])
+    if component is not None:
+        out.extra = component_rows(component, out.extra)
+    if opts.morphology:
+        merge_columns(out.extra, distances.instance_morphology(labels, k))
     if other_mask is not None:
-        for e, c in zip(extra, distances.instance_contacts(labels, k, other_mask, contact_radius, other_name)):
-            e.update(c)
-    return extra
+        merge_columns(out.extra, distances.instance_contacts(labels, k, other_mask, opts.contact_radius, other_name))
+    if partner is not None:
+        partner_labels, partner_k = partner()
+        out.pairs = distances.instance_pair_contacts(labels, k, partner_labels, partner_k, opts.contact_radius)
+        merge_columns(out.extra, distances.partner_rows(out.pairs, k, partner_name))
+    if opts.shape:
+        merge_columns(out.extra, instance_shape(labels, k, opts.connectivity))
+    # one distance map for both; either alone computes its own, and so does morphology
+    d2 = distances.edt_squared(labels) if opts.skeleton and opts.thickness else None
+    if opts.skeleton:
+        out.skeleton, line_table = skeleton_volume(labels, k, opts.skeleton_end_radius, d2)
+        merge_columns(out.extra, skeleton_rows(line_table))
+    if opts.thickness:
+        out.t2, thick_table = thickness_volume(labels, k, d2)
+        merge_columns(out.extra, thickness_rows(thick_table))
+    if opts.mesh:
+        vertices, triangles, ids, mesh_table = mesh_arrays(labels, k, opts.mesh_smooth)
+        out.mesh = (vertices, triangles, ids)
+        merge_columns(out.extra, mesh_rows(mesh_table))
+    return out
 
 
 def _other_preds(path: Path, datasets: dict, name: str, distance_to_dir):
@@ -117,31 +238,12 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
                thickness: bool = False, mesh: bool = False, mesh_smooth: int = 0, mesh_format: str = "ply") -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
-    ``result_dir`` (default: the file's folder, i.e. in place).  ``morphology`` adds the thickness / surface / deepest-voxel
-    columns, ``distance_to`` the gap and contact columns against ``<distance_to>_preds`` (of the same file, else of
-    ``distance_to_dir/<same stem>.hdf``) within ``contact_radius`` voxels.  ``split_radius`` splits the labelled instances at
-    their necks first (``split_volume``, cores of at least ``split_min_core`` voxels): the volume, the rows and the distance
-    columns are then those of the pieces, and every row carries ``component``, the id the piece had before.
-    ``contacts_with`` names another label whose instances (``<contacts_with>_instances`` of the same file, else of
-    ``distance_to_dir/<same stem>.hdf``: the ids of that label's own CSV; failing both, ``<contacts_with>_preds`` labelled afresh
-    under ``connectivity`` with no ``min_size``) are paired with this label's: ``contacts/<stem>_<label>_<contacts_with>.csv``
-    under ``result_dir`` gets one row per pair of an instance and the other instance nearest to some of its voxels within
-    ``contact_radius`` voxels (``analysis.distances.PAIR_COLUMNS``), and every instance row gains ``partners_<contacts_with>``,
-    the number of such partners, after the ``distance_to`` columns.  ``shape`` adds ``analysis.shape.SHAPE_COLUMNS`` (surface area,
-    sphericity, Euler number under ``connectivity``, principal axes and direction; of the pieces after a split) as the last
-    columns of every row.  ``skeleton`` thins every instance (after a split: every piece) to its centreline
-    (``analysis.skeleton.skeleton_volume``; a line's end is kept from ``skeleton_end_radius`` voxels of depth on), writes it as
-    ``<label>_skeleton`` (int32, every voxel with its instance's id) beside ``<label>_instances`` and adds
-    ``analysis.skeleton.SKELETON_COLUMNS`` after the shape columns.  Like ``<label>_instances``, a ``<label>_skeleton`` that an
-    earlier run left in the file is not written back, with or without ``skeleton``: it would carry the ids of that run's
-    labelling.  ``thickness`` maps the local thickness of the labelled volume (``analysis.thickness``: at every voxel the diameter of
-    the largest ball inside the structure that contains it; after a split, of the union of touching pieces), writes it as
-    ``<label>_thickness`` (float32, voxels) beside ``<label>_instances`` and adds ``analysis.thickness.THICKNESS_COLUMNS`` as the last
-    columns, after the skeleton columns; with ``skeleton`` the two share one distance map.  An earlier run's ``<label>_thickness``
-    is not written back either.  ``mesh`` writes the surface of the labelled mask as ``meshes/<stem>_<label>.<mesh_format>`` (``ply`` or
-    ``stl``) under ``result_dir`` (``analysis.mesh``: one closed, oriented triangle mesh of ``labels > 0`` with the volume's border taken
-    as background; touching pieces are meshed as their union), after ``mesh_smooth`` pairs of Taubin steps, and adds
-    ``analysis.mesh.MESH_COLUMNS`` as the last columns, after the thickness columns.  Returns the written file."""
+    ``result_dir`` (default: the file's folder, i.e. in place).  The measurements are those of ``InstanceOptions``.
+    ``distance_to`` names another label whose mask (``<distance_to>_preds`` of the same file, else of
+    ``distance_to_dir/<same stem>.hdf``) the gap and contact columns are taken against.  ``contacts_with`` names another label
+    whose instances are paired with this label's: ``<contacts_with>_instances`` of the same file, else of
+    ``distance_to_dir/<same stem>.hdf`` (the ids of that label's own CSV); failing both, ``<contacts_with>_preds`` labelled afresh
+    under ``connectivity`` with no ``min_size``.  Returns the written file."""
     import torch
 
     from cryovit_amd import io
@@ -153,24 +255,15 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     datasets = io.read_all_flat(path)
     if key not in datasets:
         raise KeyError(f"{path} holds no '{key}' dataset (found {sorted(datasets)})")
-    datasets.pop(f"{label}_instances", None)  # an earlier run's result is replaced
-    datasets.pop(f"{label}_skeleton", None)  # and so is its skeleton, whose ids would be stale, whether or not a new one is made
-    datasets.pop(f"{label}_thickness", None)  # the thickness map belongs to the mask as that run filtered and labelled it
+    for stale in ("instances", "skeleton", "thickness"):  # an earlier run's results carry that run's ids and filtering
+        datasets.pop(f"{label}_{stale}", None)
     preds = datasets[key]
     if preds.ndim != 3:
         raise ValueError(f"'{key}' of {path} must be a [D, H, W] volume, got shape {preds.shape}")
-    if not contact_radius >= 0:
-        raise ValueError(f"contact_radius must be >= 0, got {contact_radius}")
-    if split_radius is not None and not split_radius >= 0:
-        raise ValueError(f"split_radius must be >= 0, got {split_radius}")
-    if split_min_core < 0:
-        raise ValueError(f"split_min_core must be >= 0, got {split_min_core}")
-    if not skeleton_end_radius >= 0:
-        raise ValueError(f"skeleton_end_radius must be >= 0, got {skeleton_end_radius}")
-    if mesh_smooth < 0:
-        raise ValueError(f"mesh_smooth must be >= 0, got {mesh_smooth}")
-    if mesh_format not in ("ply", "stl"):
-        raise ValueError(f"mesh_format must be 'ply' or 'stl', got {mesh_format!r}")
+    opts = InstanceOptions(connectivity=connectivity, min_size=min_size, morphology=morphology, split_radius=split_radius,
+                           split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
+                           thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format,
+                           contact_radius=contact_radius).validate()
     other = None
     if distance_to is not None:
         other = _other_preds(path, datasets, distance_to, distance_to_dir)
@@ -185,66 +278,23 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
             raise ValueError(f"'{contacts_with}_{'preds' if fresh else 'instances'}' has shape {partner.shape}, '{key}' of {path} has "
                              f"{preds.shape}")
     device = select_device(device)
-    mask = torch.from_numpy(np.ascontiguousarray(preds != 0).view(np.uint8)).to(device)
-    labels, table = label_volume(mask, connectivity=connectivity, min_size=min_size)
-    component = None
-    if split_radius is not None:
-        labels, table, component = split_volume(labels, int(table.shape[0]), radius=split_radius, min_core=split_min_core,
-                                                connectivity=connectivity)
-    rows = instance_rows(table)
-    if morphology or other is not None or component is not None:
-        other_mask = None if other is None else torch.from_numpy(np.ascontiguousarray(other != 0).view(np.uint8)).to(device)
-        extra = distance_rows(labels, len(rows), morphology=morphology, other_mask=other_mask, other_name=distance_to or "other",
-                              contact_radius=contact_radius)
-        for r, e in zip(rows, extra if component is None else component_rows(component, extra)):
-            r.update(e)
+
+    def on_device(mask):
+        return torch.from_numpy(np.ascontiguousarray(mask != 0).view(np.uint8)).to(device)
+
+    def partner_instances():
+        if not fresh:
+            return torch.from_numpy(np.ascontiguousarray(partner, dtype=np.int32)).to(device), int(partner.max()) if partner.size else 0
+        partner_labels, partner_table = label_volume(on_device(partner), connectivity=connectivity, min_size=0)
+        logging.info("%s holds no '%s_instances': the other ids come from a fresh labelling of '%s_preds' (connectivity %d)",
+                     path, contacts_with, contacts_with, connectivity)
+        return partner_labels, int(partner_table.shape[0])
+
+    labels, table, component = label_and_split(on_device(preds), opts)
+    found = measure(labels, int(table.shape[0]), component, opts, other_mask=None if other is None else on_device(other),
+                    other_name=distance_to, partner=None if partner is None else partner_instances, partner_name=contacts_with)
     result_dir = result_dir if result_dir is not None else path.parent
-    if partner is not None:
-        from cryovit_amd.analysis import distances
-
-        if fresh:
-            partner_labels, partner_table = label_volume(torch.from_numpy(np.ascontiguousarray(partner != 0).view(np.uint8)).to(device),
-                                                         connectivity=connectivity, min_size=0)
-            partner_k = int(partner_table.shape[0])
-            logging.info("%s holds no '%s_instances': the other ids come from a fresh labelling of '%s_preds' (connectivity %d)",
-                         path, contacts_with, contacts_with, connectivity)
-        else:
-            partner_labels = torch.from_numpy(np.ascontiguousarray(partner, dtype=np.int32)).to(device)
-            partner_k = int(partner.max()) if partner.size else 0
-        pairs = distances.instance_pair_contacts(labels, len(rows), partner_labels, partner_k, contact_radius)
-        for r, e in zip(rows, distances.partner_rows(pairs, len(rows), contacts_with)):
-            r.update(e)
-        writers.write_contacts(result_dir, path.name, label, contacts_with, pairs)
-    if shape:
-        from cryovit_amd.analysis.shape import instance_shape
-
-        for r, e in zip(rows, instance_shape(labels, len(rows), connectivity)):
-            r.update(e)
-    lines, d2 = None, None
-    if skeleton and thickness:  # one distance map for both
-        from cryovit_amd.analysis.distances import edt_squared
-
-        d2 = edt_squared(labels)
-    if skeleton:
-        from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
-
-        lines, line_table = skeleton_volume(labels, len(rows), skeleton_end_radius, d2)
-        for r, e in zip(rows, skeleton_rows(line_table)):
-            r.update(e)
-        lines = lines.cpu().numpy()
-    more = {}
-    if thickness:
-        from cryovit_amd.analysis.thickness import thickness_map, thickness_rows, thickness_volume
-
-        t2, thick_table = thickness_volume(labels, len(rows), d2)
-        for r, e in zip(rows, thickness_rows(thick_table)):
-            r.update(e)
-        more["thickness"] = thickness_map(t2)
-    if mesh:
-        from cryovit_amd.analysis.mesh import mesh_arrays, mesh_rows
-
-        vertices, triangles, ids, mesh_table = mesh_arrays(labels, len(rows), mesh_smooth)
-        for r, e in zip(rows, mesh_rows(mesh_table)):
-            r.update(e)
-        writers.write_mesh(result_dir, path.name, label, vertices.cpu().numpy(), triangles.cpu().numpy(), ids.cpu().numpy(), mesh_format)
-    return writers.write_instances(result_dir, path.name, label, datasets, labels.cpu().numpy(), rows, skeleton=lines, **more)
+    if found.pairs is not None:
+        writers.write_contacts(result_dir, path.name, label, contacts_with, found.pairs)
+    return writers.write_measured(result_dir, path.name, label, datasets, labels.cpu().numpy(), table.cpu().numpy(),
+                                  found.arrays(lambda a: a.cpu().numpy()), mesh_format)

@@ -43,16 +43,11 @@ from pathlib import Path
 
 import numpy as np
 
+from cryovit_amd.analysis._tables import host_table
+
 MESH_COLUMNS = ["mesh_triangles", "mesh_area", "mesh_volume"]
 MESH_FORMATS = ("ply", "stl")
 UNIT = 256  # vertex units per voxel
-
-
-def _host(a, dtype, cols) -> np.ndarray:
-    if hasattr(a, "detach"):
-        a = a.detach().cpu().numpy()
-    a = np.asarray(a, dtype=dtype)
-    return a.reshape(-1, cols) if cols else a.reshape(-1)
 
 
 def mesh_rows(table) -> list[dict]:
@@ -64,7 +59,7 @@ def mesh_rows(table) -> list[dict]:
     ``mesh_volume``     c2 / 6 / 256^3
 
     An id without a triangle gives 0, 0.0, 0.0."""
-    return [dict(zip(MESH_COLUMNS, (int(n), area2 / 2 / 65536, det / 6 / 256**3))) for n, area2, det in _host(table, np.int64, 3).tolist()]
+    return [dict(zip(MESH_COLUMNS, (int(n), area2 / 2 / 65536, det / 6 / 256**3))) for n, area2, det in host_table(table, 3).tolist()]
 
 
 def mesh_arrays(labels, k: int, smooth: int = 0):
@@ -87,9 +82,9 @@ def instance_mesh(labels, k: int, smooth: int = 0) -> list[dict]:
 
 def _file_arrays(vertices, triangles, ids):
     """(float32 [V, 3] in x, y, z and voxels, int32 [T, 3] with outward winding in that order, int32 [T])"""
-    v = _host(vertices, np.int32, 3)
-    t = _host(triangles, np.int32, 3)
-    i = _host(ids, np.int32, 0)
+    v = host_table(vertices, 3, np.int32)
+    t = host_table(triangles, 3, np.int32)
+    i = host_table(ids, 0, np.int32)
     if len(i) != len(t):
         raise ValueError(f"{len(i)} ids for {len(t)} triangles")
     if len(t) and (t.min() < 0 or t.max() >= len(v)):

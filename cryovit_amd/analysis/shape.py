@@ -19,6 +19,8 @@ import math
 
 import numpy as np
 
+from cryovit_amd.analysis._tables import host_table
+
 SHAPE_COLUMNS = ["surface_area", "sphericity", "euler", "axis_major", "axis_mid", "axis_minor", "elongation", "dir_z", "dir_y", "dir_x"]
 
 # the 13 directions of the table's crossing counts: lexicographically after (0,0,0), in lexicographic order
@@ -31,12 +33,6 @@ CELL_SHARE = {1: 0.0457778912048, 2: 0.0369806278761, 3: 0.0351956397823}
 
 # w_d / |d| with w_d = 2 c_d, per direction of DIRECTIONS
 _WEIGHT = [2.0 * CELL_SHARE[sum(map(abs, d))] / math.sqrt(sum(c * c for c in d)) for d in DIRECTIONS]
-
-
-def _host(stats) -> np.ndarray:
-    if hasattr(stats, "detach"):
-        stats = stats.detach().cpu().numpy()
-    return np.asarray(stats, dtype=np.int64).reshape(-1, 24)
 
 
 def shape_rows(stats) -> list[dict]:
@@ -55,7 +51,7 @@ def shape_rows(stats) -> list[dict]:
 
     An id without a voxel gives 0.0, nan, 0, 0.0, 0.0, 0.0, nan, nan, nan, nan."""
     rows = []
-    for r in _host(stats).tolist():
+    for r in host_table(stats, 24).tolist():
         n, (sz, sy, sx), (szz, syy, sxx, szy, szx, syx), euler, cross = r[0], r[1:4], r[4:10], r[10], r[11:24]
         if n <= 0:
             rows.append(dict(zip(SHAPE_COLUMNS, (0.0, math.nan, euler, 0.0, 0.0, 0.0, math.nan, math.nan, math.nan, math.nan))))

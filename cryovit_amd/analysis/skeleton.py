@@ -29,17 +29,11 @@ from __future__ import annotations
 
 import math
 
-import numpy as np
+from cryovit_amd.analysis._tables import host_table
 
 SKELETON_COLUMNS = ["skeleton_voxels", "skeleton_length", "skeleton_ends", "skeleton_branches", "skeleton_rms_radius"]
 
 _SQRT2, _SQRT3 = math.sqrt(2.0), math.sqrt(3.0)
-
-
-def _host(table) -> np.ndarray:
-    if hasattr(table, "detach"):
-        table = table.detach().cpu().numpy()
-    return np.asarray(table, dtype=np.int64).reshape(-1, 8)
 
 
 def skeleton_rows(table) -> list[dict]:
@@ -54,7 +48,7 @@ def skeleton_rows(table) -> list[dict]:
 
     An id without a voxel gives 0, 0.0, 0, 0, nan."""
     rows = []
-    for n, ends, branches, _, face, edge, corner, sum_d2 in _host(table).tolist():
+    for n, ends, branches, _, face, edge, corner, sum_d2 in host_table(table, 8).tolist():
         if n <= 0:
             rows.append(dict(zip(SKELETON_COLUMNS, (0, 0.0, 0, 0, math.nan))))
             continue

@@ -32,13 +32,9 @@ import math
 
 import numpy as np
 
+from cryovit_amd.analysis._tables import host_table
+
 THICKNESS_COLUMNS = ["thickness_mean", "thickness_std", "thickness_min", "thickness_max"]
-
-
-def _host(table) -> np.ndarray:
-    if hasattr(table, "detach"):
-        table = table.detach().cpu().numpy()
-    return np.asarray(table, dtype=np.int64).reshape(-1, 5)
 
 
 def thickness_rows(table) -> list[dict]:
@@ -52,7 +48,7 @@ def thickness_rows(table) -> list[dict]:
 
     An id without a voxel (n == 0) gives four nans."""
     rows = []
-    for n, sum_t2, sum_r, lo, hi in _host(table).tolist():
+    for n, sum_t2, sum_r, lo, hi in host_table(table, 5).tolist():
         if n <= 0:
             rows.append(dict.fromkeys(THICKNESS_COLUMNS, math.nan))
             continue

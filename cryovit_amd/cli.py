@@ -3,30 +3,22 @@
 
     python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize]
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
-                                    [--instances [--min-size N] [--connectivity 6|26] [--morphology] [--shape]
-                                     [--split-radius R [--split-min-core N]] [--skeleton [--skeleton-end-radius R]]]
+                                    [--instances <measurements>]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
-    python -m cryovit_amd.cli instances <predictions> --label NAME [--min-size N] [--connectivity 6|26] [--result-folder DIR]
-                                        [--morphology] [--distance-to NAME] [--contacts-with NAME]
-                                        [--distance-to-folder DIR] [--contact-radius R]
-                                        [--split-radius R [--split-min-core N]] [--shape]
-                                        [--skeleton [--skeleton-end-radius R]]
+    python -m cryovit_amd.cli instances <predictions> --label NAME [--result-folder DIR] <measurements>
+                                        [--distance-to NAME] [--contacts-with NAME] [--distance-to-folder DIR] [--contact-radius R]
+
+    <measurements>: [--min-size N] [--connectivity 6|26] [--split-radius R [--split-min-core N]] [--morphology] [--shape]
+                    [--skeleton [--skeleton-end-radius R]] [--thickness] [--mesh [--mesh-smooth N] [--mesh-format ply|stl]]
 
 ``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
 replace the network fetch of the encoder weights or add what the reference leaves to the user: ``instances`` (and
-``infer --instances``) labels the connected instances of a predicted mask on the GPU and tabulates their size and position;
-``--morphology`` and ``--distance-to`` add columns read from exact distance maps (surface voxels, inscribed radius, deepest voxel;
-gap and contact voxels against another label), all in voxels.  ``--split-radius R`` splits instances that touch over a neck
-before they are measured: cores deeper than R voxels (of at least ``--split-min-core`` voxels) are grown back inside their
-instance, and the CSV gains ``component``, the id a piece had before the split.  ``--contacts-with NAME`` says which instance
-touches which: every instance gains ``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance,
-nearest instance of NAME within ``--contact-radius``) the voxels in contact, the narrowest gap and where it is.  ``--shape`` adds,
-as the last columns, what shape every instance (after ``--split-radius``: every piece) has: surface area (discrete Crofton
-estimate over 13 directions), sphericity, Euler number under ``--connectivity``, the three principal-axis lengths, elongation
-and the direction of the major axis, all in voxels.  ``--skeleton`` thins every instance (piece) on the GPU to its centreline,
-writes it as ``<label>_skeleton`` and adds, after the shape columns, the centreline's voxels, length, ends, branch voxels and
-RMS radius; ``--skeleton-end-radius R`` is the depth from which a line's end is kept (1: every surface bump keeps a spur; larger:
-spurs go, and structures thinner than R everywhere shrink to a point or a ring).
+``infer --instances``) labels the connected instances of a predicted mask on the GPU, tabulates their size and position and
+measures them.  The measurement options are declared once, below, for both commands; each is a field of
+``analysis.instances.InstanceOptions``, which says what it computes and writes.  ``--distance-to NAME`` adds the gap to another
+label's mask and the voxels in contact with it; ``--contacts-with NAME`` says which instance touches which: every instance gains
+``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance, nearest instance of NAME within
+``--contact-radius``) the voxels in contact, the narrowest gap and where it is.
 """
 
 from __future__ import annotations
@@ -59,44 +51,28 @@ def _load_encoder(encoder: Optional[str], checkpoint: Optional[str], synthetic_s
                         synthetic_seed=ov.get("synthetic_seed"))
 
 
-def _check_connectivity(value: int) -> int:
-    if value not in (6, 26):
-        raise typer.BadParameter("connectivity must be 6 (faces) or 26 (faces, edges and corners)")
-    return value
+def _checked(ok, message: str):
+    """A typer callback that turns a value down with ``message`` unless ``ok(value)``: a usage error while the arguments are parsed,
+    before anything that labels or infers is imported."""
+    def check(value):
+        if value is not None and not ok(value):
+            raise typer.BadParameter(message)
+        return value
+
+    return check
 
 
-def _check_contact_radius(value: float) -> float:
-    if not value >= 0:
-        raise typer.BadParameter("contact radius must be >= 0 (voxels)")
-    return value
+def _non_negative(what: str):
+    return _checked(lambda v: v >= 0, f"{what} must be >= 0 (voxels)")
 
 
-def _check_split_radius(value: Optional[float]) -> Optional[float]:
-    if value is not None and not value >= 0:
-        raise typer.BadParameter("split radius must be >= 0 (voxels)")
-    return value
-
-
-def _check_mesh_smooth(value: int) -> int:
-    if value < 0:
-        raise typer.BadParameter("mesh smoothing iterations must be >= 0")
-    return value
-
-
-def _check_mesh_format(value: str) -> str:
-    if value not in ("ply", "stl"):
-        raise typer.BadParameter("mesh format must be ply or stl")
-    return value
-
-
-def _check_skeleton_end_radius(value: float) -> float:
-    if not value >= 0:
-        raise typer.BadParameter("skeleton end radius must be >= 0 (voxels)")
-    return value
-
-
+# The measurement options `infer` and `instances` share, each declared once; analysis.instances.InstanceOptions has the full account.
+_MIN_SIZE_HELP = "drop instances of fewer voxels (with infer: with --instances)"
+_CONNECTIVITY_HELP = "6 (faces) or 26 (faces, edges and corners) (with infer: with --instances)"
+_MORPHOLOGY_HELP = ("add surface voxels, inscribed radius and deepest voxel per instance (exact distance map on the GPU; voxels; with "
+                    "infer: needs --instances)")
 _SPLIT_RADIUS_HELP = ("split instances that touch over a neck: cores deeper than this many voxels are grown back inside their "
-                      "instance; the CSV gains the column component (voxels, >= 0)")
+                      "instance; the CSV gains the column component (voxels, >= 0; with infer: needs --instances)")
 _SPLIT_MIN_CORE_HELP = "with --split-radius, ignore cores of fewer voxels"
 _SHAPE_HELP = ("add surface area (Crofton estimate over 13 directions), sphericity, Euler number (under --connectivity), principal-axis "
                "lengths, elongation and major-axis direction per instance as the last CSV columns (voxels; with infer: needs --instances)")
@@ -122,6 +98,26 @@ _MESH_SMOOTH_HELP = ("with --mesh, relax the mesh by N pairs of integer Taubin s
                      "written; 0 keeps the raw mesh, about 10 gives a surface to quote beside surface_area of --shape")
 _MESH_FORMAT_HELP = ("with --mesh, the file format: ply (binary, shared vertices, an instance id per face) or stl (binary, the id in "
                      "the attribute word, saturated at 65535)")
+_EXT = "build extension: "
+
+MinSize = Annotated[int, Option(min=0, help=_EXT + _MIN_SIZE_HELP)]
+Connectivity = Annotated[int, Option(callback=_checked(lambda v: v in (6, 26), "connectivity must be 6 (faces) or 26 (faces, edges and corners)"),
+                                     help=_EXT + _CONNECTIVITY_HELP)]
+Morphology = Annotated[bool, Option("--morphology", help=_EXT + _MORPHOLOGY_HELP)]
+SplitRadius = Annotated[Optional[float], Option(callback=_non_negative("split radius"), help=_EXT + _SPLIT_RADIUS_HELP)]
+SplitMinCore = Annotated[int, Option(min=0, help=_EXT + _SPLIT_MIN_CORE_HELP)]
+Shape = Annotated[bool, Option("--shape", help=_EXT + _SHAPE_HELP)]
+Skeleton = Annotated[bool, Option("--skeleton", help=_EXT + _SKELETON_HELP)]
+SkeletonEndRadius = Annotated[float, Option(callback=_non_negative("skeleton end radius"), help=_EXT + _SKELETON_END_RADIUS_HELP)]
+Thickness = Annotated[bool, Option("--thickness", help=_EXT + _THICKNESS_HELP)]
+Mesh = Annotated[bool, Option("--mesh", help=_EXT + _MESH_HELP)]
+MeshSmooth = Annotated[int, Option("--mesh-smooth", callback=_checked(lambda v: v >= 0, "mesh smoothing iterations must be >= 0"),
+                                   help=_EXT + _MESH_SMOOTH_HELP)]
+MeshFormat = Annotated[str, Option("--mesh-format", callback=_checked(lambda v: v in ("ply", "stl"), "mesh format must be ply or stl"),
+                                   help=_EXT + _MESH_FORMAT_HELP)]
+
+# infer measures nothing without --instances: asking for one of these without it is a usage error
+_NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh")
 
 
 def _encoder_overrides(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]) -> dict:
@@ -167,32 +163,28 @@ def infer(
     checkpoint: Annotated[Optional[str], Option(help="build extension: local DINOv2 state_dict file")] = None,
     synthetic_seed: Annotated[Optional[int], Option(help="build extension: seeded random encoder weights")] = None,
     instances: Annotated[bool, Option("--instances", help="build extension: also label the connected instances of each mask on the GPU (<label>_instances dataset and instances/<tomogram>_<label>.csv)")] = False,
-    min_size: Annotated[int, Option(min=0, help="build extension: with --instances, drop instances of fewer voxels")] = 0,
-    connectivity: Annotated[int, Option(callback=_check_connectivity, help="build extension: with --instances, 6 (faces) or 26 (faces, edges and corners)")] = 26,
-    morphology: Annotated[bool, Option("--morphology", help="build extension: with --instances, add surface voxels, inscribed radius and deepest voxel per instance (exact distance map on the GPU; voxels)")] = False,
-    split_radius: Annotated[Optional[float], Option(callback=_check_split_radius, help="build extension: with --instances, " + _SPLIT_RADIUS_HELP)] = None,
-    split_min_core: Annotated[int, Option(min=0, help="build extension: " + _SPLIT_MIN_CORE_HELP)] = 0,
-    shape: Annotated[bool, Option("--shape", help="build extension: " + _SHAPE_HELP)] = False,
-    skeleton: Annotated[bool, Option("--skeleton", help="build extension: " + _SKELETON_HELP)] = False,
-    skeleton_end_radius: Annotated[float, Option(callback=_check_skeleton_end_radius, help="build extension: " + _SKELETON_END_RADIUS_HELP)] = 2.0,
-    thickness: Annotated[bool, Option("--thickness", help="build extension: " + _THICKNESS_HELP)] = False,
-    mesh: Annotated[bool, Option("--mesh", help="build extension: " + _MESH_HELP)] = False,
-    mesh_smooth: Annotated[int, Option("--mesh-smooth", callback=_check_mesh_smooth, help="build extension: " + _MESH_SMOOTH_HELP)] = 0,
-    mesh_format: Annotated[str, Option("--mesh-format", callback=_check_mesh_format, help="build extension: " + _MESH_FORMAT_HELP)] = "ply",
+    min_size: MinSize = 0,
+    connectivity: Connectivity = 26,
+    morphology: Morphology = False,
+    split_radius: SplitRadius = None,
+    split_min_core: SplitMinCore = 0,
+    shape: Shape = False,
+    skeleton: Skeleton = False,
+    skeleton_end_radius: SkeletonEndRadius = 2.0,
+    thickness: Thickness = False,
+    mesh: Mesh = False,
+    mesh_smooth: MeshSmooth = 0,
+    mesh_format: MeshFormat = "ply",
 ):
     """Segment tomograms using a pre-trained model."""
-    if morphology and not instances:
-        raise typer.BadParameter("--morphology needs --instances", param_hint="--morphology")
-    if shape and not instances:
-        raise typer.BadParameter("--shape needs --instances", param_hint="--shape")
-    if skeleton and not instances:
-        raise typer.BadParameter("--skeleton needs --instances", param_hint="--skeleton")
-    if split_radius is not None and not instances:
-        raise typer.BadParameter("--split-radius needs --instances", param_hint="--split-radius")
-    if thickness and not instances:
-        raise typer.BadParameter("--thickness needs --instances", param_hint="--thickness")
-    if mesh and not instances:
-        raise typer.BadParameter("--mesh needs --instances", param_hint="--mesh")
+    measurements = dict(min_size=min_size, connectivity=connectivity, morphology=morphology, split_radius=split_radius,
+                        split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
+                        thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
+    for name in _NEEDS_INSTANCES:
+        value = measurements[name]  # a flag that is off is False, a radius that is not given None; a radius of 0 is given
+        if not instances and value is not False and value is not None:
+            flag = "--" + name.replace("_", "-")
+            raise typer.BadParameter(f"{flag} needs --instances", param_hint=flag)
     from cryovit_amd.run.infer_model import run_inference
     from cryovit_amd.utils import load_files_from_path
 
@@ -203,34 +195,31 @@ def infer(
     assert model_path.exists() and model_path.suffix == ".model", "Model path does not exist or is not a .model file."
     result_path.mkdir(parents=True, exist_ok=True)
     run_inference(load_files_from_path(tomograms_path), model_path, result_path, threshold=threshold,
-                  encoder=_load_encoder(encoder, checkpoint, synthetic_seed), instances=instances, min_size=min_size,
-                  connectivity=connectivity, morphology=morphology, split_radius=split_radius, split_min_core=split_min_core,
-                  shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius, thickness=thickness,
-                  mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
+                  encoder=_load_encoder(encoder, checkpoint, synthetic_seed), instances=instances, **measurements)
 
 
 @cli.command(name="instances", no_args_is_help=True)
 def instances_cmd(
     predictions: Annotated[str, Argument(help="Path to the folder or .txt file containing prediction files written by `infer`.")],
     label: Annotated[str, Option(help="build extension: label name; the <label>_preds dataset of every file is labelled.")],
-    min_size: Annotated[int, Option(min=0, help="build extension: drop instances of fewer voxels")] = 0,
-    connectivity: Annotated[int, Option(callback=_check_connectivity, help="build extension: 6 (faces) or 26 (faces, edges and corners)")] = 26,
+    min_size: MinSize = 0,
+    connectivity: Connectivity = 26,
     result_folder: Annotated[Optional[str], Option(help="build extension: folder for the labelled files and instances/*.csv.",
                                                    show_default="the folder of the predictions (files are updated in place)")] = None,
-    morphology: Annotated[bool, Option("--morphology", help="build extension: add surface voxels, inscribed radius and deepest voxel per instance (exact distance map on the GPU; voxels)")] = False,
+    morphology: Morphology = False,
     distance_to: Annotated[Optional[str], Option(help="build extension: another label NAME; add the gap to <NAME>_preds and the voxels in contact with it (voxels)")] = None,
     distance_to_folder: Annotated[Optional[str], Option(help="build extension: folder whose <same stem>.hdf holds <NAME>_preds (for --contacts-with also <NAME>_instances) when the prediction file itself does not; serves --distance-to and --contacts-with")] = None,
-    contact_radius: Annotated[float, Option(callback=_check_contact_radius, help="build extension: with --distance-to or --contacts-with, voxels within this distance of the other label count as contact (voxels, >= 0)")] = 1.0,
+    contact_radius: Annotated[float, Option(callback=_non_negative("contact radius"), help="build extension: with --distance-to or --contacts-with, voxels within this distance of the other label count as contact (voxels, >= 0)")] = 1.0,
     contacts_with: Annotated[Optional[str], Option(help="build extension: another label NAME; write contacts/<tomo>_<label>_<NAME>.csv, one row per pair of an instance and the instance of NAME nearest to some of its voxels within --contact-radius (voxels in contact, gap, where), and add partners_<NAME> per instance")] = None,
-    split_radius: Annotated[Optional[float], Option(callback=_check_split_radius, help="build extension: " + _SPLIT_RADIUS_HELP)] = None,
-    split_min_core: Annotated[int, Option(min=0, help="build extension: " + _SPLIT_MIN_CORE_HELP)] = 0,
-    shape: Annotated[bool, Option("--shape", help="build extension: " + _SHAPE_HELP)] = False,
-    skeleton: Annotated[bool, Option("--skeleton", help="build extension: " + _SKELETON_HELP)] = False,
-    skeleton_end_radius: Annotated[float, Option(callback=_check_skeleton_end_radius, help="build extension: " + _SKELETON_END_RADIUS_HELP)] = 2.0,
-    thickness: Annotated[bool, Option("--thickness", help="build extension: " + _THICKNESS_HELP)] = False,
-    mesh: Annotated[bool, Option("--mesh", help="build extension: " + _MESH_HELP)] = False,
-    mesh_smooth: Annotated[int, Option("--mesh-smooth", callback=_check_mesh_smooth, help="build extension: " + _MESH_SMOOTH_HELP)] = 0,
-    mesh_format: Annotated[str, Option("--mesh-format", callback=_check_mesh_format, help="build extension: " + _MESH_FORMAT_HELP)] = "ply",
+    split_radius: SplitRadius = None,
+    split_min_core: SplitMinCore = 0,
+    shape: Shape = False,
+    skeleton: Skeleton = False,
+    skeleton_end_radius: SkeletonEndRadius = 2.0,
+    thickness: Thickness = False,
+    mesh: Mesh = False,
+    mesh_smooth: MeshSmooth = 0,
+    mesh_format: MeshFormat = "ply",
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     from cryovit_amd.analysis.instances import label_file

@@ -9,6 +9,7 @@
                          instances, int32 beyond; gzip), with a skeleton also ``<label>_skeleton`` (int32 ids; gzip), with a
                          thickness map also ``<label>_thickness`` (float32, voxels; gzip), and
                          <results_dir>/instances/<tomo stem>_<label>.csv, one row per instance
+  write_measured         (not in the reference) write_mesh and write_instances of one ``analysis.instances.measure`` result
   write_mesh             (not in the reference) <results_dir>/meshes/<tomo stem>_<label>.ply or .stl, the surface of the labelled mask
   write_contacts        (not in the reference) <results_dir>/contacts/<tomo stem>_<label>_<other>.csv, one row per pair of an
                          instance of <label> and an instance of <other> in contact
@@ -26,6 +27,9 @@ from pathlib import Path
 import numpy as np
 
 from cryovit_amd import io
+from cryovit_amd.analysis.distances import PAIR_COLUMNS
+from cryovit_amd.analysis.instances import INSTANCE_COLUMNS, instance_rows, merge_columns
+from cryovit_amd.analysis.thickness import thickness_map
 
 
 def write_test_prediction(results_dir, sample: str, tomo_name: str, label_key: str, data: np.ndarray, labels: np.ndarray,
@@ -55,7 +59,14 @@ def write_segmentation(results_dir, tomo_name: str, label_key: str, data: np.nda
     return out
 
 
-INSTANCE_COLUMNS = ["id", "voxels", "z", "y", "x", "z0", "z1", "y0", "y1", "x0", "x1"]
+def _write_rows(path: Path, columns: list[str], rows: list[dict]) -> None:
+    """The CSV ``path`` of ``rows`` under the header ``columns``; floats written with ``repr``."""
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=columns)
+        w.writeheader()
+        for r in rows:
+            w.writerow({k: repr(v) if isinstance(v, float) else v for k, v in r.items()})
 
 
 def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[str, np.ndarray], labels: np.ndarray,
@@ -64,7 +75,7 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
     gzip, dtypes as given) and ``<label>_instances`` = ``labels`` (uint16 while the largest id fits, else int32: a 128x512x512
     int32 volume would make the gzip of the writer thread the slowest stage of ``infer``), and the CSV
     <results_dir>/instances/<tomo stem>_<label>.csv of ``rows`` (``analysis.instance_rows``; floats written with ``repr``; no
-    instances: header only; keys beyond ``INSTANCE_COLUMNS``, e.g. those of ``analysis.distance_rows``, become further columns in
+    instances: header only; keys beyond ``INSTANCE_COLUMNS``, those of ``analysis.instances.measure``, become further columns in
     the rows' own order).  ``skeleton`` (the instances' centrelines, every voxel with its instance's id) is written as
     ``<label>_skeleton`` in int32 beside ``<label>_instances``: it is nearly all zeros and gzips to little.  ``thickness``
     (``analysis.thickness.thickness_map``: the local thickness in voxels, 0 on the background, inf without any background) is written
@@ -84,15 +95,23 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
         if thickness is not None:
             fh.create_dataset(f"{label_key}_thickness", thickness.astype(np.float32, copy=False), compression="gzip")
     os.replace(tmp, out)
-    csv_path = results_dir / "instances" / f"{out.stem}_{label_key}.csv"
-    csv_path.parent.mkdir(parents=True, exist_ok=True)
-    with open(csv_path, "w", newline="") as f:
-        extras = [k for k in (rows[0] if rows else ()) if k not in INSTANCE_COLUMNS]  # every row carries the same keys
-        w = csv.DictWriter(f, fieldnames=INSTANCE_COLUMNS + extras)
-        w.writeheader()
-        for r in rows:
-            w.writerow({k: repr(v) if isinstance(v, float) else v for k, v in r.items()})
+    extras = [k for k in (rows[0] if rows else ()) if k not in INSTANCE_COLUMNS]  # every row carries the same keys
+    _write_rows(results_dir / "instances" / f"{out.stem}_{label_key}.csv", INSTANCE_COLUMNS + extras, rows)
     return out
+
+
+def write_measured(results_dir, tomo_name: str, label_key: str, datasets: dict[str, np.ndarray], labels: np.ndarray, table: np.ndarray,
+                   measured, mesh_format: str = "ply") -> Path:
+    """Everything one file gets from ``analysis.instances.measure``, for ``label_file`` and for the writer thread of ``infer``:
+    ``write_mesh`` where ``measured`` (an ``analysis.instances.Measured`` of host arrays) holds a mesh, and ``write_instances`` of the
+    rows of the host ``table`` with the columns of ``measured.extra`` after them, the skeleton and the thickness map (the root of
+    ``measured.t2`` is taken here, off the thread that feeds the GPU).  Returns the .hdf path."""
+    if measured.mesh is not None:
+        write_mesh(results_dir, tomo_name, label_key, *measured.mesh, mesh_format)
+    rows = instance_rows(table)
+    merge_columns(rows, measured.extra)
+    return write_instances(results_dir, tomo_name, label_key, datasets, labels, rows, skeleton=measured.skeleton,
+                           thickness=None if measured.t2 is None else thickness_map(measured.t2))
 
 
 def write_mesh(results_dir, tomo_name: str, label_key: str, vertices: np.ndarray, triangles: np.ndarray, ids: np.ndarray,
@@ -105,19 +124,11 @@ def write_mesh(results_dir, tomo_name: str, label_key: str, vertices: np.ndarray
     return write(Path(results_dir) / "meshes" / f"{Path(tomo_name).stem}_{label_key}.{fmt}", vertices, triangles, ids, fmt)
 
 
-PAIR_COLUMNS = ["id", "other_id", "contact_voxels", "gap_d2", "gap", "at_z", "at_y", "at_x"]
-
-
 def write_contacts(results_dir, tomo_name: str, label_key: str, other_name: str, rows: list[dict]) -> Path:
     """The CSV <results_dir>/contacts/<tomo stem>_<label>_<other>.csv of ``rows`` (``analysis.distances.pair_rows``: columns
     ``PAIR_COLUMNS``; floats written with ``repr``; no pairs: header only).  Returns its path."""
     path = Path(results_dir) / "contacts" / f"{Path(tomo_name).stem}_{label_key}_{other_name}.csv"
-    path.parent.mkdir(parents=True, exist_ok=True)
-    with open(path, "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=PAIR_COLUMNS)
-        w.writeheader()
-        for r in rows:
-            w.writerow({k: repr(v) if isinstance(v, float) else v for k, v in r.items()})
+    _write_rows(path, PAIR_COLUMNS, rows)
     return path
 
 

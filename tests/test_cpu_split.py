@@ -238,6 +238,7 @@ def test_split_cli_surface_and_refusals(tmp_path, monkeypatch):
         monkeypatch.delitem(sys.modules, name, raising=False)
     model = ["--model", str(tmp_path / "m.model")]
     for args, words in ((["infer", str(tmp_path), *model, "--split-radius", "1.5"], "--split-radius needs --instances"),
+                        (["infer", str(tmp_path), *model, "--split-radius", "0"], "--split-radius needs --instances"),  # 0 is a radius
                         (["infer", str(tmp_path), *model, "--instances", "--split-radius", "-1"], "split radius must be >= 0"),
                         (["infer", str(tmp_path), *model, "--instances", "--split-radius", "2", "--split-min-core", "-1"], "split-min-core"),
                         (["instances", str(tmp_path), "--label", "mito", "--split-radius", "-0.5"], "split radius must be >= 0"),

@@ -327,3 +327,25 @@ def test_cli_instances_on_existing_predictions(inferred):
     assert np.array_equal(io.read_dataset(plain, "mito_instances"), want)
     res = CliRunner().invoke(cli, ["instances", str(tmp / "again"), "--label", "nucleus"])
     assert res.exit_code != 0 and "nucleus_preds" in repr(res.exception)
+
+
+def test_both_routes_write_the_same_bytes_with_every_option(inferred):
+    """``run_inference`` and ``label_file`` share one pipeline: with every option of both on, the same datasets, CSV and mesh."""
+    from cryovit_amd import io
+    from cryovit_amd.analysis import label_file
+    from cryovit_amd.run.infer_model import run_inference
+
+    tmp = inferred[0]
+    opts = dict(min_size=5, morphology=True, split_radius=1.0, split_min_core=2, shape=True, skeleton=True, thickness=True, mesh=True,
+                mesh_smooth=2)
+    (one,) = run_inference([tmp / "in" / "tomo0.hdf"], tmp / "demo.model", tmp / "all_infer", threshold=0.4, instances=True, **opts)
+    two = label_file(one, "mito", result_dir=tmp / "all_label", **opts)
+    names = ["data", "mito_instances", "mito_preds", "mito_skeleton", "mito_thickness"]
+    assert sorted(io.list_keys(one)) == sorted(io.list_keys(two)) == names
+    for name in names:
+        a, b = io.read_dataset(one, name), io.read_dataset(two, name)
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), name
+    assert int(io.read_dataset(one, "mito_instances").max()) >= 1  # something was measured
+    for rel in ("instances/tomo0_mito.csv", "meshes/tomo0_mito.ply"):
+        a, b = (tmp / "all_infer" / rel).read_bytes(), (tmp / "all_label" / rel).read_bytes()
+        assert len(a) > 0 and a == b, rel
