@@ -38,6 +38,9 @@ template <class E, class = void> struct epi_has_produce : std::false_type {};
 template <class E> struct epi_has_produce<E, std::enable_if_t<(E::OUT16 > 0)>> : std::true_type {};
 template <class E, class = void> struct epi_has_preload : std::false_type {};
 template <class E> struct epi_has_preload<E, std::enable_if_t<E::HAS_PRELOAD>> : std::true_type {};
+// epilogues with the LayerNorm fold (`static constexpr bool LNFOLD = true`, `rowstat` = fp32 [rows][2]): produce() takes the row constants
+template <class E, class = void> struct epi_is_ln : std::false_type {};
+template <class E> struct epi_is_ln<E, std::enable_if_t<E::LNFOLD>> : std::true_type {};
 
 // diagnostic builds only (G256Stamp): per-wave cycle sums of the four parts of a phase, block 0 (PerPhase), or of the
 // prologue / K loop / epilogue of one block (Coarse)
@@ -523,7 +526,15 @@ __device__ __forceinline__ void gemm256_body(const uint16_t* __restrict__ Rmat, 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[f * 4 + e] = acc[f][2 * q + bb][e];
                 uint32_t w[O16 / 2];
-                epi.produce(ctx, v, w);
+                if constexpr (epi_is_ln<Epi>::value) {
+                    // the row constants (rstd, -mu * rstd) of the row these 16 accumulators belong to; without them the fold
+                    // degenerates to b' (rs = 0): the persistent tile read them, this kernel did not
+                    const long mrow = l0 + wl * 128 + 32 * q + 16 * bb + (lane & 15);
+                    const float2 rs = mrow < epi.m_valid ? *(const float2*)(epi.rowstat + 2 * mrow) : float2{0.f, 0.f};
+                    epi.produce(ctx, v, w, rs);
+                } else {
+                    epi.produce(ctx, v, w);
+                }
                 char* dst = stg + (16 * bb + (lane & 15)) * PITCHB + gq * (O16 * 2);
                 if constexpr (O16 == 16) {
                     *(uint4*)dst = uint4{w[0], w[1], w[2], w[3]};

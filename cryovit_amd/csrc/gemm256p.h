@@ -52,8 +52,6 @@ template <class E> struct epi_is_mreg<E, std::enable_if_t<E::MREG16>> : std::tru
 
 template <class E, class = void> struct epi_has_hl : std::false_type {};
 template <class E> struct epi_has_hl<E, std::enable_if_t<E::HAS_HL>> : std::true_type {};
-template <class E, class = void> struct epi_is_ln : std::false_type {};
-template <class E> struct epi_is_ln<E, std::enable_if_t<E::LNFOLD>> : std::true_type {};
 
 template <class Epi> constexpr int epi_stores_per_wave() {
     if constexpr (epi_is_mreg<Epi>::value) return 16;                            // 8 fragments x 2 stores of 8 rows

@@ -1,5 +1,8 @@
-"""Kernel-level parity: every HIP op (through the C ABI) against a torch-CPU fp32 computation of the same op on the
-same bf16-rounded operands.  Tolerances are stated per test; bf16 has 8 significand bits (rel. 2^-9 per rounding)."""
+"""Kernel-level parity: every HIP op (through the C ABI) against a torch-CPU computation of the same op on the same bf16- / fp16-rounded
+operands.  Two kinds of check stand side by side: an elementwise band against the fp32 CPU result (tolerances stated per test; bf16
+has 8 significand bits, rel. 2^-9 per rounding), and, in the ``*_error_budget*`` tests, the rms error against a float64 reference
+measured in units of the error the kernel's documented roundings must produce (tests/error_budget.py: R_all, R_row, R_col with bounds
+derived on the CPU; the fp32-storing GEMM epilogues get the elementwise forward bound of fp32 accumulation instead)."""
 
 import functools
 import math
@@ -12,6 +15,8 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 import os
+
+import error_budget as eb
 
 # The product library holds the SHIPPED variant of every kernel (plus the general fall-backs); the measured-and-rejected schedules
 # live in the -DCVX_ABLATION build only.  Their parity tests run when this module is imported with CVX_ABLATION_LIB=1 -- which
@@ -398,6 +403,15 @@ def test_attention_forced_rescale(gpu, attn_variant, spike):
     ref = torch.softmax(qf @ kf.T, -1) @ vf
     got = out[:nt].float().cpu()
     assert torch.allclose(got, ref, atol=2e-2, rtol=2e-2), float((got - ref).abs().max())
+    if spike in eb.RESCALE_SPIKES:
+        # ... and the rms error in units of the rounding budget, over the output and per query row, against the emulation of THIS variant's
+        # anchoring: the running maximum (0, 4), anchors raised wave by wave beyond 2^3 (6), or the first tile's anchor with the spiked
+        # tile redone against raised anchors (7, 8, 9).  Most rows are a single key here -- query 7 sees key 150 alone -- so a row's budget
+        # is one rounding of one probability: only the right emulation has R_row near 1.  (The rows behind token 200 are zeros in this
+        # buffer: score 0, as eb._anchors pads a wave.)
+        assert all(torch.equal(a, b) for a, b in zip((q, k, v), eb.rescale_operands(spike)))
+        fam = eb.rescale_case(spike, eb.ATTENTION_FORM_OF_VARIANT[attn_variant], full=False)
+        eb.check("attention_rescale", f"spike={spike} variant={attn_variant}", got.double().unsqueeze(0), fam.ref, fam.emu)
 
 
 @pytest.mark.parametrize("dtype", ["u8", "f32"])
@@ -954,15 +968,27 @@ def _check_resid_hl(gpu, M, N, K, n_pad=None):
     got = (got_h + got_l).double()
     # the pair carries 16+ significant bits; the fp32 accumulation order of the MFMA differs from the CPU's
     assert torch.allclose(got, ref, atol=2e-4, rtol=3e-5), float((got - ref).abs().max())
-    # hi = bf16(x); re-rounding hi + lo can only differ where lo itself was rounded up to exactly half an ulp of hi (a tie).
-    # Expected rate 2^-10 = 9.8e-4: the remainder x - hi is spread evenly over [0, h], h = half an ulp of hi, and bf16 values just
-    # below h are h * 2^-8 apart, so bf16(x - hi) reaches h for the top 2^-9 of them; hi + lo is then halfway between hi and its
-    # neighbour and round-to-nearest-even leaves hi for the half of the cases in which hi's last bit is odd.
-    assert float((got_h != bf(got_h + got_l).float()).float().mean()) <= 5e-3, "hi is not bf16(hi + lo)"
+    # hi = bf16(x); re-rounding hi + lo can only differ where lo itself was rounded up to exactly half an ulp of hi: hi + lo is then a tie
+    # between hi and its neighbour, and round-to-nearest-even leaves hi where hi's last bit is odd.  (Expected rate 2^-10: the remainder
+    # x - hi is spread over [0, h], h = half an ulp of hi, bf16 values just below h are h * 2^-8 apart, so bf16(x - hi) reaches h for the top
+    # 2^-9 of them, half of them with an odd hi.)  Stated exactly: EVERY mismatch is such a tie, |lo| = ulp(hi) / 2.
     s = got_h + got_l  # exact in fp32: x has 24 significant bits, hi the first 8 of them
     moved = got_h != bf(s).float()
     print(f"resid_hl M={M} N={N} n_pad={n_pad} K={K}: hi != bf16(hi + lo) at {float(moved.float().mean()):.3e} of the positions")
     assert bool(((s.view(torch.int32) & 0xFFFF) == 0x8000)[moved].all()), "hi != bf16(hi + lo) where hi + lo is not a tie between two bf16 values"
+    mant, expo = torch.frexp(got_h)  # |hi| = mant * 2^expo, mant in [0.5, 1); bf16 has 8 significant bits: ulp(hi) = 2^(expo - 8)
+    half_ulp = torch.ldexp(torch.ones_like(got_h), expo - 9)
+    # (towards zero from a power of two the bf16 spacing is half as wide)
+    half_ulp = torch.where((mant.abs() == 0.5) & (torch.sign(got_l) != torch.sign(got_h)), half_ulp / 2, half_ulp)
+    assert torch.equal(got_l.abs()[moved], half_ulp[moved]), "hi != bf16(hi + lo) where |lo| is not half an ulp of hi"
+    # the sum against float64, elementwise: the forward bound of fp32 accumulation (error_budget.fp32_forward_bound) plus what the pair
+    # itself cannot hold -- lo is a bf16 (rel. 2^-9) of a remainder of at most half an ulp of hi (2^-8 |hi|): 2^-17 |x|.
+    # (The bare forward bound is marginal for the pair: 0.97 of it is used at K = 128, where (K + 3) 2^-24 is about that 2^-17.)
+    x_in = (hi0.float() + lo0.float()).double()
+    bound = eb.fp32_forward_bound(bf(a), bf(w[:N]), K, b[:N], gain=g[:N], x0=x_in)
+    excess = (got - ref).abs() - (bound + 2.0**-17 * (ref.abs() + bound))
+    print(f"resid_hl M={M} N={N} K={K}: max |got - ref64| / forward bound {float(((got - ref).abs() / bound).max()):.3f}")
+    assert float(excess.max()) <= 0, float(excess.max())
     assert float((got_l.abs() - got_h.abs() * 2.0**-8).max()) <= 0, "lo is not the rounding remainder of hi"
     assert torch.all(xh[M:].float() == 7.0) and torch.all(xl[M:].float() == 7.0), "rows beyond M were written"
     p = part[: N // 64, :M].cpu().double()
@@ -1255,6 +1281,327 @@ def test_final_norm_hl_equals_fp32_form(gpu, hp, wp, C):
         assert torch.equal(a, c)
     ref = F.layer_norm(xs.cpu().reshape(-1, C)[: slices * ntp].reshape(slices, ntp, C)[:, tok0 : tok0 + npatch], (C,), w.cpu(), b.cpu(), 1e-6)
     assert torch.allclose(outs[1][2].cpu(), ref, atol=1e-4, rtol=1e-4)
+
+
+# ---- error budgets: the rms error in units of the error the documented roundings must produce (tests/error_budget.py) ----------
+# Operands, junk padding and seeds are those of the band tests above; the band and "pads untouched" assertions are repeated, the
+# statistics R_all / R_row / R_col come on top (bounds from the CPU rule, tests/test_cpu_error_budget.py; eb.check prints all three).
+
+
+def _budget_attention_operands(nt, slices, heads, ops):
+    """test_attention's buffers: (qk with junk pad rows, vt with 3.0 in the pad tokens, the same as one row-major qkv buffer)."""
+    C = heads * 64
+    ntp, kp = ops.round_up(nt, 8), ops.round_up(nt, 64)
+    M = slices * ntp
+    q, k, v = eb.attention_operands(nt, slices, heads)
+    qk = torch.randn(ops.alloc_rows(M), 2 * C, generator=torch.Generator().manual_seed(27)).to(torch.bfloat16)  # junk pad
+    rows = qk[:M].reshape(slices, ntp, 2 * C)
+    rows[:, :nt, :C] = bf(q * 0.125 * LOG2E).reshape(slices, nt, C)
+    rows[:, :nt, C:] = bf(k).reshape(slices, nt, C)
+    vt = torch.zeros(slices, heads, 64, kp, dtype=torch.bfloat16)
+    vt[..., :nt] = bf(v).permute(0, 2, 3, 1)
+    vt[..., nt:ntp] = 3.0  # finite garbage in the pad tokens must be masked out
+    qkv = torch.randn(ops.alloc_rows(M), 3 * C, generator=torch.Generator().manual_seed(27)).to(torch.bfloat16)  # junk pad rows
+    rows3 = qkv[:M].reshape(slices, ntp, 3 * C)
+    rows3[:, :nt, : 2 * C] = rows[:, :nt]
+    rows3[:, :nt, 2 * C :] = bf(v).reshape(slices, nt, C)
+    return qk, vt, qkv, ntp, kp, M, C
+
+
+def _budget_attention_check(out, nt, slices, heads, ntp, M, C, label, form="anchor", qk=None):
+    """form: how the kernel anchors P before rounding it (eb._anchors).  "deferred" (variant 6) re-anchors a whole wave of 32 query
+    rows at once, so it needs `qk`, the buffer the kernel read: the rows behind a slice's last token sit in its last wave."""
+    if form == "deferred":
+        ext = -(-nt // eb.WAVE_ROWS) * eb.WAVE_ROWS
+        rows = torch.stack([qk[s * ntp : s * ntp + ext] for s in range(slices)]).double()  # [slices, ext, 2C], Q in log2 units
+        qe = rows[..., :C].reshape(slices, ext, heads, 64).permute(0, 2, 1, 3).reshape(slices * heads, ext, 64)
+        ke = rows[:, :nt, C:].reshape(slices, nt, heads, 64).permute(0, 2, 1, 3).reshape(slices * heads, nt, 64)
+        fam = eb.attention_family(*eb.attention_qkv64(*eb.attention_operands(nt, slices, heads)), form, full=False, s2_wave=qe @ ke.transpose(1, 2))
+    else:
+        fam = eb.attention_case(nt, slices, heads, form, full=False)
+    got = out[:M].float().cpu().reshape(slices, ntp, C)
+    rows = eb.attention_rows(got[:, :nt], slices, nt, heads)
+    assert torch.allclose(rows.float(), fam.ref.float(), atol=2e-2, rtol=2e-2), float((rows - fam.ref).abs().max())
+    assert torch.all(got[:, nt:] == 0), "padding rows must not be written"
+    eb.check("attention", label, rows, fam.ref, fam.emu)
+
+
+@pytest.mark.parametrize("attn_variant", [0, 3, 4, 5, 6, 7, 8, 9], indirect=True)
+@pytest.mark.parametrize("nt,slices,heads", eb.ATTENTION_CASES)
+def test_attention_error_budget(gpu, nt, slices, heads, attn_variant):
+    """cvx_attention_bf16, every kept variant: 29 = one partial key tile; 133 = a lone-wave last query block and 5 valid keys in the
+    last key tile; 261; 1029.  emu rounds P relative to what the variant's source anchors it at: the bf16 maximum of the first key tile
+    (7, 8, 9), the running maximum (0, 3, 4, 5), or anchors raised wave by wave (6)."""
+    from cryovit_amd.engine import ops
+
+    qk, vt, _, ntp, kp, M, C = _budget_attention_operands(nt, slices, heads, ops)
+    out = torch.zeros(ops.alloc_rows(M), C, dtype=torch.bfloat16, device=gpu)
+    ops.attention(qk.to(gpu), vt.to(gpu), out, slices=slices, heads=heads, ntok=nt, ntp=ntp, kp=kp)
+    _budget_attention_check(out, nt, slices, heads, ntp, M, C, f"nt={nt} slices={slices} heads={heads} variant={attn_variant}",
+                            eb.ATTENTION_FORM_OF_VARIANT[attn_variant], qk)
+
+
+@pytest.mark.parametrize("nt,slices,heads", eb.ATTENTION_CASES)
+def test_attention_error_budget_qkv(gpu, nt, slices, heads):
+    """cvx_attention_qkv_bf16 (row-major V; always the shipped kernel, whatever attn_variant says) on the same operands."""
+    from cryovit_amd.engine import ops
+
+    _, _, qkv, ntp, kp, M, C = _budget_attention_operands(nt, slices, heads, ops)
+    out = torch.zeros(ops.alloc_rows(M), C, dtype=torch.bfloat16, device=gpu)
+    ops.attention_qkv(qkv.to(gpu), out, slices=slices, heads=heads, ntok=nt, ntp=ntp)
+    _budget_attention_check(out, nt, slices, heads, ntp, M, C, f"nt={nt} slices={slices} heads={heads} qkv")
+
+
+def _swiglu_interleave(n):
+    """packed row r of a SwiGLU weight with n = 2 Hd natural rows (gate | value): blocks of 8 gate rows, then the 8 matching value rows"""
+    r = torch.arange(n)
+    j, e = r // 16, r % 16
+    return torch.where(e < 8, 8 * j + e, n // 2 + 8 * j + e - 8)
+
+
+def _budget_gemm(gpu, M, N, n_pad, K, k_pad, epi, ln):
+    """One bf16-storing GEMM (epi: bf16 | gelu | swiglu | vt; ln: the LayerNorm fold with the row constants cvx_split_stream wrote)
+    against float64 on the rounded operands: the band and pad assertions of the tests above, then the statistics.  With n_pad given
+    the weight rows / bias entries N .. n_pad hold values, not zeros, and the output is exactly N wide."""
+    from cryovit_amd import _lib
+    from cryovit_amd.engine import ops
+    from cryovit_amd.engine.head import _npad
+
+    R = ops.alloc_rows(M)
+    fill_pad = n_pad is not None
+    n_pad = n_pad or (ops.round_up(N, 128) if ln else _npad(N))
+    rs = rs_cpu = cs = None
+    if ln:
+        x, w, bias, gamma, beta = eb.gemm_operands(M, N, K, True)
+        xd = torch.zeros(R, k_pad, device=gpu)
+        xd[:M, :K] = x.to(gpu)
+        A, xl, rs = torch.zeros(R, k_pad, dtype=torch.bfloat16, device=gpu), torch.zeros(R, k_pad, dtype=torch.bfloat16, device=gpu), torch.zeros(R, 2, device=gpu)
+        ops.split_stream(xd, A, xl, rs, rows=M, Cdim=K, eps=1e-6)
+        a16 = bf(x)
+        assert torch.equal(A[:M, :K].cpu(), a16) and torch.all(A[:, K:] == 0)
+        w16, bias, cs = eb.ln_fold_operands(w, bias, gamma, beta)
+        rs_cpu = rs[:M].cpu()
+        assert torch.allclose(rs_cpu.double(), eb.row_constants(x).double(), rtol=1e-5, atol=1e-6)
+    else:
+        a, w, bias = eb.gemm_operands(M, N, K, False)
+        a16, w16 = bf(a), bf(w)
+        A = torch.zeros(R, k_pad, dtype=torch.bfloat16)
+        A[:M, :K] = a16
+        A = A.to(gpu)
+    perm = _swiglu_interleave(N) if epi == "swiglu" else torch.arange(N)
+    Wd = torch.zeros(n_pad, k_pad, dtype=torch.bfloat16)
+    Wd[:N, :K] = w16[perm]
+    bc = torch.zeros(2 if ln else 1, n_pad)
+    bc[0, :N] = bias[perm]
+    if fill_pad and n_pad > N:
+        Wd[N:, :K] = bf(rnd(n_pad - N, K, seed=329, scale=K**-0.5))
+        bc[0, N:] = 3.0
+    if ln:
+        bc[1] = Wd.double().sum(1).float()
+        assert torch.equal(bc[1, :N], cs[perm])
+    else:
+        bc = bc[0]
+    kw = dict(m=M, n=N, ln_rowstat=rs) if ln else dict(m=M, n=N)
+    if epi == "vt":
+        heads, ntp = N // 64, ops.round_up(M, 8)
+        kp = ops.round_up(ntp, 64)
+        vt = torch.zeros(1, heads, 64, kp, dtype=torch.bfloat16, device=gpu)
+        ops.gemm(_lib.EPI_VT, A, Wd.to(gpu), vt, bc.to(gpu), heads=heads, ntp=ntp, kp=kp, ldc=0, **kw)
+        assert torch.all(vt[..., ntp:] == 0), "V^T columns beyond ntp were written"
+        got = vt[0].reshape(N, kp)[:, :M].t().float().cpu()
+    else:
+        cols = N // 2 if epi == "swiglu" else N
+        out = torch.full((R, cols), 7.0, dtype=torch.bfloat16, device=gpu)
+        ops.gemm({"bf16": _lib.EPI_BF16, "gelu": _lib.EPI_BF16_GELU, "swiglu": _lib.EPI_SWIGLU}[epi], A, Wd.to(gpu), out, bc.to(gpu), **kw)
+        assert torch.all(out[M:].float() == 7.0), "rows beyond M were written"
+        got = out[:M].float().cpu()
+    ref = eb.gemm_act(eb.gemm_lin(a16, w16, bias, rs_cpu, cs), epi)
+    assert torch.allclose(got, ref.float(), atol=3e-2 if ln else 2e-2, rtol=1e-2), float((got - ref).abs().max())
+    u = lambda t: t.double().unsqueeze(0)
+    eb.check(eb.GEMM_OP_OF[epi], f"{M}x{N}x{K} {epi}{' ln' if ln else ''}", u(got), u(ref), u(eb.rb(ref)))
+
+
+def _gemm_budget_params(shapes):
+    return [pytest.param(M, N, n_pad, K, k_pad, epi, id=f"{M}x{N}x{K}-{epi}") for M, N, n_pad, K, k_pad in shapes for epi in eb.GEMM_EPILOGUES
+            if eb.gemm_epilogue_fits(epi, M, N)]
+
+
+@pytest.mark.parametrize("ln", [False, True], ids=["plain", "ln"])
+@pytest.mark.parametrize("M,N,n_pad,K,k_pad,epi", _gemm_budget_params(eb.GEMM_SHAPES))
+def test_gemm_error_budget(gpu, M, N, n_pad, K, k_pad, epi, ln):
+    """The bf16-storing epilogues on the 64- / 128-wide tiles, with and without the LayerNorm fold: N = 16 and 40 (narrow tiles, one
+    column group), 300 x 256 (two row tiles with a ragged last one; the only one of these shapes SwiGLU -- hidden width a multiple of 64 --
+    and V^T -- whole heads, one slice of 304 token rows -- fit), and the ragged LayerNorm-fold width 432 -> 448 with K 144 -> 192.
+    R_col's last group is the last valid column (M >= 64 rows each), R_row's the last valid row(s)."""
+    _budget_gemm(gpu, M, N, n_pad, K, k_pad, epi, ln)
+
+
+@pytest.mark.parametrize("ln", [False, True], ids=["plain", "ln"])
+@pytest.mark.parametrize("gemm256_variant", [(1, 0), (1, 1), (1, 5), (1, 6), (1, 9), (2, 0)], indirect=True)
+@pytest.mark.parametrize("M,N,n_pad,K,k_pad,epi", _gemm_budget_params(eb.GEMM256_SHAPES))
+def test_gemm256_error_budget(gpu, M, N, n_pad, K, k_pad, epi, ln, gemm256_variant):
+    """The same on the 256-tile path: 2065 x 512 x 256 (9 x 2 tiles, ragged last row tile, the shortest K loop) and 1300 x 576 -> 768 x 576
+    (padded columns: one of the last column tile's four wave columns is inside N)."""
+    _budget_gemm(gpu, M, N, n_pad, K, k_pad, epi, ln)
+
+
+def _assert_fp32_forward_bound(name, got, ref, bound):
+    ratio = float(((got.double() - ref).abs() / bound).max())
+    print(f"fp32 forward bound {name}: max |got - ref64| / bound = {ratio:.3f}")
+    assert ratio <= 1.0, (name, ratio)
+
+
+@pytest.mark.parametrize("M,N,K", [(300, 256, 192), (130, 144, 320), (2065, 512, 256)])
+def test_gemm_fp32_epilogues_forward_bound(gpu, M, N, K):
+    """F32, RESID and PATCH store fp32: no emulation, the elementwise forward bound of fp32 accumulation in any order
+    (error_budget.fp32_forward_bound) against float64, beside the bands of the tests above.  (RESID_HL: _check_resid_hl.)"""
+    from cryovit_amd._lib import EPI_F32, EPI_PATCH, EPI_RESID
+    from cryovit_amd.engine import ops
+    from cryovit_amd.engine.hiera import _npad
+
+    a, w, b, gam = rnd(M, K, seed=71), rnd(N, K, seed=72, scale=K**-0.5), rnd(N, seed=73), rnd(N, seed=74) + 1
+    n_pad, k_pad = _npad(N, K), ops.round_up(K, 64)
+    R = ops.alloc_rows(M)
+    A, Wd = padded_bf16(a, R, k_pad, gpu), padded_bf16(w, n_pad, k_pad, gpu)
+    lin = bf(a).double() @ bf(w).double().t() + b.double()
+    # F32: out = gamma * (acc + bias)
+    out = torch.full((R, N), float("nan"), device=gpu)
+    ops.gemm(EPI_F32, A, Wd, out, padded_f32(b, n_pad, gpu), gamma=padded_f32(gam, n_pad + 256, gpu), m=M, n=N)
+    ref = gam.double() * lin
+    assert torch.allclose(out[:M].cpu(), ref.float(), atol=2e-3, rtol=1e-3) and torch.isnan(out[M:]).all()
+    _assert_fp32_forward_bound(f"F32 {M}x{N}x{K}", out[:M].cpu(), ref, eb.fp32_forward_bound(bf(a), bf(w), K, b, gain=gam))
+    # RESID: x += gamma * (acc + bias)
+    x0 = rnd(M, N, seed=11)
+    x = torch.zeros(R, N, device=gpu)
+    x[:M] = x0.to(gpu)
+    ops.gemm(EPI_RESID, A, Wd, x, padded_f32(b, n_pad, gpu), m=M, n=N, gamma=padded_f32(gam, n_pad, gpu))
+    ref = x0.double() + gam.double() * lin
+    assert torch.allclose(x[:M].cpu(), ref.float(), atol=1e-4, rtol=1e-4) and torch.all(x[M:] == 0)
+    _assert_fp32_forward_bound(f"RESID {M}x{N}x{K}", x[:M].cpu(), ref, eb.fp32_forward_bound(bf(a), bf(w), K, b, gain=gam, x0=x0))
+    # PATCH: token rows of one slice = acc + bias + pos (M patches, no class / register tokens in front)
+    pos = rnd(1 + M, N, seed=15)
+    ntp = ops.round_up(M, 8)
+    xt = torch.zeros(ops.alloc_rows(ntp), N, device=gpu)
+    ops.gemm(EPI_PATCH, A, Wd, xt, padded_f32(b, n_pad, gpu), m=M, n=N, pos=pos.to(gpu), npatch=M, ntp=ntp, tok0=0)
+    ref = lin + pos[1:].double()
+    assert torch.allclose(xt[:M].cpu(), ref.float(), atol=1e-4, rtol=1e-4) and torch.all(xt[M:] == 0)
+    _assert_fp32_forward_bound(f"PATCH {M}x{N}x{K}", xt[:M].cpu(), ref, eb.fp32_forward_bound(bf(a), bf(w), K, b, x0=pos[1:]))
+
+
+@pytest.mark.parametrize("rows,C", eb.LAYERNORM_CASES)
+def test_layernorm_error_budget(gpu, rows, C):
+    """70 rows (two-rows-per-wave kernel with a clamped last row pair at the narrow widths) at C = 128, 144 -- where dividing by C - 1
+    shows (R_all 2.2 / 2.0; at 1536 it is 1.01 and cannot) -- and at the workload's 1536."""
+    from cryovit_amd.engine import ops
+
+    x, w, b = eb.layernorm_operands(rows, C)
+    out = torch.full((rows, C + 16), 7.0, dtype=torch.bfloat16, device=gpu)
+    ops.layernorm(x.to(gpu), w.to(gpu), b.to(gpu), out, rows, C, 1e-6)
+    fam = eb.layernorm_case(rows, C, full=False)
+    got = out[:, :C].float().cpu()
+    assert torch.allclose(got, fam.ref[0].float(), atol=2e-2, rtol=1e-2)
+    assert torch.all(out[:, C:].float() == 7.0), "the pad columns of the output rows were written"
+    eb.check("layernorm", f"rows={rows} C={C}", got.double().unsqueeze(0), fam.ref, fam.emu)
+
+
+def test_final_norm_error_budget(gpu):
+    """cvx_final_norm_features (fp16 stores) on test_final_norm_and_k9_layout's operands: both fp16 copies against float64."""
+    from cryovit_amd.engine import ops
+
+    x, w, bb, (b, hp, wp, C, n_reg, nt, ntp) = eb.final_norm_operands()
+    f16 = torch.full((C, b, hp, wp), -9.0, dtype=torch.float16, device=gpu)
+    cl = torch.zeros(b, hp, wp, C, dtype=torch.float16, device=gpu)
+    ops.final_norm_features(x.reshape(-1, C).to(gpu), w.to(gpu), bb.to(gpu), 1e-6, slices=b, ntp=ntp, tok0=1 + n_reg, hp=hp, wp=wp,
+                            Cdim=C, feats_f16=f16, d_total=b, d0=0, feats_cl=cl)
+    fam = eb.final_norm_case(full=False)
+    got = cl.float().cpu().reshape(1, b * hp * wp, C)
+    assert torch.allclose(got, fam.ref.float(), atol=3e-3, rtol=2e-3)
+    assert torch.equal(cl.cpu().permute(3, 0, 1, 2), f16.cpu())
+    eb.check("final_norm", "3x(4x6) C=128", got.double(), fam.ref, fam.emu)
+
+
+@pytest.mark.parametrize("C,G,act", [(32, 8, 0), (8, 8, 0), (8, 8, 1)])
+def test_groupnorm_error_budget(gpu, C, G, act):
+    """GroupNorm (4 channels per group) and, G = C, InstanceNorm with and without the fused GELU; columns are channels, so R_col's last
+    group holds the last group's statistics."""
+    from cryovit_amd.engine import ops
+
+    x, w, b = eb.groupnorm_operands(C, G)
+    D, H, W = eb.GROUPNORM_DHW
+    out = torch.zeros_like(x, device=gpu)
+    stats = torch.zeros(ops.gn_stats_size(G), device=gpu)
+    ops.groupnorm(x.to(gpu), w.to(gpu), b.to(gpu), out, stats, nvox=D * H * W, Cdim=C, G=G, eps=1e-3, act=act)
+    fam = eb.groupnorm_case(C, G, bool(act), full=False)
+    got = out.float().cpu().reshape(1, -1, C)
+    assert torch.allclose(got, fam.ref.float(), atol=4e-3, rtol=2e-3), float((got - fam.ref).abs().max())
+    eb.check("groupnorm", f"C={C} G={G}{' gelu' if act else ''}", got.double(), fam.ref, fam.emu)
+
+
+def _budget_conv3d(gpu, case, seed, halo_options):
+    from cryovit_amd import _lib
+    from cryovit_amd.engine import ops
+    from cryovit_amd.engine.head import _conv3_weight, _npad, _pad1
+
+    Cin, Cout, dil, D, H, W = case
+    x, w, b = eb.conv3d_operands(*case, seed)
+    fam = eb.conv3d_case(*case, seed=seed, full=False)
+    nv = D * H * W
+    zero = torch.zeros(256, dtype=torch.uint8, device=gpu)
+    try:
+        for halo in halo_options:
+            _lib.set_option("conv_halo", halo)
+            out = torch.full((nv + 8, Cout), 7.0, dtype=torch.float16, device=gpu)
+            ops.conv3d(x.to(gpu), _conv3_weight(w).to(gpu), _pad1(b, _npad(Cout)).to(gpu), out, zero, Cin=Cin, D=D, H=H, W=W, dil=dil,
+                       cout=Cout, act=1)
+            got = out[:nv].float().cpu().reshape(D * H, W, Cout)
+            assert torch.allclose(got, fam.ref.float(), atol=3e-3, rtol=2e-3), float((got - fam.ref).abs().max())
+            assert torch.all(out[nv:].float() == 7.0)
+            eb.check("conv", f"conv3d {case} conv_halo={halo}", got.double(), fam.ref, fam.emu)
+    finally:
+        _lib.set_option("conv_halo", 2)
+
+
+@pytest.mark.parametrize("case", eb.CONV3D_CASES, ids=str)
+def test_conv3d_error_budget(gpu, case):
+    """3x3x3 convolution + GELU, dilation 1 and 2 in z, at 8 -> 8 and 32 -> 16 channels, on the kernel the call takes by default and on
+    the implicit-GEMM kernel; row groups stay inside one line of one plane (faces and corners form their own groups)."""
+    _budget_conv3d(gpu, case, 38, (2, 0))
+
+
+@pytest.mark.parametrize("case", eb.HALO_CASES, ids=str)
+def test_conv3d_halo_kernel_error_budget(gpu, case):
+    """The LDS kernels of the few-channel layers at a ragged x tile (W = 66): the z-marching ring kernel, the tile-halo kernel on the
+    ablation build, and the implicit-GEMM kernel of the same call."""
+    _budget_conv3d(gpu, case, 58, (2, 1, 0) if ABLATION else (2, 0))
+
+
+@pytest.mark.parametrize("c2,c3,D,H,W", eb.CONVT_CASES)
+def test_conv_transpose_error_budget(gpu, c2, c3, D, H, W):
+    """The (1, 2, 2) transposed convolution + GELU: the dedicated few-channel kernel and the GEMM-tile path of the same call."""
+    from cryovit_amd import _lib
+    from cryovit_amd._lib import EPI_CONVT
+    from cryovit_amd.engine import ops
+    from cryovit_amd.engine.head import _npad, _pad1, _pad2
+
+    nv = D * H * W
+    x, wt, b = eb.convt_operands(c2, c3, D, H, W)
+    fam = eb.convt_case(c2, c3, D, H, W, full=False)
+    A = torch.zeros(ops.alloc_rows(nv) * c2 + 4096, dtype=torch.float16)
+    A[: nv * c2] = x.reshape(-1)
+    A = A.to(gpu)
+    a2 = torch.as_strided(A, (ops.alloc_rows(nv), c2), (c2, 1))
+    wg = wt[:, :, 0].permute(2, 3, 1, 0).reshape(4 * c3, c2)
+    wp, bp = _pad2(wg, _npad(4 * c3), ops.round_up(c2, 64)).to(gpu), _pad1(b.repeat(4), _npad(4 * c3)).to(gpu)
+    try:
+        for small in (1, 0):
+            _lib.set_option("convt_small", small)
+            out = torch.full((D, 2 * H, 2 * W, c3), 7.0, dtype=torch.float16, device=gpu)
+            ops.gemm(EPI_CONVT, a2, wp, out, bp, m=nv, n=4 * c3, H=H, W=W, cout=c3, act=1, ldc=c3)
+            got = out.float().cpu().reshape(D * 2 * H, 2 * W, c3)
+            assert torch.allclose(got, fam.ref.float(), atol=3e-3, rtol=2e-3), float((got - fam.ref).abs().max())
+            eb.check("conv", f"convt {(c2, c3, D, H, W)} convt_small={small}", got.double(), fam.ref, fam.emu)
+    finally:
+        _lib.set_option("convt_small", 1)
 
 
 def test_variants_on_the_ablation_build(gpu):

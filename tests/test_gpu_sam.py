@@ -71,6 +71,41 @@ def _window_attention_case(gpu, ops, G, ws, heads, hd, pooled):
     assert torch.all(out[:, C:] == 0) and torch.all(out[D * Gq * Gq :] == 0)  # nothing outside the valid block is written
 
 
+@pytest.mark.parametrize("G,ws,heads,hd,pooled", [(8, 4, 3, 72, False), (16, 8, 2, 72, True), (32, 16, 2, 56, False), (16, 8, 1, 96, True)])
+@pytest.mark.parametrize("x32", [0, 1])
+def test_window_attention_error_budget(gpu, G, ws, heads, hd, pooled, x32):
+    """The rms error of hiera.hip's window attention against float64, in units of the error its documented roundings must produce
+    (tests/error_budget.py; bounds from the CPU rule): 16 keys (a quarter tile), 64 keys with pooled queries, 256 keys (the online
+    rescale over four tiles) at head dim 56 (rows merged in pairs), head dim 96.  Operands and band of test_window_attention."""
+    import error_budget as eb
+    from cryovit_amd import _lib
+    from cryovit_amd.engine import ops
+
+    D, C = eb.WINDOW_D, heads * hd
+    qkv = eb.window_operands(G, ws, heads, hd)
+    rows = D * G * G
+    buf = torch.zeros(ops.alloc_rows(rows), 3 * C, dtype=torch.bfloat16, device=gpu)
+    buf[:rows] = _rows_from_grid(qkv).to(gpu)
+    Gq, wsq = (G // 2, ws // 2) if pooled else (G, ws)
+    out = torch.zeros(ops.alloc_rows(D * Gq * Gq), C + 24, dtype=torch.bfloat16, device=gpu)
+    _lib.set_option("win_attn_x32", x32)
+    try:
+        if pooled:
+            qp = torch.zeros(ops.alloc_rows(D * Gq * Gq), C, dtype=torch.bfloat16, device=gpu)
+            ops.pool2x2(buf, qp, slices=D, grid=G, C=C)
+            ops.window_attention(qp, 0, buf, C, 2 * C, out, slices=D, heads=heads, head_dim=hd, grid=G, window=ws, q_grid=Gq, q_window=wsq)
+        else:
+            ops.window_attention(buf, 0, buf, C, 2 * C, out, slices=D, heads=heads, head_dim=hd, grid=G, window=ws, q_grid=G, q_window=ws)
+    finally:
+        _lib.set_option("win_attn_x32", 0)
+    fam = eb.window_case(G, ws, heads, hd, pooled, full=False)
+    got = eb.window_rows(out[: D * Gq * Gq, :C].float().cpu(), Gq, wsq, heads, hd)
+    err = (got - fam.ref).abs()
+    assert err.max() <= 3e-2 and err.mean() <= 3e-3, (float(err.max()), float(err.mean()))
+    assert torch.all(out[:, C:] == 0) and torch.all(out[D * Gq * Gq :] == 0)  # nothing outside the valid block is written
+    eb.check("window_attention", f"G={G} ws={ws} heads={heads} hd={hd} pooled={pooled} x32={x32}", got, fam.ref, fam.emu)
+
+
 def test_pool_cast_fpn(gpu):
     from cryovit_amd.engine import ops
 

@@ -37,6 +37,27 @@ def test_conv2s2(gpu, C, Cout, D, H, W):
     assert torch.all(out[nvo:].float() == 7.0)
 
 
+@pytest.mark.parametrize("C,Cout,D,H,W", [(8, 8, 4, 6, 10)])
+def test_conv2s2_error_budget(gpu, C, Cout, D, H, W):
+    """The rms error of the stride-2 convolution against float64 in units of its one fp16 store rounding (tests/error_budget.py; bounds
+    from the CPU rule); operands and band of test_conv2s2.  Row groups stay inside one line of one output plane."""
+    import error_budget as eb
+    from cryovit_amd.engine import ops
+    from cryovit_amd.engine.head import _npad, _pad1, _pad2
+
+    x, w, b = eb.conv2s2_operands(C, Cout, D, H, W)
+    fam = eb.conv2s2_case(C, Cout, D, H, W, full=False)
+    nvo = D * H * W // 8
+    out = torch.full((nvo + 8, Cout), 7.0, dtype=torch.float16, device=gpu)
+    zero = torch.zeros(256, dtype=torch.uint8, device=gpu)
+    wp = _pad2(w.permute(0, 2, 3, 4, 1).reshape(Cout, 8 * C), _npad(Cout), 8 * C)
+    ops.conv2s2(x.to(gpu), wp.to(gpu), _pad1(b, _npad(Cout)).to(gpu), out, zero, Cin=C, D=D, H=H, W=W, cout=Cout, act=0)
+    got = out[:nvo].float().cpu().reshape(D // 2 * (H // 2), W // 2, Cout)
+    assert torch.allclose(got, fam.ref.float(), atol=3e-3, rtol=2e-3), float((got - fam.ref).abs().max())
+    assert torch.all(out[nvo:].float() == 7.0)
+    eb.check("conv", f"conv2s2 {(C, Cout, D, H, W)}", got.double(), fam.ref, fam.emu)
+
+
 @pytest.mark.parametrize("c2,c3", [(32, 16), (16, 8), (256, 64)])
 def test_conv_transpose_3d(gpu, c2, c3):
     """nn.ConvTranspose3d(c2, c3, 2, stride=2): GEMM with N = 8*c3 and the 3-D pixel-shuffle epilogue."""
