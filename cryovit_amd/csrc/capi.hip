@@ -9,6 +9,10 @@ int cvx_fail(const char* msg) {
     snprintf(g_err, sizeof(g_err), "%s", msg);
     return CVX_ERR_ARG;
 }
+int cvx_fail(const char* entry, const char* why) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", entry, why);
+    return CVX_ERR_ARG;
+}
 int cvx_fail_hip(hipError_t e, const char* what) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
     return CVX_ERR_HIP;

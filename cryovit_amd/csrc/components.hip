@@ -13,10 +13,7 @@
 //   6. relabel+table labels = id, and the table rows by integer atomic add / min / max (exact and commutative)
 // Only the backward half of the neighbourhood (3 of 6, 13 of 26) is visited: the relation is symmetric.
 // Every sum is an integer, so the labels and the table are bit-identical from run to run.
-#include "voxel_rows.h"
-#include "host_util.h"
-
-#include <limits.h>
+#include "entry_checks.h"
 
 namespace cvx {
 
@@ -198,8 +195,7 @@ __global__ __launch_bounds__(kCclThreads) void k_ccl_count_roots(const int* __re
 #pragma unroll
         for (int i = 0; i < RV; ++i) c += i < cnt && is_kept_root(p[i], base + i, count, min_size);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -207,17 +203,6 @@ __global__ __launch_bounds__(kCclThreads) void k_ccl_count_roots(const int* __re
         for (int w = 0; w < kCclThreads / 64; ++w) s += red[w];
         partial[blockIdx.x] = s;
     }
-}
-
-// inclusive scan over the lanes of a wave
-__device__ __forceinline__ int wave_scan_incl(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
 }
 
 // 5b. partial[] -> its exclusive prefix sums, *k_out = the total: one workgroup walking the array in index order
@@ -277,14 +262,6 @@ __global__ __launch_bounds__(kCclThreads) void k_ccl_assign(int* __restrict__ pa
     }
 }
 
-// table rows start as the empty box: counts and sums 0, lower bounds past the volume, upper bounds -1
-__global__ __launch_bounds__(kCclThreads) void k_ccl_table_init(long long* __restrict__ table, long k, Dims d) {
-    const long i = (long)blockIdx.x * kCclThreads + threadIdx.x;
-    if (i >= k * CVX_COMPONENT_COLS) return;
-    const int c = (int)(i % CVX_COMPONENT_COLS);
-    table[i] = table_empty(c, d);
-}
-
 // 6. labels[v] = id of v's root (0: background or removed), and the table from runs of one id along x
 __global__ __launch_bounds__(kCclThreads) void k_ccl_relabel(const int* __restrict__ parent, int* __restrict__ labels,
                                                              long long* __restrict__ table, long k, Dims d, int segs) {
@@ -320,11 +297,7 @@ struct CclLayout {
 
 // scratch: [0, 16) K (int32), then the block counts, then parent int32 [n]; every piece 16-B aligned
 bool ccl_layout(int D, int H, int W, CclLayout& L) {
-    if (D < 0 || H < 0 || W < 0) return false;
-    L.n = (long)D * H;  // < 2^62
-    if (W && L.n > CVX_COMPONENT_MAX_VOXELS / W) return false;
-    L.n *= W;
-    if (L.n > CVX_COMPONENT_MAX_VOXELS) return false;
+    if (extents_fault(D, H, W, kExtentAny, L.n)) return false;
     L.nb = (L.n + kChunk - 1) / kChunk;
     L.off_partial = 16;
     L.off_parent = L.off_partial + (L.nb * 4 + 15) / 16 * 16;
@@ -336,14 +309,14 @@ bool ccl_layout(int D, int H, int W, CclLayout& L) {
 
 extern "C" long cvx_components_scratch_bytes(int D, int H, int W) {
     CclLayout L;
-    if (!ccl_layout(D, H, W, L)) return cvx_fail("components: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (!ccl_layout(D, H, W, L)) return cvx_fail("components", kExtentsRule);
     return L.bytes;
 }
 
 extern "C" int cvx_components_label(const uint8_t* mask, int D, int H, int W, int connectivity, long min_size, int32_t* labels,
                                     void* scratch, long scratch_bytes, hipStream_t st) {
     CclLayout L;
-    if (!ccl_layout(D, H, W, L)) return cvx_fail("components_label: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (!ccl_layout(D, H, W, L)) return cvx_fail("components_label", kExtentsRule);
     if (connectivity != 6 && connectivity != 26) return cvx_fail("components_label: connectivity must be 6 or 26");
     if (min_size < 0) return cvx_fail("components_label: min_size < 0");
     if (!scratch || scratch_bytes < L.bytes) return cvx_fail("components_label: null or short scratch (cvx_components_scratch_bytes)");
@@ -357,11 +330,11 @@ extern "C" int cvx_components_label(const uint8_t* mask, int D, int H, int W, in
     int* partial = (int*)((char*)scratch + L.off_partial);
     int* parent = (int*)((char*)scratch + L.off_parent);
     const Dims d = ccl_dims(D, H, W);
-    const int ms = (int)(min_size < INT_MAX ? min_size : INT_MAX);
-    const long tiles = (long)d.tx * d.ty * ((D + TZ - 1) / TZ);  // <= n
-    const unsigned nlin = (unsigned)((L.n + kCclThreads - 1) / kCclThreads);
+    const int ms = clamp_int(min_size);
+    const long tiles = tile_count(d);
+    const unsigned nlin = blocks_of(L.n);
     const int segs = (W + RV - 1) / RV;
-    const unsigned nrow = (unsigned)(((long)D * H * segs + kCclThreads - 1) / kCclThreads);
+    const unsigned nrow = blocks_of((long)D * H * segs);
     int rc;
     if (connectivity == 26) hipLaunchKernelGGL(k_ccl_tile<26>, dim3((unsigned)tiles), dim3(kCclThreads), 0, st, mask, parent, d);
     else hipLaunchKernelGGL(k_ccl_tile<6>, dim3((unsigned)tiles), dim3(kCclThreads), 0, st, mask, parent, d);
@@ -387,7 +360,7 @@ extern "C" int cvx_components_label(const uint8_t* mask, int D, int H, int W, in
 extern "C" int cvx_components_table(int D, int H, int W, long k, int32_t* labels, int64_t* table, const void* scratch,
                                     long scratch_bytes, hipStream_t st) {
     CclLayout L;
-    if (!ccl_layout(D, H, W, L)) return cvx_fail("components_table: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (!ccl_layout(D, H, W, L)) return cvx_fail("components_table", kExtentsRule);
     if (k < 0 || k > L.n) return cvx_fail("components_table: k outside [0, D*H*W]");
     if (!scratch || scratch_bytes < L.bytes) return cvx_fail("components_table: null or short scratch (cvx_components_scratch_bytes)");
     if (L.n == 0) return 0;
@@ -401,11 +374,9 @@ extern "C" int cvx_components_table(int D, int H, int W, long k, int32_t* labels
     const int* parent = (const int*)((const char*)scratch + L.off_parent);
     const Dims d = ccl_dims(D, H, W);
     const int segs = (W + RV - 1) / RV;
-    const unsigned nrow = (unsigned)(((long)D * H * segs + kCclThreads - 1) / kCclThreads);
-    const unsigned ninit = (unsigned)((k * CVX_COMPONENT_COLS + kCclThreads - 1) / kCclThreads);
-    hipLaunchKernelGGL(k_ccl_table_init, dim3(ninit), dim3(kCclThreads), 0, st, (long long*)table, k, d);
+    hipLaunchKernelGGL(k_table_init<CVX_COMPONENT_COLS>, dim3(blocks_of(k * CVX_COMPONENT_COLS)), dim3(kCclThreads), 0, st, (long long*)table, k, d);
     int rc = cvx_check_launch();
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ccl_relabel, dim3(nrow), dim3(kCclThreads), 0, st, parent, labels, (long long*)table, k, d, segs);
+    hipLaunchKernelGGL(k_ccl_relabel, dim3(blocks_of((long)D * H * segs)), dim3(kCclThreads), 0, st, parent, labels, (long long*)table, k, d, segs);
     return cvx_check_launch();
 }

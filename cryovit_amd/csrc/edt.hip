@@ -24,9 +24,7 @@
 // squared step alone reaches the largest of the wave's current minima.  The site bitmaps and the walk are in edt_pieces.h, which
 // nearest.hip shares.
 #include "edt_pieces.h"
-#include "host_util.h"
-
-#include <limits.h>
+#include "entry_checks.h"
 
 namespace cvx {
 
@@ -112,8 +110,8 @@ __global__ __launch_bounds__(kLineWavesMax * 64) void k_edt_lines_long(int* vol,
 // ---- per-instance statistics over (labels, d2) ----
 
 // table rows while the voxels are reduced: count, min d2, the key (d2 << 32 | INT32_MAX - index), unused
-__global__ __launch_bounds__(kStatThreads) void k_dstat_init(long long* __restrict__ out, long k) {
-    const long i = (long)blockIdx.x * kStatThreads + threadIdx.x;
+__global__ __launch_bounds__(kCclThreads) void k_dstat_init(long long* __restrict__ out, long k) {
+    const long i = (long)blockIdx.x * kCclThreads + threadIdx.x;
     if (i >= k * CVX_DSTAT_COLS) return;
     const int c = (int)(i % CVX_DSTAT_COLS);
     out[i] = c == 1 ? LLONG_MAX : c == 2 ? -1 : 0;
@@ -133,32 +131,18 @@ __device__ __forceinline__ void dstat_flush(long long* __restrict__ out, const D
     if (r.key > *(volatile long long*)(row + 2)) atomicMax(row + 2, r.key);
 }
 
-__global__ __launch_bounds__(kStatThreads) void k_dstat_reduce(const int* __restrict__ labels, const int* __restrict__ d2, long long* __restrict__ out,
-                                                               long k, int thr, long rows, int W, int segs) {
-    const long t = (long)blockIdx.x * kStatThreads + threadIdx.x;
-    const long row = t / segs;
-    if (row >= rows) return;
-    const int x0 = (int)(t % segs) * kStatRv;
-    const int cnt = min(kStatRv, W - x0);
-    const long v0 = row * W + x0;
-    int id[kStatRv], d[kStatRv];
-    if (cnt == kStatRv && (((uintptr_t)(labels + v0) | (uintptr_t)(d2 + v0)) & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < kStatRv / 4; ++q) {
-            const int4 a = ((const int4*)(labels + v0))[q], b = ((const int4*)(d2 + v0))[q];
-            id[4 * q] = a.x; id[4 * q + 1] = a.y; id[4 * q + 2] = a.z; id[4 * q + 3] = a.w;
-            d[4 * q] = b.x; d[4 * q + 1] = b.y; d[4 * q + 2] = b.z; d[4 * q + 3] = b.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < kStatRv; ++i) {
-            id[i] = i < cnt ? labels[v0 + i] : 0;
-            d[i] = i < cnt ? d2[v0 + i] : kEdtNone;
-        }
-    }
+__global__ __launch_bounds__(kCclThreads) void k_dstat_reduce(const int* __restrict__ labels, const int* __restrict__ d2, long long* __restrict__ out,
+                                                              long k, int thr, Dims dims, int segs) {
+    long row;
+    int x0, cnt;
+    if (!row_piece(dims, segs, row, x0, cnt)) return;
+    const long v0 = row * dims.W + x0;
+    int id[RV], d[RV];
+    row_load(labels + v0, cnt, id);
+    row_load(d2 + v0, cnt, d);  // past the row's end id and d are 0: the id is looked at first, and 0 is nobody's
     DstatRun r{0, 0, 0, -1};
 #pragma unroll
-    for (int i = 0; i < kStatRv; ++i) {
+    for (int i = 0; i < RV; ++i) {
         const int c = id[i] >= 1 && id[i] <= k ? id[i] : 0;  // ids past the table are nobody's
         if (c != r.id) {
             dstat_flush(out, r);
@@ -172,8 +156,8 @@ __global__ __launch_bounds__(kStatThreads) void k_dstat_reduce(const int* __rest
     dstat_flush(out, r);
 }
 
-__global__ __launch_bounds__(kStatThreads) void k_dstat_finalize(long long* __restrict__ out, long k) {
-    const long i = (long)blockIdx.x * kStatThreads + threadIdx.x;
+__global__ __launch_bounds__(kCclThreads) void k_dstat_finalize(long long* __restrict__ out, long k) {
+    const long i = (long)blockIdx.x * kCclThreads + threadIdx.x;
     if (i >= k) return;
     long long* row = out + i * CVX_DSTAT_COLS;
     const long long key = row[2];
@@ -221,7 +205,7 @@ int edt_launch_lines(int* vol, int n, long stride, long lines, long ostride, int
 
 extern "C" int cvx_edt_squared(const void* src, int src_dtype, int sites, int D, int H, int W, int32_t* out, hipStream_t st) {
     long n;
-    if (!edt_extents(D, H, W, n)) return cvx_fail("edt_squared: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("edt_squared", kExtentsRule);
     if (src_dtype != CVX_EDT_U8 && src_dtype != CVX_EDT_I32) return cvx_fail("edt_squared: src_dtype must be CVX_EDT_U8 or CVX_EDT_I32");
     if (sites != CVX_EDT_SITES_ZERO && sites != CVX_EDT_SITES_NONZERO) return cvx_fail("edt_squared: sites must be CVX_EDT_SITES_ZERO or CVX_EDT_SITES_NONZERO");
     if (n == 0) return 0;
@@ -239,21 +223,20 @@ extern "C" int cvx_edt_squared(const void* src, int src_dtype, int sites, int D,
 extern "C" int cvx_instance_distance_stats(const int32_t* labels, const int32_t* d2, int D, int H, int W, long k, int threshold_d2,
                                            int64_t* out, hipStream_t st) {
     long n;
-    if (!edt_extents(D, H, W, n)) return cvx_fail("instance_distance_stats: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("instance_distance_stats", kExtentsRule);
     if (k < 0) return cvx_fail("instance_distance_stats: k < 0");
     if (k == 0) return 0;
     if (!out || (n > 0 && (!labels || !d2))) return cvx_fail("instance_distance_stats: null pointer");
     if (((uintptr_t)out & 7) || (((uintptr_t)labels | (uintptr_t)d2) & 3)) return cvx_fail("instance_distance_stats: misaligned pointer");
-    const unsigned nk = (unsigned)((k * CVX_DSTAT_COLS + kStatThreads - 1) / kStatThreads);
-    hipLaunchKernelGGL(k_dstat_init, dim3(nk), dim3(kStatThreads), 0, st, (long long*)out, k);
+    hipLaunchKernelGGL(k_dstat_init, dim3(blocks_of(k * CVX_DSTAT_COLS)), dim3(kCclThreads), 0, st, (long long*)out, k);
     int rc = cvx_check_launch();
     if (rc) return rc;
     if (n > 0) {
-        const int segs = (W + kStatRv - 1) / kStatRv;
-        const unsigned nrow = (unsigned)(((long)D * H * segs + kStatThreads - 1) / kStatThreads);
-        hipLaunchKernelGGL(k_dstat_reduce, dim3(nrow), dim3(kStatThreads), 0, st, labels, d2, (long long*)out, k, threshold_d2, (long)D * H, W, segs);
+        const int segs = (W + RV - 1) / RV;
+        hipLaunchKernelGGL(k_dstat_reduce, dim3(blocks_of((long)D * H * segs)), dim3(kCclThreads), 0, st, labels, d2, (long long*)out, k, threshold_d2,
+                           ccl_dims(D, H, W), segs);
         if ((rc = cvx_check_launch())) return rc;
     }
-    hipLaunchKernelGGL(k_dstat_finalize, dim3((unsigned)((k + kStatThreads - 1) / kStatThreads)), dim3(kStatThreads), 0, st, (long long*)out, k);
+    hipLaunchKernelGGL(k_dstat_finalize, dim3(blocks_of(k)), dim3(kCclThreads), 0, st, (long long*)out, k);
     return cvx_check_launch();
 }

@@ -1,5 +1,5 @@
 // What the distance map (edt.hip) and the nearest-instance map (nearest.hip) share: the site bitmaps of the row pass, the
-// pruned min-plus walk of the line passes and its tiling, the geometry of the lines and the extent check of the entry points.
+// pruned min-plus walk of the line passes and its tiling, and the geometry of the lines.
 #pragma once
 #include "common.h"
 #include "../../include/cryovit_hip.h"
@@ -14,8 +14,6 @@ constexpr int kSlab = 64;                  // min-plus passes: adjacent x per wo
 constexpr int kIpt = 8;                    // outputs per thread
 constexpr int kJu = 8;                     // sources fetched per pruning test
 constexpr int kLineWavesMax = 16;
-constexpr int kStatThreads = 256;
-constexpr int kStatRv = 16;                // voxels of one row per thread in the reductions over a volume
 
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
@@ -155,14 +153,5 @@ struct LineGeom {
     long ostride;  // between two lines of one slab column
     int W, nslab;  // row length, slabs per row
 };
-
-// extents >= 0 and D*H*W <= CVX_COMPONENT_MAX_VOXELS; n = the voxel count
-inline bool edt_extents(int D, int H, int W, long& n) {
-    if (D < 0 || H < 0 || W < 0) return false;
-    n = (long)D * H;  // < 2^62
-    if (W && n > CVX_COMPONENT_MAX_VOXELS / W) return false;
-    n *= W;
-    return n <= CVX_COMPONENT_MAX_VOXELS;
-}
 
 }  // namespace cvx

@@ -4,8 +4,7 @@
 // HBM-bound streaming kernels: 16-B loads, grid-stride, ragged tail on block 0.  Integer results only: min / max / the
 // presence bitmap / the counts are combined with integer atomics (min, max, or, add), which are exact and commutative, so
 // every call gives the same bits whatever the block order; no float atomics.
-#include "common.h"
-#include "../../include/cryovit_hip.h"
+#include "voxel_rows.h"  // wave_sum
 #include "host_util.h"
 
 #include <limits.h>
@@ -67,11 +66,6 @@ __device__ __forceinline__ int wave_max_i(int v) {
 __device__ __forceinline__ uint32_t wave_or_u(uint32_t v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
@@ -211,7 +205,7 @@ __global__ __launch_bounds__(kLabelThreads) void k_label_metrics(const float* __
     const int wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const unsigned long long s = wave_sum_u64(acc[k]);
+        const unsigned long long s = (unsigned long long)wave_sum((long long)acc[k]);  // two's complement: the same bits
         if ((threadIdx.x & 63) == 0) red[k][wave] = s;
     }
     __syncthreads();

@@ -28,15 +28,11 @@
 // the triangles of one row of cells change id every few dozen (a row crosses several instances): with only thickness.hip's "a
 // wave of one id" stage most waves fell through to global atomics on a few dozen hot rows (30 ms for 9e6 triangles).  The smoothing step accumulates the neighbour sums
 // by 64-bit integer atomics (order-independent) and applies them per vertex with a floor division.
-#include "voxel_rows.h"
-#include "host_util.h"
+#include "entry_checks.h"
 #include "mesh_tables.h"
-
-#include <limits.h>
 
 namespace cvx {
 
-constexpr int kMeshExtentMax = 32768;
 constexpr int kMeshScanThreads = 1024, kMeshScanPer = 4;
 constexpr int kMeshRows = (TZ + 1) * (TY + 1), kMeshRowLen = TX + 1;  // the voxels whose vertices a tile's triangles use
 constexpr long kMeshIndexEnd = 1L << 31;                              // V and T stay below
@@ -86,22 +82,6 @@ __device__ __forceinline__ int mesh_cell_triangles(unsigned cube) {
            mesh_case_triangles(__popc(mesh_tet_case<4>(cube))) + mesh_case_triangles(__popc(mesh_tet_case<5>(cube)));
 }
 
-__device__ __forceinline__ int mesh_wave_scan_incl(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int mesh_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // cd: the extents of the cell lattice (D + 1, H + 1, W + 1) and its tiles
 __global__ __launch_bounds__(kCclThreads) void k_mesh_classify(const int* __restrict__ labels, int D, int H, int W, Dims cd,
                                                                int* __restrict__ seg_v, int* __restrict__ seg_t) {
@@ -117,8 +97,8 @@ __global__ __launch_bounds__(kCclThreads) void k_mesh_classify(const int* __rest
     for (int yy = 0; yy < TY && y0 + yy < cd.H; ++yy) {
         // a cell past the lattice along x has only background corners: it counts nothing
         const unsigned cube = mesh_cube(ids, wave, yy, lane);
-        const int nv = mesh_wave_sum(__popc(mesh_edge_mask(cube)));
-        const int nt = mesh_wave_sum(mesh_cell_triangles(cube));
+        const int nv = wave_sum((int)__popc(mesh_edge_mask(cube)));
+        const int nt = wave_sum(mesh_cell_triangles(cube));
         if (lane == 0) {
             const long seg = ((long)cz * cd.H + y0 + yy) * cd.tx + x0 / TX;
             seg_v[seg] = nv;
@@ -144,7 +124,7 @@ __global__ __launch_bounds__(kMeshScanThreads) void k_mesh_scan(int* __restrict_
             sv += v[j];
             st += t[j];
         }
-        const int incl_v = mesh_wave_scan_incl(sv), incl_t = mesh_wave_scan_incl(st);  // below 4096 * 64 * 12
+        const int incl_v = wave_scan_incl(sv), incl_t = wave_scan_incl(st);  // below 4096 * 64 * 12
         if ((threadIdx.x & 63) == 63) wsum_v[wave] = incl_v, wsum_t[wave] = incl_t;
         __syncthreads();
         int woff_v = 0, woff_t = 0, total_v = 0, total_t = 0;
@@ -198,7 +178,7 @@ __global__ __launch_bounds__(kCclThreads) void k_mesh_emit(const int* __restrict
         const bool row = cz < cd.D && cy < cd.H;  // the whole wave alike; a voxel past the lattice has no active edge
         const unsigned mask = row ? mesh_edge_mask(mesh_cube(ids, a, b, lane)) : 0u;
         const int cnt = __popc(mask);
-        const int first = (row ? seg_v[((long)cz * cd.H + cy) * cd.tx + xt] : 0) + mesh_wave_scan_incl(cnt) - cnt;
+        const int first = (row ? seg_v[((long)cz * cd.H + cy) * cd.tx + xt] : 0) + wave_scan_incl(cnt) - cnt;
         vbase[r * kMeshRowLen + lane] = first;
         vmask[r * kMeshRowLen + lane] = (unsigned char)mask;
         if (a < TZ && b < TY && mask) {
@@ -231,7 +211,7 @@ __global__ __launch_bounds__(kCclThreads) void k_mesh_emit(const int* __restrict
     for (int yy = 0; yy < TY && y0 + yy < cd.H; ++yy) {
         const unsigned cube = mesh_cube(ids, wave, yy, lane);
         const int nt = mesh_cell_triangles(cube);
-        int slot = seg_t[((long)cz * cd.H + y0 + yy) * cd.tx + xt] + mesh_wave_scan_incl(nt) - nt;
+        int slot = seg_t[((long)cz * cd.H + y0 + yy) * cd.tx + xt] + wave_scan_incl(nt) - nt;
         if (nt == 0) continue;
         const int vcell = (wave * (TY + 1) + yy) * kMeshRowLen + lane;  // the cell's corner 0 in vbase / vmask
         const int icell = (wave * kHaloY + yy) * kHaloX + lane;         // and in ids
@@ -350,17 +330,15 @@ __global__ __launch_bounds__(kCclThreads) void k_mesh_stats(const int* __restric
                    U(p[0][1]) * (U(p[1][2]) * U(p[2][0]) - U(p[1][0]) * U(p[2][2])) +
                    U(p[0][2]) * (U(p[1][0]) * U(p[2][1]) - U(p[1][1]) * U(p[2][0]));
     }
-    // the wave: one id among the threads that hold one?
-    const unsigned long long has = __ballot(cur != 0);
-    const int first = has ? __shfl(cur, __ffsll((long long)has) - 1) : 0;
-    const bool uniform = __all(cur == 0 || cur == first);
-    if (!uniform) {
+    // the wave: one id among the threads that hold one?  Then lane 0 deposits the wave's sums; else every thread its own
+    const int one = wave_single_id(cur);
+    if (!one) {
         if (cur) deposit(cur, acc);
-    } else if (first) {
+    } else {
         acc.n = wave_sum(acc.n);
         acc.area2 = (unsigned long long)wave_sum((long long)acc.area2);
         acc.det = (unsigned long long)wave_sum((long long)acc.det);
-        if (lane == 0) deposit(first, acc);
+        if (lane == 0) deposit(one, acc);
     }
     __syncthreads();
     // the workgroup: one set of 64-bit integer atomics per id it met
@@ -421,26 +399,15 @@ struct MeshLayout {
 
 // what every entry refuses about the volume.  nullptr: fine
 const char* mesh_extents(int D, int H, int W, MeshLayout& L) {
-    if (D < 0 || H < 0 || W < 0) return "negative extent";
-    if (D > kMeshExtentMax || H > kMeshExtentMax || W > kMeshExtentMax) return "an extent above 32768";
-    L.n = (long)D * H * W;  // <= 2^45
-    if (L.n > CVX_COMPONENT_MAX_VOXELS) return "D*H*W must be <= 2^31 - 2";
-    const long tx = (W + 1 + TX - 1) / TX, ty = (H + 1 + TY - 1) / TY, tz = (D + 1 + TZ - 1) / TZ;
-    L.nseg = (long)(D + 1) * (H + 1) * tx;
-    L.tiles = tx * ty * tz;
+    if (const char* why = extents_fault(D, H, W, kExtentMax, L.n)) return why;
+    const Dims cd = ccl_dims(D + 1, H + 1, W + 1);
+    L.nseg = (long)cd.D * cd.H * cd.tx;
+    L.tiles = tile_count(cd);
     L.off_t = (L.nseg * (long)sizeof(int) + 15) / 16 * 16;
     L.off_totals = 2 * L.off_t;
     L.bytes = L.off_totals + 2 * (long)sizeof(long long);
     return nullptr;
 }
-
-int mesh_fail(const char* entry, const char* why) {
-    static thread_local char msg[160];
-    snprintf(msg, sizeof msg, "%s: %s", entry, why);
-    return cvx_fail(msg);
-}
-
-unsigned mesh_blocks(long items) { return (unsigned)((items + kCclThreads - 1) / kCclThreads); }
 
 }  // namespace
 
@@ -453,10 +420,10 @@ extern "C" long cvx_mesh_workspace_bytes(int D, int H, int W) {
 extern "C" int cvx_mesh_count(const int32_t* labels, int D, int H, int W, void* workspace, long workspace_bytes, int64_t* totals,
                               hipStream_t st) {
     MeshLayout L;
-    if (const char* why = mesh_extents(D, H, W, L)) return mesh_fail("mesh_count", why);
-    if (!totals || !workspace || (L.n > 0 && !labels)) return mesh_fail("mesh_count", "null pointer");
-    if (((uintptr_t)labels & 3) || ((uintptr_t)totals & 7) || ((uintptr_t)workspace & 15)) return mesh_fail("mesh_count", "misaligned pointer");
-    if (workspace_bytes < cvx_mesh_workspace_bytes(D, H, W)) return mesh_fail("mesh_count", "workspace shorter than cvx_mesh_workspace_bytes");
+    if (const char* why = mesh_extents(D, H, W, L)) return cvx_fail("mesh_count", why);
+    if (!totals || !workspace || (L.n > 0 && !labels)) return cvx_fail("mesh_count", "null pointer");
+    if (((uintptr_t)labels & 3) || ((uintptr_t)totals & 7) || ((uintptr_t)workspace & 15)) return cvx_fail("mesh_count", "misaligned pointer");
+    if (workspace_bytes < cvx_mesh_workspace_bytes(D, H, W)) return cvx_fail("mesh_count", "workspace shorter than cvx_mesh_workspace_bytes");
     if (L.n == 0) {  // no voxel, no surface
         CVX_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(int64_t), st));
         CVX_HIP(hipMemsetAsync(workspace, 0, 2 * sizeof(long long), st));
@@ -475,14 +442,14 @@ extern "C" int cvx_mesh_count(const int32_t* labels, int D, int H, int W, void* 
 extern "C" int cvx_mesh_emit(const int32_t* labels, int D, int H, int W, const void* workspace, long workspace_bytes, long V, long T,
                              int32_t* vertices, int32_t* triangles, int32_t* ids, hipStream_t st) {
     MeshLayout L;
-    if (const char* why = mesh_extents(D, H, W, L)) return mesh_fail("mesh_emit", why);
-    if (V < 0 || T < 0) return mesh_fail("mesh_emit", "V or T < 0");
-    if (V >= kMeshIndexEnd || T >= kMeshIndexEnd) return mesh_fail("mesh_emit", "V and T must stay below 2^31 (int32 indices)");
-    if (!workspace || (L.n > 0 && !labels) || (V > 0 && !vertices) || (T > 0 && (!triangles || !ids))) return mesh_fail("mesh_emit", "null pointer");
+    if (const char* why = mesh_extents(D, H, W, L)) return cvx_fail("mesh_emit", why);
+    if (V < 0 || T < 0) return cvx_fail("mesh_emit", "V or T < 0");
+    if (V >= kMeshIndexEnd || T >= kMeshIndexEnd) return cvx_fail("mesh_emit", "V and T must stay below 2^31 (int32 indices)");
+    if (!workspace || (L.n > 0 && !labels) || (V > 0 && !vertices) || (T > 0 && (!triangles || !ids))) return cvx_fail("mesh_emit", "null pointer");
     if ((((uintptr_t)labels | (uintptr_t)vertices | (uintptr_t)triangles | (uintptr_t)ids) & 3) || ((uintptr_t)workspace & 15))
-        return mesh_fail("mesh_emit", "misaligned pointer");
-    if (workspace_bytes < cvx_mesh_workspace_bytes(D, H, W)) return mesh_fail("mesh_emit", "workspace shorter than cvx_mesh_workspace_bytes");
-    if (L.n == 0) return (V || T) ? mesh_fail("mesh_emit", "an empty volume has no vertices and no triangles") : 0;
+        return cvx_fail("mesh_emit", "misaligned pointer");
+    if (workspace_bytes < cvx_mesh_workspace_bytes(D, H, W)) return cvx_fail("mesh_emit", "workspace shorter than cvx_mesh_workspace_bytes");
+    if (L.n == 0) return (V || T) ? cvx_fail("mesh_emit", "an empty volume has no vertices and no triangles") : 0;
     if (V == 0 && T == 0) return 0;
     const int* seg_v = (const int*)workspace;
     const int* seg_t = (const int*)((const char*)workspace + L.off_t);
@@ -506,16 +473,16 @@ const char* mesh_arrays(const int32_t* vertices, const int32_t* triangles, long 
 
 extern "C" int cvx_mesh_stats(const int32_t* vertices, const int32_t* triangles, const int32_t* ids, long V, long T, long k, int64_t* table,
                               hipStream_t st) {
-    if (const char* why = mesh_arrays(vertices, triangles, V, T)) return mesh_fail("mesh_stats", why);
-    if (k < 0) return mesh_fail("mesh_stats", "k < 0");
-    if (k > LONG_MAX / (CVX_MESH_COLS * (long)sizeof(int64_t))) return mesh_fail("mesh_stats", "k rows do not fit in memory");
+    if (const char* why = mesh_arrays(vertices, triangles, V, T)) return cvx_fail("mesh_stats", why);
+    if (k < 0) return cvx_fail("mesh_stats", "k < 0");
+    if (!rows_fit(k, CVX_MESH_COLS)) return cvx_fail("mesh_stats", "k rows do not fit in memory");
     if (k == 0) return 0;
-    if (!table || (T > 0 && !ids)) return mesh_fail("mesh_stats", "null pointer");
-    if (((uintptr_t)table & 7) || ((uintptr_t)ids & 3)) return mesh_fail("mesh_stats", "misaligned pointer");
+    if (!table || (T > 0 && !ids)) return cvx_fail("mesh_stats", "null pointer");
+    if (((uintptr_t)table & 7) || ((uintptr_t)ids & 3)) return cvx_fail("mesh_stats", "misaligned pointer");
     CVX_HIP(hipMemsetAsync(table, 0, (size_t)k * CVX_MESH_COLS * sizeof(int64_t), st));
     if (T == 0) return 0;
-    hipLaunchKernelGGL(k_mesh_stats, dim3(mesh_blocks((T + kMeshStatsPer - 1) / kMeshStatsPer)), dim3(kCclThreads), 0, st, vertices, triangles, ids, V, T,
-                       (int)(k < INT_MAX ? k : INT_MAX), (long long*)table);  // an int32 id is never above it
+    hipLaunchKernelGGL(k_mesh_stats, dim3(blocks_of((T + kMeshStatsPer - 1) / kMeshStatsPer)), dim3(kCclThreads), 0, st, vertices, triangles, ids, V, T,
+                       clamp_int(k), (long long*)table);
     return cvx_check_launch();
 }
 
@@ -526,20 +493,20 @@ extern "C" long cvx_mesh_smooth_workspace_bytes(long V) {
 
 extern "C" int cvx_mesh_smooth_step(const int32_t* vertices, int32_t* moved, const int32_t* triangles, long V, long T, int c, void* workspace,
                                     long workspace_bytes, hipStream_t st) {
-    if (const char* why = mesh_arrays(vertices, triangles, V, T)) return mesh_fail("mesh_smooth_step", why);
-    if (c < -CVX_MESH_FACTOR_MAX || c > CVX_MESH_FACTOR_MAX) return mesh_fail("mesh_smooth_step", "factor outside [-2, 2] (c = factor * 65536)");
+    if (const char* why = mesh_arrays(vertices, triangles, V, T)) return cvx_fail("mesh_smooth_step", why);
+    if (c < -CVX_MESH_FACTOR_MAX || c > CVX_MESH_FACTOR_MAX) return cvx_fail("mesh_smooth_step", "factor outside [-2, 2] (c = factor * 65536)");
     if (V == 0) return 0;
-    if (!moved || !workspace) return mesh_fail("mesh_smooth_step", "null pointer");
-    if (((uintptr_t)moved & 3) || ((uintptr_t)workspace & 7)) return mesh_fail("mesh_smooth_step", "misaligned pointer");
+    if (!moved || !workspace) return cvx_fail("mesh_smooth_step", "null pointer");
+    if (((uintptr_t)moved & 3) || ((uintptr_t)workspace & 7)) return cvx_fail("mesh_smooth_step", "misaligned pointer");
     if (workspace_bytes < cvx_mesh_smooth_workspace_bytes(V))
-        return mesh_fail("mesh_smooth_step", "workspace shorter than cvx_mesh_smooth_workspace_bytes");
+        return cvx_fail("mesh_smooth_step", "workspace shorter than cvx_mesh_smooth_workspace_bytes");
     CVX_HIP(hipMemsetAsync(workspace, 0, (size_t)V * 4 * sizeof(long long), st));
     if (T > 0) {
-        hipLaunchKernelGGL(k_mesh_smooth_gather, dim3(mesh_blocks(T)), dim3(kCclThreads), 0, st, vertices, triangles, V, T,
+        hipLaunchKernelGGL(k_mesh_smooth_gather, dim3(blocks_of(T)), dim3(kCclThreads), 0, st, vertices, triangles, V, T,
                            (unsigned long long*)workspace);
         if (const int rc = cvx_check_launch()) return rc;
     }
-    hipLaunchKernelGGL(k_mesh_smooth_apply, dim3(mesh_blocks(V)), dim3(kCclThreads), 0, st, vertices, moved, V, (long long)c,
+    hipLaunchKernelGGL(k_mesh_smooth_apply, dim3(blocks_of(V)), dim3(kCclThreads), 0, st, vertices, moved, V, (long long)c,
                        (const long long*)workspace);
     return cvx_check_launch();
 }

@@ -34,7 +34,7 @@
 // keys), and a table that was too small says so in status[0] and is discarded: the rows depend on neither capacity nor
 // scheduling.  As in k_dstat_reduce a thread merges runs of equal (a, b) along 16 voxels of a row before it touches the table.
 #include "edt_pieces.h"
-#include "host_util.h"
+#include "entry_checks.h"
 
 namespace cvx {
 
@@ -182,8 +182,8 @@ __device__ __forceinline__ unsigned long pair_slot(const PairTable& t, nkey_t ke
     return t.mask ? ((unsigned long)key * 0x9E3779B97F4A7C15ul) >> t.shift : 0;
 }
 
-__global__ __launch_bounds__(kStatThreads) void k_pair_init(PairTable t) {
-    const unsigned long i = (unsigned long)blockIdx.x * kStatThreads + threadIdx.x;
+__global__ __launch_bounds__(kCclThreads) void k_pair_init(PairTable t) {
+    const unsigned long i = (unsigned long)blockIdx.x * kCclThreads + threadIdx.x;
     if (i < 2) t.status[i] = 0;
     if (i > t.mask) return;
     t.keys[i] = kPairEmpty;
@@ -221,31 +221,16 @@ __device__ __forceinline__ void pair_accumulate(const PairTable& t, nkey_t key, 
 
 // PHASE 0: claim a slot for every pair; PHASE 1: accumulate into the claimed slots
 template <int PHASE>
-__global__ __launch_bounds__(kStatThreads) void k_pair_reduce(const int* __restrict__ labels_a, const int* __restrict__ nearest_b, const int* __restrict__ d2_b,
-                                                              PairTable t, int ka, int thr, long rows, int W, int segs) {
-    const long tid = (long)blockIdx.x * kStatThreads + threadIdx.x;
-    const long row = tid / segs;
-    if (row >= rows) return;
-    const int x0 = (int)(tid % segs) * kStatRv;
-    const int cnt = min(kStatRv, W - x0);
-    const long v0 = row * W + x0;
-    int a[kStatRv], b[kStatRv], d[kStatRv];
-    if (cnt == kStatRv && (((uintptr_t)(labels_a + v0) | (uintptr_t)(nearest_b + v0) | (uintptr_t)(d2_b + v0)) & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < kStatRv / 4; ++q) {
-            const int4 va = ((const int4*)(labels_a + v0))[q], vb = ((const int4*)(nearest_b + v0))[q], vd = ((const int4*)(d2_b + v0))[q];
-            a[4 * q] = va.x; a[4 * q + 1] = va.y; a[4 * q + 2] = va.z; a[4 * q + 3] = va.w;
-            b[4 * q] = vb.x; b[4 * q + 1] = vb.y; b[4 * q + 2] = vb.z; b[4 * q + 3] = vb.w;
-            d[4 * q] = vd.x; d[4 * q + 1] = vd.y; d[4 * q + 2] = vd.z; d[4 * q + 3] = vd.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < kStatRv; ++i) {
-            a[i] = i < cnt ? labels_a[v0 + i] : 0;
-            b[i] = i < cnt ? nearest_b[v0 + i] : 0;
-            d[i] = i < cnt ? d2_b[v0 + i] : kEdtNone;
-        }
-    }
+__global__ __launch_bounds__(kCclThreads) void k_pair_reduce(const int* __restrict__ labels_a, const int* __restrict__ nearest_b, const int* __restrict__ d2_b,
+                                                              PairTable t, int ka, int thr, Dims dims, int segs) {
+    long row;
+    int x0, cnt;
+    if (!row_piece(dims, segs, row, x0, cnt)) return;
+    const long v0 = row * dims.W + x0;
+    int a[RV], b[RV], d[RV];
+    row_load(labels_a + v0, cnt, a);
+    row_load(nearest_b + v0, cnt, b);
+    row_load(d2_b + v0, cnt, d);  // past the row's end a, b and d are 0: a is looked at first, and 0 is nobody's
     auto flush = [&](nkey_t key, long long count, nkey_t lo) {
         if (key < 0) return;
         if (PHASE == 0) pair_claim(t, key);
@@ -254,7 +239,7 @@ __global__ __launch_bounds__(kStatThreads) void k_pair_reduce(const int* __restr
     nkey_t run = -1, lo = LLONG_MAX;  // -1: no pair
     long long count = 0;
 #pragma unroll
-    for (int i = 0; i < kStatRv; ++i) {
+    for (int i = 0; i < RV; ++i) {
         const bool hit = a[i] >= 1 && a[i] <= ka && b[i] != 0 && d[i] >= 0 && d[i] <= thr;
         const nkey_t key = hit ? ((nkey_t)a[i] << 32) | (unsigned)b[i] : -1;
         if (key != run) {
@@ -268,8 +253,8 @@ __global__ __launch_bounds__(kStatThreads) void k_pair_reduce(const int* __restr
     flush(run, count, lo);
 }
 
-__global__ __launch_bounds__(kStatThreads) void k_pair_rows(PairTable t, const long long* __restrict__ order, long p, long long* __restrict__ rows) {
-    const long i = (long)blockIdx.x * kStatThreads + threadIdx.x;
+__global__ __launch_bounds__(kCclThreads) void k_pair_rows(PairTable t, const long long* __restrict__ order, long p, long long* __restrict__ rows) {
+    const long i = (long)blockIdx.x * kCclThreads + threadIdx.x;
     if (i >= p) return;
     const unsigned long s = (unsigned long)order[i];
     long long* r = rows + i * CVX_PAIR_COLS;
@@ -321,13 +306,13 @@ bool pair_table(int64_t* table, long capacity, int64_t* status, PairTable& t) {
 
 extern "C" long cvx_nearest_workspace_bytes(int D, int H, int W) {
     long n;
-    return edt_extents(D, H, W, n) ? n * (long)sizeof(nkey_t) : -1;
+    return extents_fault(D, H, W, kExtentAny, n) ? -1 : n * (long)sizeof(nkey_t);
 }
 
 extern "C" int cvx_nearest_instance(const int32_t* labels, long k, int D, int H, int W, int32_t* d2_out, int32_t* nearest_out,
                                     void* workspace, hipStream_t st) {
     long n;
-    if (!edt_extents(D, H, W, n)) return cvx_fail("nearest_instance: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("nearest_instance", kExtentsRule);
     if (k < 0) return cvx_fail("nearest_instance: k < 0");
     if (n == 0) return 0;
     const long long far = (long long)(D - 1) * (D - 1) + (long long)(H - 1) * (H - 1) + (long long)(W - 1) * (W - 1);
@@ -339,7 +324,7 @@ extern "C" int cvx_nearest_instance(const int32_t* labels, long k, int D, int H,
     const long rows = (long)D * H;
     const int nc = (W + 63) / 64;
     hipLaunchKernelGGL(k_near_rows, dim3((unsigned)((rows + kRowThreads / 64 - 1) / (kRowThreads / 64))), dim3(kRowThreads), edt_row_lds_bytes(nc), st, labels,
-                       out.keys, rows, W, nc, (int)(k < INT_MAX ? k : INT_MAX));
+                       out.keys, rows, W, nc, clamp_int(k));
     int rc = cvx_check_launch();
     if (rc) return rc;
     if (H > 1 && (rc = near_launch_lines<false>(out, H, W, D, (long)H * W, W, st))) return rc;  // y: one line per (z, x)
@@ -349,22 +334,22 @@ extern "C" int cvx_nearest_instance(const int32_t* labels, long k, int D, int H,
 extern "C" int cvx_instance_pair_contacts(const int32_t* labels_a, long ka, const int32_t* nearest_b, const int32_t* d2_b, int threshold_d2,
                                           int D, int H, int W, int64_t* table, long capacity, int64_t* status, hipStream_t st) {
     long n;
-    if (!edt_extents(D, H, W, n)) return cvx_fail("instance_pair_contacts: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("instance_pair_contacts", kExtentsRule);
     if (ka < 0) return cvx_fail("instance_pair_contacts: ka < 0");
     PairTable t;
     if (!pair_table(table, capacity, status, t)) return cvx_fail("instance_pair_contacts: capacity must be a power of two in 1..2^31");
     if (!table || !status || (n > 0 && (!labels_a || !nearest_b || !d2_b))) return cvx_fail("instance_pair_contacts: null pointer");
     if ((((uintptr_t)table | (uintptr_t)status) & 7) || (((uintptr_t)labels_a | (uintptr_t)nearest_b | (uintptr_t)d2_b) & 3))
         return cvx_fail("instance_pair_contacts: misaligned pointer");
-    hipLaunchKernelGGL(k_pair_init, dim3((unsigned)((capacity + kStatThreads - 1) / kStatThreads)), dim3(kStatThreads), 0, st, t);
+    hipLaunchKernelGGL(k_pair_init, dim3(blocks_of(capacity)), dim3(kCclThreads), 0, st, t);
     int rc = cvx_check_launch();
     if (rc || n == 0 || ka == 0) return rc;
-    const int segs = (W + kStatRv - 1) / kStatRv;
-    const dim3 grid((unsigned)(((long)D * H * segs + kStatThreads - 1) / kStatThreads));
-    const int k = (int)(ka < INT_MAX ? ka : INT_MAX);
-    hipLaunchKernelGGL(k_pair_reduce<0>, grid, dim3(kStatThreads), 0, st, labels_a, nearest_b, d2_b, t, k, threshold_d2, (long)D * H, W, segs);
+    const int segs = (W + RV - 1) / RV;
+    const dim3 grid(blocks_of((long)D * H * segs));
+    const Dims d = ccl_dims(D, H, W);
+    hipLaunchKernelGGL(k_pair_reduce<0>, grid, dim3(kCclThreads), 0, st, labels_a, nearest_b, d2_b, t, clamp_int(ka), threshold_d2, d, segs);
     if ((rc = cvx_check_launch())) return rc;
-    hipLaunchKernelGGL(k_pair_reduce<1>, grid, dim3(kStatThreads), 0, st, labels_a, nearest_b, d2_b, t, k, threshold_d2, (long)D * H, W, segs);
+    hipLaunchKernelGGL(k_pair_reduce<1>, grid, dim3(kCclThreads), 0, st, labels_a, nearest_b, d2_b, t, clamp_int(ka), threshold_d2, d, segs);
     return cvx_check_launch();
 }
 
@@ -375,7 +360,6 @@ extern "C" int cvx_instance_pair_rows(const int64_t* table, long capacity, const
     if (p == 0) return 0;
     if (!table || !order || !rows) return cvx_fail("instance_pair_rows: null pointer");
     if (((uintptr_t)table | (uintptr_t)order | (uintptr_t)rows) & 7) return cvx_fail("instance_pair_rows: misaligned pointer");
-    hipLaunchKernelGGL(k_pair_rows, dim3((unsigned)((p + kStatThreads - 1) / kStatThreads)), dim3(kStatThreads), 0, st, t, (const long long*)order, p,
-                       (long long*)rows);
+    hipLaunchKernelGGL(k_pair_rows, dim3(blocks_of(p)), dim3(kCclThreads), 0, st, t, (const long long*)order, p, (long long*)rows);
     return cvx_check_launch();
 }

@@ -35,10 +35,7 @@
 // waves of a workgroup that hold the same id are summed through LDS, and the workgroup sends one add per nonzero column and id.  A
 // tile inside one instance costs at most 24 atomics.  The threads of a wave that ends on several ids send their own sums.
 // Zero terms are never sent.  kShapeCombine = false (timing only) sends every voxel's terms on their own.
-#include "voxel_rows.h"
-#include "host_util.h"
-
-#include <limits.h>
+#include "entry_checks.h"
 
 namespace cvx {
 
@@ -48,7 +45,6 @@ constexpr bool kShapeCombine = false;
 constexpr bool kShapeCombine = true;
 #endif
 
-constexpr int kShapeExtentMax = 32768;
 // columns of a row
 constexpr int kColN = 0, kColSum = 1, kColSq = 4, kColEuler = 10, kColCross = 11;
 
@@ -109,16 +105,6 @@ __device__ __forceinline__ void shape_voxel(uint32_t m, int z, int y, int x, lon
     for (int j = 0; j < 13; ++j) acc[kColCross + j] += (~m >> (14 + j)) & 1;
 }
 
-// the nonzero sums go to row id - 1; acc = 0
-__device__ __forceinline__ void shape_flush(long long* __restrict__ out, int id, long long (&acc)[CVX_SHAPE_COLS]) {
-    auto* row = (unsigned long long*)(out + (long)(id - 1) * CVX_SHAPE_COLS);
-#pragma unroll
-    for (int c = 0; c < CVX_SHAPE_COLS; ++c) {
-        if (acc[c]) atomicAdd(row + c, (unsigned long long)acc[c]);
-        acc[c] = 0;
-    }
-}
-
 template <int CONN>
 __global__ __launch_bounds__(kCclThreads) void k_shape_stats(const int* __restrict__ labels, long long* __restrict__ out, Dims d, int k) {
     static_assert(kCclThreads == TZ * TX && TX == 64, "one wave per z plane of the tile, one lane per x");
@@ -139,7 +125,7 @@ __global__ __launch_bounds__(kCclThreads) void k_shape_stats(const int* __restri
         const int id = ids[c];  // 0 outside the volume as well
         if (id == 0) continue;
         if (id != cur) {
-            if (cur) shape_flush(out, cur, acc);
+            if (cur) table_flush(out, cur, acc);
             cur = id;
         }
         uint32_t m = 0;
@@ -152,33 +138,29 @@ __global__ __launch_bounds__(kCclThreads) void k_shape_stats(const int* __restri
                     if (ids[c + (dz * kHaloY + dy) * kHaloX + dx] == id) m |= nb_bit(dz, dy, dx);
         shape_voxel<CONN>(m, z0 + wave, y0 + yy, x0 + lane, acc);
         if (!kShapeCombine) {
-            shape_flush(out, cur, acc);
+            table_flush(out, cur, acc);
             cur = 0;
         }
     }
     if (!kShapeCombine) return;
-    // the wave: one id among the threads that hold one?
-    const unsigned long long has = __ballot(cur != 0);
-    const int first = has ? __shfl(cur, __ffsll((long long)has) - 1) : 0;
-    const bool uniform = __all(cur == 0 || cur == first);
-    if (!uniform) {
-        if (cur) shape_flush(out, cur, acc);
-    } else if (first) {
+    // the wave: one id among the threads that hold one?  Then its sums meet in LDS; else every thread sends its own
+    const int one = wave_single_id(cur);
+    if (one) {
 #pragma unroll
         for (int c = 0; c < CVX_SHAPE_COLS; ++c) {
             const long long s = wave_sum(acc[c]);
             if (lane == 0) wave_acc[wave][c] = s;
         }
+    } else if (cur) {
+        table_flush(out, cur, acc);
     }
-    if (lane == 0) wave_id_of[wave] = uniform ? first : 0;
+    if (lane == 0) wave_id_of[wave] = one;
     __syncthreads();
     // the workgroup: thread c adds column c of the waves that hold the same id, once per id
     if (threadIdx.x >= CVX_SHAPE_COLS) return;
     for (int w = 0; w < TZ; ++w) {
+        if (!first_wave_of_id(wave_id_of, w)) continue;
         const int id = wave_id_of[w];
-        bool seen = id == 0;
-        for (int u = 0; u < w; ++u) seen |= wave_id_of[u] == id;
-        if (seen) continue;
         long long s = 0;
         for (int u = w; u < TZ; ++u)
             if (wave_id_of[u] == id) s += wave_acc[u][threadIdx.x];
@@ -192,12 +174,10 @@ using namespace cvx;
 
 extern "C" int cvx_instance_shape_stats(const int32_t* labels, int D, int H, int W, long k, int connectivity, int64_t* out,
                                         hipStream_t st) {
-    if (D < 0 || H < 0 || W < 0) return cvx_fail("instance_shape_stats: negative extent");
-    if (D > kShapeExtentMax || H > kShapeExtentMax || W > kShapeExtentMax) return cvx_fail("instance_shape_stats: an extent above 32768");
-    const long n = (long)D * H * W;  // <= 2^45
-    if (n > CVX_COMPONENT_MAX_VOXELS) return cvx_fail("instance_shape_stats: D*H*W must be <= 2^31 - 2");
+    long n = 0;
+    if (const char* why = extents_fault(D, H, W, kExtentMax, n)) return cvx_fail("instance_shape_stats", why);
     if (k < 0) return cvx_fail("instance_shape_stats: k < 0");
-    if (k > LONG_MAX / (CVX_SHAPE_COLS * (long)sizeof(int64_t))) return cvx_fail("instance_shape_stats: k rows do not fit in memory");
+    if (!rows_fit(k, CVX_SHAPE_COLS)) return cvx_fail("instance_shape_stats: k rows do not fit in memory");
     if (connectivity != 6 && connectivity != 26) return cvx_fail("instance_shape_stats: connectivity must be 6 or 26");
     if (k == 0) return 0;
     if (!out || (n > 0 && !labels)) return cvx_fail("instance_shape_stats: null pointer");
@@ -205,9 +185,8 @@ extern "C" int cvx_instance_shape_stats(const int32_t* labels, int D, int H, int
     CVX_HIP(hipMemsetAsync(out, 0, (size_t)k * CVX_SHAPE_COLS * sizeof(int64_t), st));
     if (n == 0) return 0;
     const Dims d = ccl_dims(D, H, W);
-    const long tiles = (long)d.tx * d.ty * ((D + TZ - 1) / TZ);  // <= n
-    const int kk = (int)(k < INT_MAX ? k : INT_MAX);              // an int32 label is never above it
-    if (connectivity == 26) hipLaunchKernelGGL(k_shape_stats<26>, dim3((unsigned)tiles), dim3(kCclThreads), 0, st, labels, (long long*)out, d, kk);
-    else hipLaunchKernelGGL(k_shape_stats<6>, dim3((unsigned)tiles), dim3(kCclThreads), 0, st, labels, (long long*)out, d, kk);
+    const dim3 tiles((unsigned)tile_count(d));
+    if (connectivity == 26) hipLaunchKernelGGL(k_shape_stats<26>, tiles, dim3(kCclThreads), 0, st, labels, (long long*)out, d, clamp_int(k));
+    else hipLaunchKernelGGL(k_shape_stats<6>, tiles, dim3(kCclThreads), 0, st, labels, (long long*)out, d, clamp_int(k));
     return cvx_check_launch();
 }

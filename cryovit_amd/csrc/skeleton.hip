@@ -19,15 +19,10 @@
 // The table pass (k_skeleton_stats) looks at every voxel, so it does use the tile with halo of voxel_rows.h, and combines like
 // shape.hip: a thread sums along y while the id stays the same, a wave whose threads end on one id sums over its lanes and
 // lane 0 sends the nonzero columns; other threads send their own.  Integer atomic adds only: two calls give the same bits.
-#include "voxel_rows.h"
+#include "entry_checks.h"
 #include "skeleton_masks.h"
-#include "host_util.h"
-
-#include <limits.h>
 
 namespace cvx {
-
-constexpr int kSkExtentMax = 32768;
 
 __global__ __launch_bounds__(kCclThreads) void k_skeleton_init(const int* __restrict__ labels, long n, int k, int* __restrict__ alive) {
     const long v = (long)blockIdx.x * kCclThreads + threadIdx.x;
@@ -72,16 +67,6 @@ __global__ __launch_bounds__(kCclThreads) void k_skeleton_pass(int* alive, const
     *changed = 1;  // every writer stores the same value
 }
 
-// the nonzero sums go to row id - 1; acc = 0
-__device__ __forceinline__ void skeleton_flush(long long* __restrict__ out, int id, long long (&acc)[CVX_SKELETON_COLS]) {
-    auto* row = (unsigned long long*)(out + (long)(id - 1) * CVX_SKELETON_COLS);
-#pragma unroll
-    for (int c = 0; c < CVX_SKELETON_COLS; ++c) {
-        if (acc[c]) atomicAdd(row + c, (unsigned long long)acc[c]);
-        acc[c] = 0;
-    }
-}
-
 // the later directions (bits 14..26) by kind
 constexpr uint32_t kSkLater = ~((2u << kSkCentre) - 1u);
 constexpr uint32_t kSkLaterFace = kSkN6 & kSkLater, kSkLaterEdge = kSkN18 & ~kSkN6 & kSkLater, kSkLaterCorner = kSkN26 & ~kSkN18 & kSkLater;
@@ -104,7 +89,7 @@ __global__ __launch_bounds__(kCclThreads) void k_skeleton_stats(const int* __res
         const int id = ids[c];  // 0 outside the volume as well
         if (id == 0) continue;
         if (id != cur) {
-            if (cur) skeleton_flush(out, cur, acc);
+            if (cur) table_flush(out, cur, acc);
             cur = id;
         }
         uint32_t m = 0;
@@ -122,17 +107,15 @@ __global__ __launch_bounds__(kCclThreads) void k_skeleton_stats(const int* __res
         acc[6] += __popc(m & kSkLaterCorner);
         acc[7] += dist == CVX_EDT_NONE ? 0 : dist;
     }
-    // the wave: one id among the threads that hold one?
-    const unsigned long long has = __ballot(cur != 0);
-    if (!has) return;
-    const int first = __shfl(cur, __ffsll((long long)has) - 1);
-    if (!__all(cur == 0 || cur == first)) {
-        if (cur) skeleton_flush(out, cur, acc);
+    // the wave: one id among the threads that hold one?  Then lane 0 sends the wave's sums; else every thread sends its own
+    const int one = wave_single_id(cur);
+    if (!one) {
+        if (cur) table_flush(out, cur, acc);
         return;
     }
 #pragma unroll
     for (int c = 0; c < CVX_SKELETON_COLS; ++c) acc[c] = wave_sum(acc[c]);
-    if (lane == 0) skeleton_flush(out, first, acc);
+    if (lane == 0) table_flush(out, one, acc);
 }
 
 }  // namespace cvx
@@ -141,45 +124,33 @@ using namespace cvx;
 
 namespace {
 
-// what every entry refuses about the volume; n = the voxel count.  nullptr: fine
+// what every entry refuses about the volume and its id count; n = the voxel count.  nullptr: fine
 const char* skeleton_extents(int D, int H, int W, long k, long& n) {
-    if (D < 0 || H < 0 || W < 0) return "negative extent";
-    if (D > kSkExtentMax || H > kSkExtentMax || W > kSkExtentMax) return "an extent above 32768";
-    n = (long)D * H * W;  // <= 2^45
-    if (n > CVX_COMPONENT_MAX_VOXELS) return "D*H*W must be <= 2^31 - 2";
-    if (k < 0) return "k < 0";
-    return nullptr;
+    if (const char* why = extents_fault(D, H, W, kExtentMax, n)) return why;
+    return k < 0 ? "k < 0" : nullptr;
 }
-
-int skeleton_fail(const char* entry, const char* why) {
-    static thread_local char msg[128];
-    snprintf(msg, sizeof msg, "%s: %s", entry, why);
-    return cvx_fail(msg);
-}
-
-int clamp_k(long k) { return (int)(k < INT_MAX ? k : INT_MAX); }  // an int32 label is never above it
 
 }  // namespace
 
 extern "C" int cvx_skeleton_init(const int32_t* labels, int D, int H, int W, long k, int32_t* alive, hipStream_t st) {
     long n = 0;
-    if (const char* why = skeleton_extents(D, H, W, k, n)) return skeleton_fail("skeleton_init", why);
+    if (const char* why = skeleton_extents(D, H, W, k, n)) return cvx_fail("skeleton_init", why);
     if (n == 0) return 0;
-    if (!labels || !alive) return skeleton_fail("skeleton_init", "null pointer");
-    if (((uintptr_t)labels | (uintptr_t)alive) & 3) return skeleton_fail("skeleton_init", "misaligned pointer");
-    hipLaunchKernelGGL(k_skeleton_init, dim3((unsigned)((n + kCclThreads - 1) / kCclThreads)), dim3(kCclThreads), 0, st, labels, n, clamp_k(k), alive);
+    if (!labels || !alive) return cvx_fail("skeleton_init", "null pointer");
+    if (((uintptr_t)labels | (uintptr_t)alive) & 3) return cvx_fail("skeleton_init", "misaligned pointer");
+    hipLaunchKernelGGL(k_skeleton_init, dim3(blocks_of(n)), dim3(kCclThreads), 0, st, labels, n, clamp_int(k), alive);
     return cvx_check_launch();
 }
 
 extern "C" int cvx_skeleton_cycles(int32_t* alive, const int32_t* d2, int D, int H, int W, long k, int level_d2, int end_d2, int cycles,
                                    int32_t* changed, hipStream_t st) {
     long n = 0;
-    if (const char* why = skeleton_extents(D, H, W, k, n)) return skeleton_fail("skeleton_cycles", why);
-    if (end_d2 < 1) return skeleton_fail("skeleton_cycles", "end_d2 < 1");
-    if (level_d2 < 0) return skeleton_fail("skeleton_cycles", "level_d2 < 0");
-    if (cycles < 1) return skeleton_fail("skeleton_cycles", "cycles < 1");
-    if (!changed || (n > 0 && (!alive || !d2))) return skeleton_fail("skeleton_cycles", "null pointer");
-    if (((uintptr_t)alive | (uintptr_t)d2 | (uintptr_t)changed) & 3) return skeleton_fail("skeleton_cycles", "misaligned pointer");
+    if (const char* why = skeleton_extents(D, H, W, k, n)) return cvx_fail("skeleton_cycles", why);
+    if (end_d2 < 1) return cvx_fail("skeleton_cycles", "end_d2 < 1");
+    if (level_d2 < 0) return cvx_fail("skeleton_cycles", "level_d2 < 0");
+    if (cycles < 1) return cvx_fail("skeleton_cycles", "cycles < 1");
+    if (!changed || (n > 0 && (!alive || !d2))) return cvx_fail("skeleton_cycles", "null pointer");
+    if (((uintptr_t)alive | (uintptr_t)d2 | (uintptr_t)changed) & 3) return cvx_fail("skeleton_cycles", "misaligned pointer");
     CVX_HIP(hipMemsetAsync(changed, 0, (size_t)cycles * sizeof(int), st));
     if (n == 0 || k == 0) return 0;
     for (int c = 0; c < cycles; ++c)
@@ -189,8 +160,8 @@ extern "C" int cvx_skeleton_cycles(int32_t* alive, const int32_t* d2, int D, int
             g.nz = (D - g.sz + 1) / 2, g.ny = (H - g.sy + 1) / 2, g.nx = (W - g.sx + 1) / 2;  // the coordinates of that parity below the extent
             const long count = (long)g.nz * g.ny * g.nx;
             if (count == 0) continue;
-            hipLaunchKernelGGL(k_skeleton_pass, dim3((unsigned)((count + kCclThreads - 1) / kCclThreads)), dim3(kCclThreads), 0, st, alive, d2, D, H,
-                               W, clamp_k(k), level_d2, end_d2, g, changed + c);
+            hipLaunchKernelGGL(k_skeleton_pass, dim3(blocks_of(count)), dim3(kCclThreads), 0, st, alive, d2, D, H,
+                               W, clamp_int(k), level_d2, end_d2, g, changed + c);
             const int rc = cvx_check_launch();
             if (rc) return rc;
         }
@@ -199,15 +170,14 @@ extern "C" int cvx_skeleton_cycles(int32_t* alive, const int32_t* d2, int D, int
 
 extern "C" int cvx_skeleton_stats(const int32_t* alive, const int32_t* d2, int D, int H, int W, long k, int64_t* table, hipStream_t st) {
     long n = 0;
-    if (const char* why = skeleton_extents(D, H, W, k, n)) return skeleton_fail("skeleton_stats", why);
-    if (k > LONG_MAX / (CVX_SKELETON_COLS * (long)sizeof(int64_t))) return skeleton_fail("skeleton_stats", "k rows do not fit in memory");
+    if (const char* why = skeleton_extents(D, H, W, k, n)) return cvx_fail("skeleton_stats", why);
+    if (!rows_fit(k, CVX_SKELETON_COLS)) return cvx_fail("skeleton_stats", "k rows do not fit in memory");
     if (k == 0) return 0;
-    if (!table || (n > 0 && (!alive || !d2))) return skeleton_fail("skeleton_stats", "null pointer");
-    if (((uintptr_t)table & 7) || (((uintptr_t)alive | (uintptr_t)d2) & 3)) return skeleton_fail("skeleton_stats", "misaligned pointer");
+    if (!table || (n > 0 && (!alive || !d2))) return cvx_fail("skeleton_stats", "null pointer");
+    if (((uintptr_t)table & 7) || (((uintptr_t)alive | (uintptr_t)d2) & 3)) return cvx_fail("skeleton_stats", "misaligned pointer");
     CVX_HIP(hipMemsetAsync(table, 0, (size_t)k * CVX_SKELETON_COLS * sizeof(int64_t), st));
     if (n == 0) return 0;
     const Dims d = ccl_dims(D, H, W);
-    const long tiles = (long)d.tx * d.ty * ((D + TZ - 1) / TZ);  // <= n
-    hipLaunchKernelGGL(k_skeleton_stats, dim3((unsigned)tiles), dim3(kCclThreads), 0, st, alive, d2, (long long*)table, d, clamp_k(k));
+    hipLaunchKernelGGL(k_skeleton_stats, dim3((unsigned)tile_count(d)), dim3(kCclThreads), 0, st, alive, d2, (long long*)table, d, clamp_int(k));
     return cvx_check_launch();
 }

@@ -16,10 +16,7 @@
 // Renumbering follows components.hip: per seed the smallest voxel index (integer atomicMin per run of a row piece), ranked by the
 // caller, then one pass writes labels = rank, the table rows (integer add / min / max) and the input id of every piece.
 // Integers only; the result does not depend on scheduling.
-#include "voxel_rows.h"
-#include "host_util.h"
-
-#include <limits.h>
+#include "entry_checks.h"
 
 namespace cvx {
 
@@ -206,11 +203,6 @@ __global__ __launch_bounds__(kCclThreads) void k_split_first(const SplitKey* __r
     }
 }
 
-__global__ __launch_bounds__(kCclThreads) void k_split_table_init(long long* __restrict__ table, long k, Dims d) {
-    const long i = (long)blockIdx.x * kCclThreads + threadIdx.x;
-    if (i < k * CVX_COMPONENT_COLS) table[i] = table_empty((int)(i % CVX_COMPONENT_COLS), d);
-}
-
 // labels_out = rank of the voxel's seed, the table rows of the pieces, and component[piece] = the input id it lies in (every
 // run of a piece stores the same value)
 __global__ __launch_bounds__(kCclThreads) void k_split_relabel(const SplitKey* __restrict__ keys, const int* __restrict__ labels,
@@ -240,38 +232,21 @@ __global__ __launch_bounds__(kCclThreads) void k_split_relabel(const SplitKey* _
 
 using namespace cvx;
 
-namespace {
-
-// extents >= 0 and D*H*W <= CVX_COMPONENT_MAX_VOXELS; n = the voxel count
-bool split_extents(int D, int H, int W, long& n) {
-    if (D < 0 || H < 0 || W < 0) return false;
-    n = (long)D * H;  // < 2^62
-    if (W && n > CVX_COMPONENT_MAX_VOXELS / W) return false;
-    n *= W;
-    return n <= CVX_COMPONENT_MAX_VOXELS;
-}
-
-unsigned lin_blocks(long n) { return (unsigned)((n + kCclThreads - 1) / kCclThreads); }
-
-unsigned row_blocks(int D, int H, int segs) { return (unsigned)(((long)D * H * segs + kCclThreads - 1) / kCclThreads); }
-
-}  // namespace
-
 extern "C" int cvx_split_core_mask(const int32_t* d2, int D, int H, int W, int threshold_d2, uint8_t* mask, hipStream_t st) {
     long n;
-    if (!split_extents(D, H, W, n)) return cvx_fail("split_core_mask: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("split_core_mask", kExtentsRule);
     if (threshold_d2 < 0) return cvx_fail("split_core_mask: threshold_d2 < 0");
     if (n == 0) return 0;
     if (!d2 || !mask) return cvx_fail("split_core_mask: null pointer");
     if ((uintptr_t)d2 & 3) return cvx_fail("split_core_mask: d2 must be 4-B aligned");
-    hipLaunchKernelGGL(k_split_core_mask, dim3(lin_blocks(n)), dim3(kCclThreads), 0, st, d2, threshold_d2, n, mask);
+    hipLaunchKernelGGL(k_split_core_mask, dim3(blocks_of(n)), dim3(kCclThreads), 0, st, d2, threshold_d2, n, mask);
     return cvx_check_launch();
 }
 
 extern "C" int cvx_split_init(const int32_t* labels, const int32_t* cores, int D, int H, int W, long k, long m, int32_t* has_core,
                               uint64_t* keys, hipStream_t st) {
     long n;
-    if (!split_extents(D, H, W, n)) return cvx_fail("split_init: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("split_init", kExtentsRule);
     if (k < 0 || m < 0 || k > n || m > n) return cvx_fail("split_init: k and m must lie in [0, D*H*W]");
     if (n == 0) return 0;
     if (!labels || !has_core || !keys || (m > 0 && !cores)) return cvx_fail("split_init: null pointer");
@@ -280,10 +255,10 @@ extern "C" int cvx_split_init(const int32_t* labels, const int32_t* cores, int D
     CVX_HIP(hipMemsetAsync(has_core, 0, (size_t)(k + 1) * sizeof(int), st));
     int rc;
     if (m > 0) {
-        hipLaunchKernelGGL(k_split_flag, dim3(lin_blocks(n)), dim3(kCclThreads), 0, st, labels, cores, n, k, has_core);
+        hipLaunchKernelGGL(k_split_flag, dim3(blocks_of(n)), dim3(kCclThreads), 0, st, labels, cores, n, k, has_core);
         if ((rc = cvx_check_launch())) return rc;
     }
-    hipLaunchKernelGGL(k_split_init, dim3(lin_blocks(n)), dim3(kCclThreads), 0, st, labels, m > 0 ? cores : nullptr, has_core, n, k, m,
+    hipLaunchKernelGGL(k_split_init, dim3(blocks_of(n)), dim3(kCclThreads), 0, st, labels, m > 0 ? cores : nullptr, has_core, n, k, m,
                        (SplitKey*)keys);
     return cvx_check_launch();
 }
@@ -291,7 +266,7 @@ extern "C" int cvx_split_init(const int32_t* labels, const int32_t* cores, int D
 extern "C" int cvx_split_rounds(const int32_t* labels, uint64_t* keys, int D, int H, int W, int connectivity, int rounds, int32_t* changed,
                                 hipStream_t st) {
     long n;
-    if (!split_extents(D, H, W, n)) return cvx_fail("split_rounds: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("split_rounds", kExtentsRule);
     if (connectivity != 6 && connectivity != 26) return cvx_fail("split_rounds: connectivity must be 6 or 26");
     if (rounds < 1) return cvx_fail("split_rounds: rounds < 1");
     if (!changed || (n > 0 && (!labels || !keys))) return cvx_fail("split_rounds: null pointer");
@@ -300,7 +275,7 @@ extern "C" int cvx_split_rounds(const int32_t* labels, uint64_t* keys, int D, in
     CVX_HIP(hipMemsetAsync(changed, 0, (size_t)rounds * sizeof(int), st));
     if (n == 0) return 0;
     const Dims d = ccl_dims(D, H, W);
-    const long tiles = (long)d.tx * d.ty * ((D + TZ - 1) / TZ);  // <= n
+    const long tiles = tile_count(d);
     for (int r = 0; r < rounds; ++r) {
         if (connectivity == 26) hipLaunchKernelGGL(k_split_round<26>, dim3((unsigned)tiles), dim3(kCclThreads), 0, st, labels, (SplitKey*)keys, d, changed + r);
         else hipLaunchKernelGGL(k_split_round<6>, dim3((unsigned)tiles), dim3(kCclThreads), 0, st, labels, (SplitKey*)keys, d, changed + r);
@@ -312,16 +287,16 @@ extern "C" int cvx_split_rounds(const int32_t* labels, uint64_t* keys, int D, in
 
 extern "C" int cvx_split_first(const int32_t* labels, const uint64_t* keys, int D, int H, int W, long seeds, int32_t* first, hipStream_t st) {
     long n;
-    if (!split_extents(D, H, W, n)) return cvx_fail("split_first: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("split_first", kExtentsRule);
     if (seeds < 0 || seeds > 2 * n) return cvx_fail("split_first: seeds outside [0, 2*D*H*W]");
     if (!first || (n > 0 && (!labels || !keys))) return cvx_fail("split_first: null pointer");
     if ((((uintptr_t)first | (uintptr_t)labels) & 3) || ((uintptr_t)keys & 7))
         return cvx_fail("split_first: first and labels must be 4-B aligned, keys 8-B aligned");
-    hipLaunchKernelGGL(k_split_fill, dim3(lin_blocks(seeds + 1)), dim3(kCclThreads), 0, st, first, seeds + 1, INT_MAX);
+    hipLaunchKernelGGL(k_split_fill, dim3(blocks_of(seeds + 1)), dim3(kCclThreads), 0, st, first, seeds + 1, INT_MAX);
     int rc = cvx_check_launch();
     if (rc || n == 0) return rc;
     const int segs = (W + RV - 1) / RV;
-    hipLaunchKernelGGL(k_split_first, dim3(row_blocks(D, H, segs)), dim3(kCclThreads), 0, st, (const SplitKey*)keys, labels, seeds, first,
+    hipLaunchKernelGGL(k_split_first, dim3(blocks_of((long)D * H * segs)), dim3(kCclThreads), 0, st, (const SplitKey*)keys, labels, seeds, first,
                        ccl_dims(D, H, W), segs);
     return cvx_check_launch();
 }
@@ -329,7 +304,7 @@ extern "C" int cvx_split_first(const int32_t* labels, const uint64_t* keys, int 
 extern "C" int cvx_split_relabel(const int32_t* labels, const uint64_t* keys, const int32_t* rank, int D, int H, int W, long seeds, long kp,
                                  int32_t* labels_out, int64_t* table, int64_t* component, hipStream_t st) {
     long n;
-    if (!split_extents(D, H, W, n)) return cvx_fail("split_relabel: extents must be >= 0 with D*H*W <= 2^31 - 2");
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("split_relabel", kExtentsRule);
     if (seeds < 0 || seeds > 2 * n || kp < 0 || kp > seeds) return cvx_fail("split_relabel: need 0 <= kp <= seeds <= 2*D*H*W");
     if (n == 0) return 0;
     if (!labels || !keys || !rank || !labels_out || (kp > 0 && (!table || !component))) return cvx_fail("split_relabel: null pointer");
@@ -338,11 +313,11 @@ extern "C" int cvx_split_relabel(const int32_t* labels, const uint64_t* keys, co
     const Dims d = ccl_dims(D, H, W);
     int rc;
     if (kp > 0) {
-        hipLaunchKernelGGL(k_split_table_init, dim3(lin_blocks(kp * CVX_COMPONENT_COLS)), dim3(kCclThreads), 0, st, (long long*)table, kp, d);
+        hipLaunchKernelGGL(k_table_init<CVX_COMPONENT_COLS>, dim3(blocks_of(kp * CVX_COMPONENT_COLS)), dim3(kCclThreads), 0, st, (long long*)table, kp, d);
         if ((rc = cvx_check_launch())) return rc;
     }
     const int segs = (W + RV - 1) / RV;
-    hipLaunchKernelGGL(k_split_relabel, dim3(row_blocks(D, H, segs)), dim3(kCclThreads), 0, st, (const SplitKey*)keys, labels, rank, seeds, kp,
+    hipLaunchKernelGGL(k_split_relabel, dim3(blocks_of((long)D * H * segs)), dim3(kCclThreads), 0, st, (const SplitKey*)keys, labels, rank, seeds, kp,
                        labels_out, (long long*)table, (long long*)component, d, segs);
     return cvx_check_launch();
 }

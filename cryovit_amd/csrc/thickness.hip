@@ -33,10 +33,7 @@
 // wave whose threads end on one id combines over its lanes, the waves of a workgroup that hold the same id combine through LDS,
 // then 64-bit integer atomics.  r_fx = floor(sqrt(t2 << 16)) starts from the double-precision root (t2 << 16 < 2^47 is exact in a
 // double) and is corrected with integer comparisons.
-#include "voxel_rows.h"
-#include "host_util.h"
-
-#include <limits.h>
+#include "entry_checks.h"
 
 namespace cvx {
 
@@ -46,7 +43,6 @@ constexpr bool kThFloor = false;
 constexpr bool kThFloor = true;
 #endif
 
-constexpr int kThExtentMax = 32768;
 constexpr int kThRow = TX + 8;                   // words between two rows of the LDS tile
 constexpr int kThCells = TZ * TY * kThRow;
 constexpr int kThQueue = 2560;                   // queued centres
@@ -270,13 +266,11 @@ __global__ __launch_bounds__(kCclThreads) void k_thickness_stats(const int* __re
             acc.lo = min(acc.lo, t);
             acc.hi = max(acc.hi, t);
         }
-    // the wave: one id among the threads that hold one?
-    const unsigned long long has = __ballot(cur != 0);
-    const int first = has ? __shfl(cur, __ffsll((long long)has) - 1) : 0;
-    const bool uniform = __all(cur == 0 || cur == first);
-    if (!uniform) {
+    // the wave: one id among the threads that hold one?  Then it combines over its lanes; else every thread sends its own
+    const int one = wave_single_id(cur);
+    if (!one) {
         if (cur) thickness_flush(out, cur, acc);
-    } else if (first) {
+    } else {
         acc.n = wave_sum(acc.n);
         acc.sum_t2 = wave_sum(acc.sum_t2);
         acc.sum_r = wave_sum(acc.sum_r);
@@ -287,15 +281,13 @@ __global__ __launch_bounds__(kCclThreads) void k_thickness_stats(const int* __re
         }
         if (lane == 0) wave_acc[wave] = acc;
     }
-    if (lane == 0) wave_id_of[wave] = uniform ? first : 0;
+    if (lane == 0) wave_id_of[wave] = one;
     __syncthreads();
     // the workgroup: thread 0 combines the waves that hold the same id, once per id
     if (threadIdx.x != 0) return;
     for (int w = 0; w < TZ; ++w) {
+        if (!first_wave_of_id(wave_id_of, w)) continue;
         const int id = wave_id_of[w];
-        bool seen = id == 0;
-        for (int u = 0; u < w; ++u) seen |= wave_id_of[u] == id;
-        if (seen) continue;
         ThAcc s = wave_acc[w];
         for (int u = w + 1; u < TZ; ++u)
             if (wave_id_of[u] == id) {
@@ -315,18 +307,9 @@ namespace {
 
 // what every entry refuses about the volume; n = the voxel count, tiles = its 4x8x64 tiles (<= n).  nullptr: fine
 const char* thickness_extents(int D, int H, int W, long& n, long& tiles) {
-    if (D < 0 || H < 0 || W < 0) return "negative extent";
-    if (D > kThExtentMax || H > kThExtentMax || W > kThExtentMax) return "an extent above 32768";
-    n = (long)D * H * W;  // <= 2^45
-    if (n > CVX_COMPONENT_MAX_VOXELS) return "D*H*W must be <= 2^31 - 2";
-    tiles = (long)((W + TX - 1) / TX) * ((H + TY - 1) / TY) * ((D + TZ - 1) / TZ);
+    if (const char* why = extents_fault(D, H, W, kExtentMax, n)) return why;
+    tiles = tile_count(ccl_dims(D, H, W));
     return nullptr;
-}
-
-int thickness_fail(const char* entry, const char* why) {
-    static thread_local char msg[128];
-    snprintf(msg, sizeof msg, "%s: %s", entry, why);
-    return cvx_fail(msg);
 }
 
 }  // namespace
@@ -340,13 +323,13 @@ extern "C" long cvx_local_thickness_workspace_bytes(int D, int H, int W) {
 extern "C" int cvx_local_thickness_squared(const int32_t* d2, int D, int H, int W, int32_t* t2, void* workspace, long workspace_bytes,
                                            hipStream_t st) {
     long n = 0, tiles = 0;
-    if (const char* why = thickness_extents(D, H, W, n, tiles)) return thickness_fail("local_thickness_squared", why);
+    if (const char* why = thickness_extents(D, H, W, n, tiles)) return cvx_fail("local_thickness_squared", why);
     if (n == 0) return 0;
-    if (!d2 || !t2 || !workspace) return thickness_fail("local_thickness_squared", "null pointer");
-    if (((uintptr_t)d2 | (uintptr_t)t2 | (uintptr_t)workspace) & 3) return thickness_fail("local_thickness_squared", "misaligned pointer");
+    if (!d2 || !t2 || !workspace) return cvx_fail("local_thickness_squared", "null pointer");
+    if (((uintptr_t)d2 | (uintptr_t)t2 | (uintptr_t)workspace) & 3) return cvx_fail("local_thickness_squared", "misaligned pointer");
     if (workspace_bytes < (tiles + 1) * (long)sizeof(int))
-        return thickness_fail("local_thickness_squared", "workspace shorter than cvx_local_thickness_workspace_bytes");
-    if (d2 == t2) return thickness_fail("local_thickness_squared", "d2 and t2 must be different arrays");
+        return cvx_fail("local_thickness_squared", "workspace shorter than cvx_local_thickness_workspace_bytes");
+    if (d2 == t2) return cvx_fail("local_thickness_squared", "d2 and t2 must be different arrays");
     int* tilemax = (int*)workspace;
     const Dims d = ccl_dims(D, H, W);
     CVX_HIP(hipMemsetAsync(tilemax + tiles, 0, sizeof(int), st));
@@ -359,20 +342,18 @@ extern "C" int cvx_local_thickness_squared(const int32_t* d2, int D, int H, int 
 extern "C" int cvx_instance_thickness_stats(const int32_t* labels, const int32_t* t2, int D, int H, int W, long k, int64_t* table,
                                             hipStream_t st) {
     long n = 0, tiles = 0;
-    if (const char* why = thickness_extents(D, H, W, n, tiles)) return thickness_fail("instance_thickness_stats", why);
-    if (k < 0) return thickness_fail("instance_thickness_stats", "k < 0");
-    if (k > LONG_MAX / (CVX_THICKNESS_COLS * (long)sizeof(int64_t))) return thickness_fail("instance_thickness_stats", "k rows do not fit in memory");
+    if (const char* why = thickness_extents(D, H, W, n, tiles)) return cvx_fail("instance_thickness_stats", why);
+    if (k < 0) return cvx_fail("instance_thickness_stats", "k < 0");
+    if (!rows_fit(k, CVX_THICKNESS_COLS)) return cvx_fail("instance_thickness_stats", "k rows do not fit in memory");
     if (k == 0) return 0;
-    if (!table || (n > 0 && (!labels || !t2))) return thickness_fail("instance_thickness_stats", "null pointer");
-    if (((uintptr_t)table & 7) || (((uintptr_t)labels | (uintptr_t)t2) & 3)) return thickness_fail("instance_thickness_stats", "misaligned pointer");
+    if (!table || (n > 0 && (!labels || !t2))) return cvx_fail("instance_thickness_stats", "null pointer");
+    if (((uintptr_t)table & 7) || (((uintptr_t)labels | (uintptr_t)t2) & 3)) return cvx_fail("instance_thickness_stats", "misaligned pointer");
     const long cells = k * CVX_THICKNESS_COLS;
-    if ((cells + kCclThreads - 1) / kCclThreads > INT_MAX) return thickness_fail("instance_thickness_stats", "k rows do not fit in one launch");
-    hipLaunchKernelGGL(k_thickness_stats_init, dim3((unsigned)((cells + kCclThreads - 1) / kCclThreads)), dim3(kCclThreads), 0, st,
-                       (long long*)table, cells);
+    if ((cells + kCclThreads - 1) / kCclThreads > INT_MAX) return cvx_fail("instance_thickness_stats", "k rows do not fit in one launch");
+    hipLaunchKernelGGL(k_thickness_stats_init, dim3(blocks_of(cells)), dim3(kCclThreads), 0, st, (long long*)table, cells);
     if (const int rc = cvx_check_launch()) return rc;
     if (n == 0) return 0;
     const Dims d = ccl_dims(D, H, W);
-    hipLaunchKernelGGL(k_thickness_stats, dim3((unsigned)tiles), dim3(kCclThreads), 0, st, labels, t2, (long long*)table, d,
-                       (int)(k < INT_MAX ? k : INT_MAX));  // an int32 label is never above it
+    hipLaunchKernelGGL(k_thickness_stats, dim3((unsigned)tiles), dim3(kCclThreads), 0, st, labels, t2, (long long*)table, d, clamp_int(k));
     return cvx_check_launch();
 }

@@ -1,7 +1,10 @@
-// Pieces shared by the passes that walk an int32 [D][H][W] volume in 16-voxel row pieces and build the per-instance table
-// (components.hip: relabel + table; split.hip: renumber + table): the piece a thread owns, its 16-B loads / stores, and the
-// integer add / min / max into a table row; and, for the passes that read a voxel's 3x3x3 neighbourhood (shape.hip), a tile's
-// ids with their one-voxel halo in LDS and the sum over a wave.  Device code only; every includer compiles its own copy.
+// Pieces shared by the passes over an int32 [D][H][W] volume that build a per-instance table.  For the passes that walk it in
+// 16-voxel row pieces (components.hip, split.hip, the reductions of edt.hip and nearest.hip): the piece a thread owns, its 16-B
+// loads / stores, the kernel that fills a component table with the empty box, and the integer add / min / max into a table row.
+// For the passes that walk it in 4x8x64 tiles (shape.hip, skeleton.hip, thickness.hip, mesh.hip): a tile's ids with their
+// one-voxel halo in LDS, and the stages of the per-id reduction: a thread's sums to a table row (table_flush), the wave's
+// single-id test (wave_single_id), the first wave of a workgroup that holds an id (first_wave_of_id).  And the sums and the scan
+// over the lanes of a wave.  Device code only; every includer compiles its own copy.
 #pragma once
 #include "common.h"
 #include "../../include/cryovit_hip.h"
@@ -52,15 +55,20 @@ __device__ __forceinline__ void row_store(int* __restrict__ p, int cnt, const in
     }
 }
 
-// thread -> RV voxels of one row: (z, y, x0 .. x0 + cnt); false past the volume
-__device__ __forceinline__ bool row_piece(const Dims& d, int segs, int& z, int& y, int& x0, int& cnt) {
+// thread -> RV voxels of one row: x0 .. x0 + cnt of row z * H + y, whose first voxel is row * W; false past the volume
+__device__ __forceinline__ bool row_piece(const Dims& d, int segs, long& row, int& x0, int& cnt) {
     const long t = (long)blockIdx.x * kCclThreads + threadIdx.x;
-    const long row = t / segs;
+    row = t / segs;
     if (row >= (long)d.D * d.H) return false;
     x0 = (int)(t % segs) * RV;
+    cnt = min(RV, d.W - x0);
+    return true;
+}
+__device__ __forceinline__ bool row_piece(const Dims& d, int segs, int& z, int& y, int& x0, int& cnt) {
+    long row;
+    if (!row_piece(d, segs, row, x0, cnt)) return false;
     y = (int)(row % d.H);
     z = (int)(row / d.H);
-    cnt = min(RV, d.W - x0);
     return true;
 }
 
@@ -76,6 +84,13 @@ __device__ __forceinline__ void table_min(long long* p, long long v) {
 }
 __device__ __forceinline__ void table_max(long long* p, long long v) {
     if (v > *(volatile long long*)p) atomicMax(p, v);
+}
+
+// the rows of a component table start as the empty box
+template <int COLS>
+__global__ __launch_bounds__(kCclThreads) void k_table_init(long long* __restrict__ table, long k, Dims d) {
+    const long i = (long)blockIdx.x * kCclThreads + threadIdx.x;
+    if (i < k * COLS) table[i] = table_empty((int)(i % COLS), d);
 }
 
 __device__ __forceinline__ void table_add_run(long long* __restrict__ table, int id, int z, int y, int xa, int xb) {
@@ -125,11 +140,56 @@ __device__ __forceinline__ void tile_load_ids(const int* __restrict__ labels, co
     }
 }
 
-// the sum of v over the 64 lanes of a wave, in every lane (all lanes call it)
+// ---- over the lanes of a wave (all 64 call these) ----
+
+// the sum of v, in every lane
 __device__ __forceinline__ long long wave_sum(long long v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the sum of v over this lane and the lanes below it
+__device__ __forceinline__ int wave_scan_incl(int v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+// ---- the per-id reduction of the tile passes: thread, wave, workgroup ----
+
+// the nonzero sums of acc go to row id - 1 of a table of COLS columns; acc = 0
+template <int COLS>
+__device__ __forceinline__ void table_flush(long long* __restrict__ out, int id, long long (&acc)[COLS]) {
+    auto* row = (unsigned long long*)(out + (long)(id - 1) * COLS);
+#pragma unroll
+    for (int c = 0; c < COLS; ++c) {
+        if (acc[c]) atomicAdd(row + c, (unsigned long long)acc[c]);
+        acc[c] = 0;
+    }
+}
+
+// cur = the id a thread's sums belong to, 0: it has none.  The id, when every lane that holds one holds the same; else 0
+__device__ __forceinline__ int wave_single_id(int cur) {
+    const unsigned long long has = __ballot(cur != 0);
+    const int first = has ? __shfl(cur, __ffsll((long long)has) - 1) : 0;
+    return __all(cur == 0 || cur == first) ? first : 0;
+}
+
+// ids[w] = the single id of wave w of the workgroup (0: none).  Is w the first wave that holds its id?
+__device__ __forceinline__ bool first_wave_of_id(const int* ids, int w) {
+    bool first = ids[w] != 0;
+    for (int u = 0; u < w; ++u) first &= ids[u] != ids[w];
+    return first;
 }
 
 }  // namespace cvx

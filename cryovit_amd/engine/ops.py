@@ -585,16 +585,11 @@ def label_components(mask: torch.Tensor, *, connectivity: int = 26, min_size: in
     background is 0; components with fewer than ``min_size`` voxels become background before the numbering.  A table row
     holds voxels, sum_z, sum_y, sum_x, z0, z1, y0, y1, x0, x1 (box inclusive).  Exact and bit-reproducible; the host waits
     once, for K."""
-    if mask.dim() != 3 or mask.dtype != torch.uint8:
-        raise _lib.CvxError(f"label_components: mask must be uint8 [D, H, W], got {mask.dtype} {tuple(mask.shape)}")
     if connectivity not in (6, 26):
         raise _lib.CvxError(f"label_components: connectivity must be 6 or 26, got {connectivity}")
     if min_size < 0:
         raise _lib.CvxError(f"label_components: min_size must be >= 0, got {min_size}")
-    dev = _dev_check(mask)
-    D, H, W = mask.shape
-    if mask.numel() > _lib.COMPONENT_MAX_VOXELS:
-        raise _lib.CvxError(f"label_components: {D}x{H}x{W} has more than 2^31 - 2 voxels")
+    dev, D, H, W = _volumes_check("label_components", mask=(mask, torch.uint8))
     lib = _lib.load()
     scratch = components_scratch(D, H, W, dev)
     labels = torch.empty((D, H, W), dtype=torch.int32, device=dev)
@@ -617,10 +612,7 @@ def edt_squared(src: torch.Tensor, *, sites: str = "zero") -> torch.Tensor:
         raise _lib.CvxError(f"edt_squared: src must be uint8 or int32 [D, H, W], got {src.dtype} {tuple(src.shape)}")
     if sites not in ("zero", "nonzero"):
         raise _lib.CvxError(f"edt_squared: sites must be 'zero' or 'nonzero', got {sites!r}")
-    dev = _dev_check(src)
-    D, H, W = src.shape
-    if src.numel() > _lib.COMPONENT_MAX_VOXELS:
-        raise _lib.CvxError(f"edt_squared: {D}x{H}x{W} has more than 2^31 - 2 voxels")
+    dev, D, H, W = _volumes_check("edt_squared", src=(src, src.dtype))
     out = torch.empty((D, H, W), dtype=torch.int32, device=dev)
     call(dev, "cvx_edt_squared", _lib.load().cvx_edt_squared, _p(src), _lib.EDT_U8 if src.dtype == torch.uint8 else _lib.EDT_I32,
          _lib.EDT_SITES_ZERO if sites == "zero" else _lib.EDT_SITES_NONZERO, D, H, W, _p(out))
@@ -631,19 +623,11 @@ def instance_distance_stats(labels: torch.Tensor, d2: torch.Tensor, k: int, thre
     """int64 [k, 4] on the device.  Row id - 1, over the voxels of ``labels`` (int32 [D, H, W], ids 0..k) with that id whose
     ``d2`` (``edt_squared``) is not ``_lib.EDT_NONE``: how many have d2 <= ``threshold_d2``, min d2, max d2, and the smallest
     linear index of a voxel attaining the max; 0, -1, -1, -1 for an id without such a voxel.  Ids past k are ignored."""
-    for name, t in (("labels", labels), ("d2", d2)):
-        if t.dim() != 3 or t.dtype != torch.int32:
-            raise _lib.CvxError(f"instance_distance_stats: {name} must be int32 [D, H, W], got {t.dtype} {tuple(t.shape)}")
-    if labels.shape != d2.shape:
-        raise _lib.CvxError(f"instance_distance_stats: labels {tuple(labels.shape)} and d2 {tuple(d2.shape)} differ in shape")
     if k < 0:
         raise _lib.CvxError(f"instance_distance_stats: k must be >= 0, got {k}")
     if threshold_d2 < 0:
         raise _lib.CvxError(f"instance_distance_stats: threshold_d2 must be >= 0, got {threshold_d2}")
-    dev = _dev_check(labels, d2)
-    D, H, W = labels.shape
-    if labels.numel() > _lib.COMPONENT_MAX_VOXELS:
-        raise _lib.CvxError(f"instance_distance_stats: {D}x{H}x{W} has more than 2^31 - 2 voxels")
+    dev, D, H, W = _volumes_check("instance_distance_stats", labels=(labels, torch.int32), d2=(d2, torch.int32))
     out = torch.empty((int(k), _lib.DSTAT_COLS), dtype=torch.int64, device=dev)
     call(dev, "cvx_instance_distance_stats", _lib.load().cvx_instance_distance_stats, _p(labels), _p(d2), D, H, W, int(k),
          min(int(threshold_d2), _lib.EDT_NONE - 1), _p(out))  # no distance is larger than EDT_NONE - 1
@@ -657,16 +641,11 @@ def instance_shape_stats(labels: torch.Tensor, k: int, *, connectivity: int = 26
     yy, xx, zy, zx, yx; the Euler number under ``connectivity`` (6 or 26); and the 13 crossing counts N_d = #{v : v + d outside}
     over the directions d lexicographically after (0,0,0), in that order.  Ids past k are ignored.  Integers only,
     bit-reproducible; the host does not wait."""
-    if labels.dim() != 3 or labels.dtype != torch.int32:
-        raise _lib.CvxError(f"instance_shape_stats: labels must be int32 [D, H, W], got {labels.dtype} {tuple(labels.shape)}")
     if k < 0:
         raise _lib.CvxError(f"instance_shape_stats: k must be >= 0, got {k}")
     if connectivity not in (6, 26):
         raise _lib.CvxError(f"instance_shape_stats: connectivity must be 6 or 26, got {connectivity}")
-    dev = _dev_check(labels)
-    D, H, W = labels.shape
-    if labels.numel() > _lib.COMPONENT_MAX_VOXELS:
-        raise _lib.CvxError(f"instance_shape_stats: {D}x{H}x{W} has more than 2^31 - 2 voxels")
+    dev, D, H, W = _volumes_check("instance_shape_stats", labels=(labels, torch.int32))
     out = torch.empty((int(k), _lib.SHAPE_COLS), dtype=torch.int64, device=dev)
     call(dev, "cvx_instance_shape_stats", _lib.load().cvx_instance_shape_stats, _p(labels), D, H, W, int(k), int(connectivity), _p(out))
     return out
@@ -683,8 +662,8 @@ def _volume_check(what: str, name: str, t, dtype) -> None:
         raise _lib.CvxError(f"{what}: {name} must be {str(dtype).removeprefix('torch.')} [D, H, W], got {got}")
 
 
-def _split_volume_check(what: str, **volumes) -> tuple[torch.device, int, int, int]:
-    """Dtype, rank, common shape, size and device of the volumes of one split stage: (device, D, H, W)."""
+def _volumes_check(what: str, **volumes) -> tuple[torch.device, int, int, int]:
+    """Dtype, rank, common shape, size and device of the volumes of one analysis stage: (device, D, H, W)."""
     shape = None
     for name, (t, dtype) in volumes.items():
         _volume_check(what, name, t, dtype)
@@ -701,7 +680,7 @@ def split_core_mask(d2: torch.Tensor, threshold_d2: int) -> torch.Tensor:
     """uint8 [D, H, W]: 1 where ``d2`` (``edt_squared``) is a distance above ``threshold_d2``: the voxels deeper than the radius."""
     if threshold_d2 < 0:
         raise _lib.CvxError(f"split_core_mask: threshold_d2 must be >= 0, got {threshold_d2}")
-    dev, D, H, W = _split_volume_check("split_core_mask", d2=(d2, torch.int32))
+    dev, D, H, W = _volumes_check("split_core_mask", d2=(d2, torch.int32))
     mask = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
     call(dev, "cvx_split_core_mask", _lib.load().cvx_split_core_mask, _p(d2), D, H, W, min(int(threshold_d2), _lib.EDT_NONE), _p(mask))
     return mask
@@ -711,7 +690,7 @@ def split_init(labels: torch.Tensor, k: int, cores: torch.Tensor | None, m: int)
     """int64 [D, H, W] regrowth keys (steps << 32 | seed id, as unsigned) of the instances 1..k: a voxel of a core 1..m starts at
     (0, core id), every voxel of an instance without a core voxel at (0, m + its id), all else at all-ones."""
     vols = {"labels": (labels, torch.int32)} | ({"cores": (cores, torch.int32)} if cores is not None else {})
-    dev, D, H, W = _split_volume_check("split_init", **vols)
+    dev, D, H, W = _volumes_check("split_init", **vols)
     if k < 0 or m < 0 or (m > 0 and cores is None):
         raise _lib.CvxError(f"split_init: need k >= 0 and m >= 0 (with cores), got k = {k}, m = {m}")
     keys = torch.empty((D, H, W), dtype=torch.int64, device=dev)
@@ -729,7 +708,7 @@ def split_regrow(labels: torch.Tensor, keys: torch.Tensor, *, connectivity: int 
         raise _lib.CvxError(f"split_regrow: connectivity must be 6 or 26, got {connectivity}")
     if max_rounds < 1:
         raise _lib.CvxError(f"split_regrow: max_rounds must be >= 1, got {max_rounds}")
-    dev, D, H, W = _split_volume_check("split_regrow", labels=(labels, torch.int32), keys=(keys, torch.int64))
+    dev, D, H, W = _volumes_check("split_regrow", labels=(labels, torch.int32), keys=(keys, torch.int64))
     lib = _lib.load()
     changed = torch.empty(SPLIT_ROUND_BATCH, dtype=torch.int32, device=dev)
     done = 0
@@ -747,7 +726,7 @@ def split_renumber(labels: torch.Tensor, keys: torch.Tensor, seeds: int) -> tupl
     """(labels' int32 [D, H, W], table' int64 [K', 10], component int64 [K']) from the regrown ``keys`` with seed ids 1..seeds: the
     pieces numbered 1..K' in ascending order of their smallest linear voxel index, their table (columns of ``label_components``)
     and the input id each lies in.  The host waits once, for K'."""
-    dev, D, H, W = _split_volume_check("split_renumber", labels=(labels, torch.int32), keys=(keys, torch.int64))
+    dev, D, H, W = _volumes_check("split_renumber", labels=(labels, torch.int32), keys=(keys, torch.int64))
     if seeds < 0:
         raise _lib.CvxError(f"split_renumber: seeds must be >= 0, got {seeds}")
     lib = _lib.load()
@@ -788,7 +767,7 @@ def split_instances(labels: torch.Tensor, k: int, *, radius: float, min_core: in
         raise _lib.CvxError(f"split_instances: connectivity must be 6 or 26, got {connectivity}")
     if max_rounds < 1:
         raise _lib.CvxError(f"split_instances: max_rounds must be >= 1, got {max_rounds}")
-    _split_volume_check("split_instances", labels=(labels, torch.int32))  # the device, before anything is launched
+    _volumes_check("split_instances", labels=(labels, torch.int32))  # the device, before anything is launched
     thr = int(radius * radius)  # floor: the square is >= 0
     cores, m = None, 0
     if thr > 0 and k > 0 and labels.numel() > 0:
@@ -811,10 +790,9 @@ def nearest_instance(labels: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.
     among sites at that distance; on a site its own id.  ``d2`` is what ``edt_squared(labels, sites="nonzero")`` gives when every
     nonzero value lies in 1..k; without a site it is ``_lib.EDT_NONE`` everywhere and ``nearest`` is 0.  Integers only, no
     atomics, bit-reproducible; 8 bytes of workspace per voxel for the duration of the call; the host does not wait."""
-    _volume_check("nearest_instance", "labels", labels, torch.int32)
     if k < 0:
         raise _lib.CvxError(f"nearest_instance: k must be >= 0, got {k}")
-    dev, D, H, W = _split_volume_check("nearest_instance", labels=(labels, torch.int32))
+    dev, D, H, W = _volumes_check("nearest_instance", labels=(labels, torch.int32))
     d2 = torch.empty((D, H, W), dtype=torch.int32, device=dev)
     nearest = torch.empty((D, H, W), dtype=torch.int32, device=dev)
     workspace = torch.empty((D, H, W), dtype=torch.int64, device=dev)
@@ -831,7 +809,7 @@ def instance_pair_contacts(labels_a: torch.Tensor, ka: int, nearest_b: torch.Ten
     linear index of a voxel attaining it.  Rows are sorted by (a, b).  The pairs are collected in a hash table of ``capacity``
     slots (rounded up to a power of two; default ``PAIR_CAPACITY``) that doubles and starts over while a pair finds no slot; the
     rows depend on neither that nor scheduling.  The host waits once per table, for the overflow flag and P."""
-    dev, D, H, W = _split_volume_check("instance_pair_contacts", labels_a=(labels_a, torch.int32), nearest_b=(nearest_b, torch.int32),
+    dev, D, H, W = _volumes_check("instance_pair_contacts", labels_a=(labels_a, torch.int32), nearest_b=(nearest_b, torch.int32),
                                        d2_b=(d2_b, torch.int32))
     if ka < 0:
         raise _lib.CvxError(f"instance_pair_contacts: ka must be >= 0, got {ka}")
@@ -865,7 +843,7 @@ SKELETON_CYCLE_BATCH = 4  # thinning cycles launched per read of their "changed"
 
 def skeleton_init(labels: torch.Tensor, k: int) -> torch.Tensor:
     """int32 [D, H, W]: ``labels`` (int32 [D, H, W]) with ids outside 1..k set to 0, the volume the thinning starts from."""
-    dev, D, H, W = _split_volume_check("skeleton_init", labels=(labels, torch.int32))
+    dev, D, H, W = _volumes_check("skeleton_init", labels=(labels, torch.int32))
     if k < 0:
         raise _lib.CvxError(f"skeleton_init: k must be >= 0, got {k}")
     alive = torch.empty((D, H, W), dtype=torch.int32, device=dev)
@@ -880,7 +858,7 @@ def skeleton_cycles(alive: torch.Tensor, d2: torch.Tensor, k: int, level_d2: int
     ``_lib.EDT_NONE``) is deleted when it is a (26,6) simple point of its own id and no protected end (exactly one neighbour and
     d2 >= ``end_d2``).  Returns int32 [cycles] on the device (``changed[:cycles]`` when one of at least that length is given):
     entry c is nonzero iff cycle c deleted a voxel.  The host does not wait."""
-    dev, D, H, W = _split_volume_check("skeleton_cycles", alive=(alive, torch.int32), d2=(d2, torch.int32))
+    dev, D, H, W = _volumes_check("skeleton_cycles", alive=(alive, torch.int32), d2=(d2, torch.int32))
     if k < 0:
         raise _lib.CvxError(f"skeleton_cycles: k must be >= 0, got {k}")
     if level_d2 < 0 or end_d2 < 1 or cycles < 1:
@@ -901,7 +879,7 @@ def skeleton_stats(alive: torch.Tensor, d2: torch.Tensor, k: int) -> torch.Tenso
     with exactly one same-id neighbour among the 26 (ends); with three or more (branch voxels); with none; the links (unordered
     26-adjacent same-id pairs) by a face, an edge and a corner step; the sum of ``d2`` over the voxels (``_lib.EDT_NONE`` adds 0).
     Integers only, bit-reproducible; the host does not wait."""
-    dev, D, H, W = _split_volume_check("skeleton_stats", alive=(alive, torch.int32), d2=(d2, torch.int32))
+    dev, D, H, W = _volumes_check("skeleton_stats", alive=(alive, torch.int32), d2=(d2, torch.int32))
     if k < 0:
         raise _lib.CvxError(f"skeleton_stats: k must be >= 0, got {k}")
     out = torch.empty((int(k), _lib.SKELETON_COLS), dtype=torch.int64, device=dev)
@@ -929,7 +907,7 @@ def skeleton_thin_level(alive: torch.Tensor, d2: torch.Tensor, k: int, level: in
         raise _lib.CvxError(f"skeleton_thin_level: need max_cycles, batch and level >= 1, got {max_cycles}, {batch}, {level}")
     if k < 0 or end_d2 < 1:
         raise _lib.CvxError(f"skeleton_thin_level: need k >= 0 and end_d2 >= 1, got {k}, {end_d2}")
-    dev, *_ = _split_volume_check("skeleton_thin_level", alive=(alive, torch.int32), d2=(d2, torch.int32))  # before anything is launched
+    dev, *_ = _volumes_check("skeleton_thin_level", alive=(alive, torch.int32), d2=(d2, torch.int32))  # before anything is launched
     changed = torch.empty(batch, dtype=torch.int32, device=dev)
     done = 0
     while done < max_cycles:
@@ -955,7 +933,7 @@ def skeletonize_instances(labels: torch.Tensor, k: int, *, d2: torch.Tensor | No
     background does not see: topology stays exact, the line near a cut face is not centred.  Exact and bit-reproducible; raises
     when a level has no fixpoint within ``max_cycles`` cycles."""
     vols = {"labels": (labels, torch.int32)} | ({"d2": (d2, torch.int32)} if d2 is not None else {})
-    _split_volume_check("skeletonize_instances", **vols)
+    _volumes_check("skeletonize_instances", **vols)
     if k < 0:
         raise _lib.CvxError(f"skeletonize_instances: k must be >= 0, got {k}")
     if not end_radius >= 0 or end_radius * end_radius >= _lib.EDT_NONE:
@@ -980,7 +958,7 @@ def local_thickness_squared(d2: torch.Tensor) -> torch.Tensor:
     with ``d2[c] > 0`` whose open ball ``|p - c|^2 < d2[c]`` holds the voxel, so never below ``d2``.  Balls are clipped by the
     volume.  If any ``d2`` is ``_lib.EDT_NONE`` every nonzero voxel gets ``_lib.EDT_NONE``.  Integers only, bit-reproducible
     (csrc/thickness.hip); 4 bytes of workspace per 4x8x64 tile for the duration of the call; the host does not wait."""
-    dev, D, H, W = _split_volume_check("local_thickness_squared", d2=(d2, torch.int32))
+    dev, D, H, W = _volumes_check("local_thickness_squared", d2=(d2, torch.int32))
     lib = _lib.load()
     t2 = torch.empty((D, H, W), dtype=torch.int32, device=dev)
     workspace = torch.empty(max(int(lib.cvx_local_thickness_workspace_bytes(D, H, W)), 4) // 4, dtype=torch.int32, device=dev)
@@ -994,7 +972,7 @@ def instance_thickness_stats(labels: torch.Tensor, t2: torch.Tensor, k: int) -> 
     (``local_thickness_squared``) is neither 0 nor ``_lib.EDT_NONE``: voxels; the sum of t2; the sum of r_fx = floor(sqrt(t2 * 2^16)),
     the exact integer root (256 times the radius, rounded down); min t2; max t2.  0, 0, 0, -1, -1 for an id without such a voxel.
     Ids past k are ignored.  Integers only, bit-reproducible; the host does not wait."""
-    dev, D, H, W = _split_volume_check("instance_thickness_stats", labels=(labels, torch.int32), t2=(t2, torch.int32))
+    dev, D, H, W = _volumes_check("instance_thickness_stats", labels=(labels, torch.int32), t2=(t2, torch.int32))
     if k < 0:
         raise _lib.CvxError(f"instance_thickness_stats: k must be >= 0, got {k}")
     out = torch.empty((int(k), _lib.THICKNESS_COLS), dtype=torch.int64, device=dev)
@@ -1008,7 +986,7 @@ def instance_thickness(labels: torch.Tensor, k: int, *, d2: torch.Tensor | None 
     Ids play no part in the map: after a split the pieces share faces, which ``d2`` to the background does not see, so a ball
     centred in one piece may cover voxels of its neighbour and the map of two touching pieces is the map of their union."""
     vols = {"labels": (labels, torch.int32)} | ({"d2": (d2, torch.int32)} if d2 is not None else {})
-    _split_volume_check("instance_thickness", **vols)
+    _volumes_check("instance_thickness", **vols)
     if k < 0:
         raise _lib.CvxError(f"instance_thickness: k must be >= 0, got {k}")
     if d2 is None:
@@ -1040,7 +1018,7 @@ def mesh_surface(labels: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torc
     Vertices are edge midpoints in z, y, x order and units of 1/256 voxel; a triangle's id is the label of its tet's first foreground
     corner; orders, winding and the 14-connectivity are laid down in include/cryovit_hip.h.  Integers only, bit-reproducible
     (csrc/mesh.hip).  The host waits once, for V and T, to size the outputs; more than 2^31 - 1 of either is refused."""
-    dev, D, H, W = _split_volume_check("mesh_surface", labels=(labels, torch.int32))
+    dev, D, H, W = _volumes_check("mesh_surface", labels=(labels, torch.int32))
     lib = _lib.load()
     workspace = torch.empty((int(lib.cvx_mesh_workspace_bytes(D, H, W)) + 15) // 16 * 4, dtype=torch.int32, device=dev)
     totals = torch.empty(2, dtype=torch.int64, device=dev)
