@@ -40,6 +40,7 @@ SKELETON_COLS = 8  # CVX_SKELETON_COLS
 THICKNESS_COLS = 5  # CVX_THICKNESS_COLS
 MESH_COLS = 3  # CVX_MESH_COLS
 MESH_FACTOR_MAX = 131072  # CVX_MESH_FACTOR_MAX
+MASK_LE, MASK_GT = 0, 1  # CVX_MASK_LE / CVX_MASK_GT
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -200,6 +201,11 @@ SIGNATURES = {
     "cvx_mesh_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_long, c_long, c_void_p, c_void_p]),
     "cvx_mesh_smooth_workspace_bytes": (c_long, [c_long]),
     "cvx_mesh_smooth_step": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_long, c_void_p]),
+    "cvx_mask_flood_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cvx_mask_flood_rounds": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_mask_flood_unpack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_mask_threshold": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_mask_added_voxels": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,10 +1,12 @@
 """Quantification of predictions after the model has run: connected instances of a predicted mask, what
 its distance maps say about them, the split of instances that touch over a neck, which instance of one label touches
 which of another, the shape of each instance (surface area, Euler number, principal axes), its centreline (length, ends, branches)
-its local thickness (mean, spread, min, max) and the surface mesh of the mask (PLY / STL; triangles, area, volume)."""
+its local thickness (mean, spread, min, max) and the surface mesh of the mask (PLY / STL; triangles, area, volume); and the
+clean-up of the mask before all of that (close, fill holes, open)."""
 
 from cryovit_amd.analysis.instances import (  # noqa: F401
     INSTANCE_COLUMNS, InstanceOptions, instance_rows, label_and_split, label_file, label_volume, measure, split_volume)
+from cryovit_amd.analysis.cleanup import CleanupOptions, clean_mask  # noqa: F401
 from cryovit_amd.analysis.distances import (  # noqa: F401
     PAIR_COLUMNS, edt_squared, instance_contacts, instance_morphology, instance_pair_contacts, pair_rows, partner_rows)
 from cryovit_amd.analysis.shape import SHAPE_COLUMNS, instance_shape, shape_rows  # noqa: F401

@@ -19,6 +19,7 @@ import numpy as np
 
 from cryovit_amd.analysis import distances
 from cryovit_amd.analysis._tables import host_table
+from cryovit_amd.analysis.cleanup import CleanupOptions, added_rows, added_voxels, clean_mask, log_totals
 from cryovit_amd.analysis.mesh import MESH_FORMATS, mesh_arrays, mesh_rows
 from cryovit_amd.analysis.shape import instance_shape
 from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
@@ -235,10 +236,14 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
                morphology: bool = False, distance_to: str | None = None, distance_to_dir=None, contact_radius: float = 1.0,
                split_radius: float | None = None, split_min_core: int = 0, contacts_with: str | None = None,
                shape: bool = False, skeleton: bool = False, skeleton_end_radius: float = 2.0,
-               thickness: bool = False, mesh: bool = False, mesh_smooth: int = 0, mesh_format: str = "ply") -> Path:
+               thickness: bool = False, mesh: bool = False, mesh_smooth: int = 0, mesh_format: str = "ply",
+               close_radius: float | None = None, fill_holes: str | None = None, open_radius: float | None = None) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  The measurements are those of ``InstanceOptions``.
+    ``close_radius``, ``fill_holes`` and ``open_radius`` are the fields of ``analysis.cleanup.CleanupOptions``: the mask is cleaned
+    on the device before it is labelled, ``<label>_cleaned`` is written beside ``<label>_preds`` (which stays as predicted) and the
+    CSV gains ``added_voxels`` as its first extra column.
     ``distance_to`` names another label whose mask (``<distance_to>_preds`` of the same file, else of
     ``distance_to_dir/<same stem>.hdf``) the gap and contact columns are taken against.  ``contacts_with`` names another label
     whose instances are paired with this label's: ``<contacts_with>_instances`` of the same file, else of
@@ -252,10 +257,11 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
 
     path = Path(path)
     key = f"{label}_preds"
+    cleanup = CleanupOptions(close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius).validate()
     datasets = io.read_all_flat(path)
     if key not in datasets:
         raise KeyError(f"{path} holds no '{key}' dataset (found {sorted(datasets)})")
-    for stale in ("instances", "skeleton", "thickness"):  # an earlier run's results carry that run's ids and filtering
+    for stale in ("instances", "skeleton", "thickness", "cleaned"):  # an earlier run's results carry that run's ids and filtering
         datasets.pop(f"{label}_{stale}", None)
     preds = datasets[key]
     if preds.ndim != 3:
@@ -290,9 +296,15 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
                      path, contacts_with, contacts_with, connectivity)
         return partner_labels, int(partner_table.shape[0])
 
-    labels, table, component = label_and_split(on_device(preds), opts)
+    predicted = on_device(preds)
+    cleaned, totals = clean_mask(predicted, cleanup, opts.connectivity)
+    labels, table, component = label_and_split(cleaned, opts)
     found = measure(labels, int(table.shape[0]), component, opts, other_mask=None if other is None else on_device(other),
                     other_name=distance_to, partner=None if partner is None else partner_instances, partner_name=contacts_with)
+    if cleanup.any:
+        found.extra = added_rows(added_voxels(labels, predicted, int(table.shape[0])), found.extra)
+        log_totals(f"{path} '{label}'", totals)
+        datasets = {name: arr for name, arr in datasets.items() if name != key} | {key: preds, f"{label}_cleaned": cleaned.cpu().numpy()}
     result_dir = result_dir if result_dir is not None else path.parent
     if found.pairs is not None:
         writers.write_contacts(result_dir, path.name, label, contacts_with, found.pairs)

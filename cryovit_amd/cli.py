@@ -8,14 +8,17 @@
     python -m cryovit_amd.cli instances <predictions> --label NAME [--result-folder DIR] <measurements>
                                         [--distance-to NAME] [--contacts-with NAME] [--distance-to-folder DIR] [--contact-radius R]
 
-    <measurements>: [--min-size N] [--connectivity 6|26] [--split-radius R [--split-min-core N]] [--morphology] [--shape]
+    <measurements>: [--close-radius R] [--fill-holes 3d|slices] [--open-radius R]
+                    [--min-size N] [--connectivity 6|26] [--split-radius R [--split-min-core N]] [--morphology] [--shape]
                     [--skeleton [--skeleton-end-radius R]] [--thickness] [--mesh [--mesh-smooth N] [--mesh-format ply|stl]]
 
 ``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
 replace the network fetch of the encoder weights or add what the reference leaves to the user: ``instances`` (and
 ``infer --instances``) labels the connected instances of a predicted mask on the GPU, tabulates their size and position and
 measures them.  The measurement options are declared once, below, for both commands; each is a field of
-``analysis.instances.InstanceOptions``, which says what it computes and writes.  ``--distance-to NAME`` adds the gap to another
+``analysis.instances.InstanceOptions``, which says what it computes and writes.  ``--close-radius``, ``--fill-holes`` and
+``--open-radius`` clean the mask on the GPU before it is labelled, in that order (``analysis.cleanup.CleanupOptions``): the file gains
+``<label>_cleaned`` and the CSV ``added_voxels``.  ``--distance-to NAME`` adds the gap to another
 label's mask and the voxels in contact with it; ``--contacts-with NAME`` says which instance touches which: every instance gains
 ``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance, nearest instance of NAME within
 ``--contact-radius``) the voxels in contact, the narrowest gap and where it is.
@@ -98,6 +101,13 @@ _MESH_SMOOTH_HELP = ("with --mesh, relax the mesh by N pairs of integer Taubin s
                      "written; 0 keeps the raw mesh, about 10 gives a surface to quote beside surface_area of --shape")
 _MESH_FORMAT_HELP = ("with --mesh, the file format: ply (binary, shared vertices, an instance id per face) or stl (binary, the id in "
                      "the attribute word, saturated at 65535)")
+_CLOSE_RADIUS_HELP = ("before labelling, close the mask by a ball of this radius on the GPU (seals pinholes and one-voxel cracks; "
+                      "applied first; writes <label>_cleaned and the CSV column added_voxels; voxels, >= 0; with infer: needs --instances)")
+_FILL_HOLES_HELP = ("before labelling, fill the background that is not connected to the border, on the GPU: 3d = enclosed cavities "
+                    "of the volume, slices = every z-slice on its own, as Fiji's Fill Holes (for structures the missing wedge leaves "
+                    "open along z); applied after --close-radius (with infer: needs --instances)")
+_OPEN_RADIUS_HELP = ("before labelling, open the mask by a ball of this radius on the GPU (removes spurs and specks; applied last; "
+                     "voxels, >= 0; with infer: needs --instances)")
 _EXT = "build extension: "
 
 MinSize = Annotated[int, Option(min=0, help=_EXT + _MIN_SIZE_HELP)]
@@ -115,9 +125,13 @@ MeshSmooth = Annotated[int, Option("--mesh-smooth", callback=_checked(lambda v: 
                                    help=_EXT + _MESH_SMOOTH_HELP)]
 MeshFormat = Annotated[str, Option("--mesh-format", callback=_checked(lambda v: v in ("ply", "stl"), "mesh format must be ply or stl"),
                                    help=_EXT + _MESH_FORMAT_HELP)]
+CloseRadius = Annotated[Optional[float], Option(callback=_non_negative("close radius"), help=_EXT + _CLOSE_RADIUS_HELP)]
+FillHoles = Annotated[Optional[str], Option(callback=_checked(lambda v: v in ("3d", "slices"), "fill holes must be 3d or slices"),
+                                            help=_EXT + _FILL_HOLES_HELP)]
+OpenRadius = Annotated[Optional[float], Option(callback=_non_negative("open radius"), help=_EXT + _OPEN_RADIUS_HELP)]
 
 # infer measures nothing without --instances: asking for one of these without it is a usage error
-_NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh")
+_NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh", "close_radius", "fill_holes", "open_radius")
 
 
 def _encoder_overrides(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]) -> dict:
@@ -175,11 +189,15 @@ def infer(
     mesh: Mesh = False,
     mesh_smooth: MeshSmooth = 0,
     mesh_format: MeshFormat = "ply",
+    close_radius: CloseRadius = None,
+    fill_holes: FillHoles = None,
+    open_radius: OpenRadius = None,
 ):
     """Segment tomograms using a pre-trained model."""
     measurements = dict(min_size=min_size, connectivity=connectivity, morphology=morphology, split_radius=split_radius,
                         split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
-                        thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
+                        thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format,
+                        close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius)
     for name in _NEEDS_INSTANCES:
         value = measurements[name]  # a flag that is off is False, a radius that is not given None; a radius of 0 is given
         if not instances and value is not False and value is not None:
@@ -220,6 +238,9 @@ def instances_cmd(
     mesh: Mesh = False,
     mesh_smooth: MeshSmooth = 0,
     mesh_format: MeshFormat = "ply",
+    close_radius: CloseRadius = None,
+    fill_holes: FillHoles = None,
+    open_radius: OpenRadius = None,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     from cryovit_amd.analysis.instances import label_file
@@ -233,7 +254,8 @@ def instances_cmd(
                          distance_to=distance_to, distance_to_dir=distance_to_folder, contact_radius=contact_radius,
                          split_radius=split_radius, split_min_core=split_min_core, contacts_with=contacts_with, shape=shape,
                          skeleton=skeleton, skeleton_end_radius=skeleton_end_radius, thickness=thickness,
-                         mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
+                         mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format,
+                         close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius)
         logging.info("Labelled %s", out)
 
 

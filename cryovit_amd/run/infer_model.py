@@ -19,6 +19,8 @@ unfiltered threshold mask.  ``morphology``, ``split_radius``, ``shape``, ``skele
 ``instances``) measure the instances while the labels are in HBM: the keywords are the fields of
 ``analysis.instances.InstanceOptions``, which says what each computes and writes, and the pipeline is the one ``cryovit instances``
 runs on a written file (``analysis.instances.label_and_split`` / ``measure``, ``writers.write_measured`` on the writer thread).
+``close_radius``, ``fill_holes`` and ``open_radius`` (with ``instances``) are the fields of ``analysis.cleanup.CleanupOptions``: the
+mask is cleaned in HBM before it is labelled, each file also holds ``<label_key>_cleaned`` and the table gains ``added_voxels``.
 """
 
 from __future__ import annotations
@@ -31,6 +33,7 @@ import numpy as np
 import torch
 
 from cryovit_amd import io
+from cryovit_amd.analysis.cleanup import CleanupOptions, added_rows, added_voxels, clean_mask, log_totals
 from cryovit_amd.analysis.instances import InstanceOptions, label_and_split, measure
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
@@ -71,10 +74,12 @@ def _predict_file(model, dataset, idx: int, threshold: float, encoder, batch_siz
     return item.aux_data["data"], mask
 
 
-def _write_measured(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, measured, mesh_format: str) -> Path:
-    """``writers.write_measured`` with the datasets of ``writers.write_segmentation``; the conversion of the raw volume to float32
-    is part of the writer thread's work."""
+def _write_measured(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, measured, mesh_format: str, cleaned=None) -> Path:
+    """``writers.write_measured`` with the datasets of ``writers.write_segmentation`` (and ``<label>_cleaned`` where the mask was
+    cleaned); the conversion of the raw volume to float32 is part of the writer thread's work."""
     datasets = {"data": raw.astype(np.float32), f"{label_key}_preds": segs.astype(np.uint8, copy=False)}
+    if cleaned is not None:
+        datasets[f"{label_key}_cleaned"] = cleaned.astype(np.uint8, copy=False)
     return writers.write_measured(result_dir, tomo_name, label_key, datasets, labels, table, measured, mesh_format)
 
 
@@ -90,17 +95,23 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                   connectivity: int = 26, morphology: bool = False, split_radius: float | None = None,
                   split_min_core: int = 0, shape: bool = False, skeleton: bool = False,
                   skeleton_end_radius: float = 2.0, thickness: bool = False, mesh: bool = False, mesh_smooth: int = 0,
-                  mesh_format: str = "ply") -> list[Path]:
+                  mesh_format: str = "ply", close_radius: float | None = None, fill_holes: str | None = None,
+                  open_radius: float | None = None) -> list[Path]:
     opts = InstanceOptions(connectivity=connectivity, min_size=min_size, morphology=morphology, split_radius=split_radius,
                            split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
                            thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
+    cleanup = CleanupOptions(close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius)
     if not instances:
         for name in InstanceOptions.MEASUREMENTS:
             if getattr(opts, name):
                 raise ValueError(f"{name}=True needs instances=True: it is measured on the labelled instances")
         if split_radius is not None:
             raise ValueError("split_radius needs instances=True: it splits the labelled instances")
+        for name in ("close_radius", "fill_holes", "open_radius"):
+            if getattr(cleanup, name) is not None:
+                raise ValueError(f"{name} needs instances=True: it cleans the mask that is labelled")
     opts.validate()
+    cleanup.validate()
     rank, _, world = world_info()
     device = select_device(device)
     model, model_type, model_name, label_key = load_model(model_path, device=device)
@@ -124,15 +135,23 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
             raw, mask = _predict_file(model, dataset, i, threshold, encoder, batch_size)
             host = torch.empty(mask.shape, dtype=torch.uint8, pin_memory=True)
             host.copy_(mask, non_blocking=True)
+            host_cleaned = None
             if instances:
-                labels, table, component = label_and_split(mask.contiguous(), opts)
+                predicted = mask.contiguous()
+                cleaned, totals = clean_mask(predicted, cleanup, opts.connectivity)
+                labels, table, component = label_and_split(cleaned, opts)
                 host_labels = _pinned(labels)  # on its way while the instances are measured
                 host_table = table.cpu().numpy()
-                found = measure(labels, int(table.shape[0]), component, opts).arrays(_pinned)
+                found = measure(labels, int(table.shape[0]), component, opts)
+                if cleanup.any:
+                    host_cleaned = _pinned(cleaned)
+                    found.extra = added_rows(added_voxels(labels, predicted, int(table.shape[0])), found.extra)
+                    log_totals(f"{files[i].tomo_path.name} '{label_key}'", totals)
+                found = found.arrays(_pinned)
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:
                 pending.append((i, writer.submit(_write_measured, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),
-                                                 host_labels, host_table, found, mesh_format)))
+                                                 host_labels, host_table, found, mesh_format, host_cleaned)))
             else:
                 pending.append((i, writer.submit(writers.write_segmentation, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy())))
             while len(pending) > 2:

@@ -751,6 +751,41 @@ long cvx_mesh_smooth_workspace_bytes(long V);
 int cvx_mesh_smooth_step(const int32_t* vertices, int32_t* moved, const int32_t* triangles, long V, long T, int c, void* workspace,
                          long workspace_bytes, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Cleaning a predicted mask before it is labelled (`--close-radius`, `--fill-holes`, `--open-radius` of `infer --instances` and
+ * `cryovit instances`).  Integers only, bit-reproducible.
+ *
+ * Fill holes.  A background voxel of mask uint8 [D][H][W] is filled unless it is connected to the border through background
+ * voxels under the background connectivity 6 or 26.  The border is the six faces of the volume; with slices = 1 every z-slice is
+ * an image of its own, the border its four edges, and the connectivity 4 (for 6) or 8 (for 26) within the slice.  The flood runs
+ * on bits: WW = ceil(W / 64) uint64 words per row, [D][H][WW], bit i of word w = voxel x = 64 w + i; bits past W are 0.
+ *   cvx_mask_flood_pack    open = (mask == 0); reach = the open bits of the border.
+ *   cvx_mask_flood_rounds  `rounds` launches of the flood kernel: every round sets bits of reach towards the fixpoint reach = open
+ *                          and (on the border or next to a reach voxel).  changed int32 [rounds] is cleared by the call; round r
+ *                          sets changed[r] = 1 iff it set a bit.  A round that set none proves the fixpoint; the caller launches
+ *                          until it sees one.  No workgroup waits for another; bits are only ever set, each word written by one
+ *                          aligned 8-byte store, so the fixpoint does not depend on scheduling (the number of rounds does).
+ *   cvx_mask_flood_unpack  out uint8 [D][H][W] = 1 where the voxel is not in reach (foreground or filled), 0 where it is.
+ * Ball steps.  cvx_mask_threshold: out uint8 [D][H][W] = d2 <= threshold_d2 (CVX_MASK_LE: with d2 = cvx_edt_squared(...,
+ *   CVX_EDT_SITES_NONZERO) the dilation by the ball |v|^2 <= threshold_d2) or d2 > threshold_d2 (CVX_MASK_GT: with
+ *   CVX_EDT_SITES_ZERO the erosion; CVX_EDT_NONE is above every threshold), where d2 int32 [D+2 pad][H+2 pad][W+2 pad] is read at
+ *   (z + pad, y + pad, x + pad): the crop of a map that was computed on a padded copy.
+ * Added voxels.  cvx_mask_added_voxels: out int64 [k], initialised by the call; out[id - 1] = the voxels with labels == id (int32
+ *   [D][H][W], ids 1..k, others ignored) where before (uint8 [D][H][W], the mask as predicted) is 0.
+ * Refused with an error before any launch: negative extents, D*H*W (for cvx_mask_threshold also the padded extents' product) >
+ * CVX_COMPONENT_MAX_VOXELS, null pointers, misaligned arrays (words and out of added_voxels: 8 bytes, int32: 4 bytes), open ==
+ * reach, slices other than 0 / 1, a background other than 6 / 26, rounds < 1, pad outside [0, 32768], another mode, a threshold
+ * outside [0, 2^31 - 2], k < 0.  An empty volume and k == 0 succeed and launch nothing.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_MASK_LE 0
+#define CVX_MASK_GT 1
+int cvx_mask_flood_pack(const uint8_t* mask, int D, int H, int W, int slices, uint64_t* open, uint64_t* reach, hipStream_t stream);
+int cvx_mask_flood_rounds(const uint64_t* open, uint64_t* reach, int D, int H, int W, int background, int slices, int rounds,
+                          int32_t* changed, hipStream_t stream);
+int cvx_mask_flood_unpack(const uint64_t* reach, int D, int H, int W, uint8_t* out, hipStream_t stream);
+int cvx_mask_threshold(const int32_t* d2, int D, int H, int W, int pad, int mode, int threshold_d2, uint8_t* out, hipStream_t stream);
+int cvx_mask_added_voxels(const int32_t* labels, const uint8_t* before, int D, int H, int W, long k, int64_t* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
