@@ -152,7 +152,7 @@ SIGNATURES = {
     "cvx_pool2x2": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_int, c_void_p]),
     "cvx_cast_bf16": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long, c_int, c_void_p]),
     "cvx_fpn_level_out": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "cvx_dice_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p]),
+    "cvx_dice_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p]),
     "cvx_dice_loss_forward": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "cvx_dice_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_float, c_int, c_void_p, c_void_p]),
     "cvx_focal_loss_forward": (c_int, [c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p, c_void_p]),

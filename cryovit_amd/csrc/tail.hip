@@ -114,23 +114,32 @@ __global__ __launch_bounds__(64) void k_dice_finalize(const float* __restrict__ 
     }
 }
 
-// Standalone masked Dice sums over probs/labels (used when predictions come from elsewhere)
+// Standalone masked Dice sums over probs/labels (used when predictions come from elsewhere).  The sums are counts: a thread
+// counts in int32 (at most n / 2^20 elements each), a block in int64, and a block's row of `partials` is exact in fp32 below
+// 2^24 elements per block (n < 2^36); k_dice_finalize adds the rows in fp64 in a fixed order.  (Float atomics rounded every
+// add once a sum passed 2^24, in the order the waves happened to arrive.)
 __global__ __launch_bounds__(256) void k_dice(const float* __restrict__ probs, const int8_t* __restrict__ labels,
-                                              float* __restrict__ dice, long n, float thr) {
-    float inter = 0.f, ysum = 0.f, psum = 0.f;
+                                              float* __restrict__ partials, long n, float thr) {
+    __shared__ long red[3][4];
+    int inter = 0, ysum = 0, psum = 0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const int lab = labels[i];
         if (lab > -1) {
-            const float ph = probs[i] < thr ? 0.f : 1.f;
-            inter += (float)lab * ph; ysum += (float)lab; psum += ph;
+            const int ph = probs[i] < thr ? 0 : 1;
+            inter += lab * ph; ysum += lab; psum += ph;
         }
     }
-    inter = wave_sum(inter); ysum = wave_sum(ysum); psum = wave_sum(psum);
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&dice[0], inter);
-        atomicAdd(&dice[1], ysum);
-        atomicAdd(&dice[2], psum);
-    }
+    long s[3] = {inter, ysum, psum};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][wv] = s[0]; red[1][wv] = s[1]; red[2][wv] = s[2]; }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        partials[(long)blockIdx.x * 3 + threadIdx.x] =
+            (float)((red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]));
 }
 
 }  // namespace cvx
@@ -153,9 +162,15 @@ extern "C" int cvx_conv3_out_fused(const void* in, const float* w, float bias, f
     return cvx_check_launch();
 }
 
-extern "C" int cvx_dice_sums(const float* probs, const int8_t* labels, float* dice, long n, float thr, hipStream_t st) {
+extern "C" int cvx_dice_sums(const float* probs, const int8_t* labels, float* dice, float* scratch, long n, float thr,
+                             hipStream_t st) {
     if (n <= 0) return 0;
-    const unsigned nblk = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_dice, dim3(nblk), dim3(256), 0, st, probs, labels, dice, n, thr);
+    if (!probs || !labels || !dice || !scratch) return cvx_fail("dice_sums: null pointer");
+    const long want = (n + 255) / 256;
+    const int nblk = (int)(want < CVX_DICE_BLOCKS ? want : CVX_DICE_BLOCKS);
+    hipLaunchKernelGGL(k_dice, dim3(nblk), dim3(256), 0, st, probs, labels, scratch, n, thr);
+    int rc = cvx_check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_dice_finalize, dim3(1), dim3(64), 0, st, scratch, nblk, dice);
     return cvx_check_launch();
 }

@@ -186,8 +186,9 @@ static unsigned stream_blocks(long n, long per_block) {
 }
 
 extern "C" int cvx_dice_loss_forward(const float* probs, const int8_t* labels, long n, float* scratch, float* out4, hipStream_t st) {
-    if (!probs || !labels || !scratch || !out4) return cvx_fail("dice_loss_forward: null pointer");
     if (n < 0) return cvx_fail("dice_loss_forward: n < 0");
+    // n == 0 (a crop without a labelled voxel, already masked): empty arrays have no address; the sums are 0 and the loss is 1
+    if ((n > 0 && (!probs || !labels)) || !scratch || !out4) return cvx_fail("dice_loss_forward: null pointer");
     if (((uintptr_t)probs & 15) || ((uintptr_t)labels & 3)) return cvx_fail("dice_loss_forward: probs must be 16-B and labels 4-B aligned");
     const unsigned nblk = stream_blocks(n, 4096);
     hipLaunchKernelGGL(k_dice_loss_partials, dim3(nblk), dim3(256), 0, st, probs, labels, n, scratch);
@@ -199,8 +200,8 @@ extern "C" int cvx_dice_loss_forward(const float* probs, const int8_t* labels, l
 
 extern "C" int cvx_dice_loss_backward(const float* probs, const float* logits, const int8_t* labels, long n, const float* sums4,
                                       float grad_out, int through_sigmoid, float* grad, hipStream_t st) {
+    if (n <= 0) return 0;  // an empty gradient
     if (!labels || !sums4 || !grad || (through_sigmoid && !probs)) return cvx_fail("dice_loss_backward: null pointer");
-    if (n <= 0) return 0;
     hipLaunchKernelGGL(k_dice_loss_backward, dim3(stream_blocks(n, 2048)), dim3(256), 0, st, probs, logits, labels, n, sums4, grad_out,
                        through_sigmoid, grad);
     return cvx_check_launch();

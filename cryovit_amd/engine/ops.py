@@ -309,8 +309,8 @@ def conv3_out_fused(x: torch.Tensor, w: torch.Tensor, bias: float, logits, probs
 
 def dice_sums(probs: torch.Tensor, labels: torch.Tensor, dice: torch.Tensor, thr: float = 0.5) -> None:
     dev = _dev_check(probs, labels, dice)
-    call(dev, "cvx_dice_sums", _lib.load().cvx_dice_sums, probs.data_ptr(), labels.data_ptr(), dice.data_ptr(), probs.numel(),
-         thr)
+    call(dev, "cvx_dice_sums", _lib.load().cvx_dice_sums, probs.data_ptr(), labels.data_ptr(), dice.data_ptr(),
+         dice_scratch(probs.device).data_ptr(), probs.numel(), thr)
 
 
 # ---- training-side pieces (SURVEY s.8f N4) ----

@@ -238,8 +238,10 @@ int cvx_conv3_out_fused(const void* in, const float* w, float bias, float* logit
                         float* dice, float* scratch, uint8_t* mask, float mask_threshold, int D, int H, int W,
                         hipStream_t stream);
 
-/* Masked Dice partial sums over existing predictions (same definition as above, threshold thr). */
-int cvx_dice_sums(const float* probs, const int8_t* labels, float* dice, long n, float thr, hipStream_t stream);
+/* Masked Dice partial sums over existing predictions (same definition as above, threshold thr): dice[k] += the three counts.
+ * The counts are accumulated as integers (per block) and added in fp64 in a fixed order, then rounded ONCE to fp32: exact and
+ * bitwise reproducible also beyond 2^24 voxels.  scratch: >= 3*CVX_DICE_BLOCKS floats. */
+int cvx_dice_sums(const float* probs, const int8_t* labels, float* dice, float* scratch, long n, float thr, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Training-side pieces of the head (csrc/train.hip).

@@ -463,6 +463,7 @@ def fp32_forward_bound(a16, w16, K, bias, gain=None, x0=None):
 LAYERNORM_CASES = [(70, 128), (70, 144), (70, 1536)]  # (rows, C); the unbiased-variance mutant is undetectable at 1536 (R 1.01)
 LAYERNORM_NARROW = (128, 144)
 GROUPNORM_CASES = [(32, 8), (8, 8)]  # (C, G)
+INSTANCENORM_GELU_CASES = [8, 16, 48]  # C = G with the GELU fused; the U-Net's widths: 16 -> 2 chunks of 8 channels, 48 -> 6 (no power of two)
 GROUPNORM_DHW = (5, 6, 7)
 
 
@@ -570,7 +571,10 @@ def groupnorm_case(C, G, gelu=False, full=True):
 CONV3D_CASES = [(8, 8, 1, 5, 9, 11), (8, 8, 2, 5, 9, 11), (32, 16, 1, 6, 8, 8), (32, 16, 2, 6, 8, 8)]  # (Cin, Cout, dil, D, H, W)
 HALO_CASES = [(8, 8, 1, 4, 7, 66)]
 CONVT_CASES = [(16, 8, 1, 1, 16), (16, 8, 3, 5, 32)]  # (c2, c3, D, H, W)
-CONV2S2_CASES = [(8, 8, 4, 6, 10)]  # (C, Cout, D, H, W)
+CONVT3_CASES = [(16, 8), (32, 16)]  # (c2, c3) of the (2, 2, 2) form, at CONVT3_DHW
+CONVT3_DHW = (3, 4, 5)
+# (C, Cout, D, H, W).  Not (32, 24, 8, 2, 2): a truncating store is only 1.558 over its 96 outputs
+CONV2S2_CASES = [(8, 8, 4, 6, 10), (16, 64, 6, 8, 8), (64, 256, 2, 4, 6)]
 
 
 def _lines(t):  # [D, H, W, C] -> [D*H, W, C]: row groups stay inside one line of one plane, so faces and corners form their own groups
@@ -627,6 +631,28 @@ def convt_case(c2, c3, D, H, W, full=True):
 
 
 @functools.lru_cache(maxsize=None)
+def convt3_operands(c2, c3):
+    """tests/test_gpu_unet.py::test_conv_transpose_3d's operands: fp16 x [nv, c2], fp32 wt [c2, c3, 2, 2, 2], bias."""
+    D, H, W = CONVT3_DHW
+    return hf(rnd(D * H * W, c2, seed=83)), rnd(c2, c3, 2, 2, 2, seed=84, scale=c2**-0.5), rnd(c3, seed=85)
+
+
+@functools.lru_cache(maxsize=None)
+def convt3_case(c2, c3, full=True):
+    """ConvTranspose3d kernel = stride = (2, 2, 2), no activation (the U-Net's up-sampling); output [2D, 2H, 2W, c3]."""
+    D, H, W = CONVT3_DHW
+    x16, wt, b = convt3_operands(c2, c3)
+    xin = x16.double().reshape(D, H, W, c2).permute(3, 0, 1, 2).unsqueeze(0)
+    ref = F.conv_transpose3d(xin, hf(wt).double(), b.double(), stride=2)[0].permute(1, 2, 3, 0)
+    fam = Family(_lines(ref), _lines(rh(ref)), {}, {})
+    if full:
+        r32 = F.conv_transpose3d(xin.float(), hf(wt).float(), b, stride=2)[0].permute(1, 2, 3, 0)
+        fam.honest["fp32 order"] = _lines(rh(r32.double()))
+        fam.mutants["truncating store"] = ("R_all", _lines(th(ref)))
+    return fam
+
+
+@functools.lru_cache(maxsize=None)
 def conv2s2_operands(C, Cout, D, H, W):
     """tests/test_gpu_unet.py::test_conv2s2's operands."""
     return hf(rnd(D, H, W, C, seed=80)), rnd(Cout, C, 2, 2, 2, seed=81, scale=(8 * C) ** -0.5), rnd(Cout, seed=82)
@@ -665,12 +691,13 @@ def families(op):
         return {"3x(4x6) C=128": final_norm_case()}
     if op == "groupnorm":
         out = {f"C={C} G={G}": groupnorm_case(C, G) for C, G in GROUPNORM_CASES}
-        out["C=8 G=8 gelu"] = groupnorm_case(8, 8, True)
+        out.update({f"C={C} G={C} gelu": groupnorm_case(C, C, True) for C in INSTANCENORM_GELU_CASES})
         return out
     if op == "conv":
         out = {f"conv3d {c}": conv3d_case(*c) for c in CONV3D_CASES}
         out.update({f"halo {c}": conv3d_case(*c, seed=58) for c in HALO_CASES})
         out.update({f"convt {c}": convt_case(*c) for c in CONVT_CASES})
+        out.update({f"convt3 {c}": convt3_case(*c) for c in CONVT3_CASES})
         out.update({f"conv2s2 {c}": conv2s2_case(*c) for c in CONV2S2_CASES})
         return out
     raise KeyError(op)
@@ -699,8 +726,10 @@ def derive(op):
 # Measured on an MI355X (R_all / R_row / R_col; a record, not the source of any bound).  Every case not listed measured
 # 1.000 / 1.000 / 1.000 to three decimals, i.e. the kernel's output is the emulation's up to a few ties:
 #   all GEMM cases (bf16, GELU, SwiGLU, V^T; plain and LayerNorm fold; the six 256-tile schedules and the 4-wave tile), LayerNorm 128 /
-#   144 / 1536, final norm, GroupNorm (32, 8), (8, 8), (8, 8) + GELU, conv3d (both kernels, the tile-halo kernel on the ablation
-#   build), the halo case, both transposed convolutions (both kernels), conv2s2, window attention at 16 and 64 keys (G 8 / ws 4, hd 96).
+#   144 / 1536, final norm, GroupNorm (32, 8), (8, 8), InstanceNorm + GELU at C = 8, 16 and 48, conv3d (both kernels, the tile-halo
+#   kernel on the ablation build), the halo case, both (1, 2, 2) transposed convolutions (both kernels), the (2, 2, 2) transposed
+#   convolutions (16, 8) and (32, 16), conv2s2 (8, 8, 4, 6, 10), (16, 64, 6, 8, 8) and (64, 256, 2, 4, 6), window attention at 16 and
+#   64 keys (G 8 / ws 4, hd 96).
 #   attention nt=1029         variants 7, 8, 9, qkv  1.000 / 1.023 / 1.001    variants 0, 3, 4, 5  1.000 / 1.058 / 1.003    variant 6  0.997 / 1.215 / 1.005
 #   attention nt=261          variants 0, 3, 4, 5    1.000 / 1.000 / 1.002    variant 6  1.001 / 1.213 / 1.011
 #   attention nt=133          variants 0, 3, 4, 5    1.000 / 1.017 / 1.002    variant 6  1.000 / 1.000 / 1.005

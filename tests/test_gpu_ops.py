@@ -673,25 +673,55 @@ def test_conv_transpose_small_kernel(gpu, c2, c3, D, H, W):
     assert float((outs[0].float() - outs[1].float()).abs().max()) <= 2e-3
 
 
-def test_conv3_out_fused_and_dice(gpu, gold):
-    from cryovit_amd.engine import ops
-
-    D, H, W = 6, 16, 70
+def _conv3_out_operands(D, H, W):
+    """The recipe of test_conv3_out_fused_and_dice: fp16 x [D, H, W, 8], fp32 w [1, 8, 3, 3, 3], bias, int8 labels in {-1, 0, 1}."""
     x = hf(rnd(D, H, W, 8, seed=44))
     w, b = rnd(1, 8, 3, 3, 3, seed=45, scale=0.3), 0.1
     labels = torch.from_numpy(np.random.default_rng(46).integers(-1, 2, size=(D, H, W)).astype(np.int8))
+    return x, w, b, labels
+
+
+def _tap_major(w):
+    return w[0].permute(1, 2, 3, 0).reshape(27, 8).contiguous()
+
+
+# Tiles are 64 (x) x 4 (y) voxels of one z plane; at most CVX_DICE_BLOCKS = 4096 blocks, each walking tiles b, b + grid, ...; a grid
+# that is a multiple of 8 starts its blocks in the XCD-permuted order.
+#   (1, 1, 1)      every tap but the centre is padding
+#   (1, 3, 63)     narrower and lower than a tile, no z neighbours
+#   (2, 4, 64)     exactly one tile per plane
+#   (3, 5, 65)     one voxel past in x and y: 12 tiles, a grid that is no multiple of 8 -> the plain block order
+#   (2, 9, 130)    3 x 3 tiles per plane
+#   (6, 16, 70)    48 tiles, XCD order
+#   (5, 8200, 3)   10250 tiles: every block walks 2 or 3 tiles from an XCD-permuted start
+#   (3, 2740, 65)  4110 tiles, two per row: only 14 blocks take a second tile, and the tile decode crosses z
+CONV3_OUT_SHAPES = [(1, 1, 1), (1, 3, 63), (2, 4, 64), (3, 5, 65), (2, 9, 130), (6, 16, 70), (5, 8200, 3), (3, 2740, 65)]
+
+
+@pytest.mark.parametrize("D,H,W", CONV3_OUT_SHAPES)
+def test_conv3_out_fused_and_dice(gpu, gold, D, H, W):
+    from cryovit_amd import _lib
+    from cryovit_amd.engine import ops
+
+    tiles = -(-W // 64) * -(-H // 4) * D
+    assert _lib.DICE_BLOCKS == 4096 and max(-(-w_ // 64) * -(-h_ // 4) * d_ for d_, h_, w_ in CONV3_OUT_SHAPES) == 10250  # (the cap the long shapes cross)
+    x, w, b, labels = _conv3_out_operands(D, H, W)
     logits = torch.zeros(D, H, W, device=gpu)
     probs = torch.zeros(D, H, W, device=gpu)
     dice = torch.zeros(3, device=gpu)
     seg = torch.full((D, H, W), 7, dtype=torch.uint8, device=gpu)
-    ops.conv3_out_fused(x.to(gpu), w[0].permute(1, 2, 3, 0).reshape(27, 8).contiguous().to(gpu), b, logits, probs, labels.to(gpu),
+    ops.conv3_out_fused(x.to(gpu), _tap_major(w).to(gpu), b, logits, probs, labels.to(gpu),
                         dice, D=D, H=H, W=W, mask=seg, mask_threshold=0.3)
     # the uint8 segmentation PredictionWriter stores: bit-exact (preds >= threshold) of the GPU's own probabilities
     assert torch.equal(seg.cpu(), (probs.cpu() >= 0.3).to(torch.uint8))
     # (the weights are rounded to fp16 inside the kernel -- fp16 autocast of the reference -- and a tap is four v_dot2_f32_f16)
-    ref = F.conv3d(x.float().permute(3, 0, 1, 2).unsqueeze(0), hf(w).float(), torch.tensor([b]), padding="same")[0, 0].clip(-5, 5)
-    assert torch.allclose(logits.cpu(), ref, atol=1e-4, rtol=1e-4)
-    assert torch.allclose(probs.cpu(), torch.sigmoid(ref), atol=1e-5)
+    # float64 reference on the fp16-rounded operands
+    ref = F.conv3d(x.double().permute(3, 0, 1, 2).unsqueeze(0), hf(w).double(), torch.tensor([b], dtype=torch.float64), padding="same")[0, 0].clip(-5, 5)
+    assert torch.allclose(logits.cpu().double(), ref, atol=1e-4, rtol=1e-4), float((logits.cpu().double() - ref).abs().max())
+    assert torch.allclose(probs.cpu().double(), torch.sigmoid(ref), atol=1e-5), float((probs.cpu().double() - torch.sigmoid(ref)).abs().max())
+    if tiles > _lib.DICE_BLOCKS:
+        assert float(ref.max()) == 5.0 and float(ref.min()) == -5.0  # the clip is exercised
+        assert float((ref.abs() == 5.0).double().mean()) > 0.1
     # Dice sums must be exact integers given the GPU's own probabilities; DiceMetric's threshold and the mask's are ONE parameter
     # (a DiceMetric(threshold != 0.5) must see the same p_hat in the fused kernel as in the stand-alone reduction)
     p = probs.cpu()
@@ -699,7 +729,7 @@ def test_conv3_out_fused_and_dice(gpu, gold):
     for thr in (0.3, 0.5):
         if thr != 0.3:
             dice.zero_()
-            ops.conv3_out_fused(x.to(gpu), w[0].permute(1, 2, 3, 0).reshape(27, 8).contiguous().to(gpu), b, logits, probs, labels.to(gpu),
+            ops.conv3_out_fused(x.to(gpu), _tap_major(w).to(gpu), b, logits, probs, labels.to(gpu),
                                 dice, D=D, H=H, W=W, mask=seg, mask_threshold=thr)
         ph = (p >= thr).float()
         exp = torch.tensor([float((labels.float() * ph)[mask].sum()), float(labels.float()[mask].sum()), float(ph[mask].sum())])
@@ -713,6 +743,107 @@ def test_conv3_out_fused_and_dice(gpu, gold):
     ops.dice_sums(torch.from_numpy(g["preds"]).to(gpu), torch.from_numpy(g["labels"]).to(gpu), d2, 0.5)
     i, sy, sp = d2.cpu().tolist()
     assert abs(2 * i / (sy + sp + 1e-3) - float(g["dice"])) < 1e-6
+
+
+def test_conv3_out_optional_outputs(gpu):
+    """The output combinations the head really uses (``infer`` passes no logits, a prediction without labels no Dice buffers ...):
+    every buffer that is passed equals the all-outputs call bit for bit, every buffer that is not passed keeps its sentinel fill --
+    the Dice accumulator too when there are no labels.  (3, 5, 65): ragged tiles in x and y, plain block order."""
+    from cryovit_amd.engine import ops
+
+    D, H, W = 3, 5, 65
+    x, w, b, labels = _conv3_out_operands(D, H, W)
+    xg, wg, lg = x.to(gpu), _tap_major(w).to(gpu), labels.to(gpu)
+
+    def buffers():
+        return {"logits": torch.full((D, H, W), -77.0, device=gpu), "probs": torch.full((D, H, W), -77.0, device=gpu),
+                "mask": torch.full((D, H, W), 7, dtype=torch.uint8, device=gpu), "dice": torch.zeros(3, device=gpu)}
+
+    full = buffers()
+    ops.conv3_out_fused(xg, wg, b, full["logits"], full["probs"], lg, full["dice"], D=D, H=H, W=W, mask=full["mask"], mask_threshold=0.3)
+    assert float(full["logits"].min()) >= -5.0 and float(full["probs"].min()) >= 0.0 and int(full["mask"].max()) <= 1  # all written
+    assert float(full["dice"][1]) == float((labels == 1).sum())
+    for absent in (("logits",), ("probs",), ("mask",), ("labels", "dice"), ("labels",)):
+        cur = buffers()
+        if "labels" in absent:
+            cur["dice"].fill_(-77.0)
+        arg = {k: (None if k in absent else v) for k, v in cur.items()}
+        ops.conv3_out_fused(xg, wg, b, arg["logits"], arg["probs"], None if "labels" in absent else lg, arg["dice"], D=D, H=H, W=W,
+                            mask=arg["mask"], mask_threshold=0.3)
+        for k, v in cur.items():
+            if k in absent or (k == "dice" and "labels" in absent):
+                assert torch.all(v == (7 if k == "mask" else -77.0)), (absent, k)  # not passed, or nothing to add: untouched
+            else:
+                assert torch.equal(v, full[k]), (absent, k)
+
+
+def test_conv3_out_dice_accumulates(gpu):
+    """include/cryovit_hip.h: ``dice[k] +=``.  Two calls without zeroing give exactly twice the (integer) sums."""
+    from cryovit_amd.engine import ops
+
+    D, H, W = 3, 5, 65
+    x, w, b, labels = _conv3_out_operands(D, H, W)
+    xg, wg, lg = x.to(gpu), _tap_major(w).to(gpu), labels.to(gpu)
+    once, twice = torch.zeros(3, device=gpu), torch.zeros(3, device=gpu)
+    ops.conv3_out_fused(xg, wg, b, None, None, lg, once, D=D, H=H, W=W)
+    for _ in range(2):
+        ops.conv3_out_fused(xg, wg, b, None, None, lg, twice, D=D, H=H, W=W)
+    assert float(once[1]) == float((labels == 1).sum()) and float(once[0]) > 0 and float(once[2]) > 0
+    assert torch.equal(twice, 2 * once)
+
+
+def test_conv3_out_threshold_tie(gpu):
+    """Zero weights and zero bias: logit 0 and probability EXACTLY 0.5 at every voxel.  The mask and p_hat are ``p >= threshold``: at
+    0.5 everything is foreground, at F1Metric._THRESH (the fp32 successor of 0.5, on which F1Metric builds the reference's strict
+    ``p > 0.5``) nothing is."""
+    from cryovit_amd.engine import ops
+    from cryovit_amd.models.metrics import F1Metric
+
+    D, H, W = 3, 5, 65
+    x, _, _, labels = _conv3_out_operands(D, H, W)
+    xg, wg, lg = x.to(gpu), torch.zeros(27, 8, device=gpu), labels.to(gpu)
+    labelled, ones = float((labels > -1).sum()), float((labels == 1).sum())
+    assert np.float32(F1Metric._THRESH) > np.float32(0.5) and np.float32(F1Metric._THRESH) == np.nextafter(np.float32(0.5), np.float32(1))
+    for thr, fg in ((0.5, 1), (F1Metric._THRESH, 0)):
+        logits, probs = torch.full((D, H, W), -77.0, device=gpu), torch.full((D, H, W), -77.0, device=gpu)
+        seg, dice = torch.full((D, H, W), 7, dtype=torch.uint8, device=gpu), torch.zeros(3, device=gpu)
+        ops.conv3_out_fused(xg, wg, 0.0, logits, probs, lg, dice, D=D, H=H, W=W, mask=seg, mask_threshold=thr)
+        assert torch.all(logits == 0.0)
+        assert torch.all(probs == 0.5), (float(probs.min()), float(probs.max()))
+        assert torch.all(seg == fg), thr
+        assert dice.cpu().tolist() == [ones * fg, ones, labelled * fg], thr
+        d2 = torch.zeros(3, device=gpu)
+        ops.dice_sums(probs, lg, d2, thr)
+        assert torch.equal(d2, dice), thr
+
+
+def test_dice_sums_exact_and_reproducible_past_2_24(gpu):
+    """cvx_dice_sums at n = 2^24 + 2^22 + 5 with all three sums beyond 2^24, where fp32 no longer holds every integer: the result is
+    the exact count rounded ONCE to fp32 (round to nearest), and repeated calls are bit-identical.  (Float atomics of wave partials
+    rounded at every add, in arrival order: a CPU simulation of that partition gave 20343116 / 20343108 / 20343048 for an exact
+    20343107.)"""
+    from cryovit_amd.engine import ops
+
+    n = (1 << 24) + (1 << 22) + 5
+    g = torch.Generator(device=gpu).manual_seed(47)
+    u = torch.rand(n, device=gpu, generator=g)
+    labels = (u < 0.97).to(torch.int8)
+    labels[torch.rand(n, device=gpu, generator=g) < 0.001] = -1  # a sprinkling of ignored voxels
+    probs = torch.rand(n, device=gpu, generator=g) * 0.97 + 0.03  # >= thr = 0.06 on about 97 %
+    thr = 0.06
+    m = labels > -1
+    ph = (probs >= thr) & m
+    exact = [int(((labels == 1) & ph).sum()), int((labels == 1).sum()), int(ph.sum())]
+    assert min(exact) > (1 << 24), exact
+    want = torch.tensor(exact, dtype=torch.int64).to(torch.float64).to(torch.float32)  # int64 -> fp64 is exact here; fp64 -> fp32 rounds to nearest
+    outs = []
+    for _ in range(3):
+        d = torch.zeros(3, device=gpu)
+        ops.dice_sums(probs, labels, d, thr)
+        outs.append(d.cpu())
+    print("dice_sums past 2^24: exact", exact, "got", [o.tolist() for o in outs])
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    assert torch.equal(outs[0], want), (outs[0].tolist(), exact)
 
 
 # ---- the 256x256 phase-pipelined tile (gemm256.h): every epilogue at shapes that dispatch to it ---------------------------
@@ -1520,10 +1651,11 @@ def test_final_norm_error_budget(gpu):
     eb.check("final_norm", "3x(4x6) C=128", got.double(), fam.ref, fam.emu)
 
 
-@pytest.mark.parametrize("C,G,act", [(32, 8, 0), (8, 8, 0), (8, 8, 1)])
+@pytest.mark.parametrize("C,G,act", [(32, 8, 0), (8, 8, 0), (8, 8, 1), (16, 16, 1), (48, 48, 1)])
 def test_groupnorm_error_budget(gpu, C, G, act):
     """GroupNorm (4 channels per group) and, G = C, InstanceNorm with and without the fused GELU; columns are channels, so R_col's last
-    group holds the last group's statistics."""
+    group holds the last group's statistics.  C = 16 and 48 are the U-Net's InstanceNorm + GELU (48: C / 8 = 6 chunks per voxel, no
+    power of two, so the statistics kernel runs with idle threads)."""
     from cryovit_amd.engine import ops
 
     x, w, b = eb.groupnorm_operands(C, G)

@@ -148,6 +148,156 @@ def test_adamw_stays_attached_or_raises(gpu):
         opt.step()
 
 
+def _focal_operands(saturated):
+    """test_focal_loss_against_oracle's input; ``saturated`` appends x in +-{10, 17, 30, 100}, each with label 0 and label 1."""
+    gen = torch.Generator().manual_seed(31)
+    n = 50021
+    x = torch.rand(n, generator=gen)            # the reference feeds probabilities
+    x[:100] = torch.randn(100, generator=gen) * 4  # ... and the formula must hold for any real input
+    labels = torch.randint(-1, 2, (n,), generator=gen)
+    if saturated:
+        x = torch.cat([x, torch.tensor([s * v for v in (10.0, 17.0, 30.0, 100.0) for s in (1, -1) for _ in (0, 1)])])
+        labels = torch.cat([labels, torch.tensor([0, 1] * 8)])
+    return x, labels
+
+
+def _focal_oracle(x, labels, gamma):
+    """(loss, d loss / d x) of the float64 oracle over labels > -1.  Where the prediction is right beyond float64 -- 1 - p_t == 0
+    exactly, |x| > 36.7 -- autograd of ``(1 - p_t) ** gamma`` yields inf * 0 = NaN for gamma < 1; the derivative there is
+    alpha_t d/dx [m^gamma ce] with m = sigmoid(-|x|) and ce = log1p(exp(-|x|)) <= m, below (1 + gamma) exp(-36.7)^(1 + gamma) < 1e-15 of
+    the O(1) gradients of the set: 0 at every tolerance used here.  Those NaNs (and only those) are replaced by 0."""
+    from oracle import train_pieces as tp
+
+    m = labels > -1
+    xr = x.double().clone().requires_grad_(True)
+    ref = tp.focal_loss(xr[m], labels[m].double(), gamma=gamma)
+    ref.backward()
+    grad = xr.grad.clone()
+    bad = torch.isnan(grad)
+    if bool(bad.any()):
+        assert gamma < 1 and bool(((x.abs() > 36.7) & m & ((x > 0) == (labels == 1)))[bad].all())
+        grad[bad] = 0.0
+    return float(ref.detach()), grad
+
+
+@pytest.mark.parametrize("gamma", [0, 0.5, 1, 3])
+def test_focal_loss_gamma_branches_and_saturated_inputs(gpu, gamma):
+    """The kernel's gamma == 0 branch (plain weighted cross-entropy), its ``powf`` path below and above 1 (0.5: m^(gamma - 1) grows
+    without bound as m -> 0 and is floored at m = 1e-30; 1; 3) beside the existing 2 and 1.5, on the existing input plus a block of
+    saturated values x in +-{10, 17, 30, 100} with both labels (sigmoid rounds to 0 / 1 in fp32 from |x| = 17 on).  Tolerances of
+    test_focal_loss_against_oracle.  They hold for the saturated block on the CPU: the oracle's formula evaluated in fp32 against its
+    float64 self on this input is off by at most 0.007 of the gradient tolerance (x = 17, label 0, gamma 3) and 2.7e-8 relative in
+    the loss (gamma 0), so no wider band is taken for it."""
+    from cryovit_amd.models.losses import FocalLoss
+
+    x, labels = _focal_operands(saturated=True)
+    ref, grad = _focal_oracle(x, labels, gamma)
+    xg = x.to(gpu).requires_grad_(True)
+    loss = FocalLoss(gamma=gamma)(xg, labels.to(gpu))
+    print(f"focal gamma={gamma}: loss {float(loss.detach())!r} oracle {ref!r}")
+    assert abs(float(loss.detach()) - ref) <= 2e-6 * max(1.0, abs(ref))
+    (2.0 * loss).backward()
+    want = 2.0 * grad.float()
+    got = xg.grad.cpu()
+    assert not bool(torch.isnan(got).any())
+    tol = 2e-4 * want.abs() + 1e-9 + 2e-6 * float(want.abs().max())
+    print(f"focal gamma={gamma}: max gradient error / tolerance {float(((got - want).abs() / tol).max()):.3f}")
+    assert torch.allclose(got, want, rtol=2e-4, atol=1e-9 + 2e-6 * float(want.abs().max()))
+    assert torch.all(xg.grad[labels.to(gpu) < 0] == 0)
+
+
+@pytest.mark.parametrize("gamma", [2, 0.5])
+def test_focal_loss_one_class_and_no_label(gpu, gamma):
+    """alpha = (n - sum y) / n at its ends.  Every labelled voxel a 1: alpha = 0, the positives' weight, so loss and gradient are
+    exactly 0.  Every labelled voxel a 0: alpha = 1, the oracle's value and gradient.  Every voxel ignored: loss 0, gradient 0, no NaN
+    (the kernel's ``cnt > 0`` guards; the reference divides 0 by 0 there)."""
+    from cryovit_amd.models.losses import FocalLoss
+
+    x, labels = _focal_operands(saturated=True)
+    keep = labels > -1
+    for fill in (1, 0, -1):
+        lab = torch.where(keep, torch.full_like(labels, fill), labels) if fill > -1 else torch.full_like(labels, -1)
+        xg = x.to(gpu).requires_grad_(True)
+        loss = FocalLoss(gamma=gamma)(xg, lab.to(gpu))
+        (2.0 * loss).backward()
+        got = xg.grad.cpu()
+        assert not bool(torch.isnan(got).any()) and torch.all(got[lab < 0] == 0)
+        if fill == 0:
+            ref, grad = _focal_oracle(x, lab, gamma)
+            want = 2.0 * grad.float()
+            assert abs(float(loss.detach()) - ref) <= 2e-6 * max(1.0, abs(ref))
+            assert torch.allclose(got, want, rtol=2e-4, atol=1e-9 + 2e-6 * float(want.abs().max()))
+        else:
+            assert float(loss.detach()) == 0.0 and torch.all(got == 0), fill
+
+
+def test_dice_loss_every_label_ignored(gpu):
+    """No labelled voxel: the sums are 0, the loss is exactly 1 - 0 / 1e-3 = 1, and the gradient is zero everywhere, in the plain
+    form and through the sigmoid (with and without the clipped logits)."""
+    from cryovit_amd.engine import ops
+    from cryovit_amd.models import DiceLoss
+    from cryovit_amd.models.losses import dice_loss_and_logit_grad
+
+    n = 4099
+    raw = torch.randn(n, generator=torch.Generator().manual_seed(n % 1000)) * 4.0  # a good share beyond the +-5 clip
+    clipped = torch.clip(raw, -5.0, 5.0)
+    probs = torch.sigmoid(clipped).to(gpu)
+    labels = torch.full((n,), -1, dtype=torch.int8, device=gpu)
+    out4 = torch.full((4,), -77.0, device=gpu)
+    ops.dice_loss_forward(probs, labels, out4)
+    assert out4.cpu().tolist() == [0.0, 0.0, 0.0, 1.0]
+    pg = probs.clone().requires_grad_(True)
+    loss = DiceLoss()(pg, labels)
+    assert float(loss.detach()) == 1.0
+    (3.0 * loss).backward()
+    assert torch.all(pg.grad == 0)
+    for lg in (clipped.to(gpu), None):
+        loss, grad = dice_loss_and_logit_grad(probs, lg, labels, 3.0)
+        assert float(loss) == 1.0 and torch.all(grad == 0) and grad.shape == probs.shape
+
+
+def test_dice_loss_empty_selection(gpu):
+    """The reference's call shape on a crop without a labelled voxel: ``masked_select`` leaves [0, 1] tensors.  The formula gives
+    1 - 0 / (0 + 1e-3) = 1 and an empty gradient (checked on the oracle here, too)."""
+    from cryovit_amd.models import DiceLoss
+    from oracle import train_pieces as tp
+
+    probs = torch.rand(4, 6, 5, generator=torch.Generator().manual_seed(3))
+    labels = torch.full((4, 6, 5), -1.0)
+    m = labels > -1
+    yr = torch.masked_select(probs, m).view(-1, 1).requires_grad_(True)
+    ref = tp.dice_loss(yr, torch.masked_select(labels, m).view(-1, 1))
+    ref.backward()
+    assert float(ref) == 1.0 and tuple(yr.grad.shape) == (0, 1)
+    yp = torch.masked_select(probs.to(gpu), m.to(gpu)).view(-1, 1).requires_grad_(True)
+    loss = DiceLoss()(yp, torch.masked_select(labels.to(gpu), m.to(gpu)).view(-1, 1))
+    assert float(loss.detach()) == 1.0
+    loss.backward()
+    assert tuple(yp.grad.shape) == (0, 1) and yp.grad.dtype == torch.float32
+
+
+@pytest.mark.parametrize("n", [3, 1026, 70001])
+def test_dice_loss_logit_grad_without_logits(gpu, n):
+    """``dice_loss_and_logit_grad(probs, None, ...)``: without the stored logits there is no clip to see, the gradient is the chain
+    through the sigmoid alone, d loss / d p * p (1 - p), at every voxel -- against autograd of the oracle expression (float64) with
+    the tolerances of test_dice_loss_sizes_and_logit_chain."""
+    from cryovit_amd.models.losses import dice_loss_and_logit_grad
+    from oracle import train_pieces as tp
+
+    gen = torch.Generator().manual_seed(n % 1000)
+    raw = torch.randn(n, generator=gen) * 4.0
+    labels = torch.randint(-1, 2, (n,), generator=gen)
+    probs = torch.sigmoid(torch.clip(raw, -5.0, 5.0))  # fp32, as the head stores them
+    z = torch.logit(probs.double()).requires_grad_(True)  # the pre-sigmoid value OF THE STORED probability
+    ref = tp.masked_dice_loss(torch.sigmoid(z), labels.double())
+    ref.backward()
+    loss, grad = dice_loss_and_logit_grad(probs.to(gpu), None, labels.to(torch.int8).to(gpu), 1.0)
+    assert abs(float(loss) - float(ref)) <= 1e-5 * max(1.0, abs(float(ref)))
+    want = z.grad.float()
+    assert torch.allclose(grad.cpu(), want, rtol=1e-4, atol=1e-12 + 1e-4 * float(want.abs().max()))
+    assert torch.all(grad.cpu()[labels < 0] == 0)
+
+
 @pytest.mark.parametrize("gamma", [2, 1.5])
 def test_focal_loss_against_oracle(gpu, gamma):
     """FocalLoss (losses.py:35-64) against the oracle restatement of torchvision's sigmoid_focal_loss (float64): value and autograd

@@ -37,10 +37,11 @@ def test_conv2s2(gpu, C, Cout, D, H, W):
     assert torch.all(out[nvo:].float() == 7.0)
 
 
-@pytest.mark.parametrize("C,Cout,D,H,W", [(8, 8, 4, 6, 10)])
+@pytest.mark.parametrize("C,Cout,D,H,W", [(8, 8, 4, 6, 10), (16, 64, 6, 8, 8), (64, 256, 2, 4, 6)])
 def test_conv2s2_error_budget(gpu, C, Cout, D, H, W):
     """The rms error of the stride-2 convolution against float64 in units of its one fp16 store rounding (tests/error_budget.py; bounds
-    from the CPU rule); operands and band of test_conv2s2.  Row groups stay inside one line of one output plane."""
+    from the CPU rule); operands and band of test_conv2s2.  Row groups stay inside one line of one output plane.  (16, 64) and
+    (64, 256) are the U-Net's pooling widths: K = 128 and 512, more than one 64-column tile of outputs."""
     import error_budget as eb
     from cryovit_amd.engine import ops
     from cryovit_amd.engine.head import _npad, _pad1, _pad2
@@ -82,6 +83,33 @@ def test_conv_transpose_3d(gpu, c2, c3):
     assert torch.allclose(out.float().cpu(), ref, atol=3e-3, rtol=2e-3), float((out.float().cpu() - ref).abs().max())
 
 
+@pytest.mark.parametrize("c2,c3", [(16, 8), (32, 16)])
+def test_conv_transpose_3d_error_budget(gpu, c2, c3):
+    """The (2, 2, 2) pixel-shuffle epilogue in units of its one fp16 store rounding (tests/error_budget.py, operation "conv"); operands and
+    band of test_conv_transpose_3d.  Row groups stay inside one line of one output plane."""
+    import error_budget as eb
+    from cryovit_amd._lib import EPI_CONVT
+    from cryovit_amd.engine import ops
+    from cryovit_amd.engine.head import _npad, _pad1, _pad2
+
+    assert (c2, c3) in eb.CONVT3_CASES
+    D, H, W = eb.CONVT3_DHW
+    nv = D * H * W
+    x, wt, b = eb.convt3_operands(c2, c3)
+    fam = eb.convt3_case(c2, c3, full=False)
+    A = torch.zeros(ops.alloc_rows(nv) * c2 + 4096, dtype=torch.float16)
+    A[: nv * c2] = x.reshape(-1)
+    A = A.to(gpu)
+    a2 = torch.as_strided(A, (ops.alloc_rows(nv), c2), (c2, 1))
+    wg = wt.permute(2, 3, 4, 1, 0).reshape(8 * c3, c2)
+    out = torch.full((2 * D, 2 * H, 2 * W, c3), 7.0, dtype=torch.float16, device=gpu)
+    ops.gemm(EPI_CONVT, a2, _pad2(wg, _npad(8 * c3), ops.round_up(c2, 64)).to(gpu), out, _pad1(b.repeat(8), _npad(8 * c3)).to(gpu),
+             m=nv, n=8 * c3, H=H, W=W, cout=c3, act=0, ldc=c3, convt_up_z=1)
+    got = out.float().cpu().reshape(2 * D * 2 * H, 2 * W, c3)
+    assert torch.allclose(got, fam.ref.float(), atol=3e-3, rtol=2e-3), float((got - fam.ref).abs().max())
+    eb.check("conv", f"convt3 {(c2, c3)}", got.double(), fam.ref, fam.emu)
+
+
 @pytest.mark.parametrize("C", [16, 48, 384])
 def test_instance_norm_gelu(gpu, C):
     """G = C (InstanceNorm3d, affine, eps 1e-3) with the GELU fused; C / 8 not a power of two (48 -> 6, 384 -> 48 chunks)."""
@@ -111,6 +139,48 @@ def test_concat_and_pointwise_out(gpu):
     ref = ((a * 3).float() @ w + 0.25).clip(-5, 5)
     assert torch.allclose(logits.cpu(), ref, atol=1e-4, rtol=1e-4) and torch.allclose(probs.cpu(), torch.sigmoid(ref), atol=1e-5)
     assert float(ref.abs().max()) == 5.0  # the clip is exercised
+
+
+@pytest.mark.parametrize("nvox", [1, 1000, 1025])
+@pytest.mark.parametrize("C", [8, 16, 32, 64])
+def test_pointwise_out_widths(gpu, C, nvox):
+    """The four template widths of k_pointwise_out at one voxel, fewer than one block's 1024 and one past it, against float64 on the
+    fp16-rounded input (tolerances of test_concat_and_pointwise_out: fp32 accumulation of at most 64 terms with |logit| <= 5).  The
+    input is scaled by 3 sqrt(16 / C), so the logits have that test's spread at every width.  Without ``logits`` or ``probs`` the
+    other output is bit-equal to the full call."""
+    from cryovit_amd.engine import ops
+
+    a = hf(rnd(nvox, C, seed=89) * (3 * (16 / C) ** 0.5))
+    w = rnd(C, seed=91)
+    ag, wg = a.to(gpu), w.to(gpu)
+    ref = (a.double() @ w.double() + 0.25).clip(-5, 5)
+    logits, probs = torch.full((nvox + 8,), -77.0, device=gpu), torch.full((nvox + 8,), -77.0, device=gpu)
+    ops.pointwise_out(ag, wg, 0.25, logits, probs, nvox=nvox, Cdim=C)
+    assert torch.allclose(logits[:nvox].cpu().double(), ref, atol=1e-4, rtol=1e-4), float((logits[:nvox].cpu().double() - ref).abs().max())
+    assert torch.allclose(probs[:nvox].cpu().double(), torch.sigmoid(ref), atol=1e-5)
+    assert torch.all(logits[nvox:] == -77.0) and torch.all(probs[nvox:] == -77.0), "written past nvox"
+    if nvox > 1:
+        assert float(ref.max()) == 5.0 and float(ref.min()) == -5.0  # the clip is exercised, on both sides
+        assert float((ref.abs() < 5.0).double().mean()) > 0.2      # ... and a good share of the voxels is inside it
+    else:  # one voxel: the clip by the bias instead
+        for bias, lim in ((100.0, 5.0), (-100.0, -5.0)):
+            ops.pointwise_out(ag, wg, bias, logits, probs, nvox=1, Cdim=C)
+            assert float(logits[0]) == lim and abs(float(probs[0]) - 1 / (1 + np.exp(-lim))) <= 1e-5
+        ops.pointwise_out(ag, wg, 0.25, logits, probs, nvox=nvox, Cdim=C)
+    only_l, only_p = torch.full_like(logits, -77.0), torch.full_like(probs, -77.0)
+    ops.pointwise_out(ag, wg, 0.25, only_l, None, nvox=nvox, Cdim=C)
+    ops.pointwise_out(ag, wg, 0.25, None, only_p, nvox=nvox, Cdim=C)
+    assert torch.equal(only_l, logits) and torch.equal(only_p, probs)
+
+
+def test_pointwise_out_refuses_other_widths(gpu):
+    from cryovit_amd._lib import CvxError
+    from cryovit_amd.engine import ops
+
+    out = torch.full((10,), -77.0, device=gpu)
+    with pytest.raises(CvxError):
+        ops.pointwise_out(torch.zeros(10, 24, dtype=torch.float16, device=gpu), torch.zeros(24, device=gpu), 0.0, out, None, nvox=10, Cdim=24)
+    assert torch.all(out == -77.0)
 
 
 def test_unet3d_narrow_against_reference_fixture(gpu, gold):
