@@ -159,6 +159,18 @@ SIGNATURES = {
     "cvx_focal_loss_backward": (c_int, [c_void_p, c_void_p, c_long, c_float, c_void_p, c_float, c_void_p, c_void_p]),
     "cvx_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, C.c_double, C.c_double, C.c_double, C.c_double,
                                C.c_double, c_int, c_void_p]),
+    "cvx_conv_wgrad_workspace_bytes": (c_long, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "cvx_conv_wgrad_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long,
+                                   c_void_p]),
+    "cvx_gelu_f16": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
+    "cvx_gelu_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "cvx_groupnorm_backward_workspace_floats": (c_long, [c_int, c_int]),
+    "cvx_groupnorm_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int,
+                                           c_int, c_float, c_void_p]),
+    "cvx_conv3_out_backward_workspace_floats": (c_long, []),
+    "cvx_conv3_out_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int,
+                                       c_void_p]),
+    "cvx_unscale_check_f32": (c_int, [c_void_p, c_long, c_float, c_void_p, c_void_p]),
     "cvx_head_forward": (c_int, [C.POINTER(HeadDesc), C.POINTER(HeadWs), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_float, c_void_p]),
     "cvx_vit_encode": (c_int, [C.POINTER(VitDesc), C.POINTER(VitWs), c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p,

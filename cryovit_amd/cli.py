@@ -1,7 +1,9 @@
 """``cryovit`` command line for the script-level flows (mirror of
-``/root/reference/src/cryovit/cli/{cli,dino_cli,infer_cli,eval_cli}.py``): same command names, arguments, options and defaults.
+``/root/reference/src/cryovit/cli/{cli,dino_cli,train_cli,infer_cli,eval_cli}.py``): same command names, arguments, options and defaults.
 
     python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize]
+    python -m cryovit_amd.cli train <train-data> <train-labels> <label-key> --labels A [--labels B ...] [--val-data ..] [--val-labels ..]
+                                    [--name ..] [--result-folder ..] [--ckpt x.model|x.pt] [--num-epochs 50]
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
                                     [--instances <measurements>]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
@@ -12,7 +14,8 @@
                     [--min-size N] [--connectivity 6|26] [--split-radius R [--split-min-core N]] [--morphology] [--shape]
                     [--skeleton [--skeleton-end-radius R]] [--thickness] [--mesh [--mesh-smooth N] [--mesh-format ply|stl]]
 
-``train`` (the Lightning training loop) is outside the hot path and not provided.  Extra options, marked "build extension",
+``train`` fits the CryoVIT head on the GPU (HIP backward, fused AdamW; ``run/train_model.py``) and writes the ``.model`` file that
+``infer`` and ``evaluate`` load; UNet3D and SAM2 training are not built.  Extra options, marked "build extension",
 replace the network fetch of the encoder weights or add what the reference leaves to the user: ``instances`` (and
 ``infer --instances``) labels the connected instances of a predicted mask on the GPU, tabulates their size and position and
 measures them.  The measurement options are declared once, below, for both commands; each is a field of
@@ -38,7 +41,7 @@ cli = typer.Typer(add_completion=False, no_args_is_help=True, pretty_exceptions_
 
 @cli.callback()
 def callback():
-    """CryoViT's command line interface (MI355X build): feature extraction, inference and evaluation."""
+    """CryoViT's command line interface (MI355X build): feature extraction, training, inference and evaluation."""
 
 
 def _load_encoder(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]):
@@ -165,6 +168,59 @@ def features(
     result_path.mkdir(parents=True, exist_ok=True)
     run_dino(load_files_from_path(tomograms_path), result_path, batch_size=batch_size, visualize=visualize,
              encoder=_encoder_overrides(encoder, checkpoint, synthetic_seed))
+
+
+@cli.command(name="train", no_args_is_help=True)
+def train(
+    train_data: Annotated[str, Argument(help="Path to the folder or .txt file containing the training tomograms.")],
+    train_labels: Annotated[str, Argument(help="Path to the folder or .txt file containing the training labels.")],
+    labels: Annotated[list[str], Option(help="List of available label names in ascending-value order.")],
+    label_key: Annotated[str, Argument(help="Label key to train on. Must be one of the provided labels.")],
+    validation_data: Annotated[Optional[str], Option("--validation-data", "--val-data", show_default=False,
+                                                     help="Path to the folder or .txt file containing the validation tomograms.")] = None,
+    validation_labels: Annotated[Optional[str], Option("--validation-labels", "--val-labels", show_default=False,
+                                                       help="Path to the folder or .txt file containing the validation labels.")] = None,
+    name: Annotated[Optional[str], Option(show_default=False, help="Name to identify the model. If not provided, a random name will be generated.")] = None,
+    model: Annotated[str, Option(help="The type of model to train (this build trains cryovit only).")] = "cryovit",
+    result_folder: Annotated[Optional[str], Option(help="Path to the folder where the trained model will be saved.",
+                                                   show_default="the current working directory")] = None,
+    ckpt: Annotated[Optional[str], Option(help="Path to a pre-trained .model file, or .pt weights (a state_dict) to fine-tune a model from.")] = None,
+    num_epochs: Annotated[int, Option(min=1, help="Number of training epochs.")] = 50,
+    encoder: Annotated[Optional[str], Option(help="build extension: encode files without dino_features on the fly with this encoder")] = None,
+    checkpoint: Annotated[Optional[str], Option(help="build extension: local DINOv2 state_dict file")] = None,
+    synthetic_seed: Annotated[Optional[int], Option(help="build extension: seeded random encoder weights")] = None,
+):
+    """Train a segmentation model on given training data and labels."""
+    import random
+    import string
+
+    if model.lower() != "cryovit":
+        raise typer.BadParameter(f"only cryovit can be trained here: training a {model} model is not built (unet3d and sam2 are inference-only).", param_hint="--model")
+    train_path, label_path = Path(train_data), Path(train_labels)
+    ckpt_path = Path(ckpt) if ckpt is not None else None
+    val_path = Path(validation_data) if validation_data else None
+    val_label_path = Path(validation_labels) if validation_labels else None
+    result_path = Path(result_folder) if result_folder else Path.cwd()
+    model_name = name or "cryovit_" + "".join(random.choices(string.ascii_uppercase + string.digits, k=6))  # (utils.id_generator of the reference)
+    assert train_path.exists(), "Training data path does not exist."
+    assert label_path.exists(), "Training labels path does not exist."
+    if val_path is not None:
+        assert val_path.exists(), "Validation data path does not exist."
+        assert val_label_path is not None and val_label_path.exists(), "Validation data provided but validation labels path does not exist."
+    if ckpt_path is not None:
+        assert ckpt_path.exists(), "Checkpoint path does not exist."
+    assert label_key in labels, f"The label key {label_key} is not in the provided labels."
+    from cryovit_amd.run.train_model import run_training
+    from cryovit_amd.types import ModelType
+    from cryovit_amd.utils import load_files_from_path
+
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
+    train_files, train_label_files = load_files_from_path(train_path), load_files_from_path(label_path)
+    val_files = load_files_from_path(val_path) if val_path is not None else None
+    val_label_files = load_files_from_path(val_label_path) if val_label_path is not None else None
+    result_path.mkdir(parents=True, exist_ok=True)
+    run_training(train_files, train_label_files, labels, ModelType.CRYOVIT, model_name, label_key, result_path, val_files, val_label_files,
+                 num_epochs=num_epochs, ckpt_path=ckpt_path, encoder=_load_encoder(encoder, checkpoint, synthetic_seed))
 
 
 @cli.command(name="infer", no_args_is_help=True)

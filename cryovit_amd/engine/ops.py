@@ -360,6 +360,105 @@ def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
          float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step))
 
 
+# ---- backward of the segmentation head (csrc/head_backward.hip) ----
+
+_bwd_ws = {}
+
+
+def _workspace(device, nbytes: int) -> torch.Tensor:
+    """Per (device, stream) byte workspace of the backward reductions, grown on demand (the kernels of one stream run in order)."""
+    key = (torch.device(device), _stream(device))
+    if key not in _bwd_ws or _bwd_ws[key].numel() < nbytes:
+        _bwd_ws[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
+    return _bwd_ws[key]
+
+
+def _f16_rows(what: str, t: torch.Tensor, numel: int) -> None:
+    if t.dtype != torch.float16 or t.numel() < numel:
+        raise _lib.CvxError(f"{what}: fp16 tensor with >= {numel} elements expected, got {t.dtype} with {t.numel()}")
+
+
+def conv_wgrad(x: torch.Tensor, dz: torch.Tensor, *, Cin: int, cout: int, taps: int, dil: int, D: int, H: int, W: int, want_bias: bool = True):
+    """(dW fp32 [cout, taps*Cin] in the forward's k = tap*Cin + c order, db fp32 [cout] or None) of a 3x3x3 "same" convolution with
+    dilation (dil, 1, 1) (taps = 27) or of a per-voxel linear map (taps = 1); x fp16 [D, H, W, Cin], dz fp16 [D, H, W, cout]."""
+    dev = _dev_check(x, dz)
+    nv = D * H * W
+    _f16_rows("conv_wgrad", x, nv * Cin)
+    _f16_rows("conv_wgrad", dz, nv * cout)
+    lib = _lib.load()
+    need = lib.cvx_conv_wgrad_workspace_bytes(Cin, cout, taps, dil, D, H, W)
+    check(min(need, 0), "cvx_conv_wgrad_workspace_bytes")
+    ws = _workspace(dev, need)
+    dW = torch.empty(cout, taps * Cin, dtype=torch.float32, device=dev)
+    db = torch.empty(cout, dtype=torch.float32, device=dev) if want_bias else None
+    call(dev, "cvx_conv_wgrad_f16", lib.cvx_conv_wgrad_f16, x.data_ptr(), dz.data_ptr(), Cin, cout, taps, dil, D, H, W, dW.data_ptr(), _p(db),
+         ws.data_ptr(), ws.numel())
+    return dW, db
+
+
+def gelu(z: torch.Tensor, y: torch.Tensor, n: int) -> None:
+    """y[:n] = gelu(z[:n]) on fp16 buffers (the training forward runs the layer kernels with act = 0 and keeps both)."""
+    dev = _dev_check(z, y)
+    _f16_rows("gelu", z, n)
+    _f16_rows("gelu", y, n)
+    call(dev, "cvx_gelu_f16", _lib.load().cvx_gelu_f16, z.data_ptr(), y.data_ptr(), n)
+
+
+def gelu_backward(dy: torch.Tensor, z: torch.Tensor, dz: torch.Tensor, n: int, *, unshuffle=None) -> None:
+    """dz = dy * gelu'(z) over n fp16 elements; ``unshuffle=(D, H, W, c3)``: dy / z are [D, 2H, 2W, c3] and dz the rows [D*H*W, 4*c3]
+    the transposed convolution's GEMM produced (n = D*H*W*4*c3)."""
+    dev = _dev_check(dy, z, dz)
+    for t in (dy, z, dz):
+        _f16_rows("gelu_backward", t, n)
+    D, H, W, c3 = unshuffle if unshuffle is not None else (0, 0, 0, 0)
+    call(dev, "cvx_gelu_backward_f16", _lib.load().cvx_gelu_backward_f16, dy.data_ptr(), z.data_ptr(), dz.data_ptr(), n,
+         int(unshuffle is not None), D, H, W, c3)
+
+
+def groupnorm_backward(x: torch.Tensor, dn: torch.Tensor, gamma: torch.Tensor, stats: torch.Tensor, dx: torch.Tensor, dgamma: torch.Tensor,
+                       dbeta: torch.Tensor, *, nvox: int, Cdim: int, G: int, eps: float) -> None:
+    """GroupNorm backward from the forward's ``stats`` buffer: dx fp16 [nvox, C], dgamma / dbeta fp32 [C] (views are fine)."""
+    dev = _dev_check(x, dn, gamma, stats, dx, dgamma, dbeta)
+    for t in (x, dn, dx):
+        _f16_rows("groupnorm_backward", t, nvox * Cdim)
+    if any(t.dtype != torch.float32 for t in (gamma, stats, dgamma, dbeta)) or min(gamma.numel(), dgamma.numel(), dbeta.numel()) < Cdim \
+            or stats.numel() < 2 * G:
+        raise _lib.CvxError("groupnorm_backward: gamma, dgamma, dbeta fp32 [C], stats fp32 [>= 2G]")
+    lib = _lib.load()
+    need = lib.cvx_groupnorm_backward_workspace_floats(Cdim, G)
+    check(min(need, 0), "cvx_groupnorm_backward_workspace_floats")
+    ws = _workspace(dev, 4 * need)
+    call(dev, "cvx_groupnorm_backward_f16", lib.cvx_groupnorm_backward_f16, x.data_ptr(), dn.data_ptr(), gamma.data_ptr(), stats.data_ptr(),
+         dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel() // 4, nvox, Cdim, G, eps)
+
+
+def conv3_out_backward(dlogit: torch.Tensor, y_mid: torch.Tensor, w: torch.Tensor, dy_mid: torch.Tensor, dW: torch.Tensor, db: torch.Tensor, *,
+                       D: int, H: int, W: int) -> None:
+    """Backward of the 8 -> 1 output convolution: dlogit fp32 [D, H, W], y_mid fp16 [D*H*W, 8], w fp32 [27, 8] -> dy_mid fp16, dW fp32
+    [27, 8], db fp32 [1]."""
+    dev = _dev_check(dlogit, y_mid, w, dy_mid, dW, db)
+    nv = D * H * W
+    _f16_rows("conv3_out_backward", y_mid, nv * 8)
+    _f16_rows("conv3_out_backward", dy_mid, nv * 8)
+    if dlogit.dtype != torch.float32 or dlogit.numel() != nv or w.dtype != torch.float32 or w.numel() != 216 or dW.dtype != torch.float32 \
+            or dW.numel() != 216 or db.dtype != torch.float32 or db.numel() < 1:
+        raise _lib.CvxError("conv3_out_backward: dlogit fp32 [D, H, W], w and dW fp32 [27, 8], db fp32 [1]")
+    lib = _lib.load()
+    need = lib.cvx_conv3_out_backward_workspace_floats()
+    ws = _workspace(dev, 4 * need)
+    call(dev, "cvx_conv3_out_backward", lib.cvx_conv3_out_backward, dlogit.data_ptr(), y_mid.data_ptr(), w.data_ptr(), dy_mid.data_ptr(),
+         dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel() // 4, D, H, W)
+
+
+def unscale_check(g: torch.Tensor, inv_scale: float, flag: torch.Tensor) -> None:
+    """g *= inv_scale in place (flat fp32) and flag (int32 [1], device) = 1 when any product is inf or nan, else 0: the one
+    finiteness reduction of a training step."""
+    dev = _dev_check(g, flag)
+    if g.dtype != torch.float32 or flag.dtype != torch.int32 or flag.numel() != 1:
+        raise _lib.CvxError("unscale_check: g fp32, flag int32 [1]")
+    call(dev, "cvx_unscale_check_f32", _lib.load().cvx_unscale_check_f32, g.data_ptr(), g.numel(), float(inv_scale), flag.data_ptr())
+
+
 # ---- alternate encoder (SAM2 Hiera) ----
 
 

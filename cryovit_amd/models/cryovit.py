@@ -4,7 +4,9 @@
 
 The module is a parameter container with reference-compatible names (``layers.0``, ``layers.{2..5}.layers.{0,1,3,5}``,
 ``output_layer.{0,2}``) so ``load_state_dict(torch.load("weights.pt"))`` works unchanged; the arithmetic runs in
-``cryovit_amd.engine.head.HeadEngine`` (HIP kernels).  Inference only: there is no backward.
+``cryovit_amd.engine.head.HeadEngine`` (HIP kernels).  Training runs in ``cryovit_amd.engine.head_train.HeadTrainEngine``
+(stored-activation forward, HIP backward, fused AdamW under a dynamic loss scale): ``training_step`` takes one step and returns
+the loss dict of ``BaseModel.compute_losses``, ``sync_trained_weights`` pulls the trained ``state_dict`` back into the module.
 """
 
 from __future__ import annotations
@@ -56,12 +58,15 @@ class CryoVIT(EvalProtocol, nn.Module):
         self.output_layer = nn.Sequential(_Params((c_tail, c_tail, 3, 3, 3), (c_tail,)), _Slot(), _Params((1, c_tail, 3, 3, 3), (1,)))
         self._device = torch.device(device)
         self._engine: HeadEngine | None = None
+        self._train_engine = None
+        self.last_step_skipped = False
 
     # any weight change invalidates the packed copy
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         own = {k: v for k, v in state_dict.items() if not k.startswith(("metric_fns.", "loss_fns."))}
         r = super().load_state_dict(own, strict=strict, **kw)
         self._engine = None
+        self._train_engine = None
         return r
 
     def _check_channels(self, C: int) -> None:
@@ -122,3 +127,81 @@ class CryoVIT(EvalProtocol, nn.Module):
             i, sy, sp = out["dice_sums"].cpu().tolist()
             dice = dice_from_sums(i, sy, sp)
         return out["probs"], dice
+
+    # ---- training (base_model.py:57-63, 115-175) ----
+
+    def configure_optimizers(self) -> dict:
+        """The hyper-parameters of ``BaseModel.configure_optimizers``: ``torch.optim.AdamW(params, lr, weight_decay)`` with torch's
+        default betas and eps, run as one fused launch by the training engine."""
+        return {"optimizer": "AdamW", "lr": float(self.lr), "weight_decay": float(self.weight_decay), "betas": (0.9, 0.999), "eps": 1e-8}
+
+    def train_engine(self):
+        """The training engine over this module's current weights (built once; ``load_state_dict`` drops it)."""
+        if self._train_engine is None:
+            from cryovit_amd.engine.head_train import HeadTrainEngine
+
+            opt = self.configure_optimizers()
+            self._train_engine = HeadTrainEngine(self.state_dict(), self._device, lr=opt["lr"], weight_decay=opt["weight_decay"],
+                                                 betas=opt["betas"], eps=opt["eps"])
+        return self._train_engine
+
+    def _loss_and_logit_grad(self, name: str, fn, probs: Tensor, logits: Tensor, labels_i8: Tensor, scale: float):
+        """(loss, scale * d loss / d logit) of one configured loss on the full volumes; voxels with label -1 are ignored inside the
+        kernels, which is ``_masked_predict``'s ``label > -1`` mask."""
+        from cryovit_amd.models.losses import DiceLoss, FocalLoss, dice_loss_and_logit_grad
+
+        if isinstance(fn, DiceLoss):
+            return dice_loss_and_logit_grad(probs, logits, labels_i8, grad_out=scale)
+        if isinstance(fn, FocalLoss):  # the reference hands the probabilities to the focal formula as its "logits" (losses.py:56-64)
+            p, y = probs.contiguous().view(-1), labels_i8.contiguous().view(-1)
+            out4 = torch.empty(4, dtype=torch.float32, device=p.device)
+            ops.focal_loss_forward(p, y, float(fn.gamma), out4)
+            grad = torch.empty_like(p)
+            ops.focal_loss_backward(p, y, float(fn.gamma), out4, scale, grad)
+            # through p = sigmoid(clip(logit, -5, 5)): p (1 - p), and 0 where the stored (clipped) logit sits on the clip
+            grad = grad.view(probs.shape) * (probs * (1.0 - probs)) * (logits.abs() < 5.0)
+            return out4[3], grad
+        raise NotImplementedError(f"loss {name} ({type(fn).__name__}): training computes DiceLoss and FocalLoss")
+
+    @torch.no_grad()
+    def training_step(self, batch, batch_idx: int = 0) -> dict:
+        """One optimisation step on one batch (``_do_step`` + backward + ``optimizer.step``): returns the loss dict of
+        ``compute_losses`` -- each configured loss and ``total``, device scalars, averaged over the tomograms of the batch --
+        evaluated on the voxels with ``label > -1`` exactly as ``_masked_predict`` selects them.  ``last_step_skipped`` tells whether
+        the loss scaler dropped the update (a non-finite gradient)."""
+        if not self.loss_fns:
+            raise ValueError("training_step: the model has no losses configured")
+        eng = self.train_engine()
+        sums, skipped = {}, False
+        for xb, yb in zip(batch.tomo_batch, batch.labels):  # [D,C,h,w], [D,H,W]
+            D, C, h, w = xb.shape
+            self._check_channels(C)
+            cl = torch.zeros(ops.alloc_rows(D * h * w), C, dtype=torch.float16, device=self._device)
+            cl[: D * h * w] = xb.to(self._device).permute(0, 2, 3, 1).reshape(-1, C).to(torch.float16)
+            labels_i8 = yb.to(self._device).to(torch.int8).contiguous()
+            logits, probs = eng.forward(cl, D, h, w)
+            if tuple(labels_i8.shape) != tuple(probs.shape):
+                raise ValueError(f"training_step: labels {tuple(labels_i8.shape)} do not match the prediction {tuple(probs.shape)}")
+            dlogit = None
+            for name, fn in self.loss_fns.items():
+                loss, g = self._loss_and_logit_grad(name, fn, probs, logits, labels_i8, eng.scaler.scale)
+                sums[name] = loss if name not in sums else sums[name] + loss
+                dlogit = g if dlogit is None else dlogit + g
+            eng.backward(dlogit.contiguous())
+            skipped = eng.optimizer_step() or skipped
+        self.last_step_skipped = skipped
+        self._engine = None  # the inference engine's packed weights are stale now
+        n = len(batch.tomo_batch)
+        losses = {k: v / n for k, v in sums.items()}
+        losses["total"] = sum(losses.values())
+        return losses
+
+    def sync_trained_weights(self) -> dict:
+        """Copy the training engine's parameters back into the module (and return them as a ``state_dict``): what ``save_model``,
+        ``forward`` and ``validation_step`` see afterwards."""
+        if self._train_engine is None:
+            return {k: v.detach().cpu() for k, v in self.state_dict().items()}
+        sd = self._train_engine.state_dict()
+        nn.Module.load_state_dict(self, sd, strict=True)
+        self._engine = None
+        return sd

@@ -64,8 +64,9 @@ class AdamW:
 
     @torch.no_grad()
     def step(self) -> None:
-        """One fused launch.  The optimizer is standalone (there is no HIP backward yet, SURVEY s.8f N4): engines that cache
-        packed weights (``model._engine``) are not invalidated here -- drop them after a step (``model._engine = None``)."""
+        """One fused launch.  The optimizer is standalone (the head's own training loop keeps its flat buffers in
+        ``engine/head_train.py``): engines that cache packed weights (``model._engine``) are not invalidated here -- drop them after a
+        step (``model._engine = None``)."""
         self._check_attached()
         self.step_count += 1
         ops.adamw_step(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, lr=self.lr, beta1=self.beta1, beta2=self.beta2,

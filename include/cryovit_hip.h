@@ -273,6 +273,42 @@ int cvx_focal_loss_backward(const float* x, const int8_t* labels, long n, float 
                             hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Backward of the segmentation head (csrc/head_backward.hip).  All volumes are channels-last fp16 unless said
+ * otherwise; no floating-point atomics: block partials in a caller-provided workspace, then a fixed-order finalize, with a slab
+ * count that depends on the shape only, so every result is bitwise reproducible.
+ *
+ * cvx_conv_wgrad_f16 -- weight and bias gradient of a 3x3x3 "same" convolution with dilation (dil, 1, 1) (taps = 27) or of a
+ *   per-voxel linear map (taps = 1: the 1x1x1 projection, and the (1,2,2) transposed convolution on its unshuffled rows):
+ *   dW[o][tap*C + c] = sum_v dz[v][o] x[v + shift(tap)][c]  (fp32 [cout][taps*C], the forward's k order; padded taps add exact
+ *   zeros),  db[o] = sum_v dz[v][o]  (fp32 [cout], nullable).  x [D][H][W][C], dz [D][H][W][cout]; C % 8 == 0, cout % 4 == 0.
+ *   workspace: cvx_conv_wgrad_workspace_bytes(...) bytes, 16-B aligned.
+ * cvx_gelu_f16 -- y = gelu(z), the exact-erf form of the forward epilogues, one fp16 rounding; n elements, 16-B aligned buffers.
+ * cvx_gelu_backward_f16 -- dz = dy (Phi(z) + z phi(z)), fp32 math, one fp16 rounding.  unshuffle = 0: elementwise over n.
+ *   unshuffle = 1: dy and z are [D][2H][2W][c3], dz is [D*H*W][4*c3] with column (i*2 + j)*c3 + o of row (z, y, x) taken from voxel
+ *   (z, 2y + i, 2x + j) -- the inverse of the transposed convolution's pixel shuffle; n = D*H*W*4*c3, c3 % 8 == 0.
+ * cvx_groupnorm_backward_f16 -- x: the GroupNorm input, dn: the gradient of its output, stats: the forward's stats buffer
+ *   (sum | sum of squares per group).  dgamma_c = sum_v dn xhat, dbeta_c = sum_v dn (fp32), dx = rstd (gamma dn - m1 - xhat m2)
+ *   (fp16) with m1, m2 the group means of gamma dn and gamma dn xhat; fp32 partials, fp64 finalize.
+ *   workspace: cvx_groupnorm_backward_workspace_floats(C, G) floats.
+ * cvx_conv3_out_backward -- the 8 -> 1 output convolution (fp32 weights w [27][8]) from the fp32 logit gradient [D][H][W]:
+ *   dy_mid[v][c] = sum_tap dlogit[v - tap] w[tap][c] (fp16), dW[tap][c] = sum_v dlogit[v] y_mid[v + tap][c] (fp32 [27][8]),
+ *   db = sum_v dlogit[v].  workspace: cvx_conv3_out_backward_workspace_floats() floats.
+ * cvx_unscale_check_f32 -- g[i] *= inv_scale in place; *flag (device int) = 1 if any product is not finite, else 0.
+ * --------------------------------------------------------------------------------------------------- */
+long cvx_conv_wgrad_workspace_bytes(int C, int cout, int taps, int dil, int D, int H, int W);
+int cvx_conv_wgrad_f16(const void* x, const void* dz, int C, int cout, int taps, int dil, int D, int H, int W, float* dW, float* db,
+                       void* workspace, long workspace_bytes, hipStream_t stream);
+int cvx_gelu_f16(const void* z, void* y, long n, hipStream_t stream);
+int cvx_gelu_backward_f16(const void* dy, const void* z, void* dz, long n, int unshuffle, int D, int H, int W, int c3, hipStream_t stream);
+long cvx_groupnorm_backward_workspace_floats(int C, int G);
+int cvx_groupnorm_backward_f16(const void* x, const void* dn, const float* gamma, const float* stats, void* dx, float* dgamma, float* dbeta,
+                               float* workspace, long workspace_floats, long nvox, int C, int G, float eps, hipStream_t stream);
+long cvx_conv3_out_backward_workspace_floats(void);
+int cvx_conv3_out_backward(const float* dlogit, const void* y_mid, const float* w, void* dy_mid, float* dW, float* db, float* workspace,
+                           long workspace_floats, int D, int H, int W, hipStream_t stream);
+int cvx_unscale_check_f32(float* g, long n, float inv_scale, int* flag, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Alternate encoder: SAM2.1 Hiera image encoder + FPN neck (BASELINE configs[4]).  These entry points, together with
  * cvx_gemm_bf16 (qkv / proj / MLP / patch-embed / lateral convs) and cvx_layernorm_bf16, replace
  * `self.model.image_encoder(flat_data)` and the resize in front of it -- SAM2.forward_features,
