@@ -171,6 +171,13 @@ SIGNATURES = {
     "cvx_conv3_out_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int,
                                        c_void_p]),
     "cvx_unscale_check_f32": (c_int, [c_void_p, c_long, c_float, c_void_p, c_void_p]),
+    "cvx_instnorm_gelu_backward_workspace_floats": (c_long, [c_int]),
+    "cvx_instnorm_gelu_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
+                                               c_long, c_int, c_float, c_void_p]),
+    "cvx_space_to_depth_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "cvx_pointwise_out_backward_workspace_floats": (c_long, [c_int]),
+    "cvx_pointwise_out_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_void_p]),
+    "cvx_concat_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p]),
     "cvx_head_forward": (c_int, [C.POINTER(HeadDesc), C.POINTER(HeadWs), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_float, c_void_p]),
     "cvx_vit_encode": (c_int, [C.POINTER(VitDesc), C.POINTER(VitWs), c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p,

@@ -195,7 +195,8 @@ def train(
     import string
 
     if model.lower() != "cryovit":
-        raise typer.BadParameter(f"only cryovit can be trained here: training a {model} model is not built (unet3d and sam2 are inference-only).", param_hint="--model")
+        raise typer.BadParameter(f"only cryovit can be trained here: this command does not train a {model} model (unet3d trains through "
+                                 "run.train_model.run_training(model_type=ModelType.UNET3D); sam2 is inference-only).", param_hint="--model")
     train_path, label_path = Path(train_data), Path(train_labels)
     ckpt_path = Path(ckpt) if ckpt is not None else None
     val_path = Path(validation_data) if validation_data else None

@@ -459,6 +459,63 @@ def unscale_check(g: torch.Tensor, inv_scale: float, flag: torch.Tensor) -> None
     call(dev, "cvx_unscale_check_f32", _lib.load().cvx_unscale_check_f32, g.data_ptr(), g.numel(), float(inv_scale), flag.data_ptr())
 
 
+# ---- backward of the UNet3D baseline (csrc/unet_backward.hip) ----
+
+
+def instnorm_gelu_backward(dy: torch.Tensor, z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, stats: torch.Tensor, dz: torch.Tensor,
+                           dgamma: torch.Tensor, dbeta: torch.Tensor, *, nvox: int, Cdim: int, eps: float) -> None:
+    """Backward of ``groupnorm(..., G=C, act=1)`` from its input ``z``, the gradient ``dy`` of its output and the forward's ``stats``:
+    dz fp16 [nvox, C], dgamma / dbeta fp32 [C] (views are fine)."""
+    dev = _dev_check(dy, z, gamma, beta, stats, dz, dgamma, dbeta)
+    for t in (dy, z, dz):
+        _f16_rows("instnorm_gelu_backward", t, nvox * Cdim)
+    if any(t.dtype != torch.float32 for t in (gamma, beta, stats, dgamma, dbeta)) or stats.numel() < 2 * Cdim \
+            or min(gamma.numel(), beta.numel(), dgamma.numel(), dbeta.numel()) < Cdim:
+        raise _lib.CvxError("instnorm_gelu_backward: gamma, beta, dgamma, dbeta fp32 [C], stats fp32 [>= 2C]")
+    lib = _lib.load()
+    need = lib.cvx_instnorm_gelu_backward_workspace_floats(Cdim)
+    check(min(need, 0), "cvx_instnorm_gelu_backward_workspace_floats")
+    ws = _workspace(dev, 4 * need)
+    call(dev, "cvx_instnorm_gelu_backward_f16", lib.cvx_instnorm_gelu_backward_f16, dy.data_ptr(), z.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+         stats.data_ptr(), dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel() // 4, nvox, Cdim, eps)
+
+
+def space_to_depth(x: torch.Tensor, out: torch.Tensor, *, D: int, H: int, W: int, Cdim: int) -> None:
+    """x fp16 [D, H, W, C] -> out fp16 [D/2 * H/2 * W/2, 8C], column ((iz*2 + iy)*2 + ix)*C + c (the rows of the pooling convolution
+    and of the transposed convolution's GEMM)."""
+    dev = _dev_check(x, out)
+    _f16_rows("space_to_depth", x, D * H * W * Cdim)
+    _f16_rows("space_to_depth", out, D * H * W * Cdim)
+    call(dev, "cvx_space_to_depth_f16", _lib.load().cvx_space_to_depth_f16, x.data_ptr(), out.data_ptr(), D, H, W, Cdim)
+
+
+def pointwise_out_backward(dlogit: torch.Tensor, y: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, dW: torch.Tensor, db: torch.Tensor, *,
+                           nvox: int, Cdim: int) -> None:
+    """Backward of the 1x1x1 output layer: dlogit fp32 [nvox], y fp16 [nvox, C], w fp32 [C] -> dy fp16 [nvox, C], dW fp32 [C], db fp32 [1]."""
+    dev = _dev_check(dlogit, y, w, dy, dW, db)
+    _f16_rows("pointwise_out_backward", y, nvox * Cdim)
+    _f16_rows("pointwise_out_backward", dy, nvox * Cdim)
+    if any(t.dtype != torch.float32 for t in (dlogit, w, dW, db)) or dlogit.numel() < nvox or w.numel() < Cdim or dW.numel() < Cdim or db.numel() < 1:
+        raise _lib.CvxError("pointwise_out_backward: dlogit fp32 [nvox], w and dW fp32 [C], db fp32 [1]")
+    lib = _lib.load()
+    need = lib.cvx_pointwise_out_backward_workspace_floats(Cdim)
+    check(min(need, 0), "cvx_pointwise_out_backward_workspace_floats")
+    ws = _workspace(dev, 4 * need)
+    call(dev, "cvx_pointwise_out_backward", lib.cvx_pointwise_out_backward, dlogit.data_ptr(), y.data_ptr(), w.data_ptr(), dy.data_ptr(),
+         dW.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel() // 4, nvox, Cdim)
+
+
+def concat_backward(dcat: torch.Tensor, d_pool, d_up, d_skip, *, nvox: int, Cup: int, Cskip: int) -> None:
+    """Splits the gradient of ``torch.cat``: d_up = dcat[:, :Cup] (dense) and d_skip = dcat[:, Cup:] + d_pool (fp32 sum, one rounding).
+    ``d_up`` or ``d_skip`` (with ``d_pool``) may be None: only the other half is produced."""
+    dev = _dev_check(dcat, d_pool, d_up, d_skip)
+    _f16_rows("concat_backward", dcat, nvox * (Cup + Cskip))
+    for t, ch in ((d_pool, Cskip), (d_up, Cup), (d_skip, Cskip)):
+        if t is not None:
+            _f16_rows("concat_backward", t, nvox * ch)
+    call(dev, "cvx_concat_backward_f16", _lib.load().cvx_concat_backward_f16, dcat.data_ptr(), _p(d_pool), _p(d_up), _p(d_skip), nvox, Cup, Cskip)
+
+
 # ---- alternate encoder (SAM2 Hiera) ----
 
 

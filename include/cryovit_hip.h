@@ -309,6 +309,37 @@ int cvx_conv3_out_backward(const float* dlogit, const void* y_mid, const float* 
 int cvx_unscale_check_f32(float* g, long n, float inv_scale, int* flag, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Backward of the UNet3D baseline (csrc/unet_backward.hip): what UNet3D has and the head does not.  Channels-last
+ * fp16 volumes, 16-B aligned; the same reduction rule as above (fp32 block partials, fp64 fixed-order finalize, bitwise reproducible).
+ *
+ * cvx_instnorm_gelu_backward_f16 -- backward of cvx_groupnorm_act_f16(G = C, act = 1) from the layer's input z [nvox][C], the gradient
+ *   dy of its output and the forward's stats buffer (sum | sum of squares per channel).  Recomputed in fp32: xhat = (z - mean) rstd,
+ *   n = gamma xhat + beta, dn = dy (Phi(n) + n phi(n)).  dbeta_c = sum_v dn, dgamma_c = sum_v dn xhat (fp32),
+ *   dz = rstd (gamma dn - mean_v(gamma dn) - xhat mean_v(gamma dn xhat)) (one fp16 rounding).  Two passes over dy and z.
+ *   C % 8 == 0, C <= CVX_GN_MAX_GROUPS, nvox >= 2; workspace: cvx_instnorm_gelu_backward_workspace_floats(C) floats.
+ * cvx_space_to_depth_f16 -- x [D][H][W][C] (even extents) -> out [D/2 * H/2 * W/2][8C], column ((iz*2 + iy)*2 + ix)*C + c of row
+ *   (z, y, x) taken from voxel (2z + iz, 2y + iy, 2x + ix): the row layout of the stride-2 pooling convolution and of the
+ *   transposed convolution's GEMM.  C % 8 == 0.
+ * cvx_pointwise_out_backward -- the 1x1x1 output layer (fp32 weights w [C], C in {8, 16, 32, 64}) from the fp32 logit gradient
+ *   [nvox] and the layer's input y: dy[v][c] = dlogit[v] w[c] (fp16), dW[c] = sum_v dlogit[v] y[v][c], db = sum_v dlogit[v] (fp32).
+ *   workspace: cvx_pointwise_out_backward_workspace_floats(C) floats.
+ * cvx_concat_backward_f16 -- dcat [nvox][c_up + c_skip] is split: d_up[v][c] = dcat[v][c] (dense [nvox][c_up]) and
+ *   d_skip[v][c] = dcat[v][c_up + c] + d_pool[v][c], summed in fp32 and rounded once.  c_up % 8 == 0, c_skip % 8 == 0.  One of d_up and
+ *   d_skip may be null (d_pool too when d_skip is): that half is neither read nor written -- the up half is needed before the
+ *   pooling branch's gradient exists.
+ * --------------------------------------------------------------------------------------------------- */
+long cvx_instnorm_gelu_backward_workspace_floats(int C);
+int cvx_instnorm_gelu_backward_f16(const void* dy, const void* z, const float* gamma, const float* beta, const float* stats, void* dz,
+                                   float* dgamma, float* dbeta, float* workspace, long workspace_floats, long nvox, int C, float eps,
+                                   hipStream_t stream);
+int cvx_space_to_depth_f16(const void* x, void* out, int D, int H, int W, int C, hipStream_t stream);
+long cvx_pointwise_out_backward_workspace_floats(int C);
+int cvx_pointwise_out_backward(const float* dlogit, const void* y, const float* w, void* dy, float* dW, float* db, float* workspace,
+                               long workspace_floats, long nvox, int C, hipStream_t stream);
+int cvx_concat_backward_f16(const void* dcat, const void* d_pool, void* d_up, void* d_skip, long nvox, int c_up, int c_skip,
+                            hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Alternate encoder: SAM2.1 Hiera image encoder + FPN neck (BASELINE configs[4]).  These entry points, together with
  * cvx_gemm_bf16 (qkv / proj / MLP / patch-embed / lateral convs) and cvx_layernorm_bf16, replace
  * `self.model.image_encoder(flat_data)` and the resize in front of it -- SAM2.forward_features,
