@@ -36,6 +36,7 @@ Rounding points (cryovit_amd/csrc):
 import functools
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -323,6 +324,224 @@ def window_case(G, ws, heads, hd, pooled, full=True):
         q, wsq = F.max_pool2d(q.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1), ws // 2
     return attention_family(_windows(q, wsq, heads, hd) / math.sqrt(hd), _windows(qkv[..., C : 2 * C], ws, heads, hd),
                             _windows(qkv[..., 2 * C :], ws, heads, hd), "running", full=full)
+
+
+# ---- window attention: every template form the entry can launch (hiera.hip:430-470) --------------------------------------------------
+
+# (G, ws, heads, hd, pooled), WINDOW_D slices.  NOT part of WINDOW_CASES / derive(): their mutants are weaker than the rule's separation
+# (the leaked key at (32, 32, 1, 88) has R_all 1.02 among 1024 keys).  They are held to the bounds WINDOW_CASES yield; that every
+# honest variant of them stays under those bounds is asserted in tests/test_cpu_error_budget.py.
+WINDOW_DISPATCH_CASES = [
+    (24, 12, 1, 72, False),  # window no power of two: the plain form at 256 threads; nq 144 = 64 + 64 + 16 queries, key tiles 64 + 64 + 16
+    (24, 12, 2, 60, True),   # hd % 8 != 0 (pad columns 60..63); pooled nq 36: 192-thread blocks, 4 valid lanes in the last wave
+    (16, 16, 1, 8, False),   # the smallest head dim
+    (32, 16, 1, 80, False),  # DSTEPS 5 with hd == KW (no pad column to zero); 256 keys
+    (16, 8, 2, 68, False),   # DSTEPS 5, hd % 8 != 0
+    (16, 8, 1, 84, True),    # DSTEPS 6, hd % 8 != 0, pooled: 64-thread blocks
+    (32, 32, 1, 88, False),  # one window of 1024 keys per slice: sixteen key tiles, sixteen query blocks; DSTEPS 6
+    (16, 16, 2, 64, True),   # pooled with nq = 64: the prefetch forms on pooled queries; hd 64, no pad
+]
+WINDOW_FORMS = ("plain", "PF", "PF2", "X32", "X32+PF")
+WINDOW_PREFETCH, WINDOW_X32 = (0, 1, 2), (0, 1)  # the values of cvx_set_option("win_attn_prefetch" / "win_attn_x32"); defaults 1 and 0
+
+
+def window_form(G, ws, heads, hd, pooled, prefetch, x32):
+    """(template form, DSTEPS, blocks renumbered) that cvx_window_attention_bf16 launches for a case laid out as the tests lay it out:
+    k and v at columns C and 2 C of a [rows, 3 C] buffer, q at column 0 of the same buffer or, pooled, of a [rows, C] buffer.  A
+    restatement of hiera.hip:443-467 (thread count, hd % 8, leading dimensions % 8, power-of-two window, nk > 64; the 16-byte
+    alignment of the k / v / q pointers follows from hd % 8 with these layouts) and of the (nb & 7) == 0 renumbering (:95-96)."""
+    C = heads * hd
+    wsq = ws // 2 if pooled else ws
+    nq, nk, ldkv, ldq = wsq * wsq, ws * ws, 3 * C, (C if pooled else 3 * C)
+    threads = 256 if nq >= 64 else 64 * (-(-nq // 16))
+    pf = bool(prefetch) and threads == 256 and hd % 8 == 0 and ldkv % 8 == 0 and ws & (ws - 1) == 0
+    pf2 = pf and prefetch >= 2 and nk > 64
+    wide = bool(x32) and hd % 8 == 0 and ldq % 8 == 0
+    form = "PF2" if pf2 and not wide else "X32+PF" if wide and pf else "X32" if wide else "PF" if pf else "plain"
+    nb = -(-nq // 64) * (G // ws) ** 2 * heads * WINDOW_D
+    return form, (4 if hd <= 64 else 5 if hd <= 80 else 6), nb % 8 == 0
+
+
+def _window_operands_f32(G, ws, heads, hd):  # window_operands before its bf16 rounding
+    g = torch.Generator().manual_seed(G * 100 + ws + hd)
+    return torch.randn(WINDOW_D, G, G, 3 * heads * hd, generator=g) * 1.5
+
+
+def _window_family(qkv, ws, heads, hd, pooled, full):
+    C = heads * hd
+    qkv = qkv.double()
+    q, wsq = qkv[..., :C], ws
+    if pooled:
+        q, wsq = F.max_pool2d(q.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1), ws // 2
+    return attention_family(_windows(q, wsq, heads, hd) / math.sqrt(hd), _windows(qkv[..., C : 2 * C], ws, heads, hd),
+                            _windows(qkv[..., 2 * C :], ws, heads, hd), "running", full=full)
+
+
+WINDOW_RESCALE_CASE = (32, 16, 1, 64, False)  # 256 keys: four key tiles
+WINDOW_RESCALE_SPIKES = (0.25, 9.0)
+
+
+@functools.lru_cache(maxsize=None)
+def window_rescale_operands(spike):
+    """The qkv grid of WINDOW_RESCALE_CASE with, in every window, key RESCALE_KEY (150: third key tile) = spike * query RESCALE_Q (7),
+    set before the bf16 rounding: the running maximum of about half the rows jumps in the third tile (hiera.hip:253-254, :294)."""
+    G, ws, heads, hd, _ = WINDOW_RESCALE_CASE
+    assert heads == 1
+    x = _window_operands_f32(G, ws, heads, hd)
+    w = x.reshape(WINDOW_D, G // ws, ws, G // ws, ws, 3 * hd)  # (a view)
+    (qy, qx), (ky, kx) = divmod(RESCALE_Q, ws), divmod(RESCALE_KEY, ws)
+    w[:, :, ky, :, kx, hd : 2 * hd] = w[:, :, qy, :, qx, :hd] * spike
+    return bf(x)
+
+
+@functools.lru_cache(maxsize=None)
+def window_rescale_case(spike, full=True):
+    """Family of one forced-rescale case of the window kernel ("running" anchors).  full: the mutant this case exists for -- the
+    output accumulator keeps its old scale when the maximum rises in the third tile (the row sum is rescaled; a rise capped at 2^30)."""
+    G, ws, heads, hd, pooled = WINDOW_RESCALE_CASE
+    qkv = window_rescale_operands(spike)
+    fam = _window_family(qkv, ws, heads, hd, pooled, full)
+    if full:
+        q, k, v = (_windows(qkv.double()[..., i * hd : (i + 1) * hd], ws, heads, hd) for i in range(3))
+        s2 = q @ k.transpose(1, 2) / math.sqrt(hd) * LOG2E
+        rise = (s2.max(-1, keepdim=True).values - s2[..., :128].max(-1, keepdim=True).values).clamp(0, 30)
+        bad = torch.softmax(s2 / LOG2E, -1)
+        bad[..., :128] *= torch.exp2(rise)
+        fam.mutants = {"output not rescaled when the maximum rises": ("R_all", rb(bad @ v)),
+                       "one query row skewed 2%": fam.mutants["one query row skewed 2%"]}
+    return fam
+
+
+# ---- elementwise bounds of the resampling input stages (hiera.hip k_sam_patches, patch.hip k_preprocess) -------------------------------
+
+U32 = 2.0**-24  # unit roundoff of fp32
+
+
+def bf16_half_ulp(x):
+    """Half a bf16 ulp at |x| (float64 tensor): 8 significand bits, so ulp = 2^(floor(log2 |x|) - 7); bf16 subnormals below 2^-126."""
+    e = torch.floor(torch.log2(x.abs().clamp(min=2.0**-126)))
+    return torch.exp2(e - 8)
+
+
+def rounded_store_bound(ref, e32):
+    """|bf16(v) - ref| for any fp32 v with |v - ref| <= e32: e32 plus half a bf16 ulp at the largest magnitude v can have."""
+    return bf16_half_ulp(ref.abs() + e32) + e32
+
+
+SAM_PATCH_CASES = [(16, 16, 16, "u8"),  # (S, H, W, mode).  G = 4: twelve of sixteen patches reach over a border; no resize
+                   (16, 16, 40, "f32"),  # H == S != W: only W is resized
+                   (16, 1, 1, "f32"),  # one source pixel
+                   (64, 23, 150, "u8"),  # up one way and down the other
+                   (64, 40, 56, "rgb")]  # three different channels, resized
+PREPROCESS_CASES = [(1, 1, "f32"), (15, 17, "u8"), (16, 16, "f32"), (33, 100, "u8")]  # (H, W, dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def sam_volume(D, H, W, mode):
+    """uint8 [D, H, W], float32 [D, H, W] in [-0.125, 1.125) or ("rgb") float32 [D, 3, H, W]."""
+    rng = np.random.default_rng(1000 * H + W + D)
+    if mode == "u8":
+        return torch.from_numpy(rng.integers(0, 256, (D, H, W), dtype=np.uint8))
+    shape = (D, 3, H, W) if mode == "rgb" else (D, H, W)
+    return torch.from_numpy(rng.random(shape, dtype=np.float32) * 1.25 - 0.125)
+
+
+def preprocess_volume(b, H, W, dtype):
+    return sam_volume(b, H, W, dtype)
+
+
+def _as_planes(vol):
+    """uint8 [D, H, W] (scaled by 1 / 255), float32 [D, H, W] (three equal channels) or float32 [D, 3, H, W] -> float64 [D, 3, H, W]."""
+    x = vol.double() / 255.0 if vol.dtype == torch.uint8 else vol.double()
+    return x if x.dim() == 4 else x[:, None].expand(-1, 3, -1, -1)
+
+
+def sam_resize64(vol, S):
+    """float64 closed form of the resize of SAM2.forward_features (oracle.sam2_hiera.resize_input: trilinear with the channel extent
+    unchanged = bilinear, align_corners False): src = max(0, (dst + 0.5) * H / S - 0.5), taps floor(src) and floor(src) + 1 clamped
+    to the image.  Identity when H == W == S.  -> [D, 3, S, S]."""
+    x = _as_planes(vol)
+    H, W = x.shape[-2:]
+    if H == S and W == S:
+        return x
+
+    def taps(n):
+        f = ((torch.arange(S, dtype=torch.double) + 0.5) * (n / S) - 0.5).clamp(min=0)
+        i0 = f.floor().clamp(max=n - 1).long()
+        return i0, (i0 + 1).clamp(max=n - 1), f - i0
+
+    y0, y1, ly = taps(H)
+    x0, x1, lx = taps(W)
+    ly = ly[:, None]
+    top = (1 - lx) * x[..., y0, :][..., x0] + lx * x[..., y0, :][..., x1]
+    bot = (1 - lx) * x[..., y1, :][..., x0] + lx * x[..., y1, :][..., x1]
+    return (1 - ly) * top + ly * bot
+
+
+def sam_patches_reference(vol, S):
+    """(ref, e32, inside) of cvx_sam_patches: ref float64 [D (S/4)^2, 147] = the 7x7 / stride 4 / pad 3 gather of sam_resize64,
+    column c * 49 + ky * 7 + kx; inside: the taps that lie in the image (the others are exactly 0); e32: a bound on the error of the
+    kernel's fp32 value before its one bf16 rounding, 0 without a resize (a copy).  With a resize (hiera.hip:48-55), u = 2^-24:
+
+      source coordinate  fy = fl(fl((y + 0.5) * fl(H / S)) - 0.5): three roundings of values below H, so |fy - exact| <= 3 u H (the
+                         clamp at 0 only shrinks it), likewise 3 u W.  The bilinear interpolant is continuous and piecewise linear in
+                         the coordinate with slopes of at most R = max - min of the source, also across a tap change, so the
+                         coordinates cost at most 3 u (H + W) R.  ly = fy - y0 is exact (Sterbenz; y0 = 0 trivially).
+      four-tap sum       (1 - ly) ((1 - lx) a + lx b) + ly ((1 - lx) e + lx f): each of the two levels rounds 1 - l, the two products
+                         and the sum, three roundings relative to a convex combination of magnitudes <= M = max |source|: 6 u M, 8 u M
+                         with the second-order terms and room for either contraction.
+      uint8 source       fl(fl(v) * fl(1 / 255)): two more roundings, 2 u M.
+
+    e32 = u (3 (H + W) R + 10 M).  Nothing here was fitted to a kernel's output."""
+    x = _as_planes(vol)
+    H, W = x.shape[-2:]
+    img = sam_resize64(vol, S)
+    D = img.shape[0]
+    ref = F.unfold(img, kernel_size=7, stride=4, padding=3).transpose(1, 2).reshape(D * (S // 4) ** 2, 147)
+    inside = F.unfold(torch.ones_like(img), kernel_size=7, stride=4, padding=3).transpose(1, 2).reshape(ref.shape) > 0
+    resized = not (H == S and W == S)
+    e32 = U32 * (3 * (H + W) * float(x.max() - x.min()) + 10 * float(x.abs().max())) if resized else 0.0
+    return ref, e32, inside
+
+
+CUBIC_SLOPE = 4.2   # max over t of sum_a |w_a'(t)| of the Keys taps, A = -0.75: |w1'| <= 1.35 (at 0.6), |w2'| <= 0.75 (at 1); two of each
+CUBIC_ABS_SUM = 1.375  # max over t of sum_a |w_a(t)| (at t = 0.5: 2 (0.59375 + 0.09375))
+CUBIC_TAP_ERR = 48 * U32  # a tap's Horner form (common.h:144-150): at most 8 roundings of intermediates of magnitude <= 6
+
+
+def preprocess_reference(vol):
+    """(ref, e32) of cvx_preprocess_patches: ref float64 [b hp wp, 196] = oracle.preprocess.bicubic_14_16_closed_form of every
+    edge-padded slice (uint8 scaled by 1 / 255), cut into 14 x 14 patches, column py * 14 + px; e32 [b hp wp, 196]: a bound on the error
+    of the kernel's fp32 value before its one bf16 rounding (patch.hip:24-54), from 16 taps and the absolute sums of their weights.
+    With u = 2^-24, M = max |source|, R = max - min, Ay / Ax = sum |w| of this output's row / column taps, Hp x Wp the padded size:
+
+      source coordinate  sy = fl(fl(scale * (oy + 0.5)) - 0.5), scale = fl(1 / 0.875): three roundings of values below Hp, 3 u Hp, likewise
+                         3 u Wp.  The Keys interpolant is C1 in the coordinate; its derivative is sum_a w_a'(t) row_a with sum_a w_a' = 0,
+                         at most CUBIC_SLOPE * (sum |w| of the other axis <= CUBIC_ABS_SUM) * R: 3 u (Hp + Wp) * 4.2 * 1.375 * R.
+      tap weights        each within CUBIC_TAP_ERR of its exact value: sum_ab |d(wy_a wx_b)| |v| <= 4 CUBIC_TAP_ERR (Ay + Ax) M to first
+                         order, the second-order term 16 CUBIC_TAP_ERR^2 M.
+      16-tap sum         rowv = sum_b wx_b v (4 products, 4 additions), acc = sum_a wy_a rowv (the same): <= 10 roundings on any path,
+                         relative to Ay Ax M; 12 u with the second-order terms.
+      uint8 source       fl(v) / 255: one rounding, u M <= u Ay Ax M (Ay, Ax >= 1).
+
+    Nothing here was fitted to a kernel's output."""
+    from oracle import preprocess as op
+
+    data = op.pad_to_16(vol.numpy().astype(np.float64) / 255.0 if vol.dtype == torch.uint8 else vol.numpy().astype(np.float64))
+    b, Hp, Wp = data.shape
+    hp, wp = Hp // 16, Wp // 16
+    img = torch.from_numpy(np.stack([op.bicubic_14_16_closed_form(s) for s in data]))  # [b, hp * 14, wp * 14]
+    patches = lambda t: t.reshape(-1, hp, 14, wp, 14).permute(0, 1, 3, 2, 4).reshape(-1, 196)
+
+    def abs_sums(n):
+        s = (np.arange(n) + 0.5) * (16.0 / 14.0) - 0.5
+        return torch.tensor([sum(abs(w) for w in op.cubic_weights(v - math.floor(v))) for v in s], dtype=torch.double)
+
+    A = abs_sums(hp * 14)[:, None] * abs_sums(wp * 14)[None, :]
+    Asum = abs_sums(hp * 14)[:, None] + abs_sums(wp * 14)[None, :]
+    M, R = float(np.abs(data).max()), float(data.max() - data.min())
+    e32 = (3 * U32 * (Hp + Wp) * CUBIC_SLOPE * CUBIC_ABS_SUM * R + (4 * CUBIC_TAP_ERR * Asum + 16 * CUBIC_TAP_ERR**2) * M + 13 * U32 * A * M)
+    return patches(img), patches(e32.expand(b, -1, -1).contiguous())
 
 
 # ---- GEMMs with a bf16 store (gemm.hip) -------------------------------------------------------------------------------------------
@@ -735,6 +954,12 @@ def derive(op):
 #   attention nt=133          variants 0, 3, 4, 5    1.000 / 1.017 / 1.002    variant 6  1.000 / 1.000 / 1.005
 #   forced rescale, spikes 9 and 60, variants 0, 4, 6, 7, 8, 9 against their own form's emulation: 1.000 / 1.000 / <= 1.001
 #   window attention (16, 8, 2, 72, pooled)  1.000 / 1.006 / 1.001     (32, 16, 2, 56)  1.000 / 1.054 / 1.001     (x32 = 0 and 1 alike)
+#   window attention, WINDOW_DISPATCH_CASES, the same at win_attn_prefetch 0 / 1 / 2 and win_attn_x32 0 / 1 (all fifteen template forms):
+#     (24, 12, 1, 72)  1.000 / 1.015 / 1.000    (24, 12, 2, 60, pooled)  1.000 / 1.000 / 1.000    (16, 16, 1, 8)  1.000 / 1.000 / 1.000
+#     (32, 16, 1, 80)  1.000 / 1.032 / 1.001    (16, 8, 2, 68)  1.000 / 1.030 / 1.002             (16, 8, 1, 84, pooled)  1.000 / 1.009 / 1.003
+#     (32, 32, 1, 88)  1.000 / 1.091 / 1.001    (16, 16, 2, 64, pooled)  1.000 / 1.000 / 1.000
+#   window attention, forced rescale at prefetch 0 / 1 / 2: spike 0.25  1.000 / 1.018 / 1.000    spike 9  1.000 / 1.043 / 1.000
+#   input stages, max |got - ref64| / (half a bf16 ulp + fp32 term): cvx_sam_patches 0.74 - 0.996, cvx_preprocess_patches 0.65 - 0.96
 #   fp32 epilogues, max |got - ref64| / forward bound: F32, RESID, PATCH 0.004 - 0.008; RESID_HL hi + lo 0.08 - 0.97 (K = 128: 0.97)
 BOUNDS = {
     "attention": {"R_all": 1.290, "R_row": 1.802},  # H 1.035 / 1.544 (row maximum as anchor), Mu 1.607 (1% skew, nt 29) / 2.102 (truncated P)

@@ -1,7 +1,9 @@
 """The error-budget rule (tests/error_budget.py) checked on the CPU: emu has R = 1, every honest variant is under its bound, every
 mutant is over the bound of the statistic meant to catch it, the committed table equals what the rule yields, and Mu / H >= 1.25
 holds for every operation.  TODAY records which mutants the elementwise allclose bands of the GPU tests let through: the gap the
-statistics close.  float64 only; no GPU."""
+statistics close.  Further down: the window kernel's dispatch cases (coverage of the fifteen template forms, honest variants under the
+unchanged bounds, the forced-rescale mutant) and the closed forms behind the input stages' elementwise bounds, pinned against the
+oracle.  float64 only; no GPU."""
 
 import math
 
@@ -172,3 +174,171 @@ def test_groups_cover_the_last_rows_and_columns():
     h = (emu - ref)[0] ** 2
     want = math.sqrt(float((h[3:10].sum() + 16 * h[10].sum()) / h[3:].sum()))  # 8 rows per group; the last group is rows 3..10
     assert abs(s["R_row"] - want) < 1e-12 and s["R_row"] > 1.2
+
+
+# ---- window attention: the dispatch cases (held to the bounds WINDOW_CASES yield, not part of the rule) -----------------------------------
+
+
+def test_window_dispatch_cases_take_every_instantiation():
+    """WINDOW_DISPATCH_CASES and WINDOW_CASES under win_attn_prefetch in {0, 1, 2} x win_attn_x32 in {0, 1} launch all five template
+    forms at all three DSTEPS, with and without the XCD block renumbering; the plain form also at full 256-thread blocks."""
+    seen, renumbered, plain_256 = set(), set(), False
+    for case in eb.WINDOW_DISPATCH_CASES + eb.WINDOW_CASES:
+        for pf in eb.WINDOW_PREFETCH:
+            for x32 in eb.WINDOW_X32:
+                form, ds, ren = eb.window_form(*case, pf, x32)
+                seen.add((form, ds))
+                renumbered.add(ren)
+                G, ws, heads, hd, pooled = case
+                plain_256 |= form == "plain" and pf == 0 and (ws // 2 if pooled else ws) ** 2 >= 64
+    assert seen == {(f, d) for f in eb.WINDOW_FORMS for d in (4, 5, 6)}, sorted(seen)
+    assert renumbered == {True, False} and plain_256
+    assert not set(eb.WINDOW_DISPATCH_CASES) & set(eb.WINDOW_CASES)
+    # the defaults (prefetch 1, x32 0) alone reach three forms' worth: what the suite ran before these cases
+    assert {eb.window_form(*c, 1, 0)[0] for c in eb.WINDOW_CASES} <= {"plain", "PF"}
+
+
+def test_window_dispatch_honest_variants_are_under_the_unchanged_bounds():
+    """Every honest variant of every dispatch case stays under BOUNDS["window_attention"] (largest R_all 1.035 against 1.361, largest
+    R_row 1.704 at (16, 16, 2, 64, pooled) against 1.835): the GPU tests may hold these cases to the bounds WINDOW_CASES yield."""
+    worst = dict.fromkeys(eb.BOUNDS["window_attention"], 0.0)
+    for case in eb.WINDOW_DISPATCH_CASES:
+        fam = eb.window_case(*case)
+        assert fam.stats(fam.emu) == {"R_all": 1.0, "R_row": 1.0, "R_col": 1.0}, case
+        assert fam.honest, case
+        for name, x in fam.honest.items():
+            s = fam.stats(x)
+            for k, bound in eb.BOUNDS["window_attention"].items():
+                assert s[k] <= bound, (case, name, k, s[k], bound)
+                worst[k] = max(worst[k], s[k])
+    print("window dispatch cases, largest honest R:", worst)
+
+
+@pytest.mark.parametrize("spike", eb.WINDOW_RESCALE_SPIKES)
+def test_window_rescale_case_separates_the_missing_rescale(spike):
+    """Forced rescale in the window kernel's third key tile: honest variants under the window bounds (R_row at most 1.717), the mutant
+    "output not rescaled when the maximum rises" far over them (R_all above 400)."""
+    import torch
+
+    fam = eb.window_rescale_case(spike)
+    G, ws, heads, hd, _ = eb.WINDOW_RESCALE_CASE
+    qkv = eb.window_rescale_operands(spike).double()
+    q, k = (eb._windows(qkv[..., i * hd : (i + 1) * hd], ws, heads, hd) for i in range(2))
+    s = q @ k.transpose(1, 2)
+    jumps = (s[..., 128:192].max(-1).values > s[..., :128].max(-1).values).double().mean()
+    assert 0.3 <= float(jumps) <= 0.7, float(jumps)  # the maximum rises in the third tile for about half the rows
+    if spike >= 1:  # (0.25: a rise of a few units, as ordinary operands have it; 9: query 7 sees key 150 alone)
+        assert bool((s[:, eb.RESCALE_Q].argmax(-1) == eb.RESCALE_KEY).all())
+    assert fam.stats(fam.emu) == {"R_all": 1.0, "R_row": 1.0, "R_col": 1.0}
+    for name, x in fam.honest.items():
+        st = fam.stats(x)
+        for key, bound in eb.BOUNDS["window_attention"].items():
+            assert st[key] <= bound, (name, key, st[key], bound)
+    name = "output not rescaled when the maximum rises"
+    r = fam.stats(fam.mutants[name][1])["R_all"]
+    print(f"window rescale spike {spike}: mutant R_all {r:.1f}")
+    assert r > 400 > eb.BOUNDS["window_attention"]["R_all"], r
+    k2, x = fam.mutants["one query row skewed 2%"]
+    assert fam.stats(x)[k2] > eb.BOUNDS["window_attention"][k2]
+
+
+# ---- the closed forms behind the input-stage bounds, pinned against the oracle -------------------------------------------------------------
+
+
+@pytest.mark.parametrize("S,H,W,mode", eb.SAM_PATCH_CASES)
+def test_sam_resize_closed_form_is_the_oracles(S, H, W, mode):
+    """eb.sam_resize64 == oracle.sam2_hiera.resize_input run in float64 (F.interpolate "trilinear" with the channel extent unchanged)."""
+    import torch
+
+    from oracle import sam2_hiera as oh
+
+    vol = eb.sam_volume(3, H, W, mode)
+    x = eb._as_planes(vol)
+    want = oh.resize_input(x[None].contiguous(), S)
+    got = eb.sam_resize64(vol, S)
+    assert got.shape == want.shape == (3, 3, S, S)
+    assert float((got - want).abs().max()) <= 1e-12 * max(1.0, float(x.abs().max()))
+    ref, e32, inside = eb.sam_patches_reference(vol, S)
+    assert (e32 == 0.0) == (H == S and W == S) and e32 < 2.0**-13  # far below half a bf16 ulp (2^-9) of values near 1
+    assert bool((ref[~inside] == 0).all()) and ref.shape == (3 * (S // 4) ** 2, 147)
+    if S == 16:  # G = 4: every patch of the first row and the first column reaches over the border; with S = 64 most do not
+        assert bool((~inside).reshape(3, 4, 4, 147).any(-1)[:, 0].all()) and bool((~inside).reshape(3, 4, 4, 147).any(-1)[:, :, 0].all())
+
+
+def test_u8_scale_by_reciprocal_rounds_like_the_division():
+    """k_sam_patches scales uint8 by fl(1 / 255) (hiera.hip:27), the float64 reference divides: the same bf16 for all 256 values, so the
+    copy path can be compared bit for bit."""
+    import torch
+
+    v = torch.arange(256, dtype=torch.float32)
+    assert torch.equal((v * torch.tensor(1.0 / 255.0, dtype=torch.float32)).to(torch.bfloat16), (v.double() / 255.0).float().to(torch.bfloat16))
+
+
+@pytest.mark.parametrize("H,W,dtype", eb.PREPROCESS_CASES)
+def test_preprocess_reference_is_the_oracles(H, W, dtype):
+    """eb.preprocess_reference (oracle.preprocess.bicubic_14_16_closed_form cut into patches) == the patches of F.interpolate
+    "bicubic" on the edge-padded slices (oracle.preprocess.dino_transform, fp32), and its fp32 term stays far below the store's."""
+    import numpy as np
+    import torch
+
+    from oracle import preprocess as op
+
+    vol = eb.preprocess_volume(2, H, W, dtype)
+    ref, e32 = eb.preprocess_reference(vol)
+    img = op.dino_transform(op.load_scale(vol.numpy()))[:, 0].double()  # [b, hp * 14, wp * 14]
+    b, hh, ww = img.shape
+    want = img.reshape(b, hh // 14, 14, ww // 14, 14).permute(0, 1, 3, 2, 4).reshape(-1, 196)
+    assert ref.shape == want.shape == e32.shape
+    # torch interpolates in fp32 with the kernel's coordinate formula: it is itself held by the fp32 term derived for the kernel
+    assert bool(((ref - want).abs() <= e32 + 2.0**-24 * want.abs()).all()), float(((ref - want).abs() / e32).max())
+    assert 0 < float(e32.max()) <= 2.0**-11  # a quarter of half a bf16 ulp of values near 1
+
+
+def test_input_stage_bounds_pass_fp32_evaluations_and_reject_mutants():
+    """The elementwise bounds of the two resampling stages on the CPU: torch's own fp32 interpolation, rounded to bf16, passes (an
+    honest evaluation in the kernels' precision); a truncating store, one element moved to the next bf16 value (what the earlier
+    4e-3 band allowed near 1), and a gather shifted by one tap do not."""
+    import torch
+    import torch.nn.functional as F
+
+    from oracle import preprocess as op
+    from oracle import sam2_hiera as oh
+
+    def one_more_ulp(ref):
+        x = eb.rb(ref)  # the largest value below 1 goes to its second-nearest bf16 value
+        i = int(torch.where(ref < 1, ref, torch.zeros_like(ref)).argmax())
+        r, v = ref.view(-1)[i], x.view(-1)[i]
+        x.view(-1)[i] = v + (-2 if v > r else 2) * eb.bf16_half_ulp(r)
+        return x
+
+    S, H, W, mode = eb.SAM_PATCH_CASES[3]
+    vol = eb.sam_volume(3, H, W, mode)
+    ref, e32, inside = eb.sam_patches_reference(vol, S)
+    ok = lambda x, b: bool(((x - ref).abs() <= b).all())
+    bound = eb.rounded_store_bound(ref, e32)
+    img32 = oh.resize_input(eb._as_planes(vol).float()[None].contiguous(), S)
+    honest = F.unfold(img32, kernel_size=7, stride=4, padding=3).transpose(1, 2).reshape(ref.shape).to(torch.bfloat16).double()
+    assert ok(honest, bound) and ok(eb.rb(ref), bound)
+    assert not ok(eb.tb(ref), bound) and not ok(one_more_ulp(ref), bound) and not ok(eb.rb(ref.roll(1, 1)), bound)
+    assert ok(one_more_ulp(ref), 4e-3 + 1e-6)  # (the band this bound replaces lets it through)
+
+    vol = eb.preprocess_volume(2, 33, 100, "u8")
+    ref, e32 = eb.preprocess_reference(vol)
+    bound = eb.rounded_store_bound(ref, e32)
+    img = op.dino_transform(op.load_scale(vol.numpy()))[:, 0]
+    b, hh, ww = img.shape
+    honest = img.reshape(b, hh // 14, 14, ww // 14, 14).permute(0, 1, 3, 2, 4).reshape(-1, 196).to(torch.bfloat16).double()
+    assert ok(honest, bound) and ok(eb.rb(ref), bound)
+    assert not ok(eb.tb(ref), bound) and not ok(one_more_ulp(ref), bound) and not ok(eb.rb(ref.roll(1, 1)), bound)
+
+
+def test_bf16_half_ulp():
+    import torch
+
+    x = torch.tensor([1.0, 1.5, 1.999, 2.0, 0.75, 3.0e-3, 0.0], dtype=torch.double)
+    want = torch.tensor([2.0**-8, 2.0**-8, 2.0**-8, 2.0**-7, 2.0**-9, 2.0**-17, 2.0**-134], dtype=torch.double)
+    assert torch.equal(eb.bf16_half_ulp(x), want)
+    # a value half an ulp above a bf16 number rounds to within the bound; the neighbour one ulp away does not pass
+    ref = torch.tensor([1.0 + 2.0**-9], dtype=torch.double)
+    assert float((eb.rb(ref) - ref).abs()) <= float(eb.rounded_store_bound(ref, 0.0))
+    assert float((eb.rb(ref) + 2.0**-7 - ref).abs()) > float(eb.rounded_store_bound(ref, 1e-6))

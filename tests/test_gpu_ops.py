@@ -62,6 +62,24 @@ def padded_f32(v, n, dev):
     return out.to(dev)
 
 
+SENTINEL = 0.3331  # fills output buffers and pad columns (tests/test_gpu_unet_backward.py): a kernel must leave it alone
+
+
+def _sentinel(shape, dtype, gpu):
+    return torch.full(shape, SENTINEL, dtype=dtype, device=gpu)
+
+
+def _untouched(t):
+    return bool((t == torch.tensor(SENTINEL, dtype=t.dtype)).all())
+
+
+def _slack_input(t, gpu):
+    """`t` on the device with NaN (uint8: 255) behind its last element, so that a read past the tensor shows in the output."""
+    flat = torch.full((t.numel() + 256,), 255 if t.dtype == torch.uint8 else float("nan"), dtype=t.dtype)
+    flat[: t.numel()] = t.reshape(-1)
+    return flat.to(gpu)[: t.numel()].view(t.shape)
+
+
 @pytest.mark.parametrize("M,N,K", [(300, 256, 192), (1000, 192, 128), (257, 40, 64), (130, 16, 320), (4096, 1536, 1536)])
 @pytest.mark.parametrize("gelu", [False, True])
 def test_gemm_bf16(gpu, M, N, K, gelu):
@@ -422,10 +440,10 @@ def test_preprocess_patches(gpu, gold, dtype):
     vol, ref = (g["vol_u8"], g["out_u8"]) if dtype == "u8" else (g["vol_f32"], g["out_f32"])
     b, H, W = vol.shape
     hp, wp = math.ceil(H / 16), math.ceil(W / 16)
-    out = torch.zeros(ops.alloc_rows(b * hp * wp), 256, dtype=torch.bfloat16, device=gpu)
+    out = _sentinel((ops.alloc_rows(b * hp * wp), 256), torch.bfloat16, gpu)
     ops.preprocess_patches(torch.from_numpy(vol).to(gpu), out)
     got = out[: b * hp * wp].float().cpu().reshape(b, hp, wp, 256)
-    assert torch.all(got[..., 196:] == 0)
+    assert torch.all(got[..., 196:] == 0) and _untouched(out[b * hp * wp :])  # (the kernel writes the K padding: zeros, not the fill)
     img = got[..., :196].reshape(b, hp, wp, 14, 14).permute(0, 1, 3, 2, 4).reshape(b, hp * 14, wp * 14)
     reft = torch.from_numpy(ref)
     # fixture = the reference's own _dino_transform output; bf16 storage of values in [-0.1, 1.1]
@@ -1734,6 +1752,99 @@ def test_conv_transpose_error_budget(gpu, c2, c3, D, H, W):
             eb.check("conv", f"convt {(c2, c3, D, H, W)} convt_small={small}", got.double(), fam.ref, fam.emu)
     finally:
         _lib.set_option("convt_small", 1)
+
+
+# ---- the ViT input stage (patch.hip) at its shape and padding edges ---------------------------------------------------------------------
+
+
+@functools.lru_cache(maxsize=None)
+def _preprocess_case(H, W, dtype):
+    vol = eb.preprocess_volume(2, H, W, dtype)
+    return (vol,) + eb.preprocess_reference(vol)
+
+
+@pytest.mark.parametrize("k_pad", [256, 320])
+@pytest.mark.parametrize("H,W,dtype", eb.PREPROCESS_CASES)
+def test_preprocess_patches_bound(gpu, H, W, dtype, k_pad):
+    """cvx_preprocess_patches against oracle.preprocess.bicubic_14_16_closed_form (float64) on the edge-padded slices, elementwise:
+    |got - ref64| <= half a bf16 ulp at ref64 + e32, e32 the fp32 term error_budget.preprocess_reference derives from the source
+    coordinate, the 16 taps and the absolute sums of their weights (at most 2^-11 here, a quarter of half an ulp of a value near 1).
+    A single pixel, sizes one below / one above / equal to a multiple of 16, two patch rows; columns 196.. are exactly 0 (the kernel
+    writes the K padding of either width), the rows behind the last patch keep their sentinel."""
+    from cryovit_amd.engine import ops
+
+    vol, ref, e32 = _preprocess_case(H, W, dtype)
+    rows = ref.shape[0]
+    assert rows == 2 * math.ceil(H / 16) * math.ceil(W / 16)
+    out = _sentinel((ops.alloc_rows(rows), k_pad), torch.bfloat16, gpu)
+    ops.preprocess_patches(_slack_input(vol, gpu), out)
+    got = out[:rows].float().cpu().double()
+    assert bool((got[:, 196:] == 0).all()) and _untouched(out[rows:])
+    err, bound = (got[:, :196] - ref).abs(), eb.rounded_store_bound(ref, e32)
+    print(f"preprocess {H}x{W} {dtype} k_pad={k_pad}: max e32 {float(e32.max()):.2e}, max err / bound {float((err / bound).max()):.3f}")
+    assert bool((err <= bound).all()), float((err / bound).max())
+
+
+@pytest.mark.parametrize("k_pad", [192, 200])
+def test_preprocess_patches_refuses_k_pad(gpu, k_pad):
+    from cryovit_amd import _lib
+    from cryovit_amd.engine import ops
+
+    out = _sentinel((512, k_pad), torch.bfloat16, gpu)
+    with pytest.raises(_lib.CvxError, match="preprocess"):
+        ops.preprocess_patches(torch.zeros(1, 16, 16, device=gpu), out)
+    torch.cuda.synchronize()
+    assert _untouched(out)
+
+
+@pytest.mark.parametrize("k_pad", [640, 704])
+@pytest.mark.parametrize("b", [1, 3])
+@pytest.mark.parametrize("Hi,Wi", [(14, 14), (28, 42)])
+def test_im2col_patches_exact(gpu, Hi, Wi, b, k_pad):
+    """fp32 [b, 3, Hi, Wi] -> bf16 patch rows, column c * 196 + py * 14 + px: the bits of F.unfold of the bf16-rounded image; columns
+    588.. are zero (written), the rows behind the last patch keep their sentinel."""
+    from cryovit_amd.engine import ops
+
+    x = rnd(b, 3, Hi, Wi, seed=Hi + Wi + b)
+    rows = b * (Hi // 14) * (Wi // 14)
+    out = _sentinel((ops.alloc_rows(rows), k_pad), torch.bfloat16, gpu)
+    ops.im2col_patches(_slack_input(x, gpu), out)
+    ref = F.unfold(bf(x).float(), kernel_size=14, stride=14).transpose(1, 2).reshape(rows, 588)
+    got = out[:rows].cpu()
+    assert torch.equal(got[:, :588].view(torch.int16), bf(ref).view(torch.int16))
+    assert bool((got[:, 588:].float() == 0).all()) and _untouched(out[rows:])
+
+
+@pytest.mark.parametrize("Hi,Wi", [(15, 14), (14, 27)])
+def test_im2col_patches_refuses_sizes_off_the_patch_grid(gpu, Hi, Wi):
+    from cryovit_amd import _lib
+    from cryovit_amd.engine import ops
+
+    out = _sentinel((512, 640), torch.bfloat16, gpu)
+    with pytest.raises(_lib.CvxError, match="im2col"):
+        ops.im2col_patches(torch.zeros(1, 3, Hi, Wi, device=gpu), out)
+    torch.cuda.synchronize()
+    assert _untouched(out)
+
+
+@pytest.mark.parametrize("C", [128, 384])
+@pytest.mark.parametrize("slices", [1, 3])
+@pytest.mark.parametrize("n_reg,ntok,ntp", [(0, 25, 32), (4, 32, 32), (4, 29, 32)])
+def test_init_tokens_exact(gpu, n_reg, ntok, ntp, slices, C):
+    """The non-patch rows of the token stream: the class row, the register rows (none; four) and the pad rows behind token ntok (seven;
+    none; three) are exact, the patch rows in between, the columns behind C (ldx > C) and the rows behind the last slice keep
+    their sentinel."""
+    from cryovit_amd.engine import ops
+
+    cls, reg = rnd(C, seed=401), rnd(n_reg, C, seed=402)
+    x = _sentinel((ops.alloc_rows(slices * ntp), C + 4), torch.float32, gpu)
+    ops.init_tokens(x, _slack_input(cls, gpu), _slack_input(reg, gpu), n_reg=n_reg, slices=slices, ntok=ntok, ntp=ntp, Cdim=C)
+    got = x[: slices * ntp].cpu().reshape(slices, ntp, C + 4)
+    assert torch.equal(got[:, 0, :C], cls.expand(slices, C))
+    assert torch.equal(got[:, 1 : 1 + n_reg, :C], reg.expand(slices, n_reg, C))
+    assert bool((got[:, ntok:, :C] == 0).all())
+    sent = torch.tensor(SENTINEL)
+    assert bool((got[:, 1 + n_reg : ntok] == sent).all()) and bool((got[..., C:] == sent).all()) and _untouched(x[slices * ntp :])
 
 
 def test_variants_on_the_ablation_build(gpu):
