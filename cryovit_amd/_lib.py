@@ -225,6 +225,10 @@ SIGNATURES = {
     "cvx_mask_flood_unpack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_mask_threshold": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_mask_added_voxels": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
+    "cvx_slices_edt_squared": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_slice_valid": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_surface_mask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_surface_distance_hist": (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]),
 }
 
 _lib = None

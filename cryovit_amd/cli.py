@@ -7,6 +7,7 @@
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
                                     [--instances <measurements>]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
+                                       [--boundary [--boundary-mode slices|3d] [--boundary-tolerance T ...]]
     python -m cryovit_amd.cli instances <predictions> --label NAME [--result-folder DIR] <measurements>
                                         [--distance-to NAME] [--contacts-with NAME] [--distance-to-folder DIR] [--contact-radius R]
 
@@ -72,6 +73,16 @@ def _non_negative(what: str):
     return _checked(lambda v: v >= 0, f"{what} must be >= 0 (voxels)")
 
 
+def _each(check):
+    """``check`` on every value of a repeatable option."""
+    def check_all(values):
+        for v in values or ():
+            check(v)
+        return values
+
+    return check_all
+
+
 # The measurement options `infer` and `instances` share, each declared once; analysis.instances.InstanceOptions has the full account.
 _MIN_SIZE_HELP = "drop instances of fewer voxels (with infer: with --instances)"
 _CONNECTIVITY_HELP = "6 (faces) or 26 (faces, edges and corners) (with infer: with --instances)"
@@ -111,6 +122,12 @@ _FILL_HOLES_HELP = ("before labelling, fill the background that is not connected
                     "open along z); applied after --close-radius (with infer: needs --instances)")
 _OPEN_RADIUS_HELP = ("before labelling, open the mask by a ball of this radius on the GPU (removes spurs and specks; applied last; "
                      "voxels, >= 0; with infer: needs --instances)")
+_BOUNDARY_HELP = ("score the predicted boundary against the annotated one on the GPU: after the model's metrics every CSV row gains hd95 "
+                  "(95th-percentile Hausdorff distance), hd, assd (average symmetric surface distance), nsd_<t> (surface Dice at each "
+                  "--boundary-tolerance) and the surface / unmatched voxel counts (voxels; exact distance maps)")
+_BOUNDARY_MODE_HELP = ("with --boundary: slices = every fully annotated z-slice scored as an image of its own (sparse CryoVIT labels), "
+                       "3d = the whole volume, which must hold no ignored (-1) voxel")
+_BOUNDARY_TOLERANCE_HELP = "with --boundary: a tolerance of the surface Dice, column nsd_<T>; repeatable (voxels, >= 0)"
 _EXT = "build extension: "
 
 MinSize = Annotated[int, Option(min=0, help=_EXT + _MIN_SIZE_HELP)]
@@ -328,6 +345,12 @@ def evaluate(
     encoder: Annotated[Optional[str], Option(help="build extension: encode files without dino_features on the fly with this encoder")] = None,
     checkpoint: Annotated[Optional[str], Option(help="build extension: local DINOv2 state_dict file")] = None,
     synthetic_seed: Annotated[Optional[int], Option(help="build extension: seeded random encoder weights")] = None,
+    boundary: Annotated[bool, Option("--boundary", help=_EXT + _BOUNDARY_HELP)] = False,
+    boundary_mode: Annotated[str, Option("--boundary-mode", callback=_checked(lambda v: v in ("slices", "3d"), "boundary mode must be slices or 3d"),
+                                         help=_EXT + _BOUNDARY_MODE_HELP)] = "slices",
+    boundary_tolerance: Annotated[Optional[list[float]], Option("--boundary-tolerance", callback=_each(_non_negative("boundary tolerance")),
+                                                                help=_EXT + _BOUNDARY_TOLERANCE_HELP,
+                                                                show_default="1 and 2")] = None,
 ):
     """Evaluate a pre-trained model on a test dataset."""
     from cryovit_amd.run.eval_model import run_evaluation
@@ -343,7 +366,8 @@ def evaluate(
     assert label_key in labels, f"The label key {label_key} used to train the model is not in the provided labels."
     result_path.mkdir(parents=True, exist_ok=True)
     run_evaluation(load_files_from_path(test_path), load_files_from_path(label_path), labels, model_path, result_path,
-                   visualize=visualize, encoder=_load_encoder(encoder, checkpoint, synthetic_seed))
+                   visualize=visualize, encoder=_load_encoder(encoder, checkpoint, synthetic_seed), boundary=boundary,
+                   boundary_mode=boundary_mode, boundary_tolerances=tuple(boundary_tolerance) if boundary_tolerance else (1.0, 2.0))
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@
 //            site inside a voxel's own bitmap, and a forward max-scan / backward min-scan over the bitmaps' last / first sites
 //            (one lane per bitmap) finds it beyond.
 //   y pass   in place, out[i] = min_j f[j] + (i - j)^2 along y (lines of H elements, stride W)
-//   z pass   the same along z (lines of D elements, stride H*W)
+//   z pass   the same along z (lines of D elements, stride H*W); cvx_slices_edt_squared leaves it out: every z-slice on its own
 // A min-plus workgroup owns a slab of 64 adjacent x (256-B row pieces: every access of either pass is a coalesced wave access)
 // times the WHOLE line, so that nothing it overwrites is still needed by another workgroup.
 //   RULE: a line of up to kLineMax = 512 elements (512 x 256 B = 128 KB of LDS) is staged in LDS once and every output is
@@ -218,6 +218,24 @@ extern "C" int cvx_edt_squared(const void* src, int src_dtype, int sites, int D,
     if (rc) return rc;
     if ((rc = edt_launch_lines(out, H, W, D, (long)H * W, W, st))) return rc;  // y: one line per (z, x)
     return edt_launch_lines(out, D, (long)H * W, H, W, W, st);                  // z: one line per (y, x)
+}
+
+// every z-slice an image of its own: the x pass and the y pass of cvx_edt_squared, no z pass
+extern "C" int cvx_slices_edt_squared(const void* src, int src_dtype, int sites, int D, int H, int W, int32_t* out, hipStream_t st) {
+    long n;
+    if (extents_fault(D, H, W, kExtentAny, n)) return cvx_fail("slices_edt_squared", kExtentsRule);
+    if (src_dtype != CVX_EDT_U8 && src_dtype != CVX_EDT_I32) return cvx_fail("slices_edt_squared: src_dtype must be CVX_EDT_U8 or CVX_EDT_I32");
+    if (sites != CVX_EDT_SITES_ZERO && sites != CVX_EDT_SITES_NONZERO)
+        return cvx_fail("slices_edt_squared: sites must be CVX_EDT_SITES_ZERO or CVX_EDT_SITES_NONZERO");
+    if (n == 0) return 0;
+    const long long far = (long long)(H - 1) * (H - 1) + (long long)(W - 1) * (W - 1);
+    if (far >= INT_MAX) return cvx_fail("slices_edt_squared: the squared diagonal (H-1)^2 + (W-1)^2 must be below INT32_MAX");
+    if (!src || !out) return cvx_fail("slices_edt_squared: null pointer");
+    if (((uintptr_t)out & 3) || (src_dtype == CVX_EDT_I32 && ((uintptr_t)src & 3))) return cvx_fail("slices_edt_squared: int32 volumes must be 4-B aligned");
+    const int rc = src_dtype == CVX_EDT_U8 ? edt_launch_rows<uint8_t>(src, sites, out, (long)D * H, W, st)
+                                           : edt_launch_rows<int32_t>(src, sites, out, (long)D * H, W, st);
+    if (rc) return rc;
+    return edt_launch_lines(out, H, W, D, (long)H * W, W, st);  // y: one line per (z, x); a slice without a site stays kEdtNone
 }
 
 extern "C" int cvx_instance_distance_stats(const int32_t* labels, const int32_t* d2, int D, int H, int W, long k, int threshold_d2,

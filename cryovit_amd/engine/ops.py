@@ -759,18 +759,22 @@ def label_components(mask: torch.Tensor, *, connectivity: int = 26, min_size: in
 
 # ---- exact distance maps and the per-instance reduction over them (`--morphology`, `cryovit instances --distance-to`) ----
 
-def edt_squared(src: torch.Tensor, *, sites: str = "zero") -> torch.Tensor:
+def edt_squared(src: torch.Tensor, *, sites: str = "zero", slices: bool = False) -> torch.Tensor:
     """int32 [D, H, W]: the exact squared Euclidean distance, in voxels, from every voxel of ``src`` (uint8 mask or int32
     instance volume, [D, H, W]) to the nearest site inside the volume: its zero voxels (``sites="zero"``: depth inside the
     foreground, scipy's convention) or its nonzero voxels (``sites="nonzero"``).  0 on a site; ``_lib.EDT_NONE`` everywhere
-    when there is no site.  Integers only, no workspace, bit-reproducible; the host does not wait."""
+    when there is no site.  With ``slices`` every z-slice is an image of its own: the distance within the slice to the nearest
+    site of the slice, ``_lib.EDT_NONE`` throughout a slice without one.  Integers only, no workspace, bit-reproducible; the host
+    does not wait."""
     if src.dim() != 3 or src.dtype not in (torch.uint8, torch.int32):
         raise _lib.CvxError(f"edt_squared: src must be uint8 or int32 [D, H, W], got {src.dtype} {tuple(src.shape)}")
     if sites not in ("zero", "nonzero"):
         raise _lib.CvxError(f"edt_squared: sites must be 'zero' or 'nonzero', got {sites!r}")
     dev, D, H, W = _volumes_check("edt_squared", src=(src, src.dtype))
     out = torch.empty((D, H, W), dtype=torch.int32, device=dev)
-    call(dev, "cvx_edt_squared", _lib.load().cvx_edt_squared, _p(src), _lib.EDT_U8 if src.dtype == torch.uint8 else _lib.EDT_I32,
+    lib = _lib.load()
+    what, fn = ("cvx_slices_edt_squared", lib.cvx_slices_edt_squared) if slices else ("cvx_edt_squared", lib.cvx_edt_squared)
+    call(dev, what, fn, _p(src), _lib.EDT_U8 if src.dtype == torch.uint8 else _lib.EDT_I32,
          _lib.EDT_SITES_ZERO if sites == "zero" else _lib.EDT_SITES_NONZERO, D, H, W, _p(out))
     return out
 
@@ -1398,4 +1402,61 @@ def mesh_smooth(vertices: torch.Tensor, triangles: torch.Tensor, iterations: int
         for c in cs:
             call(dev, "cvx_mesh_smooth_step", lib.cvx_mesh_smooth_step, _p(out), _p(out), _p(triangles), V, T, c, _p(workspace),
                  workspace.numel() * 8)
+    return out
+
+
+# ---- a prediction scored at its boundary (`cryovit evaluate --boundary`): scored slices, surfaces, distance histograms ----
+
+HIST_BINS_MAX = 2**24 + 1  # of surface_distance_hist
+
+
+def slice_valid(y: torch.Tensor, *, out=None) -> torch.Tensor:
+    """int32 [D]: 1 for every z-slice of the decoded label volume ``y`` (int8 [D, H, W]) that holds no ignored voxel (y <= -1),
+    0 for the others.  ``out`` (int32 [D]) receives it when given.  The host does not wait."""
+    dev, D, H, W = _volumes_check("slice_valid", y=(y, torch.int8))
+    if out is None:
+        out = torch.empty(D, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (D,):
+        raise _lib.CvxError(f"slice_valid: out must be int32 [{D}], got {out.dtype} {tuple(out.shape)}")
+    _dev_check(y, out)
+    call(dev, "cvx_slice_valid", _lib.load().cvx_slice_valid, _p(y), D, H, W, _p(out))
+    return out
+
+
+def mask_surface(mask: torch.Tensor, *, slices: bool = False, valid=None, out=None) -> torch.Tensor:
+    """uint8 [D, H, W], 0 / 1: the surface voxels of ``mask`` (uint8 [D, H, W], nonzero = foreground): foreground with a face
+    neighbour that is background or outside the volume (``m & ~binary_erosion(m, cross, border_value=0)``, MedPy's convention).
+    ``slices``: the 4 neighbours within the z-slice rather than the 6 in 3-D, and ``valid`` (int32 [D], ``slice_valid``) empties
+    the slices it marks 0; ``valid`` without ``slices`` is refused.  ``out`` receives the result when given.  Exact; the host does
+    not wait."""
+    dev, D, H, W = _volumes_check("mask_surface", mask=(mask, torch.uint8))
+    if valid is not None and (valid.dtype != torch.int32 or tuple(valid.shape) != (D,)):
+        raise _lib.CvxError(f"mask_surface: valid must be int32 [{D}], got {valid.dtype} {tuple(valid.shape)}")
+    if out is None:
+        out = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
+    else:
+        _volumes_check("mask_surface", mask=(mask, torch.uint8), out=(out, torch.uint8))
+    _dev_check(mask, valid, out)
+    call(dev, "cvx_surface_mask", _lib.load().cvx_surface_mask, _p(mask), _p(valid), D, H, W, int(bool(slices)), _p(out))
+    return out
+
+
+def surface_distance_hist(surf: torch.Tensor, d2: torch.Tensor, bins: int, *, out=None) -> torch.Tensor:
+    """int64 [bins + 1] on the device: over the voxels with ``surf`` != 0 (uint8, any shape) the histogram of ``d2`` (int32, as many
+    elements; ``edt_squared``): entry d2 for d2 < bins - 1; entry bins - 1 (overflow) for larger and for negative values; entry
+    bins for ``_lib.EDT_NONE`` (unmatched).  ``bins`` in 2..``HIST_BINS_MAX``.  ``out`` receives it when given.  Integer atomics
+    only: bit-reproducible; the host does not wait."""
+    if not isinstance(surf, torch.Tensor) or surf.dtype != torch.uint8:
+        raise _lib.CvxError("surface_distance_hist: surf must be a uint8 tensor")
+    if not isinstance(d2, torch.Tensor) or d2.dtype != torch.int32 or d2.numel() != surf.numel():
+        raise _lib.CvxError("surface_distance_hist: d2 must be int32 with as many elements as surf")
+    bins = int(bins)
+    if out is None:
+        if not 2 <= bins <= HIST_BINS_MAX:
+            raise _lib.CvxError(f"surface_distance_hist: bins must lie in [2, 2^24 + 1], got {bins}")
+        out = torch.empty(bins + 1, dtype=torch.int64, device=surf.device)
+    elif out.dtype != torch.int64 or out.numel() < max(bins, 0) + 1:
+        raise _lib.CvxError(f"surface_distance_hist: out must be int64 with at least bins + 1 = {bins + 1} elements")
+    dev = _dev_check(surf, d2, out)
+    call(dev, "cvx_surface_distance_hist", _lib.load().cvx_surface_distance_hist, _p(surf), _p(d2), surf.numel(), bins, _p(out))
     return out

@@ -21,6 +21,7 @@ import logging
 import random
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
+from typing import Sequence
 
 import numpy as np
 import torch
@@ -209,19 +210,58 @@ def _probabilities(model, batch, raw, encoder, batch_size: int) -> torch.Tensor:
     return model.engine().forward(cl, vol.shape[0], hp, wp)["probs"]
 
 
+def boundary_threshold(metric_fns: dict) -> float:
+    """The threshold of the mask the boundary metrics score: the model's DiceMetric threshold, 0.5 without one."""
+    for m in metric_fns.values():
+        if type(m).__name__ == "DiceMetric":
+            return float(m.thresh)
+    return 0.5
+
+
+def _check_csv_columns(results_dir: Path, samples, columns: list[str]) -> None:
+    """``update_metrics_csv`` rewrites ``<sample>.csv`` under the columns of the row it adds: earlier rows lose the columns the new
+    row lacks and read empty in the ones it brings.  With the boundary columns that would silently mix two kinds of rows, so a file
+    written with other columns is refused before anything is computed."""
+    import csv
+
+    for sample in sorted(set(samples)):
+        path = Path(results_dir) / f"{sample}.csv"
+        if not path.exists():
+            continue
+        with open(path, newline="") as f:
+            header = next(csv.reader(f), [])
+        if header != columns:
+            raise ValueError(f"{path} was written with the columns {header}, this run writes {columns}: rows of both kinds in one file "
+                             "would leave blanks or drop columns.  Use another --result-folder, or remove the file.")
+
+
 def run_evaluation(test_data: list[Path], test_labels: list[Path], labels: list[str], model_path: Path, result_dir: Path,
-                   visualize: bool = True, *, encoder=None, batch_size: int = 128, device: str | None = None) -> Path:
+                   visualize: bool = True, *, encoder=None, batch_size: int = 128, device: str | None = None, boundary: bool = False,
+                   boundary_mode: str = "slices", boundary_tolerances: Sequence[float] = (1.0, 2.0)) -> Path:
     """Score the ``.model`` at ``model_path`` on ``test_data`` / ``test_labels`` (paired in order; ``labels``: the label names in
     ascending value order).  Writes ``<result_dir>/results/<name>/<sample>.csv`` (CsvWriter) and, with ``visualize``,
     ``<result_dir>/predictions/<name>/<sample>/<file>`` (TestPredictionWriter).  Returns the directory holding the CSV files
     (the reference returns ``results/<name>.csv``, a file its CsvWriter never writes: DESIGN.md s.7).
 
-    ``encoder`` (extension, as in ``run_inference``): CryoVIT data files without ``dino_features`` are encoded on the fly."""
+    ``encoder`` (extension, as in ``run_inference``): CryoVIT data files without ``dino_features`` are encoded on the fly.
+    ``boundary`` (extension): after the model's metrics every row gains the boundary columns of ``analysis.boundary``
+    (``hd95``, ``hd``, ``assd``, one ``nsd_<t>`` per entry of ``boundary_tolerances``, the surface counts) of the mask ``probs >=
+    boundary_threshold(model.metric_fns)`` against the decoded labels, per annotated z-slice (``boundary_mode="slices"``) or in 3-D
+    (``"3d"``).  A results CSV written earlier with other columns is refused."""
+    from cryovit_amd.analysis import boundary as bnd
     from cryovit_amd.datamodules import FileDataModule
     from cryovit_amd.run.infer_model import _has_key
     from cryovit_amd.types import BatchedModelResult
     from cryovit_amd.utils import load_model
 
+    boundary_tolerances = [float(t) for t in boundary_tolerances]
+    if boundary:
+        if boundary_mode not in bnd.BOUNDARY_MODES:
+            raise ValueError(f"boundary_mode must be one of {bnd.BOUNDARY_MODES}, got {boundary_mode!r}")
+        for t in boundary_tolerances:
+            bnd.contact_threshold(t)  # raises on a negative or NaN tolerance
+        if len({bnd.nsd_column(t) for t in boundary_tolerances}) != len(boundary_tolerances):
+            raise ValueError(f"boundary_tolerances {boundary_tolerances} give the same column twice")
     rank, _, world = world_info()
     device = select_device(device)
     model, model_type, model_name, label_key = load_model(model_path, device=device)
@@ -243,6 +283,9 @@ def run_evaluation(test_data: list[Path], test_labels: list[Path], labels: list[
     file_cbs = [cb for k, cb in callbacks.items() if k != "csv_writer"]
     csv_cb = callbacks["csv_writer"]
     mine = shard_records(records, rank, world)
+    if boundary:
+        _check_csv_columns(csv_cb.results_dir, [fd.sample for fd in records],
+                           ["sample", "tomo_name", *model.metric_fns, *bnd.boundary_columns(boundary_tolerances)])
 
     def load(i):
         on_the_fly = encoder is not None and model.input_key == "dino_features" and not _has_key(records[i].tomo_path, "dino_features")
@@ -259,9 +302,13 @@ def run_evaluation(test_data: list[Path], test_labels: list[Path], labels: list[
             probs = _probabilities(model, batch, raw, encoder, batch_size)
             labels_dev = torch.from_numpy(raw_labels).to(probs.device)
             mode, value = label_plan(labels_dev, fd.label_path, list(labels), label_key)
-            metrics, y = score_labels(probs, labels_dev, mode, value, model.metric_fns, want_labels=bool(file_cbs))
+            metrics, y = score_labels(probs, labels_dev, mode, value, model.metric_fns, want_labels=bool(file_cbs) or boundary)
+            if boundary:
+                pred_mask = (probs >= boundary_threshold(model.metric_fns)).to(torch.uint8).reshape(y.shape)
+                metrics.update(bnd.boundary_scores(*bnd.boundary_histograms(pred_mask, y, boundary_mode), boundary_tolerances))
+                del pred_mask
             out = BatchedModelResult(num_tomos=1, samples=[fd.sample], tomo_names=[fd.tomo_path.name], split_id=None, data=[aux],
-                                     label=[y.cpu().numpy().astype(np.float32)] if y is not None else [],
+                                     label=[y.cpu().numpy().astype(np.float32)] if file_cbs else [],
                                      preds=[probs.float().cpu().numpy()] if file_cbs else [], losses={}, metrics=metrics, aux_data=None)
             logging.info("[rank %d] %s/%s %s", rank, fd.sample, fd.tomo_path.name, " ".join(f"{m}={v:.4f}" for m, v in metrics.items()))
             for cb in file_cbs:

@@ -855,6 +855,32 @@ int cvx_mask_flood_unpack(const uint64_t* reach, int D, int H, int W, uint8_t* o
 int cvx_mask_threshold(const int32_t* d2, int D, int H, int W, int pad, int mode, int threshold_d2, uint8_t* out, hipStream_t stream);
 int cvx_mask_added_voxels(const int32_t* labels, const uint8_t* before, int D, int H, int W, long k, int64_t* out, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Scoring a prediction at its boundary (`cryovit evaluate --boundary`: HD95, surface distance, surface Dice).  Integers only, no
+ * float atomics, bit-reproducible.
+ *
+ * cvx_slices_edt_squared: the contract of cvx_edt_squared with every z-slice an image of its own: out[z][y][x] = min over the
+ *   sites s of slice z of (y - sy)^2 + (x - sx)^2; a slice without a site is CVX_EDT_NONE throughout, whatever its neighbours
+ *   hold.  Refused like cvx_edt_squared, the diagonal rule being (H-1)^2 + (W-1)^2 < INT32_MAX.
+ * cvx_slice_valid: y int8 [D][H][W], a decoded label volume in which a value <= -1 means "not annotated"; valid int32 [D],
+ *   every entry written by plain stores: valid[z] = 1 iff no voxel of slice z has y <= -1 (an empty slice is valid).
+ * cvx_surface_mask: mask uint8 [D][H][W] (nonzero = foreground); out uint8 [D][H][W], every voxel written: 1 iff the voxel is
+ *   foreground and one of its face neighbours is background or outside the volume (MedPy's surface, m & ~erosion(m, cross,
+ *   border_value = 0)).  slices = 1: the 4 neighbours within the z-slice, and valid (int32 [D], nullable = every slice) zeroes the
+ *   slices with valid[z] == 0.  slices = 0: the 6 neighbours in 3-D; a non-null valid is refused.  out must not be mask.
+ * cvx_surface_distance_hist: surf uint8 [n], d2 int32 [n] (a distance map as cvx_edt_squared writes it), hist int64 [bins + 1],
+ *   initialised by the call.  Every voxel with surf != 0 adds 1 to one entry: hist[bins] when d2 == CVX_EDT_NONE (unmatched: there
+ *   was nothing to measure against); else hist[bins - 1] when (uint32)d2 >= bins - 1 (overflow, which also takes a negative d2);
+ *   else hist[d2].  32-bit LDS and 64-bit global integer adds only, so the histogram does not depend on scheduling.
+ * Refused with an error before any launch: negative extents, D*H*W > CVX_COMPONENT_MAX_VOXELS, null pointers, misaligned arrays
+ * (int32: 4 bytes, hist: 8 bytes), slices other than 0 / 1, valid with slices = 0, mask == out, n outside [0, 2^40], bins outside
+ * [2, 2^24 + 1].  An empty volume succeeds and launches nothing; n == 0 succeeds and leaves hist zero.
+ * ------------------------------------------------------------------------------------------------- */
+int cvx_slices_edt_squared(const void* src, int src_dtype, int sites, int D, int H, int W, int32_t* out, hipStream_t stream);
+int cvx_slice_valid(const int8_t* y, int D, int H, int W, int32_t* valid, hipStream_t stream);
+int cvx_surface_mask(const uint8_t* mask, const int32_t* valid, int D, int H, int W, int slices, uint8_t* out, hipStream_t stream);
+int cvx_surface_distance_hist(const uint8_t* surf, const int32_t* d2, long n, long bins, int64_t* hist, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
