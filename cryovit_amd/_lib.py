@@ -41,6 +41,9 @@ THICKNESS_COLS = 5  # CVX_THICKNESS_COLS
 MESH_COLS = 3  # CVX_MESH_COLS
 MESH_FACTOR_MAX = 131072  # CVX_MESH_FACTOR_MAX
 MASK_LE, MASK_GT = 0, 1  # CVX_MASK_LE / CVX_MASK_GT
+CURVATURE_COLS = 7  # CVX_CURVATURE_COLS
+CURVATURE_RADIUS_MIN, CURVATURE_RADIUS_MAX = 2, 16  # CVX_CURVATURE_RADIUS_MIN / CVX_CURVATURE_RADIUS_MAX
+CURV_NONE = -(2**31)  # CVX_CURV_NONE
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -229,6 +232,9 @@ SIGNATURES = {
     "cvx_slice_valid": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_surface_mask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_surface_distance_hist": (c_int, [c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]),
+    "cvx_curvature_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "cvx_curvature_map": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
+    "cvx_curvature_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
 }
 
 _lib = None

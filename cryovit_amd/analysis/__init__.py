@@ -1,7 +1,8 @@
 """Quantification of predictions after the model has run: connected instances of a predicted mask, what
 its distance maps say about them, the split of instances that touch over a neck, which instance of one label touches
 which of another, the shape of each instance (surface area, Euler number, principal axes), its centreline (length, ends, branches)
-its local thickness (mean, spread, min, max) and the surface mesh of the mask (PLY / STL; triangles, area, volume); the
+its local thickness (mean, spread, min, max), the surface mesh of the mask (PLY / STL; triangles, area, volume) and the mean
+curvature of its membrane (ball-volume integral invariant; mean, spread, min, max, convex share); the
 clean-up of the mask before all of that (close, fill holes, open); and, against annotated labels, how far the predicted boundary
 lies from the true one (HD95, surface distance, surface Dice)."""
 
@@ -14,6 +15,8 @@ from cryovit_amd.analysis.shape import SHAPE_COLUMNS, instance_shape, shape_rows
 from cryovit_amd.analysis.skeleton import SKELETON_COLUMNS, instance_skeleton, skeleton_rows, skeleton_volume  # noqa: F401
 from cryovit_amd.analysis.thickness import THICKNESS_COLUMNS, instance_thickness, thickness_rows, thickness_volume  # noqa: F401
 from cryovit_amd.analysis.mesh import MESH_COLUMNS, instance_mesh, mesh_arrays, mesh_rows, write_mesh, write_ply, write_stl  # noqa: F401
+from cryovit_amd.analysis.curvature import (  # noqa: F401
+    CURVATURE_COLUMNS, CurvatureOptions, curvature_map, curvature_rows, curvature_volume, vertex_curvature)
 from cryovit_amd.analysis.boundary import (  # noqa: F401
     BOUNDARY_COUNT_COLUMNS, BOUNDARY_DISTANCE_COLUMNS, BOUNDARY_MODES, boundary_columns, boundary_histograms, boundary_scores, check_scored,
     nsd_column)

@@ -62,17 +62,20 @@ def mesh_rows(table) -> list[dict]:
     return [dict(zip(MESH_COLUMNS, (int(n), area2 / 2 / 65536, det / 6 / 256**3))) for n, area2, det in host_table(table, 3).tolist()]
 
 
-def mesh_arrays(labels, k: int, smooth: int = 0):
+def mesh_arrays(labels, k: int, smooth: int = 0, raw: bool = False):
     """(vertices int32 [V, 3], triangles int32 [T, 3], ids int32 [T], table int64 [k, 3]) of the int32 device volume ``labels``
-    with the instances 1..k; all stay on the device.  ``smooth``: pairs of Taubin steps applied before the table is taken."""
+    with the instances 1..k; all stay on the device.  ``smooth``: pairs of Taubin steps applied before the table is taken.
+    ``raw``: a fifth entry, the vertices before smoothing (the midpoints, from which a vertex's two voxels can be recovered)."""
     from cryovit_amd.engine import ops
 
     if smooth < 0:
         raise ValueError(f"smooth must be >= 0, got {smooth}")
     vertices, triangles, ids = ops.mesh_surface(labels)
+    unsmoothed = vertices
     if smooth:
         vertices = ops.mesh_smooth(vertices, triangles, smooth)
-    return vertices, triangles, ids, ops.mesh_stats(vertices, triangles, ids, k)
+    out = (vertices, triangles, ids, ops.mesh_stats(vertices, triangles, ids, k))
+    return (*out, unsmoothed) if raw else out
 
 
 def instance_mesh(labels, k: int, smooth: int = 0) -> list[dict]:
@@ -104,18 +107,27 @@ def _replace_into(path, write) -> Path:
     return path
 
 
-def write_ply(path, vertices, triangles, ids) -> Path:
-    """Binary little-endian PLY of a mesh as ``engine.ops.mesh_surface`` returns it (host arrays or tensors)."""
+def write_ply(path, vertices, triangles, ids, vertex_values=None) -> Path:
+    """Binary little-endian PLY of a mesh as ``engine.ops.mesh_surface`` returns it (host arrays or tensors).  ``vertex_values``
+    (float [V], ``analysis.curvature.vertex_curvature``): written as ``property float curvature`` after x, y, z of every vertex;
+    without it the file is the one it always was."""
     xyz, faces, inst = _file_arrays(vertices, triangles, ids)
+    points = xyz.astype("<f4")
+    if vertex_values is not None:
+        values = host_table(vertex_values, 0, np.float32)
+        if len(values) != len(xyz):
+            raise ValueError(f"{len(values)} vertex values for {len(xyz)} vertices")
+        points = np.concatenate([points, values.astype("<f4")[:, None]], axis=1)
     header = ("ply\nformat binary_little_endian 1.0\ncomment cryovit_amd surface mesh, voxel units\n"
               f"element vertex {len(xyz)}\nproperty float x\nproperty float y\nproperty float z\n"
+              + ("property float curvature\n" if vertex_values is not None else "") +
               f"element face {len(faces)}\nproperty list uchar int vertex_indices\nproperty int instance\nend_header\n")
     rec = np.zeros(len(faces), dtype=np.dtype([("n", "u1"), ("v", "<i4", 3), ("instance", "<i4")]))
     rec["n"], rec["v"], rec["instance"] = 3, faces, inst
 
     def write(fh):
         fh.write(header.encode("ascii"))
-        fh.write(xyz.astype("<f4").tobytes())
+        fh.write(points.tobytes())
         fh.write(rec.tobytes())
 
     return _replace_into(path, write)
@@ -141,7 +153,11 @@ def write_stl(path, vertices, triangles, ids) -> Path:
     return _replace_into(path, write)
 
 
-def write_mesh(path, vertices, triangles, ids, fmt: str = "ply") -> Path:
+def write_mesh(path, vertices, triangles, ids, fmt: str = "ply", vertex_values=None) -> Path:
     if fmt not in MESH_FORMATS:
         raise ValueError(f"mesh format must be one of {MESH_FORMATS}, got {fmt!r}")
-    return (write_ply if fmt == "ply" else write_stl)(path, vertices, triangles, ids)
+    if vertex_values is None:
+        return (write_ply if fmt == "ply" else write_stl)(path, vertices, triangles, ids)
+    if fmt != "ply":
+        raise ValueError("an STL file has no per-vertex data: vertex values need the format 'ply'")
+    return write_ply(path, vertices, triangles, ids, vertex_values)

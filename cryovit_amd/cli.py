@@ -14,6 +14,7 @@
     <measurements>: [--close-radius R] [--fill-holes 3d|slices] [--open-radius R]
                     [--min-size N] [--connectivity 6|26] [--split-radius R [--split-min-core N]] [--morphology] [--shape]
                     [--skeleton [--skeleton-end-radius R]] [--thickness] [--mesh [--mesh-smooth N] [--mesh-format ply|stl]]
+                    [--curvature [--curvature-radius R]]
 
 ``train`` fits the CryoVIT head on the GPU (HIP backward, fused AdamW; ``run/train_model.py``) and writes the ``.model`` file that
 ``infer`` and ``evaluate`` load; UNet3D and SAM2 training are not built.  Extra options, marked "build extension",
@@ -22,7 +23,8 @@ replace the network fetch of the encoder weights or add what the reference leave
 measures them.  The measurement options are declared once, below, for both commands; each is a field of
 ``analysis.instances.InstanceOptions``, which says what it computes and writes.  ``--close-radius``, ``--fill-holes`` and
 ``--open-radius`` clean the mask on the GPU before it is labelled, in that order (``analysis.cleanup.CleanupOptions``): the file gains
-``<label>_cleaned`` and the CSV ``added_voxels``.  ``--distance-to NAME`` adds the gap to another
+``<label>_cleaned`` and the CSV ``added_voxels``.  ``--curvature`` maps the mean curvature of the membrane at the scale
+``--curvature-radius`` (``analysis.curvature.CurvatureOptions``).  ``--distance-to NAME`` adds the gap to another
 label's mask and the voxels in contact with it; ``--contacts-with NAME`` says which instance touches which: every instance gains
 ``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance, nearest instance of NAME within
 ``--contact-radius``) the voxels in contact, the narrowest gap and where it is.
@@ -128,6 +130,15 @@ _BOUNDARY_HELP = ("score the predicted boundary against the annotated one on the
 _BOUNDARY_MODE_HELP = ("with --boundary: slices = every fully annotated z-slice scored as an image of its own (sparse CryoVIT labels), "
                        "3d = the whole volume, which must hold no ignored (-1) voxel")
 _BOUNDARY_TOLERANCE_HELP = "with --boundary: a tolerance of the surface Dice, column nsd_<T>; repeatable (voxels, >= 0)"
+_CURVATURE_HELP = ("map the mean curvature of the membrane on the GPU (ball-volume integral invariant: the share of a ball centred "
+                   "on the surface that lies inside the object; exact integer arithmetic): write it as <label>_curvature (1/voxel, NaN "
+                   "off the surface) and add curvature_mean, curvature_std, curvature_min, curvature_max, convex_fraction, "
+                   "curvature_voxels and curvature_unscored as the last CSV columns; with --mesh the PLY gains a curvature per vertex "
+                   "(not with --mesh-format stl).  Positive is convex, negative concave (a cavity wall, an invagination); surface "
+                   "voxels within the ball radius + 1 of the volume's border are not scored; touching pieces after --split-radius are "
+                   "scored as their union (with infer: needs --instances)")
+_CURVATURE_RADIUS_HELP = ("with --curvature, the radius of the ball: the scale at which the surface is read.  Larger is quieter (the "
+                          "per-voxel noise falls with 1/R^2) and blurs features smaller than R (voxels, an integer in 2..16)")
 _EXT = "build extension: "
 
 MinSize = Annotated[int, Option(min=0, help=_EXT + _MIN_SIZE_HELP)]
@@ -149,9 +160,20 @@ CloseRadius = Annotated[Optional[float], Option(callback=_non_negative("close ra
 FillHoles = Annotated[Optional[str], Option(callback=_checked(lambda v: v in ("3d", "slices"), "fill holes must be 3d or slices"),
                                             help=_EXT + _FILL_HOLES_HELP)]
 OpenRadius = Annotated[Optional[float], Option(callback=_non_negative("open radius"), help=_EXT + _OPEN_RADIUS_HELP)]
+Curvature = Annotated[bool, Option("--curvature", help=_EXT + _CURVATURE_HELP)]
+CurvatureRadius = Annotated[int, Option("--curvature-radius", callback=_checked(lambda v: 2 <= v <= 16, "curvature radius must lie in 2..16 (voxels)"),
+                                        help=_EXT + _CURVATURE_RADIUS_HELP)]
 
 # infer measures nothing without --instances: asking for one of these without it is a usage error
-_NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh", "close_radius", "fill_holes", "open_radius")
+_NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh", "close_radius", "fill_holes", "open_radius",
+                    "curvature")
+
+
+def _refuse_stl_curvature(curvature: bool, mesh: bool, mesh_format: str) -> None:
+    """A usage error for --curvature with an STL mesh: the format has no per-vertex data to hold the values."""
+    if curvature and mesh and mesh_format == "stl":
+        raise typer.BadParameter("--curvature colours the mesh per vertex, which an STL file cannot hold: use --mesh-format ply",
+                                 param_hint="--mesh-format")
 
 
 def _encoder_overrides(encoder: Optional[str], checkpoint: Optional[str], synthetic_seed: Optional[int]) -> dict:
@@ -266,12 +288,16 @@ def infer(
     close_radius: CloseRadius = None,
     fill_holes: FillHoles = None,
     open_radius: OpenRadius = None,
+    curvature: Curvature = False,
+    curvature_radius: CurvatureRadius = 5,
 ):
     """Segment tomograms using a pre-trained model."""
     measurements = dict(min_size=min_size, connectivity=connectivity, morphology=morphology, split_radius=split_radius,
                         split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
                         thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format,
-                        close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius)
+                        close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius,
+                        curvature=curvature, curvature_radius=curvature_radius)
+    _refuse_stl_curvature(curvature, mesh, mesh_format)
     for name in _NEEDS_INSTANCES:
         value = measurements[name]  # a flag that is off is False, a radius that is not given None; a radius of 0 is given
         if not instances and value is not False and value is not None:
@@ -315,8 +341,11 @@ def instances_cmd(
     close_radius: CloseRadius = None,
     fill_holes: FillHoles = None,
     open_radius: OpenRadius = None,
+    curvature: Curvature = False,
+    curvature_radius: CurvatureRadius = 5,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
+    _refuse_stl_curvature(curvature, mesh, mesh_format)
     from cryovit_amd.analysis.instances import label_file
     from cryovit_amd.utils import load_files_from_path
 
@@ -329,7 +358,8 @@ def instances_cmd(
                          split_radius=split_radius, split_min_core=split_min_core, contacts_with=contacts_with, shape=shape,
                          skeleton=skeleton, skeleton_end_radius=skeleton_end_radius, thickness=thickness,
                          mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format,
-                         close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius)
+                         close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius,
+                         curvature=curvature, curvature_radius=curvature_radius)
         logging.info("Labelled %s", out)
 
 

@@ -1,7 +1,7 @@
 // Pieces shared by the passes over an int32 [D][H][W] volume that build a per-instance table.  For the passes that walk it in
 // 16-voxel row pieces (components.hip, split.hip, cleanup.hip, the reductions of edt.hip and nearest.hip): the piece a thread owns, its 16-B
 // loads / stores, the kernel that fills a component table with the empty box, and the integer add / min / max into a table row.
-// For the passes that walk it in 4x8x64 tiles (shape.hip, skeleton.hip, thickness.hip, mesh.hip, cleanup.hip): a tile's ids with their
+// For the passes that walk it in 4x8x64 tiles (shape.hip, skeleton.hip, thickness.hip, mesh.hip, cleanup.hip, curvature.hip): a tile's ids with their
 // one-voxel halo in LDS, and the stages of the per-id reduction: a thread's sums to a table row (table_flush), the wave's
 // single-id test (wave_single_id), the first wave of a workgroup that holds an id (first_wave_of_id).  And the sums and the scan
 // over the lanes of a wave.  Device code only; every includer compiles its own copy.

@@ -1405,6 +1405,53 @@ def mesh_smooth(vertices: torch.Tensor, triangles: torch.Tensor, iterations: int
     return out
 
 
+# ---- membrane curvature (`--curvature`): the ball-volume integral invariant on the surface, and the per-instance table over it ----
+
+def _curvature_radius(what: str, radius) -> int:
+    if int(radius) != radius or not _lib.CURVATURE_RADIUS_MIN <= radius <= _lib.CURVATURE_RADIUS_MAX:
+        raise _lib.CvxError(f"{what}: radius must be an integer in [{_lib.CURVATURE_RADIUS_MIN}, {_lib.CURVATURE_RADIUS_MAX}], got {radius}")
+    return int(radius)
+
+
+def curvature_map(labels: torch.Tensor, radius: int) -> torch.Tensor:
+    """int32 [D, H, W]: h, the mean curvature of the surface of ``labels > 0`` (int32 [D, H, W]) in units of 1/4096 per voxel, from
+    the foreground count under the ball of ``radius`` (2..16) voxels at every scored surface voxel and at its background face
+    neighbours (the definition is in include/cryovit_hip.h); ``_lib.CURV_NONE`` everywhere else.  Positive is convex.  Ids play no
+    part.  Integers only, no atomics, bit-reproducible (csrc/curvature.hip); one bit of workspace per voxel for the duration of the
+    call; the host does not wait."""
+    dev, D, H, W = _volumes_check("curvature_map", labels=(labels, torch.int32))
+    radius = _curvature_radius("curvature_map", radius)
+    lib = _lib.load()
+    h = torch.empty((D, H, W), dtype=torch.int32, device=dev)
+    workspace = torch.empty(max(int(lib.cvx_curvature_workspace_bytes(D, H, W)), 8) // 8, dtype=torch.int64, device=dev)
+    call(dev, "cvx_curvature_map", lib.cvx_curvature_map, _p(labels), D, H, W, radius, _p(h), _p(workspace), workspace.numel() * 8)
+    return h
+
+
+def curvature_stats(labels: torch.Tensor, h: torch.Tensor, k: int) -> torch.Tensor:
+    """int64 [k, 7] on the device.  Row id - 1 over the voxels of ``labels`` (int32 [D, H, W]) with that id in 1..k: the scored
+    voxels (``h``, of ``curvature_map``, is not ``_lib.CURV_NONE``); the sum of h; the sum of h^2; min h; max h (both 0 without a
+    scored voxel); the scored voxels with h > 0; the surface voxels of ``labels > 0`` without a score.  Ids past k are ignored.
+    Integers only, bit-reproducible; the host does not wait."""
+    dev, D, H, W = _volumes_check("curvature_stats", labels=(labels, torch.int32), h=(h, torch.int32))
+    if k < 0:
+        raise _lib.CvxError(f"curvature_stats: k must be >= 0, got {k}")
+    out = torch.empty((int(k), _lib.CURVATURE_COLS), dtype=torch.int64, device=dev)
+    call(dev, "cvx_curvature_stats", _lib.load().cvx_curvature_stats, _p(labels), _p(h), D, H, W, int(k), _p(out))
+    return out
+
+
+def instance_curvature(labels: torch.Tensor, k: int, radius: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(h int32 [D, H, W], table int64 [k, 7]) of the instances 1..k of ``labels`` (int32 [D, H, W]): ``curvature_map`` at ``radius``
+    and ``curvature_stats`` over it.  Ids play no part in the map: pieces that share a face are scored as their union, and the
+    plane between them is no surface."""
+    _volumes_check("instance_curvature", labels=(labels, torch.int32))
+    if k < 0:
+        raise _lib.CvxError(f"instance_curvature: k must be >= 0, got {k}")
+    h = curvature_map(labels, radius)
+    return h, curvature_stats(labels, h, k)
+
+
 # ---- a prediction scored at its boundary (`cryovit evaluate --boundary`): scored slices, surfaces, distance histograms ----
 
 HIST_BINS_MAX = 2**24 + 1  # of surface_distance_hist

@@ -21,6 +21,8 @@ unfiltered threshold mask.  ``morphology``, ``split_radius``, ``shape``, ``skele
 runs on a written file (``analysis.instances.label_and_split`` / ``measure``, ``writers.write_measured`` on the writer thread).
 ``close_radius``, ``fill_holes`` and ``open_radius`` (with ``instances``) are the fields of ``analysis.cleanup.CleanupOptions``: the
 mask is cleaned in HBM before it is labelled, each file also holds ``<label_key>_cleaned`` and the table gains ``added_voxels``.
+``curvature`` and ``curvature_radius`` (with ``instances``) are the fields of ``analysis.curvature.CurvatureOptions``: the membrane
+curvature is measured last, each file also holds ``<label_key>_curvature`` and the table gains its columns after every other.
 """
 
 from __future__ import annotations
@@ -34,6 +36,7 @@ import torch
 
 from cryovit_amd import io
 from cryovit_amd.analysis.cleanup import CleanupOptions, added_rows, added_voxels, clean_mask, log_totals
+from cryovit_amd.analysis.curvature import CurvatureOptions, check_mesh_format
 from cryovit_amd.analysis.instances import InstanceOptions, label_and_split, measure
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
@@ -96,12 +99,15 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                   split_min_core: int = 0, shape: bool = False, skeleton: bool = False,
                   skeleton_end_radius: float = 2.0, thickness: bool = False, mesh: bool = False, mesh_smooth: int = 0,
                   mesh_format: str = "ply", close_radius: float | None = None, fill_holes: str | None = None,
-                  open_radius: float | None = None) -> list[Path]:
+                  open_radius: float | None = None, curvature: bool = False, curvature_radius: int = 5) -> list[Path]:
     opts = InstanceOptions(connectivity=connectivity, min_size=min_size, morphology=morphology, split_radius=split_radius,
                            split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
                            thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
     cleanup = CleanupOptions(close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius)
+    curve = CurvatureOptions(curvature=curvature, curvature_radius=curvature_radius)
     if not instances:
+        if curvature:
+            raise ValueError("curvature=True needs instances=True: it is measured on the labelled instances")
         for name in InstanceOptions.MEASUREMENTS:
             if getattr(opts, name):
                 raise ValueError(f"{name}=True needs instances=True: it is measured on the labelled instances")
@@ -112,6 +118,8 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 raise ValueError(f"{name} needs instances=True: it cleans the mask that is labelled")
     opts.validate()
     cleanup.validate()
+    curve.validate()
+    check_mesh_format(curvature, mesh, mesh_format)
     rank, _, world = world_info()
     device = select_device(device)
     model, model_type, model_name, label_key = load_model(model_path, device=device)
@@ -142,7 +150,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 labels, table, component = label_and_split(cleaned, opts)
                 host_labels = _pinned(labels)  # on its way while the instances are measured
                 host_table = table.cpu().numpy()
-                found = measure(labels, int(table.shape[0]), component, opts)
+                found = measure(labels, int(table.shape[0]), component, opts, curvature=curve)
                 if cleanup.any:
                     host_cleaned = _pinned(cleaned)
                     found.extra = added_rows(added_voxels(labels, predicted, int(table.shape[0])), found.extra)

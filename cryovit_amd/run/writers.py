@@ -7,7 +7,8 @@
                          at <results_dir>/<tomo stem>.hdf
   write_instances        (not in the reference) the prediction file with ``<label>_instances`` added (uint16 up to 65535
                          instances, int32 beyond; gzip), with a skeleton also ``<label>_skeleton`` (int32 ids; gzip), with a
-                         thickness map also ``<label>_thickness`` (float32, voxels; gzip), and
+                         thickness map also ``<label>_thickness`` (float32, voxels; gzip), with a curvature map also
+                         ``<label>_curvature`` (float32, 1/voxel, NaN off the scored surface; gzip), and
                          <results_dir>/instances/<tomo stem>_<label>.csv, one row per instance
   write_measured         (not in the reference) write_mesh and write_instances of one ``analysis.instances.measure`` result
   write_mesh             (not in the reference) <results_dir>/meshes/<tomo stem>_<label>.ply or .stl, the surface of the labelled mask
@@ -29,6 +30,7 @@ import numpy as np
 from cryovit_amd import io
 from cryovit_amd.analysis.distances import PAIR_COLUMNS
 from cryovit_amd.analysis.instances import INSTANCE_COLUMNS, instance_rows, merge_columns
+from cryovit_amd.analysis.curvature import curvature_map
 from cryovit_amd.analysis.thickness import thickness_map
 
 
@@ -70,7 +72,8 @@ def _write_rows(path: Path, columns: list[str], rows: list[dict]) -> None:
 
 
 def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[str, np.ndarray], labels: np.ndarray,
-                    rows: list[dict], skeleton: np.ndarray | None = None, thickness: np.ndarray | None = None) -> Path:
+                    rows: list[dict], skeleton: np.ndarray | None = None, thickness: np.ndarray | None = None,
+                    curvature: np.ndarray | None = None) -> Path:
     """The prediction file <results_dir>/<tomo stem>.hdf with every array of ``datasets`` (``data``, ``<label>_preds``, ...:
     gzip, dtypes as given) and ``<label>_instances`` = ``labels`` (uint16 while the largest id fits, else int32: a 128x512x512
     int32 volume would make the gzip of the writer thread the slowest stage of ``infer``), and the CSV
@@ -79,7 +82,8 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
     the rows' own order).  ``skeleton`` (the instances' centrelines, every voxel with its instance's id) is written as
     ``<label>_skeleton`` in int32 beside ``<label>_instances``: it is nearly all zeros and gzips to little.  ``thickness``
     (``analysis.thickness.thickness_map``: the local thickness in voxels, 0 on the background, inf without any background) is written
-    as ``<label>_thickness`` in float32 after them.  The file is written beside its final name and moved there, so re-writing a file from its own
+    as ``<label>_thickness`` in float32 after them, and ``curvature`` (``analysis.curvature.curvature_map``: the mean curvature in
+    1/voxel at the scored surface voxels, NaN elsewhere) as ``<label>_curvature`` in float32 after that.  The file is written beside its final name and moved there, so re-writing a file from its own
     datasets cannot leave it half written.  Returns the .hdf path."""
     results_dir = Path(results_dir)
     out = (results_dir / tomo_name).with_suffix(".hdf")
@@ -94,6 +98,8 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
             fh.create_dataset(f"{label_key}_skeleton", skeleton.astype(np.int32, copy=False), compression="gzip")
         if thickness is not None:
             fh.create_dataset(f"{label_key}_thickness", thickness.astype(np.float32, copy=False), compression="gzip")
+        if curvature is not None:
+            fh.create_dataset(f"{label_key}_curvature", curvature.astype(np.float32, copy=False), compression="gzip")
     os.replace(tmp, out)
     extras = [k for k in (rows[0] if rows else ()) if k not in INSTANCE_COLUMNS]  # every row carries the same keys
     _write_rows(results_dir / "instances" / f"{out.stem}_{label_key}.csv", INSTANCE_COLUMNS + extras, rows)
@@ -105,23 +111,26 @@ def write_measured(results_dir, tomo_name: str, label_key: str, datasets: dict[s
     """Everything one file gets from ``analysis.instances.measure``, for ``label_file`` and for the writer thread of ``infer``:
     ``write_mesh`` where ``measured`` (an ``analysis.instances.Measured`` of host arrays) holds a mesh, and ``write_instances`` of the
     rows of the host ``table`` with the columns of ``measured.extra`` after them, the skeleton and the thickness map (the root of
-    ``measured.t2`` is taken here, off the thread that feeds the GPU).  Returns the .hdf path."""
+    ``measured.t2`` is taken here, off the thread that feeds the GPU) and the curvature map (``measured.curvature`` becomes the
+    float volume here as well; ``measured.vertex_curvature`` goes into the PLY).  Returns the .hdf path."""
     if measured.mesh is not None:
-        write_mesh(results_dir, tomo_name, label_key, *measured.mesh, mesh_format)
+        write_mesh(results_dir, tomo_name, label_key, *measured.mesh, mesh_format, vertex_values=measured.vertex_curvature)
     rows = instance_rows(table)
     merge_columns(rows, measured.extra)
     return write_instances(results_dir, tomo_name, label_key, datasets, labels, rows, skeleton=measured.skeleton,
-                           thickness=None if measured.t2 is None else thickness_map(measured.t2))
+                           thickness=None if measured.t2 is None else thickness_map(measured.t2),
+                           curvature=None if measured.curvature is None else curvature_map(measured.curvature))
 
 
 def write_mesh(results_dir, tomo_name: str, label_key: str, vertices: np.ndarray, triangles: np.ndarray, ids: np.ndarray,
-               fmt: str = "ply") -> Path:
+               fmt: str = "ply", vertex_values: np.ndarray | None = None) -> Path:
     """The surface mesh <results_dir>/meshes/<tomo stem>_<label>.<fmt> (``analysis.mesh.write_ply`` / ``write_stl``: binary PLY with
     shared vertices and an ``instance`` per face, or binary STL with the id in the attribute word) of the arrays of
-    ``engine.ops.mesh_surface`` on the host.  Written beside its final name and moved there.  Returns its path."""
+    ``engine.ops.mesh_surface`` on the host; ``vertex_values`` (PLY only): ``property float curvature`` per vertex.  Written beside
+    its final name and moved there.  Returns its path."""
     from cryovit_amd.analysis.mesh import write_mesh as write
 
-    return write(Path(results_dir) / "meshes" / f"{Path(tomo_name).stem}_{label_key}.{fmt}", vertices, triangles, ids, fmt)
+    return write(Path(results_dir) / "meshes" / f"{Path(tomo_name).stem}_{label_key}.{fmt}", vertices, triangles, ids, fmt, vertex_values)
 
 
 def write_contacts(results_dir, tomo_name: str, label_key: str, other_name: str, rows: list[dict]) -> Path:

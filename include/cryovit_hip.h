@@ -881,6 +881,43 @@ int cvx_slice_valid(const int8_t* y, int D, int H, int W, int32_t* valid, hipStr
 int cvx_surface_mask(const uint8_t* mask, const int32_t* valid, int D, int H, int W, int slices, uint8_t* out, hipStream_t stream);
 int cvx_surface_distance_hist(const uint8_t* surf, const int32_t* d2, long n, long bins, int64_t* hist, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Membrane curvature (`infer --instances --curvature`, `cryovit instances --curvature`): the mean curvature H of the surface of
+ * labels > 0 by the ball-volume integral invariant, and the per-instance table over it.  The fraction of a ball of radius r,
+ * centred on the surface, that lies inside the object is 1/2 - (3/16) r H (exact for a sphere).  Integers only, no float atomics,
+ * bit-reproducible.
+ *
+ * labels int32 [D][H][W], F = labels > 0 (ids play no part in the map: pieces that share a face are scored as their union);
+ * radius r, CVX_CURVATURE_RADIUS_MIN <= r <= CVX_CURVATURE_RADIUS_MAX.  B = {o in Z^3 : |o|^2 <= r^2}, N = |B|,
+ * n(v) = #{o in B : v + o in F}.
+ *   Surface voxel  p in F with at least one face neighbour that is inside the volume and not in F; Q(p) = those neighbours, m = |Q(p)|.
+ *   Scored voxel   a surface voxel with r + 1 <= index <= extent - r - 2 on every axis: no ball at p or at a q of Q(p) is clipped.
+ *                  A volume with an extent below 2 r + 3 has none.
+ *   h[p]           floor(32768 (m N - m n(p) - S) / (3 r m N)), S = the sum of n(q) over Q(p), in int64 and rounded towards minus
+ *                  infinity: H in units of 1/4096 per voxel, |h| <= 5462.  Positive = convex (a ball), negative = concave (a cavity
+ *                  wall).  Pairing p with its outside neighbours cancels the half-voxel offset of the ball's centre: on an
+ *                  axis-aligned face n(p) + n(q) = N and h = 0.  Every other voxel of h is CVX_CURV_NONE.
+ *   cvx_curvature_workspace_bytes  8 bytes per 64 voxels of a row (the foreground as bits); < 0 on bad extents.
+ *   cvx_curvature_map              h int32 [D][H][W], every voxel written; workspace: that many bytes, 8-byte aligned; its contents
+ *                                  after the call mean nothing.
+ *   cvx_curvature_stats            table int64 [k][CVX_CURVATURE_COLS], initialised by the call.  Row id - 1 over the voxels with
+ *                                  that id in 1..k: 0 scored voxels (h != CVX_CURV_NONE); 1 the sum of h; 2 the sum of h^2; 3 min h;
+ *                                  4 max h (both 0 without a scored voxel); 5 scored voxels with h > 0; 6 surface voxels (of
+ *                                  labels > 0, as above) whose h is CVX_CURV_NONE.
+ * Refused with an error before any launch: negative extents, an extent above 32768, D*H*W > CVX_COMPONENT_MAX_VOXELS, a radius
+ * outside [2, 16], k < 0, k rows that cannot be addressed, null pointers, misaligned arrays (int32: 4 bytes, workspace and table:
+ * 8 bytes), a workspace shorter than cvx_curvature_workspace_bytes, labels == h.  k == 0 and an empty volume succeed and launch
+ * nothing; a volume too small for a scored voxel gets CVX_CURV_NONE throughout.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_CURVATURE_COLS 7
+#define CVX_CURVATURE_RADIUS_MIN 2
+#define CVX_CURVATURE_RADIUS_MAX 16
+#define CVX_CURV_NONE INT32_MIN
+long cvx_curvature_workspace_bytes(int D, int H, int W);
+int cvx_curvature_map(const int32_t* labels, int D, int H, int W, int radius, int32_t* h, void* workspace, long workspace_bytes,
+                      hipStream_t stream);
+int cvx_curvature_stats(const int32_t* labels, const int32_t* h, int D, int H, int W, long k, int64_t* table, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
