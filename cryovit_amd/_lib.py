@@ -205,6 +205,7 @@ SIGNATURES = {
     "cvx_instance_pair_contacts": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p,
                                            c_void_p]),
     "cvx_instance_pair_rows": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p]),
+    "cvx_overlap_instances": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
     "cvx_split_core_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_split_init": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_void_p, c_void_p, c_void_p]),
     "cvx_split_rounds": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

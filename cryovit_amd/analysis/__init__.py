@@ -4,7 +4,8 @@ which of another, the shape of each instance (surface area, Euler number, princi
 its local thickness (mean, spread, min, max), the surface mesh of the mask (PLY / STL; triangles, area, volume) and the mean
 curvature of its membrane (ball-volume integral invariant; mean, spread, min, max, convex share); the
 clean-up of the mask before all of that (close, fill holes, open); and, against annotated labels, how far the predicted boundary
-lies from the true one (HD95, surface distance, surface Dice)."""
+lies from the true one (HD95, surface distance, surface Dice) and how well the annotated objects are recovered one by one (detection
+F1, panoptic quality, Rand index, split / merge variation of information)."""
 
 from cryovit_amd.analysis.instances import (  # noqa: F401
     INSTANCE_COLUMNS, InstanceOptions, instance_rows, label_and_split, label_file, label_volume, measure, split_volume)
@@ -20,3 +21,7 @@ from cryovit_amd.analysis.curvature import (  # noqa: F401
 from cryovit_amd.analysis.boundary import (  # noqa: F401
     BOUNDARY_COUNT_COLUMNS, BOUNDARY_DISTANCE_COLUMNS, BOUNDARY_MODES, boundary_columns, boundary_histograms, boundary_scores, check_scored,
     nsd_column)
+# (the function instance_scores stays in its module: here the name is the module analysis.instance_scores)
+from cryovit_amd.analysis.instance_scores import (  # noqa: F401
+    INSTANCE_LIST_COLUMNS, INSTANCE_MODES, OverlapTables, check_instance_options, f1_column, instance_columns, instance_list_rows,
+    instance_overlap_tables)

@@ -8,6 +8,8 @@
                                     [--instances <measurements>]
     python -m cryovit_amd.cli evaluate <test-data> <test-labels> x.model --labels A [--labels B ...] [--result-folder DIR] [-v]
                                        [--boundary [--boundary-mode slices|3d] [--boundary-tolerance T ...]]
+                                       [--instance-metrics [--instance-mode slices|3d] [--instance-connectivity 6|26]
+                                                           [--instance-min-size N] [--instance-iou T ...]]
     python -m cryovit_amd.cli instances <predictions> --label NAME [--result-folder DIR] <measurements>
                                         [--distance-to NAME] [--contacts-with NAME] [--distance-to-folder DIR] [--contact-radius R]
 
@@ -130,6 +132,19 @@ _BOUNDARY_HELP = ("score the predicted boundary against the annotated one on the
 _BOUNDARY_MODE_HELP = ("with --boundary: slices = every fully annotated z-slice scored as an image of its own (sparse CryoVIT labels), "
                        "3d = the whole volume, which must hold no ignored (-1) voxel")
 _BOUNDARY_TOLERANCE_HELP = "with --boundary: a tolerance of the surface Dice, column nsd_<T>; repeatable (voxels, >= 0)"
+_INSTANCE_METRICS_HELP = ("score the prediction object by object on the GPU: the connected instances of the predicted mask against those "
+                          "of the annotation.  After the model's metrics (and the boundary columns) every CSV row gains inst_f1_<T> "
+                          "(detection F1, a pair matched iff IoU > T, per --instance-iou), at IoU > 0.5 inst_tp, inst_precision, "
+                          "inst_recall, inst_sq (mean IoU of the matches) and inst_pq (panoptic quality), over the annotated voxels "
+                          "inst_ari (adjusted Rand index), inst_vi_split and inst_vi_merge (variation of information, bits), and the "
+                          "counts inst_pred, inst_true, inst_merged_true, inst_split_true; results/<name>/instances/<sample>_<tomo>.csv "
+                          "lists every annotated instance with its best predicted partner, then the unmatched predicted ones")
+_INSTANCE_MODE_HELP = ("with --instance-metrics: slices = every fully annotated z-slice an image of its own, its instances the "
+                       "components in the plane (sparse CryoVIT labels), 3d = the components of the whole volume, which must hold no "
+                       "ignored (-1) voxel; with --boundary it must agree with --boundary-mode")
+_INSTANCE_CONNECTIVITY_HELP = "with --instance-metrics: 6 (faces; 4 in a slice) or 26 (faces, edges and corners; 8 in a slice)"
+_INSTANCE_MIN_SIZE_HELP = "with --instance-metrics: instances of fewer voxels are background, predicted and annotated alike"
+_INSTANCE_IOU_HELP = "with --instance-metrics: an IoU threshold of the detection F1, column inst_f1_<T>; repeatable (in [0.5, 1))"
 _CURVATURE_HELP = ("map the mean curvature of the membrane on the GPU (ball-volume integral invariant: the share of a ball centred "
                    "on the surface that lies inside the object; exact integer arithmetic): write it as <label>_curvature (1/voxel, NaN "
                    "off the surface) and add curvature_mean, curvature_std, curvature_min, curvature_max, convex_fraction, "
@@ -381,8 +396,24 @@ def evaluate(
     boundary_tolerance: Annotated[Optional[list[float]], Option("--boundary-tolerance", callback=_each(_non_negative("boundary tolerance")),
                                                                 help=_EXT + _BOUNDARY_TOLERANCE_HELP,
                                                                 show_default="1 and 2")] = None,
+    instance_metrics: Annotated[bool, Option("--instance-metrics", help=_EXT + _INSTANCE_METRICS_HELP)] = False,
+    instance_mode: Annotated[Optional[str], Option("--instance-mode", callback=_checked(lambda v: v in ("slices", "3d"), "instance mode must be slices or 3d"),
+                                                   help=_EXT + _INSTANCE_MODE_HELP, show_default="slices; with --boundary, --boundary-mode")] = None,
+    instance_connectivity: Annotated[int, Option("--instance-connectivity", callback=_checked(lambda v: v in (6, 26), "instance connectivity must be 6 or 26"),
+                                                 help=_EXT + _INSTANCE_CONNECTIVITY_HELP)] = 26,
+    instance_min_size: Annotated[int, Option("--instance-min-size", callback=_checked(lambda v: v >= 0, "instance min size must be >= 0"),
+                                             help=_EXT + _INSTANCE_MIN_SIZE_HELP)] = 0,
+    instance_iou: Annotated[Optional[list[float]], Option("--instance-iou", callback=_each(_checked(lambda v: 0.5 <= v < 1.0, "an instance IoU threshold must lie in [0.5, 1)")),
+                                                          help=_EXT + _INSTANCE_IOU_HELP, show_default="0.5 and 0.75")] = None,
 ):
     """Evaluate a pre-trained model on a test dataset."""
+    instance_iou = tuple(instance_iou) if instance_iou else (0.5, 0.75)
+    if len({f"{t:g}" for t in instance_iou}) != len(instance_iou):
+        raise typer.BadParameter(f"the thresholds {list(instance_iou)} give the same column twice", param_hint="--instance-iou")
+    if instance_metrics and boundary and instance_mode is not None and instance_mode != boundary_mode:
+        raise typer.BadParameter(f"--instance-mode {instance_mode} and --boundary-mode {boundary_mode} would score different regions: give one, or "
+                                 "the same value to both", param_hint="--instance-mode")
+
     from cryovit_amd.run.eval_model import run_evaluation
     from cryovit_amd.utils import load_files_from_path, load_model
 
@@ -397,7 +428,9 @@ def evaluate(
     result_path.mkdir(parents=True, exist_ok=True)
     run_evaluation(load_files_from_path(test_path), load_files_from_path(label_path), labels, model_path, result_path,
                    visualize=visualize, encoder=_load_encoder(encoder, checkpoint, synthetic_seed), boundary=boundary,
-                   boundary_mode=boundary_mode, boundary_tolerances=tuple(boundary_tolerance) if boundary_tolerance else (1.0, 2.0))
+                   boundary_mode=boundary_mode, boundary_tolerances=tuple(boundary_tolerance) if boundary_tolerance else (1.0, 2.0),
+                   instance_metrics=instance_metrics, instance_mode=instance_mode, instance_connectivity=instance_connectivity,
+                   instance_min_size=instance_min_size, instance_iou=instance_iou)
 
 
 if __name__ == "__main__":

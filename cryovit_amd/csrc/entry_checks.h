@@ -1,4 +1,4 @@
-// What the entry points of the analysis passes (components, edt, nearest, split, shape, skeleton, thickness, mesh, cleanup, curvature) check and
+// What the entry points of the analysis passes (components, edt, nearest, overlap, split, shape, skeleton, thickness, mesh, cleanup, curvature) check and
 // compute on the host before they launch: the extents of the volume, the clamp of an id count, the block and tile counts of a
 // launch, whether k table rows can be addressed.  Refusals go through cvx_fail(entry, why) of host_util.h.
 #pragma once

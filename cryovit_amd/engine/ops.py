@@ -1150,25 +1150,48 @@ def instance_pair_contacts(labels_a: torch.Tensor, ka: int, nearest_b: torch.Ten
         raise _lib.CvxError(f"instance_pair_contacts: ka must be >= 0, got {ka}")
     if threshold_d2 < 0:
         raise _lib.CvxError(f"instance_pair_contacts: threshold_d2 must be >= 0, got {threshold_d2}")
+    return _pair_table_rows("instance_pair_contacts", dev, capacity, lambda lib, table, cap, status: call(
+        dev, "cvx_instance_pair_contacts", lib.cvx_instance_pair_contacts, _p(labels_a), int(ka), _p(nearest_b), _p(d2_b),
+        min(int(threshold_d2), _lib.EDT_NONE - 1), D, H, W, _p(table), cap, _p(status)))  # no distance is larger than EDT_NONE - 1
+
+
+def _pair_table_rows(what: str, dev: torch.device, capacity: int | None, fill) -> torch.Tensor:
+    """int64 [P, 5] on the device, sorted by (a, b): the rows of the pair table that ``fill(lib, table, cap, status)`` fills
+    (csrc/pair_table.h).  The table starts at ``capacity`` slots (rounded up to a power of two; default ``PAIR_CAPACITY``) and
+    doubles and starts over while a pair finds no slot.  The host waits once per table, for the overflow flag and P."""
     if capacity is not None and not 1 <= capacity <= _lib.PAIR_MAX_CAPACITY:
-        raise _lib.CvxError(f"instance_pair_contacts: capacity must lie in 1..2^31, got {capacity}")
+        raise _lib.CvxError(f"{what}: capacity must lie in 1..2^31, got {capacity}")
     lib = _lib.load()
     cap = 1 << (int(capacity if capacity is not None else PAIR_CAPACITY) - 1).bit_length()
     status = torch.empty(2, dtype=torch.int64, device=dev)
     while True:
         table = torch.empty((3, cap), dtype=torch.int64, device=dev)
-        call(dev, "cvx_instance_pair_contacts", lib.cvx_instance_pair_contacts, _p(labels_a), int(ka), _p(nearest_b), _p(d2_b),
-             min(int(threshold_d2), _lib.EDT_NONE - 1), D, H, W, _p(table), cap, _p(status))  # no distance is larger than EDT_NONE - 1
+        fill(lib, table, cap, status)
         overflow, p = status.tolist()  # the wait
         if not overflow:
             break
         if cap >= _lib.PAIR_MAX_CAPACITY:  # at most 31 doublings; more slots than voxels cannot overflow
-            raise _lib.CvxError(f"instance_pair_contacts: the pair table overflowed at {cap} slots")
+            raise _lib.CvxError(f"{what}: the pair table overflowed at {cap} slots")
         cap *= 2
     rows = torch.empty((p, _lib.PAIR_COLS), dtype=torch.int64, device=dev)
     order = torch.sort(table[0]).indices  # the keys a << 32 | b are distinct; empty slots hold INT64_MAX and sort last
     call(dev, "cvx_instance_pair_rows", lib.cvx_instance_pair_rows, _p(table), cap, _p(order), p, _p(rows))
     return rows
+
+
+def instance_overlaps(labels_a: torch.Tensor, ka: int, labels_b: torch.Tensor, kb: int, capacity: int | None = None) -> torch.Tensor:
+    """int64 [P, 4] on the device, one row ``a, b, voxels, at`` per pair of an instance a of ``labels_a`` (int32 [D, H, W], ids
+    1..ka) and an instance b of ``labels_b`` (the same shape, ids 1..kb) that share a voxel: how many they share and the smallest
+    linear index of one.  Values outside 1..ka / 1..kb are nobody's.  Rows are sorted by (a, b).  The contingency table of two
+    segmentations (csrc/overlap.hip), collected in the pair table of ``instance_pair_contacts`` (``capacity`` as there); the rows
+    depend on neither that nor scheduling."""
+    dev, D, H, W = _volumes_check("instance_overlaps", labels_a=(labels_a, torch.int32), labels_b=(labels_b, torch.int32))
+    if ka < 0 or kb < 0:
+        raise _lib.CvxError(f"instance_overlaps: ka and kb must be >= 0, got {ka} and {kb}")
+    rows = _pair_table_rows("instance_overlaps", dev, capacity, lambda lib, table, cap, status: call(
+        dev, "cvx_overlap_instances", lib.cvx_overlap_instances, _p(labels_a), int(ka), _p(labels_b), int(kb), D, H, W, _p(table), cap,
+        _p(status)))
+    return rows[:, [0, 1, 2, 4]].contiguous()
 
 
 # ---- centreline skeletons of instances (`--skeleton`): thinning in the order of the distance map, and the table of the result ----

@@ -220,7 +220,7 @@ def boundary_threshold(metric_fns: dict) -> float:
 
 def _check_csv_columns(results_dir: Path, samples, columns: list[str]) -> None:
     """``update_metrics_csv`` rewrites ``<sample>.csv`` under the columns of the row it adds: earlier rows lose the columns the new
-    row lacks and read empty in the ones it brings.  With the boundary columns that would silently mix two kinds of rows, so a file
+    row lacks and read empty in the ones it brings.  With the boundary or the instance columns that would silently mix two kinds of rows, so a file
     written with other columns is refused before anything is computed."""
     import csv
 
@@ -237,7 +237,9 @@ def _check_csv_columns(results_dir: Path, samples, columns: list[str]) -> None:
 
 def run_evaluation(test_data: list[Path], test_labels: list[Path], labels: list[str], model_path: Path, result_dir: Path,
                    visualize: bool = True, *, encoder=None, batch_size: int = 128, device: str | None = None, boundary: bool = False,
-                   boundary_mode: str = "slices", boundary_tolerances: Sequence[float] = (1.0, 2.0)) -> Path:
+                   boundary_mode: str = "slices", boundary_tolerances: Sequence[float] = (1.0, 2.0), instance_metrics: bool = False,
+                   instance_mode: str | None = None, instance_connectivity: int = 26, instance_min_size: int = 0,
+                   instance_iou: Sequence[float] = (0.5, 0.75)) -> Path:
     """Score the ``.model`` at ``model_path`` on ``test_data`` / ``test_labels`` (paired in order; ``labels``: the label names in
     ascending value order).  Writes ``<result_dir>/results/<name>/<sample>.csv`` (CsvWriter) and, with ``visualize``,
     ``<result_dir>/predictions/<name>/<sample>/<file>`` (TestPredictionWriter).  Returns the directory holding the CSV files
@@ -247,10 +249,18 @@ def run_evaluation(test_data: list[Path], test_labels: list[Path], labels: list[
     ``boundary`` (extension): after the model's metrics every row gains the boundary columns of ``analysis.boundary``
     (``hd95``, ``hd``, ``assd``, one ``nsd_<t>`` per entry of ``boundary_tolerances``, the surface counts) of the mask ``probs >=
     boundary_threshold(model.metric_fns)`` against the decoded labels, per annotated z-slice (``boundary_mode="slices"``) or in 3-D
-    (``"3d"``).  A results CSV written earlier with other columns is refused."""
+    (``"3d"``).  ``instance_metrics`` (extension): after those every row gains the instance columns of ``analysis.instance_scores``
+    (``inst_f1_<T>`` per entry of ``instance_iou``, ``inst_tp`` .. ``inst_pq``, ``inst_ari``, ``inst_vi_split``, ``inst_vi_merge``, the
+    counts) of the instances of the same mask against those of the decoded labels, under ``instance_connectivity`` (6 or 26) with
+    instances below ``instance_min_size`` voxels dropped, per annotated z-slice or in 3-D (``instance_mode``; None: ``boundary_mode``
+    with ``boundary``, else ``"slices"``; with ``boundary`` the two must agree), and ``<results dir>/instances/<sample>_<tomo>.csv``
+    lists every annotated instance with its best predicted partner, then the unmatched predicted instances.  Bad options raise
+    ValueError before a file is read.  A results CSV written earlier with other columns is refused."""
     from cryovit_amd.analysis import boundary as bnd
+    from cryovit_amd.analysis import instance_scores as ins
     from cryovit_amd.datamodules import FileDataModule
     from cryovit_amd.run.infer_model import _has_key
+    from cryovit_amd.run.writers import write_instance_matches
     from cryovit_amd.types import BatchedModelResult
     from cryovit_amd.utils import load_model
 
@@ -262,6 +272,12 @@ def run_evaluation(test_data: list[Path], test_labels: list[Path], labels: list[
             bnd.contact_threshold(t)  # raises on a negative or NaN tolerance
         if len({bnd.nsd_column(t) for t in boundary_tolerances}) != len(boundary_tolerances):
             raise ValueError(f"boundary_tolerances {boundary_tolerances} give the same column twice")
+    if instance_metrics:
+        if instance_mode is None:
+            instance_mode = boundary_mode if boundary else "slices"
+        instance_iou = ins.check_instance_options(instance_iou, instance_connectivity, instance_min_size, instance_mode)
+        if boundary and instance_mode != boundary_mode:
+            raise ValueError(f"instance_mode {instance_mode!r} and boundary_mode {boundary_mode!r} would score different regions")
     rank, _, world = world_info()
     device = select_device(device)
     model, model_type, model_name, label_key = load_model(model_path, device=device)
@@ -283,9 +299,9 @@ def run_evaluation(test_data: list[Path], test_labels: list[Path], labels: list[
     file_cbs = [cb for k, cb in callbacks.items() if k != "csv_writer"]
     csv_cb = callbacks["csv_writer"]
     mine = shard_records(records, rank, world)
-    if boundary:
-        _check_csv_columns(csv_cb.results_dir, [fd.sample for fd in records],
-                           ["sample", "tomo_name", *model.metric_fns, *bnd.boundary_columns(boundary_tolerances)])
+    _check_csv_columns(csv_cb.results_dir, [fd.sample for fd in records],
+                       ["sample", "tomo_name", *model.metric_fns, *(bnd.boundary_columns(boundary_tolerances) if boundary else ()),
+                        *(ins.instance_columns(instance_iou) if instance_metrics else ())])
 
     def load(i):
         on_the_fly = encoder is not None and model.input_key == "dino_features" and not _has_key(records[i].tomo_path, "dino_features")
@@ -302,10 +318,15 @@ def run_evaluation(test_data: list[Path], test_labels: list[Path], labels: list[
             probs = _probabilities(model, batch, raw, encoder, batch_size)
             labels_dev = torch.from_numpy(raw_labels).to(probs.device)
             mode, value = label_plan(labels_dev, fd.label_path, list(labels), label_key)
-            metrics, y = score_labels(probs, labels_dev, mode, value, model.metric_fns, want_labels=bool(file_cbs) or boundary)
-            if boundary:
+            metrics, y = score_labels(probs, labels_dev, mode, value, model.metric_fns, want_labels=bool(file_cbs) or boundary or instance_metrics)
+            if boundary or instance_metrics:
                 pred_mask = (probs >= boundary_threshold(model.metric_fns)).to(torch.uint8).reshape(y.shape)
-                metrics.update(bnd.boundary_scores(*bnd.boundary_histograms(pred_mask, y, boundary_mode), boundary_tolerances))
+                if boundary:
+                    metrics.update(bnd.boundary_scores(*bnd.boundary_histograms(pred_mask, y, boundary_mode), boundary_tolerances))
+                if instance_metrics:
+                    found = ins.instance_overlap_tables(pred_mask, y, instance_mode, instance_connectivity, instance_min_size)
+                    metrics.update(ins.instance_scores(found.rows, found.size_p, found.size_t, instance_iou))
+                    write_instance_matches(csv_cb.results_dir, fd.sample, fd.tomo_path.name, ins.instance_list_rows(found))
                 del pred_mask
             out = BatchedModelResult(num_tomos=1, samples=[fd.sample], tomo_names=[fd.tomo_path.name], split_id=None, data=[aux],
                                      label=[y.cpu().numpy().astype(np.float32)] if file_cbs else [],

@@ -12,6 +12,8 @@
                          <results_dir>/instances/<tomo stem>_<label>.csv, one row per instance
   write_measured         (not in the reference) write_mesh and write_instances of one ``analysis.instances.measure`` result
   write_mesh             (not in the reference) <results_dir>/meshes/<tomo stem>_<label>.ply or .stl, the surface of the labelled mask
+  write_instance_matches (not in the reference) <results_dir>/instances/<sample>_<tomo stem>.csv of ``cryovit evaluate
+                        --instance-metrics``: every annotated instance with its best predicted partner, then the unmatched predicted ones
   write_contacts        (not in the reference) <results_dir>/contacts/<tomo stem>_<label>_<other>.csv, one row per pair of an
                          instance of <label> and an instance of <other> in contact
   update_metrics_csv     CsvWriter l.112-206:           <results_dir>/<sample>[_<split>].csv, columns sample, tomo_name,
@@ -138,6 +140,16 @@ def write_contacts(results_dir, tomo_name: str, label_key: str, other_name: str,
     ``PAIR_COLUMNS``; floats written with ``repr``; no pairs: header only).  Returns its path."""
     path = Path(results_dir) / "contacts" / f"{Path(tomo_name).stem}_{label_key}_{other_name}.csv"
     _write_rows(path, PAIR_COLUMNS, rows)
+    return path
+
+
+def write_instance_matches(results_dir, sample: str, tomo_name: str, rows: list[dict]) -> Path:
+    """The CSV <results_dir>/instances/<sample>_<tomo stem>.csv of ``rows`` (``analysis.instance_scores.instance_list_rows``:
+    columns ``INSTANCE_LIST_COLUMNS``; floats written with ``repr``; no instances: header only).  Returns its path."""
+    from cryovit_amd.analysis.instance_scores import INSTANCE_LIST_COLUMNS
+
+    path = Path(results_dir) / "instances" / f"{sample}_{Path(tomo_name).stem}.csv"
+    _write_rows(path, INSTANCE_LIST_COLUMNS, rows)
     return path
 
 

@@ -629,6 +629,19 @@ int cvx_instance_pair_contacts(const int32_t* labels_a, long ka, const int32_t* 
 int cvx_instance_pair_rows(const int64_t* table, long capacity, const int64_t* order, long p, int64_t* rows, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The contingency table between two instance volumes (`cryovit evaluate --instance-metrics`).
+ *
+ * cvx_overlap_instances: over the voxels v with a = labels_a[v] in 1..ka and b = labels_b[v] in 1..kb (other values are
+ * nobody's), every pair (a, b) accumulates its number of voxels and the smallest linear index of one.  Table, status, capacity,
+ * overflow and refusals are those of cvx_instance_pair_contacts (kb < 0 is refused as ka < 0 is); the third word of a slot holds
+ * the index (a gap_d2 of 0), so cvx_instance_pair_rows reads the rows out as a, b, voxels, 0, at.  Counts are reduced per
+ * thread, per wave and per workgroup (a small table in LDS) before they reach the table; integer atomics only, and no part of
+ * a table that did not overflow, other than which slot a pair sits in, depends on capacity or scheduling.
+ * ------------------------------------------------------------------------------------------------- */
+int cvx_overlap_instances(const int32_t* labels_a, long ka, const int32_t* labels_b, long kb, int D, int H, int W, int64_t* table,
+                          long capacity, int64_t* status, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Per-instance shape (`infer --instances --shape`, `cryovit instances --shape`): the integer sums from which the surface area
  * (discrete Crofton estimate), the Euler number and the principal axes of every instance follow.
  *
