@@ -44,6 +44,10 @@ MASK_LE, MASK_GT = 0, 1  # CVX_MASK_LE / CVX_MASK_GT
 CURVATURE_COLS = 7  # CVX_CURVATURE_COLS
 CURVATURE_RADIUS_MIN, CURVATURE_RADIUS_MAX = 2, 16  # CVX_CURVATURE_RADIUS_MIN / CVX_CURVATURE_RADIUS_MAX
 CURV_NONE = -(2**31)  # CVX_CURV_NONE
+VOL_I8, VOL_U8, VOL_I16, VOL_U16, VOL_I32, VOL_F32 = range(6)  # CVX_VOL_* element types
+BIN_MAX = 8  # CVX_BIN_MAX
+MOMENT_GROUP, MOMENT_CHAIN, MOMENT_TREE = 4096, 16, 8  # CVX_MOMENT_*
+SELECT_BINS, SELECT_MAX_RANKS = 2048, 2  # CVX_SELECT_BINS / CVX_SELECT_MAX_RANKS
 
 c_long, c_int, c_float, c_void_p = C.c_long, C.c_int, C.c_float, C.c_void_p
 
@@ -236,6 +240,10 @@ SIGNATURES = {
     "cvx_curvature_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     "cvx_curvature_map": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
     "cvx_curvature_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
+    "cvx_volume_bin": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_volume_moments": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_volume_select_hist": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cvx_volume_quantize": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

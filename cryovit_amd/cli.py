@@ -1,7 +1,8 @@
 """``cryovit`` command line for the script-level flows (mirror of
 ``/root/reference/src/cryovit/cli/{cli,dino_cli,train_cli,infer_cli,eval_cli}.py``): same command names, arguments, options and defaults.
 
-    python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize]
+    python -m cryovit_amd.cli preprocess <tomograms> <result-folder> <normalisation>
+    python -m cryovit_amd.cli features <tomograms> <result-folder> [--batch-size 64] [--visualize] [--normalize <normalisation>]
     python -m cryovit_amd.cli train <train-data> <train-labels> <label-key> --labels A [--labels B ...] [--val-data ..] [--val-labels ..]
                                     [--name ..] [--result-folder ..] [--ckpt x.model|x.pt] [--num-epochs 50]
     python -m cryovit_amd.cli infer <tomograms> --model x.model [--result-folder DIR] [--threshold 0.5]
@@ -13,11 +14,16 @@
     python -m cryovit_amd.cli instances <predictions> --label NAME [--result-folder DIR] <measurements>
                                         [--distance-to NAME] [--contacts-with NAME] [--distance-to-folder DIR] [--contact-radius R]
 
+    <normalisation>: [--bin K] [--bin-z KZ] [--clip sigma|percentile|minmax|range] [--sigma S] [--percentile LO HI] [--range LO HI]
+                     [--per-slice] [--invert]
     <measurements>: [--close-radius R] [--fill-holes 3d|slices] [--open-radius R]
                     [--min-size N] [--connectivity 6|26] [--split-radius R [--split-min-core N]] [--morphology] [--shape]
                     [--skeleton [--skeleton-end-radius R]] [--thickness] [--mesh [--mesh-smooth N] [--mesh-format ply|stl]]
                     [--curvature [--curvature-radius R]]
 
+``preprocess`` (build extension) turns raw reconstructions (int8 / uint8 / int16 / uint16 / float MRC, TIFF or HDF5, as IMOD or AreTomo
+write them) into the uint8 tomograms every other command expects, on the GPU: bin, clip, rescale to [0, 255]
+(``run.preprocess.PreprocessOptions``); ``features --normalize`` does the same on the fly and feeds the encoder from the device.
 ``train`` fits the CryoVIT head on the GPU (HIP backward, fused AdamW; ``run/train_model.py``) and writes the ``.model`` file that
 ``infer`` and ``evaluate`` load; UNet3D and SAM2 training are not built.  Extra options, marked "build extension",
 replace the network fetch of the encoder weights or add what the reference leaves to the user: ``instances`` (and
@@ -179,6 +185,30 @@ Curvature = Annotated[bool, Option("--curvature", help=_EXT + _CURVATURE_HELP)]
 CurvatureRadius = Annotated[int, Option("--curvature-radius", callback=_checked(lambda v: 2 <= v <= 16, "curvature radius must lie in 2..16 (voxels)"),
                                         help=_EXT + _CURVATURE_RADIUS_HELP)]
 
+# The normalisation options `preprocess` and `features --normalize` share; run.preprocess.PreprocessOptions has the full account.
+Bin = Annotated[int, Option("--bin", min=1, max=8, help=_EXT + "sum the raw volume over boxes of this size in y and x before anything else (1..8)")]
+BinZ = Annotated[Optional[int], Option("--bin-z", min=1, max=8, help=_EXT + "box size in z (1..8)", show_default="--bin")]
+Clip = Annotated[str, Option("--clip", callback=_checked(lambda v: v in ("sigma", "percentile", "minmax", "range"),
+                                                         "clip must be sigma, percentile, minmax or range"),
+                             help=_EXT + "where 0 and 255 lie: mean -+ --sigma standard deviations, the --percentile pair, the extremes, or --range")]
+Sigma = Annotated[float, Option("--sigma", callback=_checked(lambda v: v > 0, "sigma must be > 0"), help=_EXT + "with --clip sigma: standard deviations either side of the mean")]
+Percentile = Annotated[tuple[float, float], Option("--percentile", help=_EXT + "with --clip percentile: the low and the high percentile (exact, lower nearest rank)")]
+Range = Annotated[Optional[tuple[float, float]], Option("--range", help=_EXT + "with --clip range: the raw values that map to 0 and 255", show_default=False)]
+PerSlice = Annotated[bool, Option("--per-slice", help=_EXT + "limits per z-slice instead of one pair for the volume")]
+Invert = Annotated[bool, Option("--invert", help=_EXT + "store 255 - q")]
+
+
+def _preprocess_options(bin_, bin_z, clip, sigma, percentile, range_, per_slice, invert):
+    """The PreprocessOptions of the shared options; what ``validate`` refuses is a usage error."""
+    from cryovit_amd.run.preprocess import PreprocessOptions
+
+    try:
+        return PreprocessOptions(bin=bin_, bin_z=bin_z, clip=clip, sigma=sigma, percentiles=tuple(percentile),
+                                 range=tuple(range_) if range_ is not None else None, per_slice=per_slice, invert=invert).validate()
+    except ValueError as e:
+        raise typer.BadParameter(str(e)) from None
+
+
 # infer measures nothing without --instances: asking for one of these without it is a usage error
 _NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh", "close_radius", "fill_holes", "open_radius",
                     "curvature")
@@ -211,8 +241,21 @@ def features(
     encoder: Annotated[Optional[str], Option(help="build extension: encoder name (default dinov2_vitg14_reg)")] = None,
     checkpoint: Annotated[Optional[str], Option(help="build extension: local DINOv2 state_dict file")] = None,
     synthetic_seed: Annotated[Optional[int], Option(help="build extension: seeded random encoder weights")] = None,
+    normalize: Annotated[bool, Option("--normalize", help=_EXT + "the files hold raw intensities: normalise each to uint8 on the GPU first (the options below, as `preprocess`); the result feeds the encoder from the device and is written as the output's data")] = False,
+    bin_: Bin = 1,
+    bin_z: BinZ = None,
+    clip: Clip = "sigma",
+    sigma: Sigma = 3.0,
+    percentile: Percentile = (0.5, 99.5),
+    range_: Range = None,
+    per_slice: PerSlice = False,
+    invert: Invert = False,
 ):
     """Compute high-level features using DINOv2 for a set of tomograms."""
+    given = dict(bin_=bin_, bin_z=bin_z, clip=clip, sigma=sigma, percentile=percentile, range_=range_, per_slice=per_slice, invert=invert)
+    if not normalize and given != dict(bin_=1, bin_z=None, clip="sigma", sigma=3.0, percentile=(0.5, 99.5), range_=None, per_slice=False, invert=False):
+        raise typer.BadParameter("the normalisation options need --normalize", param_hint="--normalize")
+    options = _preprocess_options(**given) if normalize else None
     from cryovit_amd.run.dino_features import run_dino
     from cryovit_amd.utils import load_files_from_path
 
@@ -220,8 +263,41 @@ def features(
     tomograms_path, result_path = Path(tomograms), Path(result_folder)
     assert tomograms_path.exists(), "Tomograms path does not exist."
     result_path.mkdir(parents=True, exist_ok=True)
+    extra = {"normalize": options} if normalize else {}  # without the flag the call is what it always was
     run_dino(load_files_from_path(tomograms_path), result_path, batch_size=batch_size, visualize=visualize,
-             encoder=_encoder_overrides(encoder, checkpoint, synthetic_seed))
+             encoder=_encoder_overrides(encoder, checkpoint, synthetic_seed), **extra)
+
+
+@cli.command(name="preprocess", no_args_is_help=True)
+def preprocess(
+    tomograms: Annotated[str, Argument(help="Path to the folder or .txt file containing the raw tomograms.")],
+    result_folder: Annotated[str, Argument(help="Path to the folder where the uint8 tomograms and preprocess.csv will be saved.")],
+    bin_: Bin = 1,
+    bin_z: BinZ = None,
+    clip: Clip = "sigma",
+    sigma: Sigma = 3.0,
+    percentile: Percentile = (0.5, 99.5),
+    range_: Range = None,
+    per_slice: PerSlice = False,
+    invert: Invert = False,
+):
+    """Bin, clip and 8-bit-normalise raw tomograms on the GPU (build extension)."""
+    options = _preprocess_options(bin_, bin_z, clip, sigma, percentile, range_, per_slice, invert)
+    tomograms_path, result_path = Path(tomograms), Path(result_folder)
+    assert tomograms_path.exists(), "Tomograms path does not exist."
+    from cryovit_amd.run.preprocess import run_preprocess
+    from cryovit_amd.run.sharding import select_device
+    from cryovit_amd.utils import load_files_from_path
+
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
+    try:
+        device = select_device()
+    except RuntimeError as e:  # no device: say so and write nothing
+        typer.echo(f"Error: {e}", err=True)
+        raise typer.Exit(1) from None
+    result_path.mkdir(parents=True, exist_ok=True)
+    for out in run_preprocess(load_files_from_path(tomograms_path), result_path, options, device=device):
+        logging.info("Wrote %s", out)
 
 
 @cli.command(name="train", no_args_is_help=True)

@@ -1530,3 +1530,143 @@ def surface_distance_hist(surf: torch.Tensor, d2: torch.Tensor, bins: int, *, ou
     dev = _dev_check(surf, d2, out)
     call(dev, "cvx_surface_distance_hist", _lib.load().cvx_surface_distance_hist, _p(surf), _p(d2), surf.numel(), bins, _p(out))
     return out
+
+
+# ---- a raw tomogram to uint8 (`cryovit preprocess`, `features --normalize`): bin, moments, order statistics, quantise ----
+
+MOMENT_GROUP = _lib.MOMENT_GROUP  # voxels of a slice under one partial of volume_moments
+MOMENT_CHAIN = _lib.MOMENT_CHAIN  # float32: the adds a thread makes in a row
+MOMENT_TREE = _lib.MOMENT_TREE    # float32: the levels of the fixed tree over the threads of a partial
+_VOL_DTYPES = {torch.int8: _lib.VOL_I8, torch.uint8: _lib.VOL_U8, torch.int16: _lib.VOL_I16, torch.uint16: _lib.VOL_U16,
+               torch.int32: _lib.VOL_I32, torch.float32: _lib.VOL_F32}
+VOLUME_RANGE = {torch.int8: (-128, 127), torch.uint8: (0, 255), torch.int16: (-32768, 32767), torch.uint16: (0, 65535),
+                torch.int32: (-(2**31), 2**31 - 1)}  # what an integer element can hold
+
+
+def _vol_check(what: str, v, *, binned: bool = True) -> tuple[torch.device, int, int, int, int]:
+    """(device, D, H, W, CVX_VOL_* code) of a volume operand: a contiguous device tensor [D, H, W] of a supported type."""
+    if not isinstance(v, torch.Tensor) or v.dim() != 3:
+        raise _lib.CvxError(f"{what}: the volume must be a [D, H, W] tensor")
+    if v.dtype not in _VOL_DTYPES or (not binned and v.dtype == torch.int32):
+        raise _lib.CvxError(f"{what}: the volume must be int8, uint8, int16, uint16{', int32' if binned else ''} or float32, got {v.dtype}")
+    dev = _dev_check(v)
+    D, H, W = (int(s) for s in v.shape)
+    return dev, D, H, W, _VOL_DTYPES[v.dtype]
+
+
+def volume_bin(v: torch.Tensor, kz: int, k: int) -> torch.Tensor:
+    """[D // kz, H // k, W // k]: the SUM of every kz x k x k block of ``v`` (int8 / uint8 / int16 / uint16 / float32 [D, H, W], which
+    may hold more than 2^31 voxels; the binned volume may not); trailing voxels that fill no block are dropped.  Integer sources
+    give exact int32 sums; float32 gives float32 sums added z outer, y, x inner from 0.0f, one rounding per add, so a host loop in
+    that order is bit-equal.  Not divided by the block size.  ``kz == k == 1`` returns ``v`` itself: no copy.  The host does not wait."""
+    dev, D, H, W, code = _vol_check("volume_bin", v, binned=False)
+    kz, k = int(kz), int(k)
+    if not (1 <= kz <= _lib.BIN_MAX and 1 <= k <= _lib.BIN_MAX):
+        raise _lib.CvxError(f"volume_bin: bin factors must lie in 1..{_lib.BIN_MAX}, got {kz} and {k}")
+    if kz == 1 and k == 1:
+        return v
+    if (D // kz) * (H // k) * (W // k) > _lib.COMPONENT_MAX_VOXELS:
+        raise _lib.CvxError("volume_bin: extents must be >= 0 with D*H*W <= 2^31 - 2 (of the binned volume)")
+    out = torch.empty((D // kz, H // k, W // k), dtype=torch.float32 if v.dtype == torch.float32 else torch.int32, device=dev)
+    call(dev, "cvx_volume_bin", _lib.load().cvx_volume_bin, _p(v), code, D, H, W, kz, k, _p(out))
+    return out
+
+
+def volume_moment_partials(v: torch.Tensor) -> torch.Tensor:
+    """int64 [D, P, 3] on the device, P = max(1, ceil(H * W / MOMENT_GROUP)): per z-slice of ``v`` and per run of MOMENT_GROUP
+    voxels of it, the finite voxels, their sum and the sum of their squares.  Integer volumes: int64 and (as bits) uint64, exact.
+    float32: the two sums are the bits of doubles (``.view(torch.float64)``), added by a fixed chain of MOMENT_CHAIN and a fixed
+    tree of MOMENT_TREE levels; NaN and +-Inf are left out.  No atomics: two calls give the same bits.  The host does not wait."""
+    dev, D, H, W, code = _vol_check("volume_moments", v)
+    P = max(1, -(-(H * W) // MOMENT_GROUP))
+    out = torch.empty((D, P, 3), dtype=torch.int64, device=dev)
+    call(dev, "cvx_volume_moments", _lib.load().cvx_volume_moments, _p(v), code, D, H, W, _p(out))
+    return out
+
+
+def volume_moments(v: torch.Tensor) -> list[tuple]:
+    """Per z-slice of ``v`` the tuple (finite voxels, sum, sum of squares), finished on the host from ``volume_moment_partials``:
+    integer volumes as Python ints (exact), float32 as floats added with ``math.fsum``.  Waits for the device."""
+    part = volume_moment_partials(v).cpu()
+    if v.dtype == torch.float32:
+        sums = part[..., 1:].contiguous().view(torch.float64).tolist()
+        return [(sum(c), math.fsum(p[0] for p in s), math.fsum(p[1] for p in s)) for c, s in zip(part[..., 0].tolist(), sums)]
+    rows = part.tolist()
+    return [(sum(p[0] for p in s), sum(p[1] for p in s), sum(p[2] % (1 << 64) for p in s)) for s in rows]
+
+
+def volume_select(v: torch.Tensor, ranks, *, per_slice: bool = False, value_range=None) -> torch.Tensor:
+    """float64 [S, R] on the device: entry [s][r] is the ``ranks[s][r]``-th smallest (0-based) finite voxel of slice s of ``v``
+    (``per_slice``; S = D) or of the whole volume (S = 1), exactly; NaN for a rank that is negative or not below the count of
+    finite voxels.  ``ranks``: S rows of R = 1 or 2 ints.  Radix select on an order-preserving 32-bit key in up to three histogram
+    passes of at most 11 bits, each restricted to the prefix found so far; the bucket is picked by a cumulative sum on the device.
+    ``value_range`` = (least, greatest) value an integer volume can hold (default: the range of its type): the bit fields cover
+    ``greatest - least`` only, and a value outside is a caller's error.  -0.0 and +0.0 are neighbours in the order and equal as
+    numbers.  Integer atomics only: bit-reproducible.  The host does not wait."""
+    dev, D, H, W, code = _vol_check("volume_select", v)
+    S, length = (D, H * W) if per_slice else (1, D * H * W)
+    ranks_t = torch.as_tensor(ranks, dtype=torch.int64).reshape(S, -1) if S else torch.zeros((0, 1), dtype=torch.int64)
+    R = ranks_t.shape[1]
+    if not 1 <= R <= _lib.SELECT_MAX_RANKS:
+        raise _lib.CvxError(f"volume_select: 1 or 2 ranks per slice, got {R}")
+    if D * H * W > _lib.COMPONENT_MAX_VOXELS:
+        raise _lib.CvxError("volume_select: extents must be >= 0 with D*H*W <= 2^31 - 2")
+    ranks_t = ranks_t.to(dev)
+    if v.dtype == torch.float32:
+        base, bits = 0, 32
+    else:
+        low, high = (int(x) for x in (value_range or VOLUME_RANGE[v.dtype]))
+        if not VOLUME_RANGE[torch.int32][0] <= low <= high <= VOLUME_RANGE[torch.int32][1]:
+            raise _lib.CvxError(f"volume_select: value_range must be an ordered pair of int32 values, got {value_range}")
+        base, bits = low, max(1, (high - low).bit_length())
+    widths = [min(11, bits), min(11, max(0, bits - 11)), max(0, bits - 22)]
+    lib = _lib.load()
+    prefix = torch.zeros((S, R, 2), dtype=torch.int64, device=dev)
+    first = torch.zeros((S, 1, 2), dtype=torch.int64, device=dev)  # no prefix yet: one histogram serves every rank
+    rem = ranks_t.clamp_min(0)
+    total, shift = None, bits
+    for i, w in enumerate(widths):
+        if w == 0 or S == 0:
+            continue
+        shift -= w
+        table = torch.empty((S, 1 if i == 0 else R, _lib.SELECT_BINS), dtype=torch.int64, device=dev)
+        call(dev, "cvx_volume_select_hist", lib.cvx_volume_select_hist, _p(v), code, S, length, base, shift, w, table.shape[1],
+             _p(first if i == 0 else prefix), _p(table))
+        cum = table.expand(S, R, _lib.SELECT_BINS).cumsum(-1)
+        if total is None:
+            total = cum[..., -1]
+        bucket = (cum <= rem[..., None]).sum(-1).clamp_max(_lib.SELECT_BINS - 1)  # the first bin whose cumulative count passes the rank
+        below = torch.where(bucket > 0, cum.gather(-1, (bucket - 1).clamp_min(0)[..., None]).squeeze(-1), torch.zeros_like(rem))
+        rem = rem - below
+        prefix[..., 0] |= bucket << shift
+        prefix[..., 1] |= ((1 << w) - 1) << shift
+    key = prefix[..., 0]
+    if v.dtype == torch.float32:
+        u = torch.where(key >= 2**31, key - 2**31, 2**32 - 1 - key)  # undo the sign-flip transform
+        value = torch.where(u >= 2**31, u - 2**32, u).to(torch.int32).view(torch.float32).double()
+    else:
+        value = (key + base).double()  # |value| < 2^31: exact
+    if total is None:
+        return torch.full((S, R), float("nan"), dtype=torch.float64, device=dev)
+    return torch.where((ranks_t >= 0) & (ranks_t < total), value, torch.full_like(value, float("nan")))
+
+
+def volume_quantize(v: torch.Tensor, params, *, per_slice: bool = False, invert: bool = False, out=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(uint8 [D, H, W], int64 [D, 2]) on the device.  ``params``: one (lo, hi, scale) of doubles for the volume, or D of them with
+    ``per_slice``.  q = floor((double(v) - lo) * scale + 0.5) with one rounding per operation, clamped to [0, 255]; 128 for NaN,
+    255 / 0 for +Inf / -Inf; ``invert`` stores 255 - q.  The second tensor counts per slice the voxels below lo and above hi.
+    ``out`` (uint8 [D, H, W]) receives the image when given.  Exact; integer atomics only; the host does not wait."""
+    dev, D, H, W, code = _vol_check("volume_quantize", v)
+    par = torch.as_tensor(params, dtype=torch.float64).reshape(-1, 3)
+    if par.shape[0] != (D if per_slice else 1):
+        raise _lib.CvxError(f"volume_quantize: {D if per_slice else 1} (lo, hi, scale) triples expected, got {par.shape[0]}")
+    par = par.to(dev).contiguous()
+    if out is None:
+        out = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (D, H, W):
+        raise _lib.CvxError(f"volume_quantize: out must be uint8 {(D, H, W)}")
+    _dev_check(v, par, out)
+    clipped = torch.empty((D, 2), dtype=torch.int64, device=dev)
+    call(dev, "cvx_volume_quantize", _lib.load().cvx_volume_quantize, _p(v), code, D, H, W, _p(par), int(bool(per_slice)), int(bool(invert)),
+         _p(out), _p(clipped))
+    return out, clipped

@@ -234,11 +234,14 @@ def run_trainer(cfg) -> None:
 
 
 def run_dino(train_data: list[Path], result_dir: Path, batch_size: int, use_sam: bool = False, visualize: bool = False, *,
-             encoder: dict | None = None) -> None:
+             encoder: dict | None = None, normalize=None) -> None:
     """Feature extraction over a list of tomogram files of any supported format (mirror of l.211-299): one
     ``<result_dir>/<stem>.hdf`` per input with ``data``, ``dino_features`` and the source's other datasets under ``labels/``;
     ``visualize``: PCA colour maps under ``<result_dir>/../dino_images/<stem>/<stem>/`` (the reference's doubled stem).
-    ``encoder`` overrides keys of the config's ``encoder`` block (name / checkpoint / synthetic_seed / device)."""
+    ``encoder`` overrides keys of the config's ``encoder`` block (name / checkpoint / synthetic_seed / device).
+    ``normalize`` (a ``run.preprocess.PreprocessOptions``): the file's volume is read as stored and normalised on the GPU
+    (``normalize_volume``); the uint8 result stays on the device as the encoder's input and is what the output file holds as
+    ``data``.  None: files are taken as already normalised, as upstream."""
     from cryovit_amd.config import compose
     from cryovit_amd.types import FileData
 
@@ -267,10 +270,18 @@ def run_dino(train_data: list[Path], result_dir: Path, batch_size: int, use_sam:
         with ThreadPoolExecutor(max_workers=2) as writer:
             pending = []
             for i in shard_records(files, rank, world):
-                x = dataset[i]
-                features = feature_fn(x.data, model, cfg.batch_size)
+                if normalize is not None:
+                    from cryovit_amd.run.preprocess import normalize_volume
+                    from cryovit_amd.utils import read_volume
+
+                    data, _ = normalize_volume(read_volume(files[i].tomo_path)[0], normalize, device=device)
+                    aux_data = {"data": data.cpu().numpy()}
+                else:
+                    x = dataset[i]
+                    data, aux_data = x.data, x.aux_data
+                features = feature_fn(data, model, cfg.batch_size)
                 result_path = result_list[i].with_suffix(".hdf")
-                pending.append(writer.submit(save, x.aux_data, features, result_path))
+                pending.append(writer.submit(save, aux_data, features, result_path))
                 while len(pending) > 2:
                     pending.pop(0).result()
             for f in pending:

@@ -227,6 +227,43 @@ def load_data(file_path, key: str | None = None) -> tuple[np.ndarray, str]:
     return data, found_key
 
 
+def read_volume(file_path, key: str | None = None) -> tuple[np.ndarray, str]:
+    """(data, key used) of one tomogram file AS STORED: the same readers and the same choice of HDF5 dataset as ``load_data``, but no
+    scaling by 1/255 and no channel axis, for ``cryovit preprocess``, which normalises raw intensities itself."""
+    file_path = Path(file_path)
+    if not file_path.exists():
+        raise FileNotFoundError(f"File {file_path} does not exist.")
+    if file_path.suffix in (".h5", ".hdf", ".hdf5"):
+        found_key, data, _ = read_hdf(file_path, key=key)
+        return data, found_key
+    if file_path.suffix in (".mrc", ".mrcs"):
+        return _read_mrc_array(file_path), ""
+    if file_path.suffix in (".tiff", ".tif"):
+        return _read_tiff_array(file_path), ""
+    raise ValueError(_UNSUPPORTED.format(file_path))
+
+
+def mrc_voxel_size(file_path) -> float | None:
+    """Voxel size along x of an MRC file, ``cella.x / mx`` of its header (words 11 and 8; Angstrom in MRC2014), or None when the file is
+    no MRC file or either value is not positive and finite."""
+    file_path = Path(file_path)
+    if file_path.suffix not in (".mrc", ".mrcs"):
+        return None
+    with open(file_path, "rb") as f:
+        header = f.read(1024)
+    if len(header) < 1024:
+        return None
+    order = ">" if header[212] == 0x11 else "<"
+    nx, ny, nz = struct.unpack(order + "3i", header[:12])
+    if not (0 < nx < 1 << 20 and 0 < ny < 1 << 20 and 0 < nz < 1 << 20):  # as _read_mrc_array picks the byte order
+        order = ">" if order == "<" else "<"
+    (mx,) = struct.unpack(order + "i", header[28:32])
+    (cella_x,) = struct.unpack(order + "f", header[40:44])
+    if mx <= 0 or not cella_x > 0 or not np.isfinite(cella_x):
+        return None
+    return float(cella_x) / mx
+
+
 def _match_label_keys_to_data(data: np.ndarray, label_keys: list[str], metadata: FileMetadata) -> dict[str, np.ndarray]:
     """One int8 {-1, 0, 1} volume per label name from a multi-valued label volume; ``label_keys`` in ascending value
     order; -1 stays "unlabelled"; a 0 that is not named is background (reference l.228-254)."""

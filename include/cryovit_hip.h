@@ -931,6 +931,54 @@ int cvx_curvature_map(const int32_t* labels, int D, int H, int W, int radius, in
                       hipStream_t stream);
 int cvx_curvature_stats(const int32_t* labels, const int32_t* h, int D, int H, int W, long k, int64_t* table, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Raw tomogram -> uint8 in [0, 255] (`cryovit preprocess`, `features --normalize`): bin, moments, order statistics, quantise.
+ * A volume is [D][H][W] of one of the CVX_VOL_* element types; CVX_VOL_I32 is what the bin pass makes of an integer source.
+ * Everything but the two float32 moment sums is exact and bit-reproducible; those two are reproducible and bounded (below).
+ *
+ * cvx_volume_bin: src [D][H][W] (int8 / uint8 / int16 / uint16 / float32; D*H*W may exceed 2^31), out [D/kz][H/k][W/k]: the
+ *   sum of every kz x k x k block, 1 <= kz, k <= CVX_BIN_MAX; trailing voxels that fill no block are dropped.  Integer sources:
+ *   out int32, exact.  float32: out float32 = (((0.0f + v0) + v1) + ...) over the block z outer, y, x inner, one rounding per add.
+ *   No division by the block size.  Every voxel of out is written.
+ * cvx_volume_moments: partials [D][P][3] of 8-byte words, P = max(1, ceil(H*W / CVX_MOMENT_GROUP)); partial (z, c) covers the
+ *   voxels [c * CVX_MOMENT_GROUP, (c + 1) * CVX_MOMENT_GROUP) of slice z: word 0 int64 the finite voxels, word 1 their sum, word 2
+ *   the sum of their squares.  Integer types: int64 and uint64, exact.  float32: doubles; a thread adds CVX_MOMENT_CHAIN consecutive
+ *   voxels in order, a fixed tree of CVX_MOMENT_TREE levels adds the threads; squares are exact.  NaN and +-Inf are left out and
+ *   not counted.  Plain stores, every word written; the caller adds the partials.
+ * cvx_volume_select_hist: one pass of an exact radix select over v [slices][len].  key(v) is 32 bits and order preserving:
+ *   (uint32)(v - base) for the integer types (base <= every v, v - base < 2^32), for float32 the bits with the sign bit set when
+ *   it was clear and all bits flipped when it was set (base unused); NaN and +-Inf are left out.  prefix int64 [slices][ranks][2]
+ *   = (value, mask); table int64 [slices][ranks][CVX_SELECT_BINS], zeroed by the call: entry [s][r][b] counts the voxels of
+ *   slice s with (key & mask) == value and ((key >> shift) & (2^width - 1)) == b.  1 <= width <= 11, shift + width <= 32,
+ *   1 <= ranks <= CVX_SELECT_MAX_RANKS, slices * len <= CVX_COMPONENT_MAX_VOXELS.  64-bit integer atomics.
+ * cvx_volume_quantize: params double [D][3] (per_slice = 1) or [1][3] = (lo, hi, scale); out uint8 [D][H][W], every voxel
+ *   written: q = floor((double(v) - lo) * scale + 0.5), each operation rounded once (no fused multiply-add), clamped to [0, 255];
+ *   128 for a NaN voxel or a NaN product, 255 / 0 for +Inf / -Inf; invert = 1 stores 255 - q.  clipped int64 [D][2], zeroed by the
+ *   call: the voxels of slice z with double(v) < lo and with double(v) > hi.
+ * Refused with an error before any launch: another dtype (cvx_volume_bin: CVX_VOL_I32 as well), negative extents, a (binned)
+ * volume with D*H*W > CVX_COMPONENT_MAX_VOXELS, bin factors outside 1..CVX_BIN_MAX, a bit field or rank count out of range, flags
+ * other than 0 / 1, null pointers, misaligned arrays (elements: their size; partials, prefix, table, params, clipped: 8 bytes),
+ * src == out.  An empty volume succeeds.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_VOL_I8 0
+#define CVX_VOL_U8 1
+#define CVX_VOL_I16 2
+#define CVX_VOL_U16 3
+#define CVX_VOL_I32 4
+#define CVX_VOL_F32 5
+#define CVX_BIN_MAX 8
+#define CVX_MOMENT_GROUP 4096
+#define CVX_MOMENT_CHAIN 16
+#define CVX_MOMENT_TREE 8
+#define CVX_SELECT_BINS 2048
+#define CVX_SELECT_MAX_RANKS 2
+int cvx_volume_bin(const void* src, int dtype, long D, long H, long W, int kz, int k, void* out, hipStream_t stream);
+int cvx_volume_moments(const void* v, int dtype, int D, int H, int W, void* partials, hipStream_t stream);
+int cvx_volume_select_hist(const void* v, int dtype, long slices, long len, long base, int shift, int width, int ranks,
+                           const int64_t* prefix, int64_t* table, hipStream_t stream);
+int cvx_volume_quantize(const void* v, int dtype, int D, int H, int W, const double* params, int per_slice, int invert, uint8_t* out,
+                        int64_t* clipped, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
