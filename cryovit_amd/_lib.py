@@ -44,6 +44,9 @@ MASK_LE, MASK_GT = 0, 1  # CVX_MASK_LE / CVX_MASK_GT
 CURVATURE_COLS = 7  # CVX_CURVATURE_COLS
 CURVATURE_RADIUS_MIN, CURVATURE_RADIUS_MAX = 2, 16  # CVX_CURVATURE_RADIUS_MIN / CVX_CURVATURE_RADIUS_MAX
 CURV_NONE = -(2**31)  # CVX_CURV_NONE
+PICK_COLS = 8  # CVX_PICK_COLS
+PICK_RADIUS_MIN, PICK_RADIUS_MAX = 2, 16  # CVX_PICK_RADIUS_MIN / CVX_PICK_RADIUS_MAX
+PICK_SPACING_MIN, PICK_SPACING_MAX = 2, 16  # CVX_PICK_SPACING_MIN / CVX_PICK_SPACING_MAX
 VOL_I8, VOL_U8, VOL_I16, VOL_U16, VOL_I32, VOL_F32 = range(6)  # CVX_VOL_* element types
 BIN_MAX = 8  # CVX_BIN_MAX
 MOMENT_GROUP, MOMENT_CHAIN, MOMENT_TREE = 4096, 16, 8  # CVX_MOMENT_*
@@ -240,6 +243,12 @@ SIGNATURES = {
     "cvx_curvature_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     "cvx_curvature_map": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
     "cvx_curvature_stats": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
+    "cvx_pick_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "cvx_pick_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p, c_long, c_void_p]),
+    "cvx_pick_rounds": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_int, C.c_uint32, c_int, c_void_p, c_void_p, c_long, c_void_p,
+                                c_void_p]),
+    "cvx_pick_count": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p]),
+    "cvx_pick_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_long, c_void_p, c_void_p]),
     "cvx_volume_bin": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_int, c_int, c_void_p, c_void_p]),
     "cvx_volume_moments": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_volume_select_hist": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -2,7 +2,8 @@
 its distance maps say about them, the split of instances that touch over a neck, which instance of one label touches
 which of another, the shape of each instance (surface area, Euler number, principal axes), its centreline (length, ends, branches)
 its local thickness (mean, spread, min, max), the surface mesh of the mask (PLY / STL; triangles, area, volume) and the mean
-curvature of its membrane (ball-volume integral invariant; mean, spread, min, max, convex share); the
+curvature of its membrane (ball-volume integral invariant; mean, spread, min, max, convex share); evenly spaced positions on
+that membrane with its normal, the particle picks of subtomogram averaging (RELION STAR / CSV); the
 clean-up of the mask before all of that (close, fill holes, open); and, against annotated labels, how far the predicted boundary
 lies from the true one (HD95, surface distance, surface Dice) and how well the annotated objects are recovered one by one (detection
 F1, panoptic quality, Rand index, split / merge variation of information)."""
@@ -18,6 +19,8 @@ from cryovit_amd.analysis.thickness import THICKNESS_COLUMNS, instance_thickness
 from cryovit_amd.analysis.mesh import MESH_COLUMNS, instance_mesh, mesh_arrays, mesh_rows, write_mesh, write_ply, write_stl  # noqa: F401
 from cryovit_amd.analysis.curvature import (  # noqa: F401
     CURVATURE_COLUMNS, CurvatureOptions, curvature_map, curvature_rows, curvature_volume, vertex_curvature)
+from cryovit_amd.analysis.picks import (  # noqa: F401
+    PICK_COLUMNS, PICK_CSV_COLUMNS, PickOptions, pick_records, pick_rows, pick_table, write_picks_csv, write_star)
 from cryovit_amd.analysis.boundary import (  # noqa: F401
     BOUNDARY_COUNT_COLUMNS, BOUNDARY_DISTANCE_COLUMNS, BOUNDARY_MODES, boundary_columns, boundary_histograms, boundary_scores, check_scored,
     nsd_column)

@@ -20,6 +20,7 @@
                     [--min-size N] [--connectivity 6|26] [--split-radius R [--split-min-core N]] [--morphology] [--shape]
                     [--skeleton [--skeleton-end-radius R]] [--thickness] [--mesh [--mesh-smooth N] [--mesh-format ply|stl]]
                     [--curvature [--curvature-radius R]]
+                    [--pick [--pick-spacing S] [--pick-radius R] [--pick-offset V] [--pick-scale F] [--pick-seed N]]
 
 ``preprocess`` (build extension) turns raw reconstructions (int8 / uint8 / int16 / uint16 / float MRC, TIFF or HDF5, as IMOD or AreTomo
 write them) into the uint8 tomograms every other command expects, on the GPU: bin, clip, rescale to [0, 255]
@@ -32,7 +33,9 @@ measures them.  The measurement options are declared once, below, for both comma
 ``analysis.instances.InstanceOptions``, which says what it computes and writes.  ``--close-radius``, ``--fill-holes`` and
 ``--open-radius`` clean the mask on the GPU before it is labelled, in that order (``analysis.cleanup.CleanupOptions``): the file gains
 ``<label>_cleaned`` and the CSV ``added_voxels``.  ``--curvature`` maps the mean curvature of the membrane at the scale
-``--curvature-radius`` (``analysis.curvature.CurvatureOptions``).  ``--distance-to NAME`` adds the gap to another
+``--curvature-radius`` (``analysis.curvature.CurvatureOptions``).  ``--pick`` places positions for subtomogram averaging on every
+instance's membrane, no two of one instance closer than ``--pick-spacing`` voxels, each with the membrane normal, and writes them as
+``picks/<tomo>_<label>.csv`` and a RELION ``.star`` (``analysis.picks.PickOptions``).  ``--distance-to NAME`` adds the gap to another
 label's mask and the voxels in contact with it; ``--contacts-with NAME`` says which instance touches which: every instance gains
 ``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance, nearest instance of NAME within
 ``--contact-radius``) the voxels in contact, the narrowest gap and where it is.
@@ -41,6 +44,7 @@ label's mask and the voxels in contact with it; ``--contacts-with NAME`` says wh
 from __future__ import annotations
 
 import logging
+import math
 from pathlib import Path
 from typing import Annotated, Optional
 
@@ -160,6 +164,21 @@ _CURVATURE_HELP = ("map the mean curvature of the membrane on the GPU (ball-volu
                    "scored as their union (with infer: needs --instances)")
 _CURVATURE_RADIUS_HELP = ("with --curvature, the radius of the ball: the scale at which the surface is read.  Larger is quieter (the "
                           "per-voxel noise falls with 1/R^2) and blurs features smaller than R (voxels, an integer in 2..16)")
+_PICK_HELP = ("place evenly spaced positions on the membrane of every instance on the GPU, each with the membrane normal: the particle "
+              "positions of subtomogram averaging.  Writes <result>/picks/<tomo>_<label>.csv (every pick: instance id, voxel, position, "
+              "outward normal, Euler angles, the ball's moment) and .star (a RELION data_particles loop of the oriented picks: "
+              "_rlnCoordinateX/Y/Z, _rlnAngleRot/Tilt/Psi with the particle's z axis along the normal) and adds picks and "
+              "picks_unoriented as the last CSV columns.  The CSV normals are the authoritative orientation (with infer: needs "
+              "--instances)")
+_PICK_SPACING_HELP = ("with --pick, the least distance between two picks of one instance, centre to centre; every surface voxel then "
+                      "has a pick of its instance closer than this (voxels, an integer in 2..16)")
+_PICK_RADIUS_HELP = ("with --pick, the radius of the ball the normal is read from; picks lie at least this far from the volume's "
+                     "border (voxels, an integer in 2..16)")
+_PICK_OFFSET_HELP = ("with --pick, move every oriented pick this far along its outward normal before it is written; negative moves "
+                     "into the object (voxels)")
+_PICK_SCALE_HELP = ("with --pick, write coordinates of a volume this many times finer: (q + 0.5) * F - 0.5, which undoes "
+                    "preprocess --bin F (> 0)")
+_PICK_SEED_HELP = "with --pick, the seed of the pseudo-random order the candidates are taken in (0 .. 2^32 - 1); same seed, same picks"
 _EXT = "build extension: "
 
 MinSize = Annotated[int, Option(min=0, help=_EXT + _MIN_SIZE_HELP)]
@@ -208,10 +227,21 @@ def _preprocess_options(bin_, bin_z, clip, sigma, percentile, range_, per_slice,
     except ValueError as e:
         raise typer.BadParameter(str(e)) from None
 
+Pick = Annotated[bool, Option("--pick", help=_EXT + _PICK_HELP)]
+PickSpacing = Annotated[int, Option("--pick-spacing", callback=_checked(lambda v: 2 <= v <= 16, "pick spacing must lie in 2..16 (voxels)"),
+                                    help=_EXT + _PICK_SPACING_HELP)]
+PickRadius = Annotated[int, Option("--pick-radius", callback=_checked(lambda v: 2 <= v <= 16, "pick radius must lie in 2..16 (voxels)"),
+                                   help=_EXT + _PICK_RADIUS_HELP)]
+PickOffset = Annotated[float, Option("--pick-offset", callback=_checked(lambda v: math.isfinite(v), "pick offset must be finite (voxels)"),
+                                     help=_EXT + _PICK_OFFSET_HELP)]
+PickScale = Annotated[float, Option("--pick-scale", callback=_checked(lambda v: math.isfinite(v) and v > 0, "pick scale must be finite and > 0"),
+                                    help=_EXT + _PICK_SCALE_HELP)]
+PickSeed = Annotated[int, Option("--pick-seed", callback=_checked(lambda v: 0 <= v < 2**32, "pick seed must lie in 0..2^32 - 1"),
+                                 help=_EXT + _PICK_SEED_HELP)]
 
 # infer measures nothing without --instances: asking for one of these without it is a usage error
 _NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh", "close_radius", "fill_holes", "open_radius",
-                    "curvature")
+                    "curvature", "pick")
 
 
 def _refuse_stl_curvature(curvature: bool, mesh: bool, mesh_format: str) -> None:
@@ -381,13 +411,21 @@ def infer(
     open_radius: OpenRadius = None,
     curvature: Curvature = False,
     curvature_radius: CurvatureRadius = 5,
+    pick: Pick = False,
+    pick_spacing: PickSpacing = 8,
+    pick_radius: PickRadius = 5,
+    pick_offset: PickOffset = 0.0,
+    pick_scale: PickScale = 1.0,
+    pick_seed: PickSeed = 0,
 ):
     """Segment tomograms using a pre-trained model."""
     measurements = dict(min_size=min_size, connectivity=connectivity, morphology=morphology, split_radius=split_radius,
                         split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
                         thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format,
                         close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius,
-                        curvature=curvature, curvature_radius=curvature_radius)
+                        curvature=curvature, curvature_radius=curvature_radius,
+                        pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
+                        pick_seed=pick_seed)
     _refuse_stl_curvature(curvature, mesh, mesh_format)
     for name in _NEEDS_INSTANCES:
         value = measurements[name]  # a flag that is off is False, a radius that is not given None; a radius of 0 is given
@@ -434,6 +472,12 @@ def instances_cmd(
     open_radius: OpenRadius = None,
     curvature: Curvature = False,
     curvature_radius: CurvatureRadius = 5,
+    pick: Pick = False,
+    pick_spacing: PickSpacing = 8,
+    pick_radius: PickRadius = 5,
+    pick_offset: PickOffset = 0.0,
+    pick_scale: PickScale = 1.0,
+    pick_seed: PickSeed = 0,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     _refuse_stl_curvature(curvature, mesh, mesh_format)
@@ -450,7 +494,9 @@ def instances_cmd(
                          skeleton=skeleton, skeleton_end_radius=skeleton_end_radius, thickness=thickness,
                          mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format,
                          close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius,
-                         curvature=curvature, curvature_radius=curvature_radius)
+                         curvature=curvature, curvature_radius=curvature_radius,
+                         pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
+                         pick_seed=pick_seed)
         logging.info("Labelled %s", out)
 
 

@@ -1475,6 +1475,112 @@ def instance_curvature(labels: torch.Tensor, k: int, radius: int) -> tuple[torch
     return h, curvature_stats(labels, h, k)
 
 
+# ---- membrane picking (`--pick`): spaced surface voxels of every instance with the moment that gives the membrane normal ----
+
+PICK_ROUND_BATCH = 4  # selection rounds launched per read of their "changed" flags
+
+
+def _pick_int(what: str, name: str, value, lo: int, hi: int) -> int:
+    if isinstance(value, bool) or int(value) != value or not lo <= value <= hi:
+        raise _lib.CvxError(f"{what}: {name} must be an integer in [{lo}, {hi}], got {value}")
+    return int(value)
+
+
+def _pick_bitmaps(what: str, D: int, H: int, W: int, **bitmaps) -> int:
+    """The bytes of one bitmap of a [D, H, W] volume; raises unless every tensor is int64 with the words of its bitmaps."""
+    words = D * H * ((W + 63) // 64)
+    for name, (t, count) in bitmaps.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.numel() != count * words:
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise _lib.CvxError(f"{what}: {name} must be int64 with {count} x {words} words for a {D}x{H}x{W} volume, got {got}")
+    return 8 * words
+
+
+def pick_pack(labels: torch.Tensor, k: int, radius: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(fg int64 [D, H, WW], state int64 [2, D, H, WW]), WW = ceil(W / 64): ``labels > 0`` as bits (bit i of word w of a row = voxel
+    x = 64 w + i) and the state the selection starts from: [0] the candidates of the instances 1..k at the normal radius ``radius``
+    (the surface voxels with an id whose ball is not clipped; the definition is in include/cryovit_hip.h), [1] nothing picked.  The
+    host does not wait."""
+    dev, D, H, W = _volumes_check("pick_pack", labels=(labels, torch.int32))
+    radius = _pick_int("pick_pack", "radius", radius, _lib.PICK_RADIUS_MIN, _lib.PICK_RADIUS_MAX)
+    if k < 0:
+        raise _lib.CvxError(f"pick_pack: k must be >= 0, got {k}")
+    ww = (W + 63) // 64
+    fg = torch.zeros((D, H, ww), dtype=torch.int64, device=dev)
+    state = torch.zeros((2, D, H, ww), dtype=torch.int64, device=dev)
+    call(dev, "cvx_pick_pack", _lib.load().cvx_pick_pack, _p(labels), D, H, W, int(k), radius, _p(fg), _p(state), fg.numel() * 8)
+    return fg, state
+
+
+def pick_select(labels: torch.Tensor, k: int, state: torch.Tensor, *, spacing: int, seed: int = 0, max_rounds: int = 4096,
+                batch: int | None = None) -> tuple[torch.Tensor, int]:
+    """(state' int64 [2, D, H, WW], rounds): the fixpoint of the selection rounds from ``state`` (``pick_pack``; it is overwritten):
+    state'[1] holds the picks, the lexicographically first maximal independent set of the candidates under "same id and closer than
+    ``spacing``" in the order of the keys of ``seed``; state'[0] is empty.  ``rounds`` counts the rounds launched up to and including
+    the one that changed nothing (which proves the fixpoint).  A round reads one state and writes another; the host reads the
+    rounds' flags once per ``batch`` (default ``PICK_ROUND_BATCH``) rounds.  Raises when ``max_rounds`` rounds did not reach the
+    fixpoint."""
+    dev, D, H, W = _volumes_check("pick_select", labels=(labels, torch.int32))
+    spacing = _pick_int("pick_select", "spacing", spacing, _lib.PICK_SPACING_MIN, _lib.PICK_SPACING_MAX)
+    seed = _pick_int("pick_select", "seed", seed, 0, 2**32 - 1)
+    batch = PICK_ROUND_BATCH if batch is None else batch
+    if k < 0 or max_rounds < 1 or batch < 1:
+        raise _lib.CvxError(f"pick_select: need k >= 0, max_rounds >= 1 and batch >= 1, got {k}, {max_rounds}, {batch}")
+    nbytes = _pick_bitmaps("pick_select", D, H, W, state=(state, 2))
+    _dev_check(labels, state)
+    if k == 0 or labels.numel() == 0:
+        return state, 0
+    lib = _lib.load()
+    other = torch.empty_like(state)
+    changed = torch.empty(batch, dtype=torch.int32, device=dev)
+    done = 0
+    while done < max_rounds:
+        n = min(batch, max_rounds - done)
+        call(dev, "cvx_pick_rounds", lib.cvx_pick_rounds, _p(labels), D, H, W, int(k), spacing, seed, n, _p(state), _p(other), nbytes, _p(changed))
+        flags = changed[:n].tolist()  # the wait
+        if 0 in flags:
+            return state, done + flags.index(0) + 1  # from that round on both states hold the fixpoint
+        done += n
+        if n % 2:
+            state, other = other, state  # the last round wrote the other one
+    raise _lib.CvxError(f"pick_select: no fixpoint after max_rounds = {max_rounds} rounds")
+
+
+def pick_emit(labels: torch.Tensor, fg: torch.Tensor, state: torch.Tensor, radius: int) -> torch.Tensor:
+    """int32 [P, 8] on the device: the picks of ``state`` (``pick_select``) in raster order, each row z, y, x, id, Mz, My, Mx, n with
+    M the sum of the offsets o of the ball of ``radius`` with p + o in ``labels > 0`` (``fg``, of ``pick_pack``) and n their count:
+    the outward normal is -M / |M|.  The host waits once, for P."""
+    dev, D, H, W = _volumes_check("pick_emit", labels=(labels, torch.int32))
+    radius = _pick_int("pick_emit", "radius", radius, _lib.PICK_RADIUS_MIN, _lib.PICK_RADIUS_MAX)
+    nbytes = _pick_bitmaps("pick_emit", D, H, W, fg=(fg, 1), state=(state, 2))
+    _dev_check(labels, fg, state)
+    lib = _lib.load()
+    row_first = torch.empty(max(D * H, 1), dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    call(dev, "cvx_pick_count", lib.cvx_pick_count, _p(state), D, H, W, nbytes, _p(row_first), _p(total))
+    count = int(total.item())  # the one wait
+    table = torch.empty((count, _lib.PICK_COLS), dtype=torch.int32, device=dev)
+    call(dev, "cvx_pick_emit", lib.cvx_pick_emit, _p(labels), _p(fg), _p(state), _p(row_first), D, H, W, radius, nbytes, count, _p(table))
+    return table
+
+
+def pick_surface(labels: torch.Tensor, k: int, *, spacing: int, radius: int, seed: int, max_rounds: int = 4096) -> torch.Tensor:
+    """int32 [P, 8] on the device, the pick table of the instances 1..k of ``labels`` (int32 [D, H, W]): surface voxels of each
+    instance no two of which are closer than ``spacing`` voxels and such that every surface voxel has one of its id closer than that
+    (``pick_pack``, ``pick_select``, ``pick_emit``; the definition is in include/cryovit_hip.h).  Rows are in raster order: z, y, x,
+    id, Mz, My, Mx, n.  Ids past k are foreground without picks.  Integers only, bit-reproducible (csrc/picks.hip)."""
+    dev, D, H, W = _volumes_check("pick_surface", labels=(labels, torch.int32))
+    if k < 0:
+        raise _lib.CvxError(f"pick_surface: k must be >= 0, got {k}")
+    spacing = _pick_int("pick_surface", "spacing", spacing, _lib.PICK_SPACING_MIN, _lib.PICK_SPACING_MAX)
+    radius = _pick_int("pick_surface", "radius", radius, _lib.PICK_RADIUS_MIN, _lib.PICK_RADIUS_MAX)
+    if k == 0 or labels.numel() == 0:
+        return torch.empty((0, _lib.PICK_COLS), dtype=torch.int32, device=dev)
+    fg, state = pick_pack(labels, k, radius)
+    state, _ = pick_select(labels, k, state, spacing=spacing, seed=seed, max_rounds=max_rounds)
+    return pick_emit(labels, fg, state, radius)
+
+
 # ---- a prediction scored at its boundary (`cryovit evaluate --boundary`): scored slices, surfaces, distance histograms ----
 
 HIST_BINS_MAX = 2**24 + 1  # of surface_distance_hist

@@ -23,6 +23,9 @@ runs on a written file (``analysis.instances.label_and_split`` / ``measure``, ``
 mask is cleaned in HBM before it is labelled, each file also holds ``<label_key>_cleaned`` and the table gains ``added_voxels``.
 ``curvature`` and ``curvature_radius`` (with ``instances``) are the fields of ``analysis.curvature.CurvatureOptions``: the membrane
 curvature is measured last, each file also holds ``<label_key>_curvature`` and the table gains its columns after every other.
+``pick`` and the other ``pick_*`` (with ``instances``) are the fields of ``analysis.picks.PickOptions``: spaced surface positions with
+membrane normals are placed after everything else and written as ``picks/<tomo stem>_<label_key>.csv`` and ``.star``; the table
+gains ``picks`` and ``picks_unoriented`` as its last columns.
 """
 
 from __future__ import annotations
@@ -38,6 +41,7 @@ from cryovit_amd import io
 from cryovit_amd.analysis.cleanup import CleanupOptions, added_rows, added_voxels, clean_mask, log_totals
 from cryovit_amd.analysis.curvature import CurvatureOptions, check_mesh_format
 from cryovit_amd.analysis.instances import InstanceOptions, label_and_split, measure
+from cryovit_amd.analysis.picks import PickOptions
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
 from cryovit_amd.run import writers
@@ -77,13 +81,14 @@ def _predict_file(model, dataset, idx: int, threshold: float, encoder, batch_siz
     return item.aux_data["data"], mask
 
 
-def _write_measured(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, measured, mesh_format: str, cleaned=None) -> Path:
+def _write_measured(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, measured, mesh_format: str, cleaned=None,
+                    picks: PickOptions | None = None) -> Path:
     """``writers.write_measured`` with the datasets of ``writers.write_segmentation`` (and ``<label>_cleaned`` where the mask was
     cleaned); the conversion of the raw volume to float32 is part of the writer thread's work."""
     datasets = {"data": raw.astype(np.float32), f"{label_key}_preds": segs.astype(np.uint8, copy=False)}
     if cleaned is not None:
         datasets[f"{label_key}_cleaned"] = cleaned.astype(np.uint8, copy=False)
-    return writers.write_measured(result_dir, tomo_name, label_key, datasets, labels, table, measured, mesh_format)
+    return writers.write_measured(result_dir, tomo_name, label_key, datasets, labels, table, measured, mesh_format, picks=picks)
 
 
 def _pinned(tensor) -> np.ndarray:
@@ -99,13 +104,19 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                   split_min_core: int = 0, shape: bool = False, skeleton: bool = False,
                   skeleton_end_radius: float = 2.0, thickness: bool = False, mesh: bool = False, mesh_smooth: int = 0,
                   mesh_format: str = "ply", close_radius: float | None = None, fill_holes: str | None = None,
-                  open_radius: float | None = None, curvature: bool = False, curvature_radius: int = 5) -> list[Path]:
+                  open_radius: float | None = None, curvature: bool = False, curvature_radius: int = 5,
+                  pick: bool = False, pick_spacing: int = 8, pick_radius: int = 5, pick_offset: float = 0.0, pick_scale: float = 1.0,
+                  pick_seed: int = 0) -> list[Path]:
     opts = InstanceOptions(connectivity=connectivity, min_size=min_size, morphology=morphology, split_radius=split_radius,
                            split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
                            thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
     cleanup = CleanupOptions(close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius)
     curve = CurvatureOptions(curvature=curvature, curvature_radius=curvature_radius)
+    picking = PickOptions(pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
+                          pick_seed=pick_seed)
     if not instances:
+        if pick:
+            raise ValueError("pick=True needs instances=True: the picks are placed on the labelled instances")
         if curvature:
             raise ValueError("curvature=True needs instances=True: it is measured on the labelled instances")
         for name in InstanceOptions.MEASUREMENTS:
@@ -119,6 +130,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
     opts.validate()
     cleanup.validate()
     curve.validate()
+    picking.validate()
     check_mesh_format(curvature, mesh, mesh_format)
     rank, _, world = world_info()
     device = select_device(device)
@@ -150,7 +162,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 labels, table, component = label_and_split(cleaned, opts)
                 host_labels = _pinned(labels)  # on its way while the instances are measured
                 host_table = table.cpu().numpy()
-                found = measure(labels, int(table.shape[0]), component, opts, curvature=curve)
+                found = measure(labels, int(table.shape[0]), component, opts, curvature=curve, picks=picking)
                 if cleanup.any:
                     host_cleaned = _pinned(cleaned)
                     found.extra = added_rows(added_voxels(labels, predicted, int(table.shape[0])), found.extra)
@@ -159,7 +171,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:
                 pending.append((i, writer.submit(_write_measured, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),
-                                                 host_labels, host_table, found, mesh_format, host_cleaned)))
+                                                 host_labels, host_table, found, mesh_format, host_cleaned, picking)))
             else:
                 pending.append((i, writer.submit(writers.write_segmentation, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy())))
             while len(pending) > 2:

@@ -11,6 +11,8 @@
                          ``<label>_curvature`` (float32, 1/voxel, NaN off the scored surface; gzip), and
                          <results_dir>/instances/<tomo stem>_<label>.csv, one row per instance
   write_measured         (not in the reference) write_mesh and write_instances of one ``analysis.instances.measure`` result
+  write_picks            (not in the reference) <results_dir>/picks/<tomo stem>_<label>.csv and .star: spaced surface positions with
+                         membrane normals, every pick in the CSV, the oriented ones as RELION particles in the STAR file
   write_mesh             (not in the reference) <results_dir>/meshes/<tomo stem>_<label>.ply or .stl, the surface of the labelled mask
   write_instance_matches (not in the reference) <results_dir>/instances/<sample>_<tomo stem>.csv of ``cryovit evaluate
                         --instance-metrics``: every annotated instance with its best predicted partner, then the unmatched predicted ones
@@ -33,6 +35,7 @@ from cryovit_amd import io
 from cryovit_amd.analysis.distances import PAIR_COLUMNS
 from cryovit_amd.analysis.instances import INSTANCE_COLUMNS, instance_rows, merge_columns
 from cryovit_amd.analysis.curvature import curvature_map
+from cryovit_amd.analysis.picks import PickOptions, pick_records, write_picks_csv, write_star
 from cryovit_amd.analysis.thickness import thickness_map
 
 
@@ -109,12 +112,15 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
 
 
 def write_measured(results_dir, tomo_name: str, label_key: str, datasets: dict[str, np.ndarray], labels: np.ndarray, table: np.ndarray,
-                   measured, mesh_format: str = "ply") -> Path:
+                   measured, mesh_format: str = "ply", picks: PickOptions | None = None) -> Path:
     """Everything one file gets from ``analysis.instances.measure``, for ``label_file`` and for the writer thread of ``infer``:
     ``write_mesh`` where ``measured`` (an ``analysis.instances.Measured`` of host arrays) holds a mesh, and ``write_instances`` of the
     rows of the host ``table`` with the columns of ``measured.extra`` after them, the skeleton and the thickness map (the root of
     ``measured.t2`` is taken here, off the thread that feeds the GPU) and the curvature map (``measured.curvature`` becomes the
-    float volume here as well; ``measured.vertex_curvature`` goes into the PLY).  Returns the .hdf path."""
+    float volume here as well; ``measured.vertex_curvature`` goes into the PLY); ``write_picks`` of ``measured.picks`` under the
+    options ``picks`` where there is a pick table.  Returns the .hdf path."""
+    if measured.picks is not None:
+        write_picks(results_dir, tomo_name, label_key, measured.picks, picks if picks is not None else PickOptions(pick=True))
     if measured.mesh is not None:
         write_mesh(results_dir, tomo_name, label_key, *measured.mesh, mesh_format, vertex_values=measured.vertex_curvature)
     rows = instance_rows(table)
@@ -122,6 +128,16 @@ def write_measured(results_dir, tomo_name: str, label_key: str, datasets: dict[s
     return write_instances(results_dir, tomo_name, label_key, datasets, labels, rows, skeleton=measured.skeleton,
                            thickness=None if measured.t2 is None else thickness_map(measured.t2),
                            curvature=None if measured.curvature is None else curvature_map(measured.curvature))
+
+
+def write_picks(results_dir, tomo_name: str, label_key: str, table: np.ndarray, opts: PickOptions) -> tuple[Path, Path]:
+    """<results_dir>/picks/<tomo stem>_<label>.csv (every pick) and .star (the oriented ones, ``_rlnMicrographName`` = the tomogram's
+    stem) of the host pick table under ``opts`` (``analysis.picks.pick_records``, ``write_picks_csv``, ``write_star``).  Returns both
+    paths."""
+    stem = Path(tomo_name).stem
+    records = pick_records(table, opts)
+    base = Path(results_dir) / "picks" / f"{stem}_{label_key}"
+    return write_picks_csv(base.with_name(base.name + ".csv"), records), write_star(base.with_name(base.name + ".star"), records, stem)
 
 
 def write_mesh(results_dir, tomo_name: str, label_key: str, vertices: np.ndarray, triangles: np.ndarray, ids: np.ndarray,

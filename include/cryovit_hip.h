@@ -932,6 +932,61 @@ int cvx_curvature_map(const int32_t* labels, int D, int H, int W, int radius, in
 int cvx_curvature_stats(const int32_t* labels, const int32_t* h, int D, int H, int W, long k, int64_t* table, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Membrane picking (`infer --instances --pick`, `cryovit instances --pick`): evenly spaced surface voxels of every instance, each
+ * with the moment of the ball that gives the membrane normal: the particle positions of subtomogram averaging.  Integers only, no
+ * atomics, bit-reproducible.
+ *
+ * labels int32 [D][H][W], F = labels > 0, instances 1..k.  Normal radius r, CVX_PICK_RADIUS_MIN <= r <= CVX_PICK_RADIUS_MAX;
+ * spacing s, CVX_PICK_SPACING_MIN <= s <= CVX_PICK_SPACING_MAX (voxels); seed, any uint32.
+ *   Candidate   a voxel p with 1 <= labels[p] <= k that is a surface voxel of F (the curvature section's surface: a face neighbour
+ *               inside the volume and not in F) and has r <= index <= extent - 1 - r on every axis, so the ball at p is not
+ *               clipped.  Ids play no part in what is surface: a face shared by two pieces is no surface.  A volume with an extent
+ *               below 2 r + 1 has no candidate.
+ *   Key         key(p) = (fmix32(i XOR seed) << 32) | i, i the linear voxel index (< 2^31 by CVX_COMPONENT_MAX_VOXELS), fmix32
+ *               murmur3's finaliser: h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16, all mod 2^32.  Keys
+ *               are distinct, so they order the candidates totally.
+ *   Picks       two candidates conflict when they carry the same id and the squared distance of their voxel centres is < s*s.  The
+ *               picks are the lexicographically first maximal independent set: go through the candidates by increasing key and take
+ *               one unless it conflicts with one already taken.  Within an id no two picks are closer than s, and every candidate
+ *               lies closer than s to a pick of its id.
+ *   Normal      at a pick p, M(p) = the sum over o in B(r) of o * [p + o in F], three int32 (z, y, x), |M| < 2^19, B the curvature
+ *               section's ball; n(p) = #{o in B(r) : p + o in F}.  The outward unit normal is -M / |M| (the host computes it in
+ *               float64); M == 0 marks the pick as unoriented (a one-voxel sheet: its two sides are indistinguishable).
+ *   Pick table  int32 [P][CVX_PICK_COLS] in raster order of the voxel index, each row z, y, x, id, Mz, My, Mx, n.
+ * The selection runs as synchronous rounds over a state of two bitmaps, uint64 [2][D][H][WW], WW = ceil(W / 64), bit i of word w of a
+ * row = voxel x = 64 w + i: [0] undecided (the candidates at the start), [1] picked (empty at the start).  In one round an undecided
+ * p is rejected when a picked voxel conflicts with it, picked when no undecided conflicting voxel has a smaller key, and waits
+ * otherwise; the fixpoint is the set of picks above, and a round after it changes nothing.
+ *   cvx_pick_workspace_bytes  the bytes B of one bitmap, 8 per 64 voxels of a row; < 0 on bad extents.  fg holds B bytes, a state
+ *                             2 B; every entry takes B as workspace_bytes and refuses a smaller one.
+ *   cvx_pick_pack             fg = F as bits; state = (candidates, none picked).
+ *   cvx_pick_rounds           `rounds` rounds; round j = 0, 1, ... reads state_a when j is even and state_b when odd, and writes the
+ *                             whole of the other (only state_a need be initialised).  changed int32 [rounds], zeroed by the call:
+ *                             changed[j] = 1 iff round j rejected or picked a voxel.  After a round with changed[j] == 0 both states
+ *                             hold the fixpoint.
+ *   cvx_pick_count            row_first int32 [D*H] = the number of picked voxels in the rows before each row; total = P.
+ *   cvx_pick_emit             the pick table of `state` from fg and row_first; P as cvx_pick_count gave it (with a larger P the
+ *                             rows past the count are zero, with a smaller one the picks past it are left out).
+ * Refused with an error before any launch: negative extents, an extent above 32768, D*H*W > CVX_COMPONENT_MAX_VOXELS, r or s
+ * outside [2, 16], k < 0, rounds < 1, P outside [0, D*H*W], null pointers, misaligned arrays (int32: 4 bytes, bitmaps and total: 8
+ * bytes), a workspace_bytes below cvx_pick_workspace_bytes, fg inside state, state_a and state_b that overlap.  k == 0, an empty
+ * volume and P == 0 succeed and launch nothing (cvx_pick_rounds and cvx_pick_count still zero changed and total).
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_PICK_COLS 8
+#define CVX_PICK_RADIUS_MIN 2
+#define CVX_PICK_RADIUS_MAX 16
+#define CVX_PICK_SPACING_MIN 2
+#define CVX_PICK_SPACING_MAX 16
+long cvx_pick_workspace_bytes(int D, int H, int W);
+int cvx_pick_pack(const int32_t* labels, int D, int H, int W, long k, int radius, uint64_t* fg, uint64_t* state, long workspace_bytes,
+                  hipStream_t stream);
+int cvx_pick_rounds(const int32_t* labels, int D, int H, int W, long k, int spacing, uint32_t seed, int rounds, uint64_t* state_a,
+                    uint64_t* state_b, long workspace_bytes, int32_t* changed, hipStream_t stream);
+int cvx_pick_count(const uint64_t* state, int D, int H, int W, long workspace_bytes, int32_t* row_first, int64_t* total, hipStream_t stream);
+int cvx_pick_emit(const int32_t* labels, const uint64_t* fg, const uint64_t* state, const int32_t* row_first, int D, int H, int W, int radius,
+                  long workspace_bytes, long P, int32_t* table, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Raw tomogram -> uint8 in [0, 255] (`cryovit preprocess`, `features --normalize`): bin, moments, order statistics, quantise.
  * A volume is [D][H][W] of one of the CVX_VOL_* element types; CVX_VOL_I32 is what the bin pass makes of an integer source.
  * Everything but the two float32 moment sums is exact and bit-reproducible; those two are reproducible and bounded (below).
