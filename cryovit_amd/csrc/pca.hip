@@ -296,16 +296,20 @@ __device__ __forceinline__ float np_mod1(float a) {
 __device__ void pca_colour(const float u[3], const float* __restrict__ mm, uint8_t rgb[3]) {
 #pragma clang fp contract(off)
     float c[3];
+    bool defined = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float sub = u[k] - mm[k];
         const float top = mm[3 + k] - mm[k];  // max over the block of (u - min): rounding is monotonic
         c[k] = sub / top;
+        // a channel that is constant over the block is 0 / 0 in numpy; its NaN goes through arr.max(-1) and ptp, `delta > 0` is
+        // false and the hue stays 0.  fmaxf / fminf would drop the NaN and take a hue from the other two channels.
+        defined = defined && top > 0.f && c[k] == c[k];
     }
     const float amax = fmaxf(fmaxf(c[0], c[1]), c[2]), amin = fminf(fminf(c[0], c[1]), c[2]);
     const float delta = amax - amin;
     float hue = 0.f;
-    if (delta > 0.f) {
+    if (defined && delta > 0.f) {
         if (c[2] == amax) hue = 4.0f + (c[0] - c[1]) / delta;
         else if (c[1] == amax) hue = 2.0f + (c[2] - c[0]) / delta;
         else if (c[0] == amax) hue = (c[1] - c[2]) / delta;
@@ -345,8 +349,8 @@ __device__ __forceinline__ uint8_t pca_grey(const void* __restrict__ data, long 
     } else {
         const float sub = ((const float*)data)[off] - mm[6];
         const float top = mm[7] - mm[6];
-        const float g = sub / top * 255.0f;
-        return (uint8_t)(int)g;
+        const float g = top > 0.f ? sub / top * 255.0f : 0.f;  // a constant volume is 0 / 0 in numpy, which nan_to_num makes 0
+        return g == g ? (uint8_t)(int)g : 0;                   // a NaN voxel likewise; never cast a NaN
     }
 }
 

@@ -58,14 +58,17 @@ def _taps(t: float) -> np.ndarray:
     return np.array([c2(t + 1), c1(t), c1(1 - t), c2(2 - t)])
 
 
-def _up_matrix(n: int) -> np.ndarray:
+def _up_matrix(n: int, taps=_taps, last=None) -> np.ndarray:
+    """[2n, n] interpolation matrix; ``taps`` and ``last`` (the index the taps clamp to, n - 1) are there for the mutants of
+    tests/pca_cases.py."""
+    last = n - 1 if last is None else last
     m = np.zeros((2 * n, n))
     for o in range(2 * n):
         s = 0.5 * (o + 0.5) - 0.5
         f = int(np.floor(s))
-        wts = _taps(s - f)
+        wts = taps(s - f)
         for k in range(4):
-            m[o, min(max(f - 1 + k, 0), n - 1)] += wts[k]
+            m[o, min(max(f - 1 + k, 0), last)] += wts[k]
     return m
 
 
@@ -118,8 +121,9 @@ def color(features: np.ndarray, hsv=(rgb_to_hsv, hsv_to_rgb)) -> np.ndarray:
     to_hsv, to_rgb = hsv
     f = np.asarray(features, dtype=np.float32)
     f = f - f.min(axis=(0, 1, 2))
-    f = f / f.max(axis=(0, 1, 2))
-    x = to_hsv(f)
+    with np.errstate(invalid="ignore"):  # a channel that is constant over the block: 0 / 0, NaN all the way to a hue of 0
+        f = f / f.max(axis=(0, 1, 2))
+        x = to_hsv(f)
     x[..., 1] = 0.9
     x[..., 2] = 0.75
     x[..., 0] = (0.0 + x[..., 0]) % 1.0
@@ -135,15 +139,18 @@ def grey(data: np.ndarray) -> np.ndarray:
         return np.nan_to_num(d * 255.0).astype(np.uint8)
 
 
-def canvases(data: np.ndarray, colour: np.ndarray) -> np.ndarray:
-    """[D', 16h, 32w, 3]: black, the flipped grey slice at (0, 0), the flipped colour map at (W, 0)."""
+def canvases(data: np.ndarray, colour: np.ndarray, x_map: int | None = None) -> np.ndarray:
+    """[D', 16h, 32w, 3]: black, the flipped colour map at (x_map, 0) (x_map = W unless given; clipped at the right edge of the
+    canvas), then the flipped grey slice at (0, 0), which wins inside x < W, y < H."""
     D, H, W = data.shape
     Dp, CH, MW = colour.shape[:3]
+    x_map = W if x_map is None else x_map
+    mw = max(min(MW, 2 * MW - x_map), 0)
     out = np.zeros((Dp, CH, 2 * MW, 3), dtype=np.uint8)
     g = grey(data)
     for j, idx in enumerate(selected(D)):
+        out[j, :, x_map : x_map + mw] = colour[j][::-1][:, :mw]
         out[j, :H, :W] = g[idx][::-1][..., None]
-        out[j, :, W : W + MW] = colour[j][::-1]
     return out
 
 
