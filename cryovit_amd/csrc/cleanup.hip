@@ -25,11 +25,10 @@
 // crops `pad` voxels from every side of the map on the way: the closing runs on a zero-padded copy.
 // ADDED VOXELS.  k_mask_added walks labels and the mask as predicted in 4x8x64 tiles and counts per id the voxels that mask did
 // not have, with the per-id reduction of voxel_rows.h.
-#include "entry_checks.h"
+#include "bit_rows.h"
 
 namespace cvx {
 
-typedef unsigned long long Word;
 constexpr int FZ = 4, FY = 16, FW = 8;             // the flood tile: planes, rows, words of a row
 constexpr int GZ = FZ + 2, GY = FY + 2, GW = FW + 2;  // with its halo
 constexpr int kFloodCells = GZ * GY * GW;          // 1080 words = 8.4 KB
@@ -43,7 +42,7 @@ struct FloodDims {
 };
 
 inline FloodDims flood_dims(int D, int H, int W) {
-    const int WW = W / 64 + (W % 64 != 0);
+    const int WW = words_per_row(W);
     return FloodDims{D, H, W, WW, (WW + FW - 1) / FW, (H + FY - 1) / FY};
 }
 inline long flood_tiles(const FloodDims& d) { return (long)d.tw * d.ty * ((d.D + FZ - 1) / FZ); }  // <= D*H*WW <= D*H*W
@@ -56,14 +55,12 @@ __device__ __forceinline__ void st_word_dev(Word* p, Word v) { __hip_atomic_stor
 // one wave per word
 __global__ __launch_bounds__(kCclThreads) void k_mask_pack(const uint8_t* __restrict__ mask, FloodDims d, long words, int slices,
                                                            Word* __restrict__ open, Word* __restrict__ reach) {
-    const int lane = threadIdx.x & 63;
-    const long g = (long)blockIdx.x * (kCclThreads / 64) + (threadIdx.x >> 6);
-    if (g >= words) return;  // the whole wave alike
-    const long row = g / d.WW;
-    const int w = (int)(g % d.WW), x = w * 64 + lane;
+    long g, row;
+    int x;
+    if (!wave_word(d.WW, words, g, row, x)) return;
     const Word o = __ballot(x < d.W && mask[row * d.W + x] == 0);
-    if (lane != 0) return;
-    const int y = (int)(row % d.H), z = (int)(row / d.H);
+    if ((threadIdx.x & 63) != 0) return;
+    const int w = (int)(g % d.WW), y =(int)(row % d.H), z = (int)(row / d.H);
     Word seed = 0;  // the border voxels of this word
     if (y == 0 || y == d.H - 1 || (!slices && (z == 0 || z == d.D - 1))) seed = ~0ull;
     if (w == 0) seed |= 1ull;
@@ -258,8 +255,7 @@ extern "C" int cvx_mask_flood_pack(const uint8_t* mask, int D, int H, int W, int
     if (open == reach) return cvx_fail("mask_flood_pack", "open and reach must be different arrays");
     const FloodDims d = flood_dims(D, H, W);
     const long words = (long)D * H * d.WW;
-    hipLaunchKernelGGL(k_mask_pack, dim3((unsigned)((words + kCclThreads / 64 - 1) / (kCclThreads / 64))), dim3(kCclThreads), 0, st, mask, d, words,
-                       slices, (Word*)open, (Word*)reach);
+    hipLaunchKernelGGL(k_mask_pack, dim3(wave_blocks_of(words)), dim3(kCclThreads), 0, st, mask, d, words, slices, (Word*)open, (Word*)reach);
     return cvx_check_launch();
 }
 

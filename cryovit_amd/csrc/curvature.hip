@@ -6,7 +6,7 @@
 // THE MAP.  n(v) = the foreground voxels under the ball at v is needed on a two-voxel shell only: the scored surface voxels p and
 // their background face neighbours q.
 //   k_curv_pack   F = labels > 0 as bits, one uint64 per 64 voxels of a row ([D][H][WW], bit i of word w = voxel x = 64 w + i;
-//                 bits past W are 0): one wave per word, one __ballot.
+//                 bits past W are 0; bit_rows.h): one wave per word, one __ballot.
 //   k_curv_map    one workgroup per 4x8x64 output tile.
 //     1. the rows of the tile with a halo of one row and one word go to LDS; 32 threads form the word of scored surface voxels
 //        of the tile's 32 rows with shifts and ANDs.  A tile without one stores CURV_NONE and is done: most tiles end here.
@@ -23,14 +23,12 @@
 // A q on the frame is also computed by the tile it lies in when that one needs it: the price of no n volume in global memory.
 //
 // THE TABLE.  k_curv_stats reads labels with the one-voxel halo of voxel_rows.h (a surface voxel without a score is found by its
-// neighbours) and h directly, and reduces per id as thickness.hip does: thread, wave with a single id, the waves of a workgroup
-// that hold the same id, then 64-bit integer atomics.  min and max start from +-2^62 and are set to 0 by k_curv_stats_fin for an
+// neighbours) and h directly, and reduces per id by table_reduce of voxel_rows.h: thread, wave with a single id, the waves of a
+// workgroup that hold the same id, then 64-bit integer atomics.  min and max start from +-2^62 and are set to 0 by k_curv_stats_fin for an
 // id without a scored voxel.
-#include "entry_checks.h"
+#include "bit_rows.h"
 
 namespace cvx {
-
-typedef unsigned long long Word;
 
 constexpr int kCurvRmin = CVX_CURVATURE_RADIUS_MIN, kCurvRmax = CVX_CURVATURE_RADIUS_MAX;
 constexpr int EZ = TZ + 2, EY = TY + 2, EX = TX + 2;  // the frame: the tile and one voxel around it
@@ -52,11 +50,8 @@ inline Ball make_ball(int r) {
     for (int dz = 0; dz <= r; ++dz) {
         int ym = 0;
         for (int dy = 0; dy <= r; ++dy) {
-            const int rem = r * r - dz * dz - dy * dy;
-            int w = -1;
-            if (rem >= 0) {
-                w = 0;
-                while ((w + 1) * (w + 1) <= rem) ++w;
+            const int w = ball_half_width(r * r, dz, dy);
+            if (w >= 0) {
                 ym = dy;
                 b.N += (2 * w + 1) * (dz ? 2 : 1) * (dy ? 2 : 1);
             }
@@ -67,25 +62,13 @@ inline Ball make_ball(int r) {
     return b;
 }
 
-struct CurvDims {
-    int D, H, W, WW;
-    int tx, ty;  // tiles along x and y
-};
-
-inline CurvDims curv_dims(int D, int H, int W) {
-    const Dims d = ccl_dims(D, H, W);
-    return CurvDims{D, H, W, W / 64 + (W % 64 != 0), d.tx, d.ty};
-}
-
 // one wave per word
-__global__ __launch_bounds__(kCclThreads) void k_curv_pack(const int* __restrict__ labels, CurvDims d, long words, Word* __restrict__ bits) {
-    const int lane = threadIdx.x & 63;
-    const long g = (long)blockIdx.x * (kCclThreads / 64) + (threadIdx.x >> 6);
-    if (g >= words) return;  // the whole wave alike
-    const long row = g / d.WW;
-    const int x = (int)(g % d.WW) * 64 + lane;
+__global__ __launch_bounds__(kCclThreads) void k_curv_pack(const int* __restrict__ labels, BitDims d, long words, Word* __restrict__ bits) {
+    long g, row;
+    int x;
+    if (!wave_word(d.WW, words, g, row, x)) return;
     const Word f = __ballot(x < d.W && labels[row * d.W + x] > 0);
-    if (lane == 0) bits[g] = f;
+    if ((threadIdx.x & 63) == 0) bits[g] = f;
 }
 
 __global__ __launch_bounds__(kCclThreads) void k_curv_fill(int* __restrict__ h, long n) {
@@ -93,7 +76,7 @@ __global__ __launch_bounds__(kCclThreads) void k_curv_fill(int* __restrict__ h, 
     if (i < n) h[i] = CVX_CURV_NONE;
 }
 
-__global__ __launch_bounds__(kCclThreads) void k_curv_map(const Word* __restrict__ bits, CurvDims d, Ball ball, int* __restrict__ h) {
+__global__ __launch_bounds__(kCclThreads) void k_curv_map(const Word* __restrict__ bits, BitDims d, Ball ball, int* __restrict__ h) {
     static_assert(kCclThreads == TZ * TX && TX == 64, "one wave per z plane of the tile, one lane per x");
     static_assert(kCclThreads >= kFrameRows && kCclThreads >= TZ * TY, "one thread per row of the frame");
     extern __shared__ Word rows[];  // [TZ + 2 R1][TY + 2 R1][3]: the rows from (z0 - R1, y0 - R1), the words x0 / 64 - 1 .. + 1
@@ -183,7 +166,7 @@ __global__ __launch_bounds__(kCclThreads) void k_curv_map(const Word* __restrict
         int slot = first[f];
         if (lane == 0 && (side & 1)) queue[slot] = (unsigned short)(f * EX);
         slot += side & 1;
-        if (nd >> lane & 1) queue[slot + __popcll(nd & ((1ull << lane) - 1))] = (unsigned short)(f * EX + 1 + lane);
+        if (nd >> lane & 1) queue[queue_slot(slot, nd, lane)] = (unsigned short)(f * EX + 1 + lane);
         if (lane == 0 && (side & 2)) queue[slot + __popcll(nd)] = (unsigned short)(f * EX + EX - 1);
     }
     __syncthreads();
@@ -199,11 +182,7 @@ __global__ __launch_bounds__(kCclThreads) void k_curv_map(const Word* __restrict
             const int az = dz < 0 ? -dz : dz, ym = ball.ymax[az];
             for (int dy = -ym; dy <= ym; ++dy) {
                 const int w = ball.hw[az][dy < 0 ? -dy : dy];
-                const Word* p = centre + (dz * HY + dy) * 3;
-                const int lo = xb - w, i0 = lo >> 6, sh = lo & 63;  // 47 <= lo <= 128; the span ends at bit xb + w <= 144
-                Word v = p[i0] >> sh;
-                if (sh) v |= p[min(i0 + 1, 2)] << (64 - sh);  // i0 == 2 only with sh == 0
-                n += __popcll(v & ((2ull << (2 * w)) - 1));
+                n += __popcll(row_span(centre + (dz * HY + dy) * 3, 3, xb - w, w));  // 47 <= xb - w <= 128, xb + w <= 144
             }
         }
         n_of[cell] = (unsigned short)n;
@@ -254,6 +233,14 @@ __global__ __launch_bounds__(kCclThreads) void k_curv_stats_fin(long long* __res
 struct CurvAcc {
     long long n, sum, sum2, convex, unscored;
     int lo, hi;
+    __device__ void wave_combine() {
+        n = wave_sum(n), sum = wave_sum(sum), sum2 = wave_sum(sum2), convex = wave_sum(convex), unscored = wave_sum(unscored);
+        lo = wave_min(lo), hi = wave_max(hi);
+    }
+    __device__ void merge(const CurvAcc& a) {
+        n += a.n, sum += a.sum, sum2 += a.sum2, convex += a.convex, unscored += a.unscored;
+        lo = min(lo, a.lo), hi = max(hi, a.hi);
+    }
 };
 constexpr CurvAcc kCurvEmpty{0, 0, 0, 0, 0, INT_MAX, INT_MIN};
 
@@ -277,8 +264,6 @@ __global__ __launch_bounds__(kCclThreads) void k_curv_stats(const int* __restric
                                                             long long* __restrict__ out, Dims d, int k) {
     static_assert(kCclThreads == TZ * TX && TX == 64, "one wave per z plane of the tile, one lane per x");
     __shared__ int ids[kHaloCells];
-    __shared__ CurvAcc wave_acc[TZ];
-    __shared__ int wave_id_of[TZ];
     int z0, y0, x0;
     tile_origin(d, z0, y0, x0);
     tile_load_ids(labels, d, z0, y0, x0, INT_MAX, ids);  // every positive label is foreground, whatever k
@@ -315,57 +300,14 @@ __global__ __launch_bounds__(kCclThreads) void k_curv_stats(const int* __restric
             acc.lo = min(acc.lo, v);
             acc.hi = max(acc.hi, v);
         }
-    // the wave: one id among the threads that hold one?  Then it combines over its lanes; else every thread sends its own
-    const int one = wave_single_id(cur);
-    if (!one) {
-        if (cur) curv_flush(out, cur, acc);
-    } else {
-        acc.n = wave_sum(acc.n);
-        acc.sum = wave_sum(acc.sum);
-        acc.sum2 = wave_sum(acc.sum2);
-        acc.convex = wave_sum(acc.convex);
-        acc.unscored = wave_sum(acc.unscored);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            acc.lo = min(acc.lo, __shfl_xor(acc.lo, o));
-            acc.hi = max(acc.hi, __shfl_xor(acc.hi, o));
-        }
-        if (lane == 0) wave_acc[wave] = acc;
-    }
-    if (lane == 0) wave_id_of[wave] = one;
-    __syncthreads();
-    // the workgroup: thread 0 combines the waves that hold the same id, once per id
-    if (threadIdx.x != 0) return;
-    for (int w = 0; w < TZ; ++w) {
-        if (!first_wave_of_id(wave_id_of, w)) continue;
-        const int id = wave_id_of[w];
-        CurvAcc s = wave_acc[w];
-        for (int u = w + 1; u < TZ; ++u)
-            if (wave_id_of[u] == id) {
-                const CurvAcc a = wave_acc[u];
-                s.n += a.n, s.sum += a.sum, s.sum2 += a.sum2, s.convex += a.convex, s.unscored += a.unscored;
-                s.lo = min(s.lo, a.lo), s.hi = max(s.hi, a.hi);
-            }
-        curv_flush(out, id, s);
-    }
+    table_reduce(acc, cur, [&](int id, CurvAcc& a) { curv_flush(out, id, a); });
 }
 
 }  // namespace cvx
 
 using namespace cvx;
 
-namespace {
-
-// the bytes of the packed foreground: one uint64 per 64 voxels of a row
-long curv_bytes(const CurvDims& d) { return (long)d.D * d.H * d.WW * (long)sizeof(Word); }
-
-}  // namespace
-
-extern "C" long cvx_curvature_workspace_bytes(int D, int H, int W) {
-    long n = 0;
-    if (extents_fault(D, H, W, kExtentMax, n)) return -1;
-    return curv_bytes(curv_dims(D, H, W));
-}
+extern "C" long cvx_curvature_workspace_bytes(int D, int H, int W) { return bitmap_workspace_bytes(D, H, W); }
 
 extern "C" int cvx_curvature_map(const int32_t* labels, int D, int H, int W, int radius, int32_t* h, void* workspace, long workspace_bytes,
                                  hipStream_t st) {
@@ -375,17 +317,16 @@ extern "C" int cvx_curvature_map(const int32_t* labels, int D, int H, int W, int
     if (n == 0) return 0;
     if (!labels || !h || !workspace) return cvx_fail("curvature_map", "null pointer");
     if ((((uintptr_t)labels | (uintptr_t)h) & 3) || ((uintptr_t)workspace & 7)) return cvx_fail("curvature_map", "misaligned pointer");
-    const CurvDims d = curv_dims(D, H, W);
-    if (workspace_bytes < curv_bytes(d)) return cvx_fail("curvature_map", "workspace shorter than cvx_curvature_workspace_bytes");
+    const BitDims d = bit_dims(D, H, W);
+    if (workspace_bytes < bitmap_bytes(d)) return cvx_fail("curvature_map", "workspace shorter than cvx_curvature_workspace_bytes");
     if (labels == h) return cvx_fail("curvature_map", "labels and h must be different arrays");
     const int least = 2 * radius + 3;  // below it no index satisfies r + 1 <= i <= extent - r - 2
     if (D < least || H < least || W < least) {
         hipLaunchKernelGGL(k_curv_fill, dim3(blocks_of(n)), dim3(kCclThreads), 0, st, h, n);
         return cvx_check_launch();
     }
-    const long words = (long)D * H * d.WW;
-    hipLaunchKernelGGL(k_curv_pack, dim3((unsigned)((words + kCclThreads / 64 - 1) / (kCclThreads / 64))), dim3(kCclThreads), 0, st, labels, d,
-                       words, (Word*)workspace);
+    const long words = bitmap_words(d);
+    hipLaunchKernelGGL(k_curv_pack, dim3(wave_blocks_of(words)), dim3(kCclThreads), 0, st, labels, d, words, (Word*)workspace);
     if (const int rc = cvx_check_launch()) return rc;
     const Ball ball = make_ball(radius);
     const size_t lds = (size_t)(TZ + 2 * (radius + 1)) * (TY + 2 * (radius + 1)) * 3 * sizeof(Word);

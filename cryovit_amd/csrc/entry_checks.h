@@ -1,6 +1,7 @@
-// What the entry points of the analysis passes (components, edt, nearest, overlap, split, shape, skeleton, thickness, mesh, cleanup, curvature) check and
-// compute on the host before they launch: the extents of the volume, the clamp of an id count, the block and tile counts of a
-// launch, whether k table rows can be addressed.  Refusals go through cvx_fail(entry, why) of host_util.h.
+// What the entry points of the analysis passes (components, edt, nearest, overlap, split, shape, skeleton, thickness, mesh, cleanup,
+// curvature, picks) check and compute on the host before they launch: the extents of the volume, the clamp of an id count, the
+// block and tile counts of a launch, whether k table rows can be addressed.  Refusals go through cvx_fail(entry, why) of
+// host_util.h.  cleanup, curvature and picks include it through bit_rows.h, which adds the word and byte counts of a bitmap.
 #pragma once
 #include "voxel_rows.h"
 #include "host_util.h"

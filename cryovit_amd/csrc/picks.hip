@@ -4,8 +4,8 @@
 // two calls give the same bits.
 //
 // PACK.  k_pick_pack: F = labels > 0 and "the label lies in 1..k" as bits, one uint64 per 64 voxels of a row ([D][H][WW], bit i of
-//   word w = voxel x = 64 w + i; bits past W are 0): one wave per word, two __ballots, as k_curv_pack.  k_pick_cand: one thread per
-//   word turns the second bitmap into the candidates with shifts and ANDs of F's words: surface, the band r <= index <= extent - 1 - r.
+//   word w = voxel x = 64 w + i; bits past W are 0; bit_rows.h): one wave per word, two __ballots.  k_pick_cand: one thread per word
+//   turns the second bitmap into the candidates with shifts and ANDs of F's words: surface, the band r <= index <= extent - 1 - r.
 //   The state of the selection is a pair of bitmaps [2][D][H][WW]: undecided (the candidates at the start) and picked (empty).
 //
 // SELECTION.  k_pick_round, one workgroup per 4x8x64 tile, one round: an undecided voxel p is rejected when a picked voxel conflicts
@@ -26,27 +26,15 @@
 //   reads it once); k_pick_place: one thread per word writes z, y, x, id of its picks at row base + popcount(bits before);
 //   k_pick_moments: one wave per pick, lanes over the (dz, dy) rows of the ball |o|^2 <= r^2: dz * popcount, dy * popcount and the
 //   x-moment of the set bits of `row & span` from six masked popcounts; a wave sum, plain stores.
-#include "entry_checks.h"
+#include "bit_rows.h"
 
 namespace cvx {
-
-typedef unsigned long long Word;
 
 constexpr int kPickRmin = CVX_PICK_RADIUS_MIN, kPickRmax = CVX_PICK_RADIUS_MAX;
 constexpr int kPickSmin = CVX_PICK_SPACING_MIN, kPickSmax = CVX_PICK_SPACING_MAX;
 constexpr int kPickRows = TZ * TY;  // 32 rows of one word per tile
 constexpr int kPickScanThreads = 1024, kPickScanPer = 4;
 constexpr int kPickHw = kPickSmax;  // half-width table [kPickHw][kPickHw]: |dz|, |dy| <= s - 1
-
-struct PickDims {
-    int D, H, W, WW;
-    int tx, ty;  // tiles along x and y
-};
-
-inline PickDims pick_dims(int D, int H, int W) {
-    const Dims d = ccl_dims(D, H, W);
-    return PickDims{D, H, W, W / 64 + (W % 64 != 0), d.tx, d.ty};
-}
 
 // murmur3's finaliser
 __device__ __forceinline__ unsigned fmix32(unsigned h) {
@@ -58,34 +46,15 @@ __device__ __forceinline__ unsigned fmix32(unsigned h) {
     return h;
 }
 
-// the half-width along x of {o : |o|^2 <= R2} in the row (az, ay); -1: the row is outside
-__device__ __forceinline__ int half_width(int R2, int az, int ay) {
-    const int rem = R2 - az * az - ay * ay;
-    if (rem < 0) return -1;
-    int w = 0;
-    while ((w + 1) * (w + 1) <= rem) ++w;
-    return w;
-}
-
-// the bits lo .. lo + 2w of a row of `words` words, as bits 0 .. 2w; 0 <= lo, lo + 2w < 64 * words, w <= 16
-__device__ __forceinline__ Word row_span(const Word* p, int words, int lo, int w) {
-    const int i0 = lo >> 6, sh = lo & 63;
-    Word v = p[i0] >> sh;
-    if (sh && i0 + 1 < words) v |= p[i0 + 1] << (64 - sh);
-    return v & ((2ull << (2 * w)) - 1);
-}
-
 // one wave per word
-__global__ __launch_bounds__(kCclThreads) void k_pick_pack(const int* __restrict__ labels, PickDims d, long words, int k, Word* __restrict__ fg,
+__global__ __launch_bounds__(kCclThreads) void k_pick_pack(const int* __restrict__ labels, BitDims d, long words, int k, Word* __restrict__ fg,
                                                            Word* __restrict__ state) {
-    const int lane = threadIdx.x & 63;
-    const long g = (long)blockIdx.x * (kCclThreads / 64) + (threadIdx.x >> 6);
-    if (g >= words) return;  // the whole wave alike
-    const long row = g / d.WW;
-    const int x = (int)(g % d.WW) * 64 + lane;
+    long g, row;
+    int x;
+    if (!wave_word(d.WW, words, g, row, x)) return;
     const int l = x < d.W ? labels[row * d.W + x] : 0;
     const Word f = __ballot(l > 0), ok = __ballot(l >= 1 && l <= k);
-    if (lane == 0) {
+    if ((threadIdx.x & 63) == 0) {
         fg[g] = f;
         state[g] = ok;
         state[words + g] = 0;
@@ -93,7 +62,7 @@ __global__ __launch_bounds__(kCclThreads) void k_pick_pack(const int* __restrict
 }
 
 // state[g] = the candidates among the voxels with an id: one thread per word, in place (only F's words of other rows are read)
-__global__ __launch_bounds__(kCclThreads) void k_pick_cand(const Word* __restrict__ fg, PickDims d, long words, int r, Word* __restrict__ state) {
+__global__ __launch_bounds__(kCclThreads) void k_pick_cand(const Word* __restrict__ fg, BitDims d, long words, int r, Word* __restrict__ state) {
     const long g = (long)blockIdx.x * kCclThreads + threadIdx.x;
     if (g >= words) return;
     const Word ok = state[g];
@@ -117,7 +86,7 @@ constexpr int kPickLdsFixed = 2 * kPickRows * (int)sizeof(Word) + 48 * (int)size
 __host__ __device__ constexpr int pick_round_lds(int s) { return 2 * pick_round_rows(s) * (int)sizeof(Word) + kPickLdsFixed; }
 
 __global__ __launch_bounds__(kCclThreads) void k_pick_round(const int* __restrict__ labels, const Word* __restrict__ in, Word* __restrict__ out,
-                                                            PickDims d, long words, int s, unsigned seed, int* __restrict__ changed) {
+                                                            BitDims d, long words, int s, unsigned seed, int* __restrict__ changed) {
     static_assert(kCclThreads == TZ * TX && TX == 64, "one wave per z plane of the tile, one lane per x");
     static_assert(kCclThreads >= kPickHw * kPickHw && kTileVox < (1 << 14), "one thread per table entry; a cell and a decision fit in a uint16");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -135,7 +104,7 @@ __global__ __launch_bounds__(kCclThreads) void k_pick_round(const int* __restric
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const Word* in_u = in;
     const Word* in_p = in + words;
-    const Word tail = d.W % 64 ? (1ull << d.W % 64) - 1 : ~0ull;  // a bit past W is never followed to a label, whatever the state holds
+    const Word tail = tail_mask(d.W);  // a bit past W is never followed to a label, whatever the state holds
     // 1. the tile's own words
     long own_g = -1;
     Word u = 0, pk = 0;
@@ -170,7 +139,7 @@ __global__ __launch_bounds__(kCclThreads) void k_pick_round(const int* __restric
         pic[c] = p;
         seen |= p != 0;
     }
-    if (threadIdx.x < kPickHw * kPickHw) hw[threadIdx.x] = (signed char)half_width(s * s - 1, threadIdx.x / kPickHw, threadIdx.x % kPickHw);
+    if (threadIdx.x < kPickHw * kPickHw) hw[threadIdx.x] = (signed char)ball_half_width(s * s - 1, threadIdx.x / kPickHw, threadIdx.x % kPickHw);
     if (threadIdx.x == 0) {
         int at = 0;
         for (int f = 0; f < kPickRows; ++f) {
@@ -183,7 +152,7 @@ __global__ __launch_bounds__(kCclThreads) void k_pick_round(const int* __restric
     // 3. the queue
     for (int f = wave; f < kPickRows; f += TZ) {
         const Word m = own_u[f];
-        if (m >> lane & 1) queue[first[f] + __popcll(m & ((1ull << lane) - 1))] = (unsigned short)(f * TX + lane);
+        if (m >> lane & 1) queue[queue_slot(first[f], m, lane)] = (unsigned short)(f * TX + lane);
     }
     __syncthreads();
     // 4. the decisions
@@ -235,7 +204,7 @@ __global__ __launch_bounds__(kCclThreads) void k_pick_round(const int* __restric
     for (int f = wave; f < kPickRows; f += TZ) {
         const Word m = own_u[f];
         int decision = 0;
-        if (m >> lane & 1) decision = queue[first[f] + __popcll(m & ((1ull << lane) - 1))] >> 14;
+        if (m >> lane & 1) decision = queue[queue_slot(first[f], m, lane)] >> 14;
         const Word gone = __ballot(decision != 0), taken = __ballot(decision == 2);
         const int z = z0 + f / TY, y = y0 + f % TY;
         if (lane == 0 && z < d.D && y < d.H) {
@@ -294,13 +263,13 @@ __global__ __launch_bounds__(kPickScanThreads) void k_pick_scan(int* __restrict_
 }
 
 // z, y, x, id of every pick: one thread per word
-__global__ __launch_bounds__(kCclThreads) void k_pick_place(const int* __restrict__ labels, const Word* __restrict__ picked, PickDims d, long words,
+__global__ __launch_bounds__(kCclThreads) void k_pick_place(const int* __restrict__ labels, const Word* __restrict__ picked, BitDims d, long words,
                                                             const int* __restrict__ row_first, long P, int* __restrict__ table) {
     const long g = (long)blockIdx.x * kCclThreads + threadIdx.x;
     if (g >= words) return;
     const int w = (int)(g % d.WW);
     Word v = picked[g];
-    if (w == d.WW - 1 && d.W % 64) v &= (1ull << d.W % 64) - 1;  // a bit past W is no voxel, whatever the state holds
+    if (w == d.WW - 1) v &= tail_mask(d.W);  // a bit past W is no voxel, whatever the state holds
     if (!v) return;
     const long row = g / d.WW;
     long slot = row_first[row];
@@ -317,7 +286,7 @@ __global__ __launch_bounds__(kCclThreads) void k_pick_place(const int* __restric
 }
 
 // M and n of every pick: one wave per pick
-__global__ __launch_bounds__(kCclThreads) void k_pick_moments(const Word* __restrict__ fg, PickDims d, int r, long P, int* __restrict__ table) {
+__global__ __launch_bounds__(kCclThreads) void k_pick_moments(const Word* __restrict__ fg, BitDims d, int r, long P, int* __restrict__ table) {
     const int lane = threadIdx.x & 63;
     const long p = (long)blockIdx.x * (kCclThreads / 64) + (threadIdx.x >> 6);
     if (p >= P) return;  // the whole wave alike
@@ -329,7 +298,7 @@ __global__ __launch_bounds__(kCclThreads) void k_pick_moments(const Word* __rest
     const int side = 2 * r + 1;
     for (int c = lane; inside && c < side * side; c += 64) {
         const int dz = c / side - r, dy = c % side - r;
-        const int w = half_width(r * r, dz < 0 ? -dz : dz, dy < 0 ? -dy : dy);
+        const int w = ball_half_width(r * r, dz < 0 ? -dz : dz, dy < 0 ? -dy : dy);
         if (w < 0) continue;
         const Word v = row_span(fg + ((long)(z + dz) * d.H + y + dy) * d.WW, d.WW, x - w, w);  // bit j: dx = j - w
         const int cnt = __popcll(v);
@@ -350,9 +319,6 @@ using namespace cvx;
 
 namespace {
 
-// the bytes of one bitmap: one uint64 per 64 voxels of a row
-long pick_bytes(const PickDims& d) { return (long)d.D * d.H * d.WW * (long)sizeof(Word); }
-
 constexpr int kNoOption = INT_MIN;  // for pick_fault: the entry has no such argument
 
 // what every entry refuses about the volume and the options it takes.  nullptr: fine
@@ -366,11 +332,7 @@ const char* pick_fault(int D, int H, int W, int radius, int spacing, long k, lon
 
 }  // namespace
 
-extern "C" long cvx_pick_workspace_bytes(int D, int H, int W) {
-    long n = 0;
-    if (extents_fault(D, H, W, kExtentMax, n)) return -1;
-    return pick_bytes(pick_dims(D, H, W));
-}
+extern "C" long cvx_pick_workspace_bytes(int D, int H, int W) { return bitmap_workspace_bytes(D, H, W); }
 
 extern "C" int cvx_pick_pack(const int32_t* labels, int D, int H, int W, long k, int radius, uint64_t* fg, uint64_t* state, long workspace_bytes,
                              hipStream_t st) {
@@ -379,13 +341,13 @@ extern "C" int cvx_pick_pack(const int32_t* labels, int D, int H, int W, long k,
     if (n == 0 || k == 0) return 0;
     if (!labels || !fg || !state) return cvx_fail("pick_pack", "null pointer");
     if (((uintptr_t)labels & 3) || (((uintptr_t)fg | (uintptr_t)state) & 7)) return cvx_fail("pick_pack", "misaligned pointer");
-    const PickDims d = pick_dims(D, H, W);
-    if (workspace_bytes < pick_bytes(d)) return cvx_fail("pick_pack", "workspace shorter than cvx_pick_workspace_bytes");
-    const long words = (long)D * H * d.WW;
+    const BitDims d = bit_dims(D, H, W);
+    if (workspace_bytes < bitmap_bytes(d)) return cvx_fail("pick_pack", "workspace shorter than cvx_pick_workspace_bytes");
+    const long words = bitmap_words(d);
     if (fg == state || fg == state + words) return cvx_fail("pick_pack", "fg and state must be different arrays");
     const int least = 2 * radius + 1;  // below it no index satisfies r <= i <= extent - 1 - r
     const bool none = D < least || H < least || W < least;
-    hipLaunchKernelGGL(k_pick_pack, dim3((unsigned)((words + kCclThreads / 64 - 1) / (kCclThreads / 64))), dim3(kCclThreads), 0, st, labels, d,
+    hipLaunchKernelGGL(k_pick_pack, dim3(wave_blocks_of(words)), dim3(kCclThreads), 0, st, labels, d,
                        words, none ? 0 : clamp_int(k), (Word*)fg, (Word*)state);
     if (const int rc = cvx_check_launch()) return rc;
     if (none) return 0;
@@ -403,15 +365,15 @@ extern "C" int cvx_pick_rounds(const int32_t* labels, int D, int H, int W, long 
     if (n > 0 && k > 0) {
         if (!labels || !state_a || !state_b) return cvx_fail("pick_rounds", "null pointer");
         if (((uintptr_t)labels & 3) || (((uintptr_t)state_a | (uintptr_t)state_b) & 7)) return cvx_fail("pick_rounds", "misaligned pointer");
-        const long bytes = pick_bytes(pick_dims(D, H, W));
+        const long bytes = bitmap_bytes(bit_dims(D, H, W));
         if (workspace_bytes < bytes) return cvx_fail("pick_rounds", "workspace shorter than cvx_pick_workspace_bytes");
         const uintptr_t a = (uintptr_t)state_a, b = (uintptr_t)state_b;
         if (a < b + 2 * (uintptr_t)bytes && b < a + 2 * (uintptr_t)bytes) return cvx_fail("pick_rounds", "state_a and state_b must not overlap");
     }
     CVX_HIP(hipMemsetAsync(changed, 0, (size_t)rounds * sizeof(int), st));
     if (n == 0 || k == 0) return 0;
-    const PickDims d = pick_dims(D, H, W);
-    const long words = (long)D * H * d.WW, tiles = tile_count(ccl_dims(D, H, W));
+    const BitDims d = bit_dims(D, H, W);
+    const long words = bitmap_words(d), tiles = tile_count(ccl_dims(D, H, W));
     CVX_HIP(hipFuncSetAttribute((const void*)k_pick_round, hipFuncAttributeMaxDynamicSharedMemorySize, pick_round_lds(kPickSmax)));
     for (int r = 0; r < rounds; ++r) {
         const Word* in = (const Word*)(r % 2 ? state_b : state_a);
@@ -434,8 +396,8 @@ extern "C" int cvx_pick_count(const uint64_t* state, int D, int H, int W, long w
     }
     if (!state || !row_first) return cvx_fail("pick_count", "null pointer");
     if (((uintptr_t)state & 7) || ((uintptr_t)row_first & 3)) return cvx_fail("pick_count", "misaligned pointer");
-    const PickDims d = pick_dims(D, H, W);
-    if (workspace_bytes < pick_bytes(d)) return cvx_fail("pick_count", "workspace shorter than cvx_pick_workspace_bytes");
+    const BitDims d = bit_dims(D, H, W);
+    if (workspace_bytes < bitmap_bytes(d)) return cvx_fail("pick_count", "workspace shorter than cvx_pick_workspace_bytes");
     const long rows = (long)D * H, words = rows * d.WW;
     hipLaunchKernelGGL(k_pick_count, dim3(blocks_of(rows)), dim3(kCclThreads), 0, st, (const Word*)state + words, rows, d.WW, row_first);
     if (const int rc = cvx_check_launch()) return rc;
@@ -452,13 +414,12 @@ extern "C" int cvx_pick_emit(const int32_t* labels, const uint64_t* fg, const ui
     if (!labels || !fg || !state || !row_first || !table) return cvx_fail("pick_emit", "null pointer");
     if ((((uintptr_t)labels | (uintptr_t)row_first | (uintptr_t)table) & 3) || (((uintptr_t)fg | (uintptr_t)state) & 7))
         return cvx_fail("pick_emit", "misaligned pointer");
-    const PickDims d = pick_dims(D, H, W);
-    if (workspace_bytes < pick_bytes(d)) return cvx_fail("pick_emit", "workspace shorter than cvx_pick_workspace_bytes");
-    const long words = (long)D * H * d.WW;
+    const BitDims d = bit_dims(D, H, W);
+    if (workspace_bytes < bitmap_bytes(d)) return cvx_fail("pick_emit", "workspace shorter than cvx_pick_workspace_bytes");
+    const long words = bitmap_words(d);
     CVX_HIP(hipMemsetAsync(table, 0, (size_t)P * CVX_PICK_COLS * sizeof(int32_t), st));  // a P above the state's count leaves zero rows
     hipLaunchKernelGGL(k_pick_place, dim3(blocks_of(words)), dim3(kCclThreads), 0, st, labels, (const Word*)state + words, d, words, row_first, P, table);
     if (const int rc = cvx_check_launch()) return rc;
-    constexpr int kWaves = kCclThreads / 64;
-    hipLaunchKernelGGL(k_pick_moments, dim3((unsigned)((P + kWaves - 1) / kWaves)), dim3(kCclThreads), 0, st, (const Word*)fg, d, radius, P, table);
+    hipLaunchKernelGGL(k_pick_moments, dim3(wave_blocks_of(P)), dim3(kCclThreads), 0, st, (const Word*)fg, d, radius, P, table);
     return cvx_check_launch();
 }

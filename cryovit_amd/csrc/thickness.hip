@@ -29,9 +29,9 @@
 // below 3 * 2^30 < 2^32: squared distances are compared as uint32 against d2 < 2^31.  CVX_EDT_NONE anywhere (the volume's
 // maximum) takes its own path: every nonzero voxel gets CVX_EDT_NONE, nothing is gathered.
 //
-// The table pass reads labels and t2 directly (no neighbourhood, no halo): a thread sums along y while the id stays the same, a
-// wave whose threads end on one id combines over its lanes, the waves of a workgroup that hold the same id combine through LDS,
-// then 64-bit integer atomics.  r_fx = floor(sqrt(t2 << 16)) starts from the double-precision root (t2 << 16 < 2^47 is exact in a
+// The table pass reads labels and t2 directly (no neighbourhood, no halo): a thread sums along y while the id stays the same, then
+// table_reduce of voxel_rows.h: a wave whose threads end on one id combines over its lanes, the waves of a workgroup that hold the
+// same id combine through LDS, then 64-bit integer atomics.  r_fx = floor(sqrt(t2 << 16)) starts from the double-precision root (t2 << 16 < 2^47 is exact in a
 // double) and is corrected with integer comparisons.
 #include "entry_checks.h"
 
@@ -131,8 +131,7 @@ __global__ __launch_bounds__(kCclThreads) void k_thickness_map(const int* __rest
         int m = INT_MAX;
         for (int yy = 0; yy < TY; ++yy)
             if (fg >> yy & 1) m = min(m, best[(wave * TY + yy) * kThRow + lane]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+        m = wave_min(m);
         if (lane == 0) wave_floor[wave] = m;
         __syncthreads();
         m = wave_floor[0];
@@ -212,6 +211,14 @@ __global__ __launch_bounds__(kCclThreads) void k_thickness_stats_init(long long*
 struct ThAcc {
     long long n, sum_t2, sum_r;
     int lo, hi;
+    __device__ void wave_combine() {
+        n = wave_sum(n), sum_t2 = wave_sum(sum_t2), sum_r = wave_sum(sum_r);
+        lo = wave_min(lo), hi = wave_max(hi);
+    }
+    __device__ void merge(const ThAcc& a) {
+        n += a.n, sum_t2 += a.sum_t2, sum_r += a.sum_r;
+        lo = min(lo, a.lo), hi = max(hi, a.hi);
+    }
 };
 constexpr ThAcc kThEmpty{0, 0, 0, INT_MAX, -1};
 
@@ -241,8 +248,6 @@ __device__ __forceinline__ void thickness_flush(long long* __restrict__ out, int
 __global__ __launch_bounds__(kCclThreads) void k_thickness_stats(const int* __restrict__ labels, const int* __restrict__ t2,
                                                                  long long* __restrict__ out, Dims d, int k) {
     static_assert(kCclThreads == TZ * TX && TX == 64, "one wave per z plane of the tile, one lane per x");
-    __shared__ ThAcc wave_acc[TZ];
-    __shared__ int wave_id_of[TZ];
     int z0, y0, x0;
     tile_origin(d, z0, y0, x0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -266,37 +271,7 @@ __global__ __launch_bounds__(kCclThreads) void k_thickness_stats(const int* __re
             acc.lo = min(acc.lo, t);
             acc.hi = max(acc.hi, t);
         }
-    // the wave: one id among the threads that hold one?  Then it combines over its lanes; else every thread sends its own
-    const int one = wave_single_id(cur);
-    if (!one) {
-        if (cur) thickness_flush(out, cur, acc);
-    } else {
-        acc.n = wave_sum(acc.n);
-        acc.sum_t2 = wave_sum(acc.sum_t2);
-        acc.sum_r = wave_sum(acc.sum_r);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            acc.lo = min(acc.lo, __shfl_xor(acc.lo, o));
-            acc.hi = max(acc.hi, __shfl_xor(acc.hi, o));
-        }
-        if (lane == 0) wave_acc[wave] = acc;
-    }
-    if (lane == 0) wave_id_of[wave] = one;
-    __syncthreads();
-    // the workgroup: thread 0 combines the waves that hold the same id, once per id
-    if (threadIdx.x != 0) return;
-    for (int w = 0; w < TZ; ++w) {
-        if (!first_wave_of_id(wave_id_of, w)) continue;
-        const int id = wave_id_of[w];
-        ThAcc s = wave_acc[w];
-        for (int u = w + 1; u < TZ; ++u)
-            if (wave_id_of[u] == id) {
-                const ThAcc a = wave_acc[u];
-                s.n += a.n, s.sum_t2 += a.sum_t2, s.sum_r += a.sum_r;
-                s.lo = min(s.lo, a.lo), s.hi = max(s.hi, a.hi);
-            }
-        thickness_flush(out, id, s);
-    }
+    table_reduce(acc, cur, [&](int id, ThAcc& a) { thickness_flush(out, id, a); });
 }
 
 }  // namespace cvx

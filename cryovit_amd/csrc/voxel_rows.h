@@ -3,8 +3,12 @@
 // loads / stores, the kernel that fills a component table with the empty box, and the integer add / min / max into a table row.
 // For the passes that walk it in 4x8x64 tiles (shape.hip, skeleton.hip, thickness.hip, mesh.hip, cleanup.hip, curvature.hip): a tile's ids with their
 // one-voxel halo in LDS, and the stages of the per-id reduction: a thread's sums to a table row (table_flush), the wave's
-// single-id test (wave_single_id), the first wave of a workgroup that holds an id (first_wave_of_id).  And the sums and the scan
-// over the lanes of a wave.  Device code only; every includer compiles its own copy.
+// single-id test (wave_single_id), the first wave of a workgroup that holds an id (first_wave_of_id), and for a row that is more
+// than sums (thickness.hip, curvature.hip: sums with a min and a max) the wave and workgroup stages as a whole, over the pass's own
+// accumulator struct and flush (table_reduce).  shape.hip (columns combined in parallel), skeleton.hip and cleanup.hip's added
+// voxels (they stop at the wave) and mesh.hip (an LDS hash) keep their own stages on purpose.  And the sums, the min / max and the
+// scan over the lanes of a wave.  The bit-packed volumes of cleanup.hip, curvature.hip and picks.hip are in bit_rows.h.  Device
+// code only; every includer compiles its own copy.
 #pragma once
 #include "common.h"
 #include "../../include/cryovit_hip.h"
@@ -154,6 +158,18 @@ __device__ __forceinline__ int wave_sum(int v) {
     return v;
 }
 
+// the smallest / largest v, in every lane
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
 // the sum of v over this lane and the lanes below it
 __device__ __forceinline__ int wave_scan_incl(int v) {
     const int lane = threadIdx.x & 63;
@@ -190,6 +206,37 @@ __device__ __forceinline__ bool first_wave_of_id(const int* ids, int w) {
     bool first = ids[w] != 0;
     for (int u = 0; u < w; ++u) first &= ids[u] != ids[w];
     return first;
+}
+
+// The wave and workgroup stages for a table whose row is not plain sums (thickness.hip, curvature.hip: sums with a min and a max).
+// acc = a thread's accumulator, cur = the id it belongs to (0: none).  Acc::wave_combine() leaves the wave's in every lane,
+// Acc::merge(a) takes in another wave's, flush(id, acc) sends one to row id - 1.  A wave whose threads hold one id combines over
+// its lanes, else every thread flushes its own; thread 0 then merges the waves of the workgroup that hold the same id and flushes
+// once per id.  Every thread of the workgroup calls it, once.
+template <class Acc, class Flush>
+__device__ __forceinline__ void table_reduce(Acc& acc, int cur, Flush flush) {
+    static_assert(kCclThreads == TZ * 64, "TZ waves");
+    __shared__ Acc wave_acc[TZ];
+    __shared__ int wave_id_of[TZ];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int one = wave_single_id(cur);
+    if (!one) {
+        if (cur) flush(cur, acc);
+    } else {
+        acc.wave_combine();
+        if (lane == 0) wave_acc[wave] = acc;
+    }
+    if (lane == 0) wave_id_of[wave] = one;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 0; w < TZ; ++w) {
+        if (!first_wave_of_id(wave_id_of, w)) continue;
+        const int id = wave_id_of[w];
+        Acc s = wave_acc[w];
+        for (int u = w + 1; u < TZ; ++u)
+            if (wave_id_of[u] == id) s.merge(wave_acc[u]);
+        flush(id, s);
+    }
 }
 
 }  // namespace cvx

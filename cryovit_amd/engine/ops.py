@@ -816,6 +816,24 @@ def instance_shape_stats(labels: torch.Tensor, k: int, *, connectivity: int = 26
 SPLIT_ROUND_BATCH = 4  # regrowth rounds launched per read of their "changed" flags
 
 
+def _to_fixpoint(launch, batch: int, limit: int, failure: str) -> int:
+    """Runs rounds ``batch`` at a time (the last batch before ``limit`` may be shorter) until one changed nothing, and returns the
+    rounds up to and including that one.  ``launch(n)`` runs n more rounds and returns their n "changed" flags as a list: the one
+    wait per batch.  Raises ``failure`` when ``limit`` rounds did not reach the fixpoint."""
+    done = 0
+    while done < limit:
+        n = min(batch, limit - done)
+        flags = launch(n)
+        if 0 in flags:
+            return done + flags.index(0) + 1
+        done += n
+    raise _lib.CvxError(failure)
+
+
+def _bit_words(W: int) -> int:  # the uint64 words of a row of W voxels as bits (csrc/bit_rows.h)
+    return (W + 63) // 64
+
+
 def _volume_check(what: str, name: str, t, dtype) -> None:
     if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != dtype:
         got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
@@ -869,17 +887,13 @@ def split_regrow(labels: torch.Tensor, keys: torch.Tensor, *, connectivity: int 
     if max_rounds < 1:
         raise _lib.CvxError(f"split_regrow: max_rounds must be >= 1, got {max_rounds}")
     dev, D, H, W = _volumes_check("split_regrow", labels=(labels, torch.int32), keys=(keys, torch.int64))
-    lib = _lib.load()
     changed = torch.empty(SPLIT_ROUND_BATCH, dtype=torch.int32, device=dev)
-    done = 0
-    while done < max_rounds:
-        batch = min(SPLIT_ROUND_BATCH, max_rounds - done)
-        call(dev, "cvx_split_rounds", lib.cvx_split_rounds, _p(labels), _p(keys), D, H, W, int(connectivity), batch, _p(changed))
-        flags = changed[:batch].tolist()  # the wait
-        if 0 in flags:
-            return done + flags.index(0) + 1
-        done += batch
-    raise _lib.CvxError(f"split_regrow: no fixpoint after max_rounds = {max_rounds} rounds")
+
+    def launch(n: int) -> list[int]:
+        call(dev, "cvx_split_rounds", _lib.load().cvx_split_rounds, _p(labels), _p(keys), D, H, W, int(connectivity), n, _p(changed))
+        return changed[:n].tolist()  # the wait
+
+    return _to_fixpoint(launch, SPLIT_ROUND_BATCH, max_rounds, f"split_regrow: no fixpoint after max_rounds = {max_rounds} rounds")
 
 
 def split_renumber(labels: torch.Tensor, keys: torch.Tensor, seeds: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -1025,7 +1039,7 @@ def mask_open(mask: torch.Tensor, radius: float) -> torch.Tensor:
 
 def _flood_words(what: str, shape, **words) -> None:
     D, H, W = shape
-    want = (D, H, (W + 63) // 64)
+    want = (D, H, _bit_words(W))
     for name, t in words.items():
         _volume_check(what, name, t, torch.int64)
         if tuple(t.shape) != want:
@@ -1037,7 +1051,7 @@ def mask_flood_pack(mask: torch.Tensor, *, slices: bool = False) -> tuple[torch.
     ``open`` = the voxels where ``mask`` (uint8 [D, H, W]) is 0, ``reach`` = those of them on the border: the six faces of the
     volume, or with ``slices`` the four edges of every z-slice."""
     dev, D, H, W = _volumes_check("mask_flood_pack", mask=(mask, torch.uint8))
-    open_, reach = (torch.empty((D, H, (W + 63) // 64), dtype=torch.int64, device=dev) for _ in range(2))
+    open_, reach = (torch.empty((D, H, _bit_words(W)), dtype=torch.int64, device=dev) for _ in range(2))
     call(dev, "cvx_mask_flood_pack", _lib.load().cvx_mask_flood_pack, _p(mask), D, H, W, int(bool(slices)), _p(open_), _p(reach))
     return open_, reach
 
@@ -1058,18 +1072,14 @@ def mask_flood(open_: torch.Tensor, reach: torch.Tensor, shape, *, background: i
     dev = _dev_check(open_, reach)
     if D * H * W == 0:
         return 0
-    lib = _lib.load()
     changed = torch.empty(MASK_ROUND_BATCH, dtype=torch.int32, device=dev)
-    done = 0
-    while done < max_rounds:
-        batch = min(MASK_ROUND_BATCH, max_rounds - done)
-        call(dev, "cvx_mask_flood_rounds", lib.cvx_mask_flood_rounds, _p(open_), _p(reach), D, H, W, int(background), int(bool(slices)),
-             batch, _p(changed))
-        flags = changed[:batch].tolist()  # the wait
-        if 0 in flags:
-            return done + flags.index(0) + 1
-        done += batch
-    raise _lib.CvxError(f"mask_flood: no fixpoint after max_rounds = {max_rounds} rounds")
+
+    def launch(n: int) -> list[int]:
+        call(dev, "cvx_mask_flood_rounds", _lib.load().cvx_mask_flood_rounds, _p(open_), _p(reach), D, H, W, int(background),
+             int(bool(slices)), n, _p(changed))
+        return changed[:n].tolist()  # the wait
+
+    return _to_fixpoint(launch, MASK_ROUND_BATCH, max_rounds, f"mask_flood: no fixpoint after max_rounds = {max_rounds} rounds")
 
 
 def mask_flood_unpack(reach: torch.Tensor, shape) -> torch.Tensor:
@@ -1267,14 +1277,8 @@ def skeleton_thin_level(alive: torch.Tensor, d2: torch.Tensor, k: int, level: in
         raise _lib.CvxError(f"skeleton_thin_level: need k >= 0 and end_d2 >= 1, got {k}, {end_d2}")
     dev, *_ = _volumes_check("skeleton_thin_level", alive=(alive, torch.int32), d2=(d2, torch.int32))  # before anything is launched
     changed = torch.empty(batch, dtype=torch.int32, device=dev)
-    done = 0
-    while done < max_cycles:
-        now = min(batch, max_cycles - done)
-        flags = skeleton_cycles(alive, d2, k, level * level, end_d2, now, changed).tolist()  # the wait
-        if 0 in flags:
-            return done + flags.index(0) + 1
-        done += now
-    raise _lib.CvxError(f"skeleton_thin_level: level {level} has no fixpoint after max_cycles = {max_cycles} cycles")
+    return _to_fixpoint(lambda n: skeleton_cycles(alive, d2, k, level * level, end_d2, n, changed).tolist(),  # the wait
+                        batch, max_cycles, f"skeleton_thin_level: level {level} has no fixpoint after max_cycles = {max_cycles} cycles")
 
 
 def skeletonize_instances(labels: torch.Tensor, k: int, *, d2: torch.Tensor | None = None, end_radius: float = 2.0,
@@ -1488,7 +1492,7 @@ def _pick_int(what: str, name: str, value, lo: int, hi: int) -> int:
 
 def _pick_bitmaps(what: str, D: int, H: int, W: int, **bitmaps) -> int:
     """The bytes of one bitmap of a [D, H, W] volume; raises unless every tensor is int64 with the words of its bitmaps."""
-    words = D * H * ((W + 63) // 64)
+    words = D * H * _bit_words(W)
     for name, (t, count) in bitmaps.items():
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.numel() != count * words:
             got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
@@ -1505,7 +1509,7 @@ def pick_pack(labels: torch.Tensor, k: int, radius: int) -> tuple[torch.Tensor, 
     radius = _pick_int("pick_pack", "radius", radius, _lib.PICK_RADIUS_MIN, _lib.PICK_RADIUS_MAX)
     if k < 0:
         raise _lib.CvxError(f"pick_pack: k must be >= 0, got {k}")
-    ww = (W + 63) // 64
+    ww = _bit_words(W)
     fg = torch.zeros((D, H, ww), dtype=torch.int64, device=dev)
     state = torch.zeros((2, D, H, ww), dtype=torch.int64, device=dev)
     call(dev, "cvx_pick_pack", _lib.load().cvx_pick_pack, _p(labels), D, H, W, int(k), radius, _p(fg), _p(state), fg.numel() * 8)
@@ -1533,17 +1537,17 @@ def pick_select(labels: torch.Tensor, k: int, state: torch.Tensor, *, spacing: i
     lib = _lib.load()
     other = torch.empty_like(state)
     changed = torch.empty(batch, dtype=torch.int32, device=dev)
-    done = 0
-    while done < max_rounds:
-        n = min(batch, max_rounds - done)
+
+    def launch(n: int) -> list[int]:
+        nonlocal state, other
         call(dev, "cvx_pick_rounds", lib.cvx_pick_rounds, _p(labels), D, H, W, int(k), spacing, seed, n, _p(state), _p(other), nbytes, _p(changed))
         flags = changed[:n].tolist()  # the wait
-        if 0 in flags:
-            return state, done + flags.index(0) + 1  # from that round on both states hold the fixpoint
-        done += n
-        if n % 2:
-            state, other = other, state  # the last round wrote the other one
-    raise _lib.CvxError(f"pick_select: no fixpoint after max_rounds = {max_rounds} rounds")
+        if n % 2 and 0 not in flags:
+            state, other = other, state  # the last round wrote the other one; from a fixpoint on both states hold it
+        return flags
+
+    rounds = _to_fixpoint(launch, batch, max_rounds, f"pick_select: no fixpoint after max_rounds = {max_rounds} rounds")
+    return state, rounds
 
 
 def pick_emit(labels: torch.Tensor, fg: torch.Tensor, state: torch.Tensor, radius: int) -> torch.Tensor:

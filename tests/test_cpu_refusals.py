@@ -176,6 +176,54 @@ ENTRIES = [
           extra=[{"V": -1}, {"T": -1}, {"V": 2**31}, {"c": 131073}, {"c": -131073}, {"workspace_bytes": 95}, {"workspace_bytes": -1},
                  {"V": 0, "T": 0}, {"V": 0, "T": 0, "vertices": None, "moved": None, "triangles": None, "workspace": None},
                  {"V": 0, "c": 131073}, {"c": 131073, "moved": None}]),
+    Entry("cvx_mask_flood_pack", [("mask", P1), ("dims", D0), ("slices", 0), ("open", P8), ("reach", P8)],
+          extra=[{"slices": 2}, {"slices": -1}, {"slices": 2, "open": None}, EMPTY, {**EMPTY, "mask": None, "open": None, "reach": None},
+                 {**EMPTY, "slices": 2}, {"reach": (1 << 20) + 4096 * 3}]),  # reach = open
+    Entry("cvx_mask_flood_rounds",
+          [("open", P8), ("reach", P8), ("dims", D0), ("background", 6), ("slices", 0), ("rounds", 1), ("changed", P4)],
+          extra=[{"background": 18}, {"background": 0}, {"slices": 2}, {"rounds": 0}, {"rounds": -1}, {"background": 18, "rounds": 0},
+                 {"slices": 2, "changed": None}, EMPTY, {**EMPTY, "open": None, "reach": None}, {**EMPTY, "changed": None},
+                 {"reach": 1 << 20}]),  # reach = open
+    Entry("cvx_mask_flood_unpack", [("reach", P8), ("dims", D0), ("out", P1)], extra=[EMPTY, {**EMPTY, "reach": None, "out": None}]),
+    Entry("cvx_mask_threshold", [("d2", P4), ("dims", D0), ("pad", 1), ("mode", 0), ("threshold_d2", 4), ("out", P1)],
+          extra=[{"pad": -1}, {"pad": 32769}, {"pad": 32768}, {"dims": (1, 1, INT_MAX - 1), "pad": 1}, {"mode": 2}, {"mode": -1},
+                 {"threshold_d2": -1}, {"threshold_d2": INT_MAX}, {"mode": 2, "threshold_d2": -1}, {"pad": -1, "mode": 2}, EMPTY,
+                 {**EMPTY, "d2": None, "out": None}, {**EMPTY, "mode": 2}]),
+    Entry("cvx_mask_added_voxels", [("labels", P4), ("before", P1), ("dims", D0), ("k", 1), ("out", P8)], k="k", cols=1,
+          extra=[{"k": 0}, {"k": 0, "labels": None, "before": None, "out": None}, {**EMPTY, "k": 0}, {"dims": (-1, 4, 4), "k": -1}]),
+    Entry("cvx_curvature_workspace_bytes", [("dims", D0)], cap=True,
+          extra=[EMPTY, {"dims": (5, 9, 65)}, {"dims": (5, 9, 64)}, {"dims": (32768, 32768, 1)}, {"dims": (32768, 32768, 2)}]),
+    Entry("cvx_curvature_map", [("labels", P4), ("dims", D0), ("radius", 2), ("h", P4), ("workspace", P8), ("workspace_bytes", BIG)], cap=True,
+          extra=[{"radius": 1}, {"radius": 17}, {"radius": 1, "labels": None}, {"dims": (32769, 4, 4), "radius": 1}, EMPTY,
+                 {**EMPTY, "labels": None, "h": None, "workspace": None}, {**EMPTY, "radius": 1}, {"workspace_bytes": 127},
+                 {"workspace_bytes": -1}, {"h": 1 << 20}, {"h": 1 << 20, "workspace_bytes": 127}, {"dims": (32768, 32768, 2)}]),  # h = labels
+    Entry("cvx_curvature_stats", [("labels", P4), ("h", P4), ("dims", D0), ("k", 1), ("table", P8)], cap=True, k="k", cols=7,
+          extra=[{"k": 0}, {"k": 0, "labels": None, "h": None, "table": None}, {**EMPTY, "k": 0},
+                 {"k": INT_MAX * 256 // 7 + 64}, {"k": INT_MAX * 256 // 7 + 64, "table": None}, {"dims": (32768, 32768, 2)}]),
+    Entry("cvx_pick_workspace_bytes", [("dims", D0)], cap=True,
+          extra=[EMPTY, {"dims": (5, 9, 65)}, {"dims": (5, 9, 64)}, {"dims": (32768, 32768, 1)}, {"dims": (32768, 32768, 2)}]),
+    Entry("cvx_pick_pack",
+          [("labels", P4), ("dims", D0), ("k", 1), ("radius", 2), ("fg", P8), ("state", P8), ("workspace_bytes", BIG)], cap=True, k="k",
+          extra=[{"radius": 1}, {"radius": 17}, {"radius": 1, "k": -1}, {"k": 0}, {"k": 0, "labels": None, "fg": None, "state": None},
+                 {"k": 0, "radius": 1}, EMPTY, {**EMPTY, "k": -1}, {"workspace_bytes": 127}, {"workspace_bytes": -1},
+                 {"state": (1 << 20) + 4096 * 4}, {"fg": (1 << 20) + 4096 * 5 + 128},  # state = fg; fg = state[1]
+                 {"dims": (32768, 32768, 2)}]),
+    Entry("cvx_pick_rounds",
+          [("labels", P4), ("dims", D0), ("k", 1), ("spacing", 2), ("seed", 0), ("rounds", 1), ("state_a", P8), ("state_b", P8),
+           ("workspace_bytes", BIG), ("changed", P4)], cap=True, k="k",
+          extra=[{"spacing": 1}, {"spacing": 17}, {"rounds": 0}, {"rounds": -1}, {"spacing": 1, "rounds": 0}, {"rounds": 0, "changed": None},
+                 {"k": 0, "changed": None}, {**EMPTY, "changed": None}, {"workspace_bytes": 127}, {"workspace_bytes": -1},
+                 {"state_b": (1 << 20) + 4096 * 6 + 8}, {"state_b": (1 << 20) + 4096 * 6 + 248},  # inside state_a's two bitmaps
+                 {"state_a": (1 << 20) + 4096 * 7 + 248}, {"dims": (32768, 32768, 2)}]),
+    Entry("cvx_pick_count", [("state", P8), ("dims", D0), ("workspace_bytes", BIG), ("row_first", P4), ("total", P8)], cap=True,
+          extra=[{"workspace_bytes": 127}, {"workspace_bytes": -1}, {**EMPTY, "total": None}, {**EMPTY, "total": (1 << 20) + 4},
+                 {"dims": (32768, 32768, 2)}]),
+    Entry("cvx_pick_emit",
+          [("labels", P4), ("fg", P8), ("state", P8), ("row_first", P4), ("dims", D0), ("radius", 2), ("workspace_bytes", BIG), ("P", 1),
+           ("table", P4)], cap=True,
+          extra=[{"radius": 1}, {"radius": 17}, {"P": -1}, {"P": 65}, {"radius": 1, "P": -1}, {"P": 0},
+                 {"P": 0, "labels": None, "fg": None, "state": None, "row_first": None, "table": None}, {"P": 0, "workspace_bytes": 127},
+                 {"workspace_bytes": 127}, {"workspace_bytes": -1}, {**EMPTY, "P": 0}, {**EMPTY, "P": 1}, {"dims": (32768, 32768, 2)}]),
 ]
 
 
@@ -214,7 +262,7 @@ def test_table_covers_every_analysis_entry():
     from cryovit_amd import _lib
 
     prefixes = ("cvx_components_", "cvx_edt_", "cvx_instance_", "cvx_split_", "cvx_nearest_", "cvx_skeleton_", "cvx_local_thickness_",
-                "cvx_mesh_")
+                "cvx_mesh_", "cvx_mask_", "cvx_curvature_", "cvx_pick_")
     want = {n for n in _lib.SIGNATURES if n.startswith(prefixes)} - {"cvx_split_stream"}  # the encoder's, no analysis entry
     assert want == {e.name for e in ENTRIES}
     for e in ENTRIES:

@@ -1,11 +1,16 @@
 """Compare the gfx950 kernels that one .hip file compiles to in two source trees (a refactor must leave them alone).
 
-    python tools/diff_kernel_asm.py OLD_TREE NEW_TREE gemm.hip [--ablation]
+    python tools/diff_kernel_asm.py OLD_TREE NEW_TREE gemm.hip [--ablation] [--by-name]
 
 Each tree's copy of the file is compiled to device assembly (``hipcc -S --cuda-device-only``: no GPU needed) with the flags
 of ``cryovit_amd/build.py`` of the NEW tree, the output is cut into one piece per kernel -- its instruction stream and its
 kernel descriptor (register counts, LDS and scratch size) -- and the kernels that differ or exist in one tree only are
 printed.  Comments, label numbers and ``__hip_cuid`` are ignored.  Exit status 1 if anything differs.
+
+Kernels are paired by their mangled name, which encodes the parameter types: after ``PickDims`` became ``BitDims`` every kernel that
+takes one is MISSING on both sides.  ``--by-name`` pairs them by the demangled qualified name with its template arguments and
+without the parameter list (``cvx::k_mask_round<26, false>``; needs ``c++filt``), and compares the bodies with the kernel's own
+symbol replaced by that name.  Overloads, which would share such a name within one tree, are reported as AMBIGUOUS and not compared.
 """
 
 from __future__ import annotations
@@ -60,16 +65,53 @@ def kernels(asm: str) -> dict[str, list[str]]:
     return out
 
 
+def qualified(mangled: list[str]) -> list[str]:
+    """the demangled names without return type and parameter list: ``void cvx::k<6, true>(int const*, cvx::A)`` -> ``cvx::k<6, true>``"""
+    r = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True)
+    out = []
+    for full in r.stdout.splitlines():
+        depth, cut = 0, len(full)
+        for i in range(len(full) - 1, -1, -1):  # the "(" that closes last: the parameter list
+            depth += (full[i] == ")") - (full[i] == "(")
+            if depth == 0 and full[i] == "(":
+                cut = i
+                break
+        head, depth, start = full[:cut], 0, 0
+        for i, c in enumerate(head):  # the last blank outside <>: the end of a template kernel's return type
+            depth += (c == "<") - (c == ">")
+            if c == " " and depth == 0:
+                start = i + 1
+        out.append(head[start:])
+    return out
+
+
+def by_name(ks: dict[str, list[str]], side: str) -> tuple[dict[str, list[str]], int]:
+    """ks keyed by qualified name, the kernel's own symbol replaced in its lines; and the number of names that collide"""
+    names = dict(zip(ks, qualified(list(ks))))
+    out: dict[str, list[str]] = {}
+    clash = {q for q in names.values() if list(names.values()).count(q) > 1}
+    for q in sorted(clash):
+        print(f"AMBIGUOUS in {side}: {q} is {', '.join(m for m in ks if names[m] == q)}")
+    for m, lines in ks.items():
+        if names[m] not in clash:
+            out[names[m]] = [ln.replace(m, names[m]) for ln in lines]
+    return out, len(clash)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("old", type=Path)
     ap.add_argument("new", type=Path)
     ap.add_argument("file", help="name of a file under cryovit_amd/csrc, e.g. gemm.hip")
     ap.add_argument("--ablation", action="store_true", help="compile with -DCVX_ABLATION")
+    ap.add_argument("--by-name", action="store_true", help="pair kernels by qualified name and template arguments, not by parameter types")
     a = ap.parse_args()
     build = load_build(a.new)
     old, new = (kernels(device_asm(build, t.resolve(), a.file, a.ablation)) for t in (a.old, a.new))
     bad = 0
+    if a.by_name:
+        (old, n_old), (new, n_new) = by_name(old, "old"), by_name(new, "new")
+        bad = n_old + n_new
     for k in sorted(set(old) | set(new)):
         if k not in old or k not in new:
             print(f"MISSING in {'old' if k not in old else 'new'}: {k}")
