@@ -21,6 +21,7 @@ from cryovit_amd.analysis import distances
 from cryovit_amd.analysis._tables import host_table
 from cryovit_amd.analysis.cleanup import CleanupOptions, added_rows, added_voxels, clean_mask, log_totals
 from cryovit_amd.analysis.curvature import CurvatureOptions, check_mesh_format, curvature_rows, curvature_volume, vertex_curvature
+from cryovit_amd.analysis.filaments import TraceOptions, filament_rows, trace_tables
 from cryovit_amd.analysis.mesh import MESH_FORMATS, mesh_arrays, mesh_rows
 from cryovit_amd.analysis.picks import PickOptions, pick_rows, pick_table
 from cryovit_amd.analysis.shape import instance_shape
@@ -59,8 +60,8 @@ class InstanceOptions:
                       volume's border taken as background; touching pieces are meshed as their union), after ``mesh_smooth`` pairs of
                       Taubin steps: ``meshes/<tomo stem>_<label>.<mesh_format>`` (``ply`` or ``stl``) and ``analysis.mesh.MESH_COLUMNS``.
 
-    ``<label>_instances``, ``<label>_skeleton``, ``<label>_thickness`` and ``<label>_curvature`` of an earlier run are never written back: they belong to
-    that run's labelling."""
+    ``<label>_instances``, ``<label>_skeleton``, ``<label>_filaments``, ``<label>_thickness`` and ``<label>_curvature`` of an earlier run
+    are never written back: they belong to that run's labelling."""
 
     connectivity: int = 26
     min_size: int = 0
@@ -106,7 +107,9 @@ class Measured:
     (int32 [D, H, W]); ``t2`` (int32 [D, H, W], the squared local radius: ``analysis.thickness.thickness_map`` takes the root);
     ``mesh`` = (vertices, triangles, ids), int32; ``curvature`` (int32 [D, H, W], h in units of 1/4096 per voxel:
     ``analysis.curvature.curvature_map`` makes the float volume); ``vertex_curvature`` (float32 [V], per vertex of ``mesh``, where
-    both were asked for); ``picks`` (int32 [P, 8], the pick table: ``analysis.picks.pick_records`` makes the particle records)."""
+    both were asked for); ``picks`` (int32 [P, 8], the pick table: ``analysis.picks.pick_records`` makes the particle records);
+    ``filament_voxels`` (int32 [N, 12]) and ``filament_branches`` (int64 [B, 16]), the two tables of the traced skeleton
+    (``analysis.filaments`` makes the branch records and the sampled positions)."""
 
     extra: list[dict] = field(default_factory=list)
     pairs: list[dict] | None = None
@@ -115,6 +118,8 @@ class Measured:
     mesh: tuple | None = None
     curvature: Any = None
     vertex_curvature: Any = None
+    filament_voxels: Any = None
+    filament_branches: Any = None
     picks: Any = None
 
     def arrays(self, fn: Callable) -> "Measured":
@@ -123,7 +128,8 @@ class Measured:
             return None if a is None else fn(a)
 
         return replace(self, skeleton=each(self.skeleton), t2=each(self.t2), mesh=None if self.mesh is None else tuple(fn(a) for a in self.mesh),
-                       curvature=each(self.curvature), vertex_curvature=each(self.vertex_curvature), picks=each(self.picks))
+                       curvature=each(self.curvature), vertex_curvature=each(self.vertex_curvature), picks=each(self.picks),
+                       filament_voxels=each(self.filament_voxels), filament_branches=each(self.filament_branches))
 
 
 def merge_columns(rows: list[dict], more: list[dict]) -> None:
@@ -174,14 +180,16 @@ def label_and_split(mask, opts: InstanceOptions):
 
 def measure(labels, k: int, component, opts: InstanceOptions, *, other_mask=None, other_name: str | None = None,
             partner: Callable | None = None, partner_name: str | None = None, curvature: CurvatureOptions | None = None,
-            picks: PickOptions | None = None) -> Measured:
+            picks: PickOptions | None = None, trace: TraceOptions | None = None) -> Measured:
     """Everything ``opts`` asks for of the instances 1..k of the int32 device volume ``labels`` (``component``: that of
     ``label_and_split``), in the order of the CSV columns.  ``other_mask``: the uint8 device mask of the label ``other_name``, for the
     gap and contact columns.  ``partner``: called when its turn comes, returns (int32 device volume, count) of the instances of the
     label ``partner_name``, for the pair contacts.  ``curvature``: the membrane curvature (``analysis.curvature``), measured last;
     with a mesh every vertex gets its value.  ``picks``: spaced surface positions with normals (``analysis.picks``), placed after
-    everything else; their counts are the last columns."""
+    everything else; their counts are the last columns.  ``trace``: the skeleton traced into filaments (``analysis.filaments``); it turns
+    the skeleton on, shares its distance map, and its columns follow the skeleton's directly."""
     curved = curvature is not None and curvature.curvature
+    traced = trace is not None and trace.trace
     out = Measured(extra=[{} for _ in range(k)])
     if component is not None:
         out.extra = component_rows(component, out.extra)
@@ -196,10 +204,13 @@ def measure(labels, k: int, component, opts: InstanceOptions, *, other_mask=None
     if opts.shape:
         merge_columns(out.extra, instance_shape(labels, k, opts.connectivity))
     # one distance map for both; either alone computes its own, and so does morphology
-    d2 = distances.edt_squared(labels) if opts.skeleton and opts.thickness else None
-    if opts.skeleton:
+    d2 = distances.edt_squared(labels) if traced or (opts.skeleton and opts.thickness) else None
+    if opts.skeleton or traced:
         out.skeleton, line_table = skeleton_volume(labels, k, opts.skeleton_end_radius, d2)
         merge_columns(out.extra, skeleton_rows(line_table))
+    if traced:
+        out.filament_voxels, out.filament_branches = trace_tables(out.skeleton, k, d2)
+        merge_columns(out.extra, filament_rows(out.filament_voxels, out.filament_branches, k))
     if opts.thickness:
         out.t2, thick_table = thickness_volume(labels, k, d2)
         merge_columns(out.extra, thickness_rows(thick_table))
@@ -263,7 +274,8 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
                close_radius: float | None = None, fill_holes: str | None = None, open_radius: float | None = None,
                curvature: bool = False, curvature_radius: int = 5,
                pick: bool = False, pick_spacing: int = 8, pick_radius: int = 5, pick_offset: float = 0.0, pick_scale: float = 1.0,
-               pick_seed: int = 0) -> Path:
+               pick_seed: int = 0, trace: bool = False, trace_spacing: float = 8.0, trace_window: float = 4.0, trace_min_length: float = 0.0,
+               trace_scale: float = 1.0, trace_angpix: float = 1.0) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  The measurements are those of ``InstanceOptions``.
@@ -274,6 +286,10 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     ``analysis.curvature.CURVATURE_COLUMNS`` after every other column and a PLY mesh of the same run a curvature per vertex.
     ``pick`` and the other ``pick_*`` are the fields of ``analysis.picks.PickOptions``: ``picks/<tomo stem>_<label>.csv`` and ``.star``
     are written under ``result_dir`` and the CSV gains ``analysis.picks.PICK_COLUMNS`` as its last columns.
+    ``trace`` and the other ``trace_*`` are the fields of ``analysis.filaments.TraceOptions``: the skeleton (which ``trace`` turns on) is
+    traced into branches, ``filaments/<tomo stem>_<label>_branches.csv``, ``filaments/<tomo stem>_<label>.csv`` and ``.star`` are written
+    under ``result_dir``, ``<label>_filaments`` beside ``<label>_skeleton``, and the CSV gains ``analysis.filaments.FILAMENT_COLUMNS``
+    directly after the skeleton's columns.
     ``distance_to`` names another label whose mask (``<distance_to>_preds`` of the same file, else of
     ``distance_to_dir/<same stem>.hdf``) the gap and contact columns are taken against.  ``contacts_with`` names another label
     whose instances are paired with this label's: ``<contacts_with>_instances`` of the same file, else of
@@ -292,10 +308,12 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     check_mesh_format(curvature, mesh, mesh_format)
     picking = PickOptions(pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
                           pick_seed=pick_seed).validate()
+    tracing = TraceOptions(trace=trace, trace_spacing=trace_spacing, trace_window=trace_window, trace_min_length=trace_min_length,
+                           trace_scale=trace_scale, trace_angpix=trace_angpix).validate()
     datasets = io.read_all_flat(path)
     if key not in datasets:
         raise KeyError(f"{path} holds no '{key}' dataset (found {sorted(datasets)})")
-    for stale in ("instances", "skeleton", "thickness", "cleaned", "curvature"):  # an earlier run's results carry that run's ids and filtering
+    for stale in ("instances", "skeleton", "thickness", "cleaned", "curvature", "filaments"):  # an earlier run's results carry that run's ids and filtering
         datasets.pop(f"{label}_{stale}", None)
     preds = datasets[key]
     if preds.ndim != 3:
@@ -335,7 +353,7 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     labels, table, component = label_and_split(cleaned, opts)
     found = measure(labels, int(table.shape[0]), component, opts, other_mask=None if other is None else on_device(other),
                     other_name=distance_to, partner=None if partner is None else partner_instances, partner_name=contacts_with,
-                    curvature=curve, picks=picking)
+                    curvature=curve, picks=picking, trace=tracing)
     if cleanup.any:
         found.extra = added_rows(added_voxels(labels, predicted, int(table.shape[0])), found.extra)
         log_totals(f"{path} '{label}'", totals)
@@ -344,4 +362,4 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     if found.pairs is not None:
         writers.write_contacts(result_dir, path.name, label, contacts_with, found.pairs)
     return writers.write_measured(result_dir, path.name, label, datasets, labels.cpu().numpy(), table.cpu().numpy(),
-                                  found.arrays(lambda a: a.cpu().numpy()), mesh_format, picks=picking)
+                                  found.arrays(lambda a: a.cpu().numpy()), mesh_format, picks=picking, trace=tracing)

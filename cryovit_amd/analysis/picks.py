@@ -34,8 +34,8 @@ What the numbers mean:
   angle is free.  The normals of the CSV (``nz, ny, nx``) are the authoritative orientation; the Euler conventions of other
   packages (Dynamo, Warp/M, emClarity) are to be derived from them, not from the STAR angles.
 
-Out of scope: picks along skeletons (filaments), spacings above 16 voxels, sampling of the smoothed mesh, particle formats other
-than RELION's.
+Out of scope: spacings above 16 voxels, sampling of the smoothed mesh, particle formats other than RELION's.  Positions along
+filaments are ``analysis.filaments``' (``--trace``).
 """
 
 from __future__ import annotations

@@ -12,7 +12,8 @@ What the numbers mean, and where they bend:
 * ``skeleton_length`` sums the steps between 26-adjacent skeleton voxels: 1 per face step, sqrt 2 per edge step, sqrt 3 per corner
   step.  EVERY adjacent pair is a link, so inside the little clique of voxels that forms a junction (three or four mutually
   adjacent voxels) all its pairs are counted, not only a spanning path: the length reads slightly high at branch points, by
-  about one to two voxels per junction.  A single-voxel skeleton has length 0.
+  about one to two voxels per junction (``analysis.filaments``' ``filament_length``, with ``--trace``, sums the branches between
+  the nodes instead and counts no pair twice).  A single-voxel skeleton has length 0.
 * ``skeleton_ends`` counts voxels with exactly one neighbour, ``skeleton_branches`` voxels with three or more: a junction's clique
   contributes several branch voxels, so compare it with 0 rather than reading it as a number of junctions.
 * ``skeleton_rms_radius`` is the root mean square of the distance to the background over the skeleton voxels: the instance's

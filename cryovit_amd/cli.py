@@ -21,6 +21,7 @@
                     [--skeleton [--skeleton-end-radius R]] [--thickness] [--mesh [--mesh-smooth N] [--mesh-format ply|stl]]
                     [--curvature [--curvature-radius R]]
                     [--pick [--pick-spacing S] [--pick-radius R] [--pick-offset V] [--pick-scale F] [--pick-seed N]]
+                    [--trace [--trace-spacing S] [--trace-window H] [--trace-min-length L] [--trace-scale F] [--trace-angpix A]]
 
 ``preprocess`` (build extension) turns raw reconstructions (int8 / uint8 / int16 / uint16 / float MRC, TIFF or HDF5, as IMOD or AreTomo
 write them) into the uint8 tomograms every other command expects, on the GPU: bin, clip, rescale to [0, 255]
@@ -35,7 +36,11 @@ measures them.  The measurement options are declared once, below, for both comma
 ``<label>_cleaned`` and the CSV ``added_voxels``.  ``--curvature`` maps the mean curvature of the membrane at the scale
 ``--curvature-radius`` (``analysis.curvature.CurvatureOptions``).  ``--pick`` places positions for subtomogram averaging on every
 instance's membrane, no two of one instance closer than ``--pick-spacing`` voxels, each with the membrane normal, and writes them as
-``picks/<tomo>_<label>.csv`` and a RELION ``.star`` (``analysis.picks.PickOptions``).  ``--distance-to NAME`` adds the gap to another
+``picks/<tomo>_<label>.csv`` and a RELION ``.star`` (``analysis.picks.PickOptions``).  ``--trace`` follows every instance's skeleton
+(it implies ``--skeleton`` and uses ``--skeleton-end-radius``) and splits it into branches between ends and junctions, and rings: how many
+filaments there are, how long and how straight each is, which meet where, and positions every ``--trace-spacing`` voxels along them with
+the tangent, as ``filaments/<tomo>_<label>_branches.csv``, ``.csv`` and a helical RELION ``.star`` (``analysis.filaments.TraceOptions``).
+``--distance-to NAME`` adds the gap to another
 label's mask and the voxels in contact with it; ``--contacts-with NAME`` says which instance touches which: every instance gains
 ``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance, nearest instance of NAME within
 ``--contact-radius``) the voxels in contact, the narrowest gap and where it is.
@@ -179,6 +184,22 @@ _PICK_OFFSET_HELP = ("with --pick, move every oriented pick this far along its o
 _PICK_SCALE_HELP = ("with --pick, write coordinates of a volume this many times finer: (q + 0.5) * F - 0.5, which undoes "
                     "preprocess --bin F (> 0)")
 _PICK_SEED_HELP = "with --pick, the seed of the pseudo-random order the candidates are taken in (0 .. 2^32 - 1); same seed, same picks"
+_TRACE_HELP = ("trace the skeleton of every instance into filaments on the GPU (implies --skeleton; uses --skeleton-end-radius): branches "
+               "between ends and junctions, and closed rings, each with its length, chord, tortuosity and radius, and positions along "
+               "them with the tangent: where to cut segments for helical averaging.  Writes <result>/filaments/<tomo>_<label>_branches.csv "
+               "(every branch), <tomo>_<label>.csv (every position: branch, instance id, arc length, position, tangent, Euler angles, "
+               "radius) and .star (a RELION data_particles loop with _rlnHelicalTubeID = the branch and _rlnHelicalTrackLengthAngst, the "
+               "particle's z axis along the filament), the dataset <label>_filaments (the branch number of every path voxel, -1 on "
+               "ends and junction voxels) and adds filament_branches, filament_rings, filament_junctions, filament_points, "
+               "filament_length, filament_longest and filament_tortuosity after the skeleton's CSV columns.  The polarity of a branch "
+               "is arbitrary and the CSV tangents are the authoritative orientation (with infer: needs --instances)")
+_TRACE_SPACING_HELP = "with --trace, the arc length between two positions of a branch, the first at its start (voxels, >= 1)"
+_TRACE_WINDOW_HELP = ("with --trace, the tangent at a position is the direction between the points this far before and after it along "
+                      "the branch; larger is smoother and blurs bends shorter than it (voxels, >= 1)")
+_TRACE_MIN_LENGTH_HELP = "with --trace, branches shorter than this get no positions; they stay in the branch CSV and the columns (voxels, >= 0)"
+_TRACE_SCALE_HELP = ("with --trace, write coordinates of a volume this many times finer: (q + 0.5) * F - 0.5, which undoes "
+                     "preprocess --bin F (> 0)")
+_TRACE_ANGPIX_HELP = "with --trace, Angstrom per voxel of that finer volume, for _rlnHelicalTrackLengthAngst = arc * F * A (> 0)"
 _EXT = "build extension: "
 
 MinSize = Annotated[int, Option(min=0, help=_EXT + _MIN_SIZE_HELP)]
@@ -239,9 +260,33 @@ PickScale = Annotated[float, Option("--pick-scale", callback=_checked(lambda v: 
 PickSeed = Annotated[int, Option("--pick-seed", callback=_checked(lambda v: 0 <= v < 2**32, "pick seed must lie in 0..2^32 - 1"),
                                  help=_EXT + _PICK_SEED_HELP)]
 
+
+
+def _trace_checked(name: str, ok, rule: str):
+    """As ``_checked``, in the words of ``analysis.filaments.TraceOptions.validate``."""
+    def check(value):
+        if value is not None and not (math.isfinite(value) and ok(value)):
+            raise typer.BadParameter(f"{name} must be a finite number {rule}, got {value!r}")
+        return value
+
+    return check
+
+
+Trace = Annotated[bool, Option("--trace", help=_EXT + _TRACE_HELP)]
+TraceSpacing = Annotated[float, Option("--trace-spacing", callback=_trace_checked("trace_spacing", lambda v: v >= 1, ">= 1"),
+                                       help=_EXT + _TRACE_SPACING_HELP)]
+TraceWindow = Annotated[float, Option("--trace-window", callback=_trace_checked("trace_window", lambda v: v >= 1, ">= 1"),
+                                      help=_EXT + _TRACE_WINDOW_HELP)]
+TraceMinLength = Annotated[float, Option("--trace-min-length", callback=_trace_checked("trace_min_length", lambda v: v >= 0, ">= 0"),
+                                         help=_EXT + _TRACE_MIN_LENGTH_HELP)]
+TraceScale = Annotated[float, Option("--trace-scale", callback=_trace_checked("trace_scale", lambda v: v > 0, "> 0"),
+                                     help=_EXT + _TRACE_SCALE_HELP)]
+TraceAngpix = Annotated[float, Option("--trace-angpix", callback=_trace_checked("trace_angpix", lambda v: v > 0, "> 0"),
+                                      help=_EXT + _TRACE_ANGPIX_HELP)]
+
 # infer measures nothing without --instances: asking for one of these without it is a usage error
 _NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh", "close_radius", "fill_holes", "open_radius",
-                    "curvature", "pick")
+                    "curvature", "pick", "trace")
 
 
 def _refuse_stl_curvature(curvature: bool, mesh: bool, mesh_format: str) -> None:
@@ -417,6 +462,12 @@ def infer(
     pick_offset: PickOffset = 0.0,
     pick_scale: PickScale = 1.0,
     pick_seed: PickSeed = 0,
+    trace: Trace = False,
+    trace_spacing: TraceSpacing = 8.0,
+    trace_window: TraceWindow = 4.0,
+    trace_min_length: TraceMinLength = 0.0,
+    trace_scale: TraceScale = 1.0,
+    trace_angpix: TraceAngpix = 1.0,
 ):
     """Segment tomograms using a pre-trained model."""
     measurements = dict(min_size=min_size, connectivity=connectivity, morphology=morphology, split_radius=split_radius,
@@ -425,7 +476,8 @@ def infer(
                         close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius,
                         curvature=curvature, curvature_radius=curvature_radius,
                         pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
-                        pick_seed=pick_seed)
+                        pick_seed=pick_seed, trace=trace, trace_spacing=trace_spacing, trace_window=trace_window,
+                        trace_min_length=trace_min_length, trace_scale=trace_scale, trace_angpix=trace_angpix)
     _refuse_stl_curvature(curvature, mesh, mesh_format)
     for name in _NEEDS_INSTANCES:
         value = measurements[name]  # a flag that is off is False, a radius that is not given None; a radius of 0 is given
@@ -478,6 +530,12 @@ def instances_cmd(
     pick_offset: PickOffset = 0.0,
     pick_scale: PickScale = 1.0,
     pick_seed: PickSeed = 0,
+    trace: Trace = False,
+    trace_spacing: TraceSpacing = 8.0,
+    trace_window: TraceWindow = 4.0,
+    trace_min_length: TraceMinLength = 0.0,
+    trace_scale: TraceScale = 1.0,
+    trace_angpix: TraceAngpix = 1.0,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     _refuse_stl_curvature(curvature, mesh, mesh_format)
@@ -496,7 +554,8 @@ def instances_cmd(
                          close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius,
                          curvature=curvature, curvature_radius=curvature_radius,
                          pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
-                         pick_seed=pick_seed)
+                         pick_seed=pick_seed, trace=trace, trace_spacing=trace_spacing, trace_window=trace_window,
+                         trace_min_length=trace_min_length, trace_scale=trace_scale, trace_angpix=trace_angpix)
         logging.info("Labelled %s", out)
 
 

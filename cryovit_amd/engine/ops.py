@@ -1585,6 +1585,129 @@ def pick_surface(labels: torch.Tensor, k: int, *, spacing: int, radius: int, see
     return pick_emit(labels, fg, state, radius)
 
 
+# ---- filament tracing (`--trace`): the skeleton as branches, ranks along them and step counts (csrc/trace.hip) ----
+
+def _trace_rows(what: str, voxels, **arrays) -> int:
+    """N, the rows of the voxel table; raises unless it and every other tensor given (name=(tensor or None, cols)) is int32 with
+    N x cols elements."""
+    N = int(voxels.shape[0]) if isinstance(voxels, torch.Tensor) and voxels.dim() == 2 else 0
+    for name, (t, cols) in {"voxels": (voxels, _lib.TRACE_VOXEL_COLS), **arrays}.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() != N * cols or (name == "voxels" and t.dim() != 2):
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise _lib.CvxError(f"{what}: {name} must be int32 [{N}, {cols}], got {got}")
+    return N
+
+
+def trace_rounds(path_voxels: int) -> int:
+    """The doubling rounds that bring every state of ``path_voxels`` path voxels to its end: ceil(log2(max(Np, 2)))."""
+    return (max(int(path_voxels), 2) - 1).bit_length()
+
+
+def trace_emit(skeleton: torch.Tensor, k: int, d2: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, int]:
+    """(voxels int32 [N, 12], nbrs int32 [N, 2], Np) of ``skeleton`` (int32 [D, H, W]; ids outside 1..k count as 0): the voxel table
+    in raster order with z, y, x, id, degree and d2 filled in (``d2``: int32 [D, H, W] or None = 0) and the other columns 0, the
+    slots of the neighbours of every end and path voxel (-1: none), and the number of path voxels.  The host waits once, for N
+    and Np."""
+    vols = {"skeleton": (skeleton, torch.int32)} | ({"d2": (d2, torch.int32)} if d2 is not None else {})
+    dev, D, H, W = _volumes_check("trace_emit", **vols)
+    if k < 0:
+        raise _lib.CvxError(f"trace_emit: k must be >= 0, got {k}")
+    lib = _lib.load()
+    words = D * H * _bit_words(W)
+    bits = torch.empty((2, max(words, 1)), dtype=torch.int64, device=dev)
+    row_first = torch.empty((2, max(D * H, 1)), dtype=torch.int32, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    call(dev, "cvx_trace_count", lib.cvx_trace_count, _p(skeleton), D, H, W, int(k), _p(bits), 8 * words, _p(row_first), _p(totals))
+    N, Np = totals.tolist()  # the wait
+    voxels = torch.empty((N, _lib.TRACE_VOXEL_COLS), dtype=torch.int32, device=dev)
+    nbrs = torch.empty((N, 2), dtype=torch.int32, device=dev)
+    call(dev, "cvx_trace_emit", lib.cvx_trace_emit, _p(skeleton), _p(d2), _p(bits), _p(row_first), D, H, W, int(k), 8 * words, N, _p(voxels),
+         _p(nbrs))
+    return voxels, nbrs, Np
+
+
+def trace_rank(voxels: torch.Tensor, nbrs: torch.Tensor, rounds: int, cut: torch.Tensor | None = None) -> torch.Tensor:
+    """int32 [2 N, 5], the direction states of the path voxels of ``voxels`` / ``nbrs`` (``trace_emit``) after ``rounds`` doubling
+    rounds: row 2 v + j = (the state reached, face / edge / corner steps up to its voxel, the smallest slot on the way) for path
+    voxel v travelling to ``nbrs[v, j]``.  ``cut`` (int32 [N], ``trace_rings``): a state stops before voxel ``cut[v]``.  A round
+    reads one buffer and writes another.  The host does not wait."""
+    N = _trace_rows("trace_rank", voxels, nbrs=(nbrs, 2), cut=(cut, 1))
+    if rounds < 0 or rounds > 32:
+        raise _lib.CvxError(f"trace_rank: rounds must lie in [0, 32], got {rounds}")
+    dev = _dev_check(voxels, nbrs, cut)
+    state = torch.empty((2, 2 * N, _lib.TRACE_STATE_BYTES // 4), dtype=torch.int32, device=dev)
+    call(dev, "cvx_trace_rank", _lib.load().cvx_trace_rank, _p(voxels), _p(nbrs), _p(cut), N, int(rounds), _p(state[0]), _p(state[1]))
+    return state[rounds % 2]
+
+
+def trace_rings(voxels: torch.Tensor, state: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(cut int32 [N], any int32 [1]) from the states of a ``trace_rank`` without cut: ``cut[v]`` = the smallest slot of the ring that
+    path voxel v lies on, -1 elsewhere; ``any`` = 1 iff there is a ring.  The host does not wait."""
+    N = _trace_rows("trace_rings", voxels, state=(state, 2 * _lib.TRACE_STATE_BYTES // 4))
+    dev = _dev_check(voxels, state)
+    cut = torch.empty(N, dtype=torch.int32, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    call(dev, "cvx_trace_rings", _lib.load().cvx_trace_rings, _p(voxels), _p(state), N, _p(cut), _p(flag))
+    return cut, flag
+
+
+def trace_finalise(voxels: torch.Tensor, nbrs: torch.Tensor, state: torch.Tensor | None, cut: torch.Tensor | None, shape) -> torch.Tensor:
+    """int64 [B, 16], the branch table; fills branch, rank, f, e, c and ring of ``voxels`` (int32 [N, 12], ``trace_emit``) in place.
+    ``state``: of the last ``trace_rank`` (None without path voxels); ``cut``: of ``trace_rings`` when there is a ring; ``shape`` =
+    (D, H, W) of the volume, for the linear indices.  The host waits once, for B."""
+    N = _trace_rows("trace_finalise", voxels, nbrs=(nbrs, 2), state=(state, 2 * _lib.TRACE_STATE_BYTES // 4), cut=(cut, 1))
+    if cut is not None and state is None:
+        raise _lib.CvxError("trace_finalise: a cut needs the states it was made from")
+    D, H, W = (int(v) for v in shape)
+    dev = _dev_check(voxels, nbrs, state, cut)
+    lib = _lib.load()
+    keys = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    call(dev, "cvx_trace_keys", lib.cvx_trace_keys, _p(voxels), _p(nbrs), _p(state), _p(cut), N, _p(keys), _p(total))
+    B = int(total.item())  # the wait
+    branches = torch.empty((B, _lib.TRACE_BRANCH_COLS), dtype=torch.int64, device=dev)
+    call(dev, "cvx_trace_branches", lib.cvx_trace_branches, _p(voxels), _p(nbrs), _p(state), _p(cut), _p(keys), D, H, W, N, B, _p(branches))
+    return branches
+
+
+def trace_skeleton(skeleton: torch.Tensor, k: int, *, d2: torch.Tensor | None = None, counters: dict | None = None):
+    """(voxels int32 [N, 12], branches int64 [B, 16]) on the device: the skeleton graph of the ids 1..k of ``skeleton`` (int32
+    [D, H, W]; in the product ``skeletonize_instances``' volume, but any volume is traced exactly) as chains, rings and links
+    (the definition and both tables' columns are in include/cryovit_hip.h).  ``d2`` (int32 [D, H, W]) fills the d2 column and the
+    branches' d2 statistics.  ``trace_emit``, ``trace_rank`` with ``trace_rounds(Np)`` rounds, ``trace_rings``, with a ring the
+    same rounds once more with the rings cut, ``trace_finalise``.  ``counters`` (a dict) receives N, Np, B, rounds, rings (whether
+    there was one) and passes (1 or 2 rank passes; 0 without path voxels).  Integers only, bit-reproducible (csrc/trace.hip).  The
+    host waits three times: for (N, Np), for the ring flag (not without path voxels) and for B."""
+    vols = {"skeleton": (skeleton, torch.int32)} | ({"d2": (d2, torch.int32)} if d2 is not None else {})
+    dev, D, H, W = _volumes_check("trace_skeleton", **vols)
+    if k < 0:
+        raise _lib.CvxError(f"trace_skeleton: k must be >= 0, got {k}")
+    seen = {"N": 0, "Np": 0, "B": 0, "rounds": 0, "rings": False, "passes": 0}
+    if k == 0 or skeleton.numel() == 0:
+        voxels = torch.empty((0, _lib.TRACE_VOXEL_COLS), dtype=torch.int32, device=dev)
+        branches = torch.empty((0, _lib.TRACE_BRANCH_COLS), dtype=torch.int64, device=dev)
+    else:
+        voxels, nbrs, Np = trace_emit(skeleton, k, d2)
+        state = cut = None
+        if Np > 0:
+            rounds = trace_rounds(Np)
+            state = trace_rank(voxels, nbrs, rounds)
+            cut, flag = trace_rings(voxels, state)
+            rings = bool(flag.item())  # the wait
+            if rings:
+                state = trace_rank(voxels, nbrs, rounds, cut)
+            else:
+                cut = None
+            seen |= {"rounds": rounds, "rings": rings, "passes": 2 if rings else 1}
+        branches = trace_finalise(voxels, nbrs, state, cut, (D, H, W))
+        seen |= {"N": int(voxels.shape[0]), "Np": Np, "B": int(branches.shape[0])}
+    if counters is not None:
+        counters.update(seen)
+    return voxels, branches
+
+
 # ---- a prediction scored at its boundary (`cryovit evaluate --boundary`): scored slices, surfaces, distance histograms ----
 
 HIST_BINS_MAX = 2**24 + 1  # of surface_distance_hist

@@ -26,6 +26,9 @@ curvature is measured last, each file also holds ``<label_key>_curvature`` and t
 ``pick`` and the other ``pick_*`` (with ``instances``) are the fields of ``analysis.picks.PickOptions``: spaced surface positions with
 membrane normals are placed after everything else and written as ``picks/<tomo stem>_<label_key>.csv`` and ``.star``; the table
 gains ``picks`` and ``picks_unoriented`` as its last columns.
+``trace`` and the other ``trace_*`` (with ``instances``) are the fields of ``analysis.filaments.TraceOptions``: the skeleton (which
+``trace`` turns on) is traced into branches while it is in HBM; ``filaments/<tomo stem>_<label_key>_branches.csv``, ``.csv`` and ``.star``
+are written, each file also holds ``<label_key>_filaments`` and the table gains the filament columns directly after the skeleton's.
 """
 
 from __future__ import annotations
@@ -40,6 +43,7 @@ import torch
 from cryovit_amd import io
 from cryovit_amd.analysis.cleanup import CleanupOptions, added_rows, added_voxels, clean_mask, log_totals
 from cryovit_amd.analysis.curvature import CurvatureOptions, check_mesh_format
+from cryovit_amd.analysis.filaments import TraceOptions
 from cryovit_amd.analysis.instances import InstanceOptions, label_and_split, measure
 from cryovit_amd.analysis.picks import PickOptions
 from cryovit_amd.config import compose, instantiate
@@ -82,13 +86,13 @@ def _predict_file(model, dataset, idx: int, threshold: float, encoder, batch_siz
 
 
 def _write_measured(result_dir, tomo_name: str, label_key: str, raw, segs, labels, table, measured, mesh_format: str, cleaned=None,
-                    picks: PickOptions | None = None) -> Path:
+                    picks: PickOptions | None = None, trace: TraceOptions | None = None) -> Path:
     """``writers.write_measured`` with the datasets of ``writers.write_segmentation`` (and ``<label>_cleaned`` where the mask was
     cleaned); the conversion of the raw volume to float32 is part of the writer thread's work."""
     datasets = {"data": raw.astype(np.float32), f"{label_key}_preds": segs.astype(np.uint8, copy=False)}
     if cleaned is not None:
         datasets[f"{label_key}_cleaned"] = cleaned.astype(np.uint8, copy=False)
-    return writers.write_measured(result_dir, tomo_name, label_key, datasets, labels, table, measured, mesh_format, picks=picks)
+    return writers.write_measured(result_dir, tomo_name, label_key, datasets, labels, table, measured, mesh_format, picks=picks, trace=trace)
 
 
 def _pinned(tensor) -> np.ndarray:
@@ -106,7 +110,8 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                   mesh_format: str = "ply", close_radius: float | None = None, fill_holes: str | None = None,
                   open_radius: float | None = None, curvature: bool = False, curvature_radius: int = 5,
                   pick: bool = False, pick_spacing: int = 8, pick_radius: int = 5, pick_offset: float = 0.0, pick_scale: float = 1.0,
-                  pick_seed: int = 0) -> list[Path]:
+                  pick_seed: int = 0, trace: bool = False, trace_spacing: float = 8.0, trace_window: float = 4.0, trace_min_length: float = 0.0,
+                  trace_scale: float = 1.0, trace_angpix: float = 1.0) -> list[Path]:
     opts = InstanceOptions(connectivity=connectivity, min_size=min_size, morphology=morphology, split_radius=split_radius,
                            split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
                            thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
@@ -114,7 +119,11 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
     curve = CurvatureOptions(curvature=curvature, curvature_radius=curvature_radius)
     picking = PickOptions(pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
                           pick_seed=pick_seed)
+    tracing = TraceOptions(trace=trace, trace_spacing=trace_spacing, trace_window=trace_window, trace_min_length=trace_min_length,
+                           trace_scale=trace_scale, trace_angpix=trace_angpix)
     if not instances:
+        if trace:
+            raise ValueError("trace=True needs instances=True: the filaments are traced along the skeletons of the labelled instances")
         if pick:
             raise ValueError("pick=True needs instances=True: the picks are placed on the labelled instances")
         if curvature:
@@ -131,6 +140,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
     cleanup.validate()
     curve.validate()
     picking.validate()
+    tracing.validate()
     check_mesh_format(curvature, mesh, mesh_format)
     rank, _, world = world_info()
     device = select_device(device)
@@ -162,7 +172,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 labels, table, component = label_and_split(cleaned, opts)
                 host_labels = _pinned(labels)  # on its way while the instances are measured
                 host_table = table.cpu().numpy()
-                found = measure(labels, int(table.shape[0]), component, opts, curvature=curve, picks=picking)
+                found = measure(labels, int(table.shape[0]), component, opts, curvature=curve, picks=picking, trace=tracing)
                 if cleanup.any:
                     host_cleaned = _pinned(cleaned)
                     found.extra = added_rows(added_voxels(labels, predicted, int(table.shape[0])), found.extra)
@@ -171,7 +181,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:
                 pending.append((i, writer.submit(_write_measured, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy(),
-                                                 host_labels, host_table, found, mesh_format, host_cleaned, picking)))
+                                                 host_labels, host_table, found, mesh_format, host_cleaned, picking, tracing)))
             else:
                 pending.append((i, writer.submit(writers.write_segmentation, result_dir, files[i].tomo_path.name, label_key, raw, host.numpy())))
             while len(pending) > 2:

@@ -13,6 +13,8 @@
   write_measured         (not in the reference) write_mesh and write_instances of one ``analysis.instances.measure`` result
   write_picks            (not in the reference) <results_dir>/picks/<tomo stem>_<label>.csv and .star: spaced surface positions with
                          membrane normals, every pick in the CSV, the oriented ones as RELION particles in the STAR file
+  write_filaments        (not in the reference) <results_dir>/filaments/<tomo stem>_<label>_branches.csv (every branch of the traced
+                         skeleton), <tomo stem>_<label>.csv (positions with tangents along them) and .star (helical RELION particles)
   write_mesh             (not in the reference) <results_dir>/meshes/<tomo stem>_<label>.ply or .stl, the surface of the labelled mask
   write_instance_matches (not in the reference) <results_dir>/instances/<sample>_<tomo stem>.csv of ``cryovit evaluate
                         --instance-metrics``: every annotated instance with its best predicted partner, then the unmatched predicted ones
@@ -35,6 +37,8 @@ from cryovit_amd import io
 from cryovit_amd.analysis.distances import PAIR_COLUMNS
 from cryovit_amd.analysis.instances import INSTANCE_COLUMNS, instance_rows, merge_columns
 from cryovit_amd.analysis.curvature import curvature_map
+from cryovit_amd.analysis.filaments import (TraceOptions, branch_records, filament_volume, sample_points, write_branches_csv, write_helical_star,
+                                            write_points_csv)
 from cryovit_amd.analysis.picks import PickOptions, pick_records, write_picks_csv, write_star
 from cryovit_amd.analysis.thickness import thickness_map
 
@@ -78,14 +82,16 @@ def _write_rows(path: Path, columns: list[str], rows: list[dict]) -> None:
 
 def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[str, np.ndarray], labels: np.ndarray,
                     rows: list[dict], skeleton: np.ndarray | None = None, thickness: np.ndarray | None = None,
-                    curvature: np.ndarray | None = None) -> Path:
+                    curvature: np.ndarray | None = None, filaments: np.ndarray | None = None) -> Path:
     """The prediction file <results_dir>/<tomo stem>.hdf with every array of ``datasets`` (``data``, ``<label>_preds``, ...:
     gzip, dtypes as given) and ``<label>_instances`` = ``labels`` (uint16 while the largest id fits, else int32: a 128x512x512
     int32 volume would make the gzip of the writer thread the slowest stage of ``infer``), and the CSV
     <results_dir>/instances/<tomo stem>_<label>.csv of ``rows`` (``analysis.instance_rows``; floats written with ``repr``; no
     instances: header only; keys beyond ``INSTANCE_COLUMNS``, those of ``analysis.instances.measure``, become further columns in
     the rows' own order).  ``skeleton`` (the instances' centrelines, every voxel with its instance's id) is written as
-    ``<label>_skeleton`` in int32 beside ``<label>_instances``: it is nearly all zeros and gzips to little.  ``thickness``
+    ``<label>_skeleton`` in int32 beside ``<label>_instances``: it is nearly all zeros and gzips to little; ``filaments``
+    (``analysis.filaments.filament_volume``: the branch number on path and ring voxels, -1 on node voxels) as ``<label>_filaments`` in int32
+    right after it.  ``thickness``
     (``analysis.thickness.thickness_map``: the local thickness in voxels, 0 on the background, inf without any background) is written
     as ``<label>_thickness`` in float32 after them, and ``curvature`` (``analysis.curvature.curvature_map``: the mean curvature in
     1/voxel at the scored surface voxels, NaN elsewhere) as ``<label>_curvature`` in float32 after that.  The file is written beside its final name and moved there, so re-writing a file from its own
@@ -101,6 +107,8 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
                           compression="gzip")
         if skeleton is not None:
             fh.create_dataset(f"{label_key}_skeleton", skeleton.astype(np.int32, copy=False), compression="gzip")
+        if filaments is not None:
+            fh.create_dataset(f"{label_key}_filaments", filaments.astype(np.int32, copy=False), compression="gzip")
         if thickness is not None:
             fh.create_dataset(f"{label_key}_thickness", thickness.astype(np.float32, copy=False), compression="gzip")
         if curvature is not None:
@@ -112,13 +120,19 @@ def write_instances(results_dir, tomo_name: str, label_key: str, datasets: dict[
 
 
 def write_measured(results_dir, tomo_name: str, label_key: str, datasets: dict[str, np.ndarray], labels: np.ndarray, table: np.ndarray,
-                   measured, mesh_format: str = "ply", picks: PickOptions | None = None) -> Path:
+                   measured, mesh_format: str = "ply", picks: PickOptions | None = None, trace: TraceOptions | None = None) -> Path:
     """Everything one file gets from ``analysis.instances.measure``, for ``label_file`` and for the writer thread of ``infer``:
     ``write_mesh`` where ``measured`` (an ``analysis.instances.Measured`` of host arrays) holds a mesh, and ``write_instances`` of the
     rows of the host ``table`` with the columns of ``measured.extra`` after them, the skeleton and the thickness map (the root of
     ``measured.t2`` is taken here, off the thread that feeds the GPU) and the curvature map (``measured.curvature`` becomes the
     float volume here as well; ``measured.vertex_curvature`` goes into the PLY); ``write_picks`` of ``measured.picks`` under the
-    options ``picks`` where there is a pick table.  Returns the .hdf path."""
+    options ``picks`` where there is a pick table; ``write_filaments`` of ``measured.filament_voxels`` and ``measured.filament_branches``
+    under the options ``trace`` where the skeleton was traced, and ``<label>_filaments`` beside the skeleton.  Returns the .hdf path."""
+    filaments = None
+    if measured.filament_voxels is not None:
+        write_filaments(results_dir, tomo_name, label_key, measured.filament_voxels, measured.filament_branches,
+                        trace if trace is not None else TraceOptions(trace=True))
+        filaments = filament_volume(measured.filament_voxels, labels.shape)
     if measured.picks is not None:
         write_picks(results_dir, tomo_name, label_key, measured.picks, picks if picks is not None else PickOptions(pick=True))
     if measured.mesh is not None:
@@ -127,7 +141,7 @@ def write_measured(results_dir, tomo_name: str, label_key: str, datasets: dict[s
     merge_columns(rows, measured.extra)
     return write_instances(results_dir, tomo_name, label_key, datasets, labels, rows, skeleton=measured.skeleton,
                            thickness=None if measured.t2 is None else thickness_map(measured.t2),
-                           curvature=None if measured.curvature is None else curvature_map(measured.curvature))
+                           curvature=None if measured.curvature is None else curvature_map(measured.curvature), filaments=filaments)
 
 
 def write_picks(results_dir, tomo_name: str, label_key: str, table: np.ndarray, opts: PickOptions) -> tuple[Path, Path]:
@@ -138,6 +152,18 @@ def write_picks(results_dir, tomo_name: str, label_key: str, table: np.ndarray, 
     records = pick_records(table, opts)
     base = Path(results_dir) / "picks" / f"{stem}_{label_key}"
     return write_picks_csv(base.with_name(base.name + ".csv"), records), write_star(base.with_name(base.name + ".star"), records, stem)
+
+
+def write_filaments(results_dir, tomo_name: str, label_key: str, voxels: np.ndarray, branches: np.ndarray, opts: TraceOptions) -> tuple[Path, Path, Path]:
+    """<results_dir>/filaments/<tomo stem>_<label>_branches.csv (every branch), <tomo stem>_<label>.csv (every sampled position with its
+    tangent) and .star (those with a tangent as helical RELION particles, ``_rlnMicrographName`` = the tomogram's stem) of the two host
+    tables of the traced skeleton under ``opts`` (``analysis.filaments.branch_records``, ``sample_points`` and its writers).  Returns
+    the three paths."""
+    stem = Path(tomo_name).stem
+    base = Path(results_dir) / "filaments" / f"{stem}_{label_key}"
+    points = sample_points(voxels, branches, opts)
+    return (write_branches_csv(base.with_name(base.name + "_branches.csv"), branch_records(voxels, branches)),
+            write_points_csv(base.with_name(base.name + ".csv"), points), write_helical_star(base.with_name(base.name + ".star"), points, stem))
 
 
 def write_mesh(results_dir, tomo_name: str, label_key: str, vertices: np.ndarray, triangles: np.ndarray, ids: np.ndarray,

@@ -987,6 +987,76 @@ int cvx_pick_emit(const int32_t* labels, const uint64_t* fg, const uint64_t* sta
                   long workspace_bytes, long P, int32_t* table, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Filament tracing (`infer --instances --trace`, `cryovit instances --trace`): the skeleton of every instance as a graph of branches,
+ * every voxel with its branch, its rank along it and the steps up to it: lengths per filament, junctions, and where to cut
+ * segments for helical averaging.  Integers only, no float atomics, bit-reproducible.
+ *
+ * sk int32 [D][H][W] (in the product the volume of the skeleton section; any volume is traced exactly), ids outside 1..k count as 0.
+ *   Neighbours   two voxels that are 26-adjacent and carry the same id; deg(v) = the number of neighbours of v.
+ *   Path voxel   deg == 2.  Node voxel: any other nonzero voxel (end: deg 1, junction voxel: deg >= 3, point: deg 0).
+ *   Chain        a maximal connected set of path voxels; each has at most two path neighbours, so it is open or a closed ring.  An
+ *                open chain has two extremal path voxels (a chain of one voxel: the same twice) and its two terminal node voxels
+ *                are their non-path neighbours.  The head is the extremal path voxel with the smaller raster index (of a
+ *                one-voxel chain the start node is the neighbour with the smaller index); the branch runs from the start node, the
+ *                terminal next to the head, through the ranks 1..n to the end node.
+ *   Ring         a chain in which every voxel has two path neighbours.  m = its voxel with the smallest raster index has rank 1, the
+ *                neighbour of m with the smaller index rank 2, and so on to rank L; start node = end node = m, and the step
+ *                counts include the step that closes the ring.
+ *   Link         an end voxel whose only neighbour is a node voxel; no path voxels; between two ends counted once, from the end
+ *                with the smaller index.  The start is that key end voxel, the end its neighbour.
+ *   Junction voxels belong to no branch; points are no branches.  The key voxel of a branch is the head of a chain, m of a ring, the
+ *   key end of a link; branches are numbered 1..B in raster order of their key voxels.
+ *   Steps        a step between neighbours is a face, an edge or a corner step.  A voxel's (f, e, c) count the steps from the start
+ *                node to it, a branch's also the step into the end node.
+ *   Voxel table  int32 [N][CVX_TRACE_VOXEL_COLS] in raster order of the N nonzero voxels: z, y, x, id, degree, branch, rank, f, e,
+ *                c, d2, ring.  branch, rank and the counts are 0 on node voxels; d2 is the caller's distance map at the voxel (0
+ *                without one, and where it holds CVX_EDT_NONE); ring is 1 on ring voxels.
+ *   Branch table int64 [B][CVX_TRACE_BRANCH_COLS]: id, kind (0 end-end, 1 end-junction, 2 junction-junction, 3 ring), path_voxels,
+ *                f, e, c, start_index, end_index (linear voxel indices), start_degree, end_degree, sum_d2, min_d2, max_d2 (over the
+ *                path voxels; 0 without any), head_index, last_index (-1 for a link), chord2 (the squared distance of the start
+ *                and end node voxels).
+ * A voxel's slot is its row in the voxel table.  The ranking runs by pointer doubling over direction states: state 2 v + j = at
+ * path voxel v, travelling to its neighbour j (0: the one with the smaller index).  A state holds CVX_TRACE_STATE_BYTES bytes.
+ *   cvx_trace_workspace_bytes  the bytes of one bitmap, 8 per 64 voxels of a row; < 0 on bad extents.  bits holds two of them.
+ *   cvx_trace_count            bits = (nonzero voxels, path voxels) as bits; row_first int32 [2][D*H]: [0] the voxels in the rows
+ *                              before each row, [1] the same of the path voxels; totals int64 [2] = N, Np, zeroed by the call.
+ *   cvx_trace_emit             z, y, x, id, degree, d2 of every voxel (the other columns 0) and nbrs int32 [N][2], the slots of the
+ *                              neighbours of an end or path voxel in raster order (-1: none; both -1 on other voxels).  d2 may
+ *                              be null.  With an N above the count the rows past it are zero, with a smaller one voxels are left out.
+ *   cvx_trace_rank             writes the states of the path voxels to state_a and runs `rounds` doubling rounds, round j = 0, 1, ...
+ *                              from state_a to state_b when j is even and back when odd: the result is in state_a after an even
+ *                              number of rounds, in state_b after an odd one.  ceil(log2(max(Np, 2))) rounds bring every chain
+ *                              state to its end of the chain.  cut int32 [N] (nullable): a state stops before voxel cut[v].
+ *   cvx_trace_rings            cut[v] = the smallest slot of the ring v lies on, -1 elsewhere, from the states of a rank without
+ *                              cut; any int32 [1], zeroed by the call, = 1 iff there is a ring.  With rings, rank again with cut.
+ *   cvx_trace_keys             rank, f, e, c and ring of every path voxel; keys int32 [N] = the key voxels before each voxel;
+ *                              total = B, zeroed by the call.  state (of the last rank) may be null when Np == 0, cut when
+ *                              there is no ring.
+ *   cvx_trace_branches         the branch column of the voxel table and the branch table; first = keys of cvx_trace_keys, B its
+ *                              total (with a larger B the rows past the count are zero, with a smaller one branches are left out).
+ * Refused with an error before any launch: negative extents, an extent above 32768, D*H*W > CVX_COMPONENT_MAX_VOXELS, k < 0, N
+ * outside [0, D*H*W] (without extents: [0, CVX_COMPONENT_MAX_VOXELS]), B outside [0, N], rounds outside [0, 32], null pointers,
+ * misaligned arrays (int32 and states: 4 bytes, bitmaps, totals and branches: 8 bytes), a workspace_bytes below
+ * cvx_trace_workspace_bytes, states that overlap, a cut without a state.  k == 0, an empty volume and N == 0 succeed and launch
+ * nothing (cvx_trace_count, cvx_trace_rings and cvx_trace_keys still zero totals, any and total).
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_TRACE_VOXEL_COLS 12
+#define CVX_TRACE_BRANCH_COLS 16
+#define CVX_TRACE_STATE_BYTES 20
+long cvx_trace_workspace_bytes(int D, int H, int W);
+int cvx_trace_count(const int32_t* sk, int D, int H, int W, long k, uint64_t* bits, long workspace_bytes, int32_t* row_first,
+                    int64_t* totals, hipStream_t stream);
+int cvx_trace_emit(const int32_t* sk, const int32_t* d2, const uint64_t* bits, const int32_t* row_first, int D, int H, int W, long k,
+                   long workspace_bytes, long N, int32_t* voxels, int32_t* nbrs, hipStream_t stream);
+int cvx_trace_rank(const int32_t* voxels, const int32_t* nbrs, const int32_t* cut, long N, int rounds, void* state_a, void* state_b,
+                   hipStream_t stream);
+int cvx_trace_rings(const int32_t* voxels, const void* state, long N, int32_t* cut, int32_t* any, hipStream_t stream);
+int cvx_trace_keys(int32_t* voxels, const int32_t* nbrs, const void* state, const int32_t* cut, long N, int32_t* keys, int64_t* total,
+                   hipStream_t stream);
+int cvx_trace_branches(int32_t* voxels, const int32_t* nbrs, const void* state, const int32_t* cut, const int32_t* first, int D, int H,
+                       int W, long N, long B, int64_t* branches, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Raw tomogram -> uint8 in [0, 255] (`cryovit preprocess`, `features --normalize`): bin, moments, order statistics, quantise.
  * A volume is [D][H][W] of one of the CVX_VOL_* element types; CVX_VOL_I32 is what the bin pass makes of an integer source.
  * Everything but the two float32 moment sums is exact and bit-reproducible; those two are reproducible and bounded (below).
