@@ -49,6 +49,9 @@ PICK_RADIUS_MIN, PICK_RADIUS_MAX = 2, 16  # CVX_PICK_RADIUS_MIN / CVX_PICK_RADIU
 PICK_SPACING_MIN, PICK_SPACING_MAX = 2, 16  # CVX_PICK_SPACING_MIN / CVX_PICK_SPACING_MAX
 TRACE_VOXEL_COLS, TRACE_BRANCH_COLS = 12, 16  # CVX_TRACE_VOXEL_COLS / CVX_TRACE_BRANCH_COLS
 TRACE_STATE_BYTES = 20  # CVX_TRACE_STATE_BYTES
+SUBTOMO_COLS = 12  # CVX_SUBTOMO_COLS
+SUBTOMO_BOX_MIN, SUBTOMO_BOX_MAX = 8, 128  # CVX_SUBTOMO_BOX_MIN / CVX_SUBTOMO_BOX_MAX
+SUBTOMO_MAX_PARTICLES = 1 << 20  # CVX_SUBTOMO_MAX_PARTICLES
 VOL_I8, VOL_U8, VOL_I16, VOL_U16, VOL_I32, VOL_F32 = range(6)  # CVX_VOL_* element types
 BIN_MAX = 8  # CVX_BIN_MAX
 MOMENT_GROUP, MOMENT_CHAIN, MOMENT_TREE = 4096, 16, 8  # CVX_MOMENT_*
@@ -260,6 +263,9 @@ SIGNATURES = {
     "cvx_trace_keys": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "cvx_trace_branches": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_void_p,
                                    c_void_p]),
+    "cvx_subtomo_extract": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p]),
+    "cvx_subtomo_sum": (c_int, [c_void_p, c_long, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "cvx_subtomo_profile": (c_int, [c_void_p, c_long, c_int, c_long, c_void_p, c_void_p]),
     "cvx_volume_bin": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_int, c_int, c_void_p, c_void_p]),
     "cvx_volume_moments": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_volume_select_hist": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -4,7 +4,8 @@ which of another, the shape of each instance (surface area, Euler number, princi
 its local thickness (mean, spread, min, max), the surface mesh of the mask (PLY / STL; triangles, area, volume) and the mean
 curvature of its membrane (ball-volume integral invariant; mean, spread, min, max, convex share); evenly spaced positions on
 that membrane with its normal, the particle picks of subtomogram averaging (RELION STAR / CSV); the centreline traced into
-filaments (branches, junctions, rings; positions with tangents along them as helical STAR / CSV); the
+filaments (branches, junctions, rings; positions with tangents along them as helical STAR / CSV); oriented subtomograms cut out
+of the tomogram at either kind of position (MRC stack, average, density profile along the axis); the
 clean-up of the mask before all of that (close, fill holes, open); and, against annotated labels, how far the predicted boundary
 lies from the true one (HD95, surface distance, surface Dice) and how well the annotated objects are recovered one by one (detection
 F1, panoptic quality, Rand index, split / merge variation of information)."""
@@ -25,6 +26,9 @@ from cryovit_amd.analysis.picks import (  # noqa: F401
 from cryovit_amd.analysis.filaments import (  # noqa: F401
     BRANCH_CSV_COLUMNS, FILAMENT_COLUMNS, POINT_CSV_COLUMNS, TraceOptions, branch_records, filament_rows, filament_volume, junction_nodes,
     sample_points, trace_tables, write_branches_csv, write_helical_star, write_points_csv)
+from cryovit_amd.analysis.subtomograms import (  # noqa: F401
+    EXTRACT_COLUMNS, ExtractOptions, extract_rows, extract_to_files, filament_particles, instance_profiles, particle_frames, particle_table,
+    pick_particles, write_particle_star, write_profiles_csv)
 from cryovit_amd.analysis.boundary import (  # noqa: F401
     BOUNDARY_COUNT_COLUMNS, BOUNDARY_DISTANCE_COLUMNS, BOUNDARY_MODES, boundary_columns, boundary_histograms, boundary_scores, check_scored,
     nsd_column)

@@ -26,6 +26,7 @@ from cryovit_amd.analysis.mesh import MESH_FORMATS, mesh_arrays, mesh_rows
 from cryovit_amd.analysis.picks import PickOptions, pick_rows, pick_table
 from cryovit_amd.analysis.shape import instance_shape
 from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
+from cryovit_amd.analysis.subtomograms import ExtractOptions, tomogram_bytes
 from cryovit_amd.analysis.thickness import thickness_rows, thickness_volume
 
 INSTANCE_COLUMNS = ["id", "voxels", "z", "y", "x", "z0", "z1", "y0", "y1", "x0", "x1"]
@@ -275,7 +276,8 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
                curvature: bool = False, curvature_radius: int = 5,
                pick: bool = False, pick_spacing: int = 8, pick_radius: int = 5, pick_offset: float = 0.0, pick_scale: float = 1.0,
                pick_seed: int = 0, trace: bool = False, trace_spacing: float = 8.0, trace_window: float = 4.0, trace_min_length: float = 0.0,
-               trace_scale: float = 1.0, trace_angpix: float = 1.0) -> Path:
+               trace_scale: float = 1.0, trace_angpix: float = 1.0, extract: str | None = None, extract_box: int = 32,
+               extract_orient: str = "aligned", extract_profile_radius: float | None = None) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  The measurements are those of ``InstanceOptions``.
@@ -290,6 +292,10 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     traced into branches, ``filaments/<tomo stem>_<label>_branches.csv``, ``filaments/<tomo stem>_<label>.csv`` and ``.star`` are written
     under ``result_dir``, ``<label>_filaments`` beside ``<label>_skeleton``, and the CSV gains ``analysis.filaments.FILAMENT_COLUMNS``
     directly after the skeleton's columns.
+    ``extract`` and the other ``extract_*`` are the fields of ``analysis.subtomograms.ExtractOptions``: ``"picks"`` turns ``pick`` on,
+    ``"filaments"`` turns ``trace`` on; oriented boxes of the file's ``data`` (a uint8 volume of the shape of the predictions, as
+    ``cryovit preprocess`` makes it) are cut at those positions, ``subtomograms/<tomo stem>_<label>.mrcs``, ``_average.mrc``, ``.star``
+    and ``_profiles.csv`` are written under ``result_dir`` and the CSV gains ``analysis.subtomograms.EXTRACT_COLUMNS`` as its last columns.
     ``distance_to`` names another label whose mask (``<distance_to>_preds`` of the same file, else of
     ``distance_to_dir/<same stem>.hdf``) the gap and contact columns are taken against.  ``contacts_with`` names another label
     whose instances are paired with this label's: ``<contacts_with>_instances`` of the same file, else of
@@ -306,6 +312,9 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     cleanup = CleanupOptions(close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius).validate()
     curve = CurvatureOptions(curvature=curvature, curvature_radius=curvature_radius).validate()
     check_mesh_format(curvature, mesh, mesh_format)
+    extracting = ExtractOptions(extract=extract, extract_box=extract_box, extract_orient=extract_orient,
+                                extract_profile_radius=extract_profile_radius).validate()
+    pick, trace = pick or extracting.extract == "picks", trace or extracting.extract == "filaments"
     picking = PickOptions(pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
                           pick_seed=pick_seed).validate()
     tracing = TraceOptions(trace=trace, trace_spacing=trace_spacing, trace_window=trace_window, trace_min_length=trace_min_length,
@@ -318,6 +327,7 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     preds = datasets[key]
     if preds.ndim != 3:
         raise ValueError(f"'{key}' of {path} must be a [D, H, W] volume, got shape {preds.shape}")
+    tomogram = tomogram_bytes(datasets.get("data"), preds.shape, str(path)) if extracting.extract else None
     opts = InstanceOptions(connectivity=connectivity, min_size=min_size, morphology=morphology, split_radius=split_radius,
                            split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
                            thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format,
@@ -359,6 +369,9 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
         log_totals(f"{path} '{label}'", totals)
         datasets = {name: arr for name, arr in datasets.items() if name != key} | {key: preds, f"{label}_cleaned": cleaned.cpu().numpy()}
     result_dir = result_dir if result_dir is not None else path.parent
+    if tomogram is not None:
+        merge_columns(found.extra, writers.write_subtomograms(result_dir, path.name, label, torch.from_numpy(tomogram).to(device), found,
+                                                              int(table.shape[0]), extracting, picking, tracing))
     if found.pairs is not None:
         writers.write_contacts(result_dir, path.name, label, contacts_with, found.pairs)
     return writers.write_measured(result_dir, path.name, label, datasets, labels.cpu().numpy(), table.cpu().numpy(),

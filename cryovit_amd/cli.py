@@ -22,6 +22,7 @@
                     [--curvature [--curvature-radius R]]
                     [--pick [--pick-spacing S] [--pick-radius R] [--pick-offset V] [--pick-scale F] [--pick-seed N]]
                     [--trace [--trace-spacing S] [--trace-window H] [--trace-min-length L] [--trace-scale F] [--trace-angpix A]]
+                    [--extract picks|filaments [--extract-box B] [--extract-orient aligned|none] [--extract-profile-radius R]]
 
 ``preprocess`` (build extension) turns raw reconstructions (int8 / uint8 / int16 / uint16 / float MRC, TIFF or HDF5, as IMOD or AreTomo
 write them) into the uint8 tomograms every other command expects, on the GPU: bin, clip, rescale to [0, 255]
@@ -40,6 +41,10 @@ instance's membrane, no two of one instance closer than ``--pick-spacing`` voxel
 (it implies ``--skeleton`` and uses ``--skeleton-end-radius``) and splits it into branches between ends and junctions, and rings: how many
 filaments there are, how long and how straight each is, which meet where, and positions every ``--trace-spacing`` voxels along them with
 the tangent, as ``filaments/<tomo>_<label>_branches.csv``, ``.csv`` and a helical RELION ``.star`` (``analysis.filaments.TraceOptions``).
+``--extract picks`` (it implies ``--pick``) and ``--extract filaments`` (it implies ``--trace``) cut a box of ``--extract-box`` voxels out
+of the uint8 tomogram around every such position, rotated so that its z axis is the membrane normal or the filament tangent, and write
+``subtomograms/<tomo>_<label>.mrcs``, their average, a RELION ``.star`` and the density profile along that axis per instance
+(``analysis.subtomograms.ExtractOptions``).
 ``--distance-to NAME`` adds the gap to another
 label's mask and the voxels in contact with it; ``--contacts-with NAME`` says which instance touches which: every instance gains
 ``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance, nearest instance of NAME within
@@ -284,9 +289,30 @@ TraceScale = Annotated[float, Option("--trace-scale", callback=_trace_checked("t
 TraceAngpix = Annotated[float, Option("--trace-angpix", callback=_trace_checked("trace_angpix", lambda v: v > 0, "> 0"),
                                       help=_EXT + _TRACE_ANGPIX_HELP)]
 
+_EXTRACT_HELP = ("cut oriented subtomograms out of the uint8 tomogram on the GPU, at the picks (picks: implies --pick) or at the "
+                 "positions along the filaments (filaments: implies --trace): a box around each, rotated so that its z axis is the membrane "
+                 "normal or the filament tangent, trilinear.  Writes <result>/subtomograms/<tomo>_<label>.mrcs (a stack of float32 "
+                 "volumes), _average.mrc, .star (the pick or helical columns and _rlnImageName) and _profiles.csv (the mean density "
+                 "per box z slab and instance) and adds extracted and extract_skipped as the last CSV columns.  The file's data must be "
+                 "the uint8 tomogram that `cryovit preprocess` makes (with infer: needs --instances)")
+Extract = Annotated[Optional[str], Option("--extract", callback=_checked(lambda v: v in ("picks", "filaments"), "extract must be picks or filaments"),
+                                          help=_EXT + _EXTRACT_HELP)]
+ExtractBox = Annotated[int, Option("--extract-box", callback=_checked(lambda v: 8 <= v <= 128 and v % 2 == 0,
+                                                                      "extract box must be even and lie in 8..128 (voxels)"),
+                                   help=_EXT + "with --extract, the edge of the box (voxels, an even integer in 8..128)")]
+ExtractOrient = Annotated[str, Option("--extract-orient", callback=_checked(lambda v: v in ("aligned", "none"), "extract orient must be aligned or none"),
+                                      help=_EXT + "with --extract, aligned: box z along the normal / tangent, angles written as 0; none: "
+                                                  "axis-parallel boxes, the angles stay priors in the STAR file")]
+ExtractProfileRadius = Annotated[Optional[float], Option("--extract-profile-radius",
+                                                         callback=_checked(lambda v: math.isfinite(v) and v >= 0,
+                                                                           "extract profile radius must be finite and >= 0 (voxels)"),
+                                                         help=_EXT + "with --extract, the radius of the disc around the axis that the density "
+                                                                     "profile averages over (voxels, >= 0)",
+                                                         show_default="a quarter of the box")]
+
 # infer measures nothing without --instances: asking for one of these without it is a usage error
 _NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh", "close_radius", "fill_holes", "open_radius",
-                    "curvature", "pick", "trace")
+                    "curvature", "pick", "trace", "extract")
 
 
 def _refuse_stl_curvature(curvature: bool, mesh: bool, mesh_format: str) -> None:
@@ -468,6 +494,10 @@ def infer(
     trace_min_length: TraceMinLength = 0.0,
     trace_scale: TraceScale = 1.0,
     trace_angpix: TraceAngpix = 1.0,
+    extract: Extract = None,
+    extract_box: ExtractBox = 32,
+    extract_orient: ExtractOrient = "aligned",
+    extract_profile_radius: ExtractProfileRadius = None,
 ):
     """Segment tomograms using a pre-trained model."""
     measurements = dict(min_size=min_size, connectivity=connectivity, morphology=morphology, split_radius=split_radius,
@@ -477,7 +507,9 @@ def infer(
                         curvature=curvature, curvature_radius=curvature_radius,
                         pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
                         pick_seed=pick_seed, trace=trace, trace_spacing=trace_spacing, trace_window=trace_window,
-                        trace_min_length=trace_min_length, trace_scale=trace_scale, trace_angpix=trace_angpix)
+                        trace_min_length=trace_min_length, trace_scale=trace_scale, trace_angpix=trace_angpix,
+                        extract=extract, extract_box=extract_box, extract_orient=extract_orient,
+                        extract_profile_radius=extract_profile_radius)
     _refuse_stl_curvature(curvature, mesh, mesh_format)
     for name in _NEEDS_INSTANCES:
         value = measurements[name]  # a flag that is off is False, a radius that is not given None; a radius of 0 is given
@@ -536,6 +568,10 @@ def instances_cmd(
     trace_min_length: TraceMinLength = 0.0,
     trace_scale: TraceScale = 1.0,
     trace_angpix: TraceAngpix = 1.0,
+    extract: Extract = None,
+    extract_box: ExtractBox = 32,
+    extract_orient: ExtractOrient = "aligned",
+    extract_profile_radius: ExtractProfileRadius = None,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     _refuse_stl_curvature(curvature, mesh, mesh_format)
@@ -555,7 +591,9 @@ def instances_cmd(
                          curvature=curvature, curvature_radius=curvature_radius,
                          pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
                          pick_seed=pick_seed, trace=trace, trace_spacing=trace_spacing, trace_window=trace_window,
-                         trace_min_length=trace_min_length, trace_scale=trace_scale, trace_angpix=trace_angpix)
+                         trace_min_length=trace_min_length, trace_scale=trace_scale, trace_angpix=trace_angpix,
+                         extract=extract, extract_box=extract_box, extract_orient=extract_orient,
+                         extract_profile_radius=extract_profile_radius)
         logging.info("Labelled %s", out)
 
 

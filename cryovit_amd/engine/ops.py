@@ -1765,6 +1765,83 @@ def surface_distance_hist(surf: torch.Tensor, d2: torch.Tensor, bins: int, *, ou
     return out
 
 
+# ---- oriented subtomograms (`--extract`): rotated boxes, their sums and profiles (csrc/subtomo.hip) ----
+
+def _subtomo_box(what: str, box) -> int:
+    if not isinstance(box, int) or isinstance(box, bool) or box % 2 or not _lib.SUBTOMO_BOX_MIN <= box <= _lib.SUBTOMO_BOX_MAX:
+        raise _lib.CvxError(f"{what}: box must be an even integer in [{_lib.SUBTOMO_BOX_MIN}, {_lib.SUBTOMO_BOX_MAX}], got {box!r}")
+    return box
+
+
+def _subtomo_stack(what: str, stack) -> tuple[int, int]:
+    """(P, B) of a stack of boxes: int32 [P, B, B, B]."""
+    if not isinstance(stack, torch.Tensor) or stack.dtype != torch.int32 or stack.dim() != 4 or len(set(stack.shape[1:])) != 1:
+        got = f"{stack.dtype} {tuple(stack.shape)}" if isinstance(stack, torch.Tensor) else type(stack).__name__
+        raise _lib.CvxError(f"{what}: stack must be int32 [P, B, B, B], got {got}")
+    P, box = int(stack.shape[0]), _subtomo_box(what, int(stack.shape[1]))
+    if P > _lib.SUBTOMO_MAX_PARTICLES:
+        raise _lib.CvxError(f"{what}: at most 2^20 particles per call, got {P}")
+    return P, box
+
+
+def extract_subtomograms(volume: torch.Tensor, table: torch.Tensor, box: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(stack int32 [P, B, B, B], status int64 [1]) on the device: around every row cz, cy, cx (Q8), m[a][j] (Q16, row by row) of
+    ``table`` (int32 [P, 12]) the box of ``box``^3 voxels whose axes are the columns of m, sampled trilinearly from ``volume`` (uint8
+    [D, H, W]) with a replicated border, in units of 2^-21 grey level (the definition is in include/cryovit_hip.h).  A particle
+    whose matrix is no rotation (a 16^3 block of it would need more than the kernel's 30 x 30 x 32 brick) is all zeros and counted
+    in ``status``.  Nobody waits.  Integers only, bit-reproducible (csrc/subtomo.hip)."""
+    _volume_check("extract_subtomograms", "volume", volume, torch.uint8)
+    box = _subtomo_box("extract_subtomograms", box)
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != _lib.SUBTOMO_COLS:
+        got = f"{table.dtype} {tuple(table.shape)}" if isinstance(table, torch.Tensor) else type(table).__name__
+        raise _lib.CvxError(f"extract_subtomograms: table must be int32 [P, {_lib.SUBTOMO_COLS}], got {got}")
+    P = int(table.shape[0])
+    if P > _lib.SUBTOMO_MAX_PARTICLES:
+        raise _lib.CvxError(f"extract_subtomograms: at most 2^20 particles per call, got {P}")
+    dev, D, H, W = _volumes_check("extract_subtomograms", volume=(volume, torch.uint8))
+    _dev_check(volume, table)
+    status = torch.zeros(1, dtype=torch.int64, device=dev)
+    if P == 0 or volume.numel() == 0:
+        return torch.zeros((P, box, box, box), dtype=torch.int32, device=dev), status
+    out = torch.empty((P, box, box, box), dtype=torch.int32, device=dev)
+    call(dev, "cvx_subtomo_extract", _lib.load().cvx_subtomo_extract, _p(volume), D, H, W, _p(table), P, box, _p(out), _p(status))
+    return out, status
+
+
+def subtomogram_sums(stack: torch.Tensor, group: torch.Tensor, groups: int = 1, sums: torch.Tensor | None = None) -> torch.Tensor:
+    """int64 [G, B, B, B] on the device: ``sums`` (default: zeros) plus, per group g, the boxes of ``stack`` (int32 [P, B, B, B]) whose
+    ``group`` (int32 [P]) is g; a particle with a group outside 0..G-1 (-1: left out) is skipped.  Given ``sums`` is added to in
+    place and returned, so the chunks of a long particle list accumulate.  64-bit integer atomics: the order plays no part."""
+    P, box = _subtomo_stack("subtomogram_sums", stack)
+    if not isinstance(groups, int) or isinstance(groups, bool) or groups < 1:
+        raise _lib.CvxError(f"subtomogram_sums: groups must be an integer >= 1, got {groups!r}")
+    if not isinstance(group, torch.Tensor) or group.dtype != torch.int32 or tuple(group.shape) != (P,):
+        got = f"{group.dtype} {tuple(group.shape)}" if isinstance(group, torch.Tensor) else type(group).__name__
+        raise _lib.CvxError(f"subtomogram_sums: group must be int32 [{P}], got {got}")
+    if sums is None:
+        sums = torch.zeros((groups, box, box, box), dtype=torch.int64, device=stack.device)
+    elif not isinstance(sums, torch.Tensor) or sums.dtype != torch.int64 or tuple(sums.shape) != (groups, box, box, box):
+        got = f"{sums.dtype} {tuple(sums.shape)}" if isinstance(sums, torch.Tensor) else type(sums).__name__
+        raise _lib.CvxError(f"subtomogram_sums: sums must be int64 [{groups}, {box}, {box}, {box}], got {got}")
+    dev = _dev_check(stack, group, sums)
+    if P:
+        call(dev, "cvx_subtomo_sum", _lib.load().cvx_subtomo_sum, _p(stack), P, box, _p(group), groups, _p(sums))
+    return sums
+
+
+def subtomogram_profiles(stack: torch.Tensor, radius2: int) -> torch.Tensor:
+    """int64 [P, B] on the device: per box of ``stack`` (int32 [P, B, B, B]) and z slab the sum of the voxels with
+    o_y^2 + o_x^2 <= ``radius2``, o = index - B/2 (``analysis.subtomograms.disc_voxels`` counts them)."""
+    P, box = _subtomo_stack("subtomogram_profiles", stack)
+    if not isinstance(radius2, int) or isinstance(radius2, bool) or radius2 < 0:
+        raise _lib.CvxError(f"subtomogram_profiles: radius2 must be an integer >= 0, got {radius2!r}")
+    dev = _dev_check(stack)
+    profile = torch.empty((P, box), dtype=torch.int64, device=dev)
+    if P:
+        call(dev, "cvx_subtomo_profile", _lib.load().cvx_subtomo_profile, _p(stack), P, box, min(radius2, 2**62), _p(profile))
+    return profile
+
+
 # ---- a raw tomogram to uint8 (`cryovit preprocess`, `features --normalize`): bin, moments, order statistics, quantise ----
 
 MOMENT_GROUP = _lib.MOMENT_GROUP  # voxels of a slice under one partial of volume_moments

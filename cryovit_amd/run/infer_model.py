@@ -29,6 +29,10 @@ gains ``picks`` and ``picks_unoriented`` as its last columns.
 ``trace`` and the other ``trace_*`` (with ``instances``) are the fields of ``analysis.filaments.TraceOptions``: the skeleton (which
 ``trace`` turns on) is traced into branches while it is in HBM; ``filaments/<tomo stem>_<label_key>_branches.csv``, ``.csv`` and ``.star``
 are written, each file also holds ``<label_key>_filaments`` and the table gains the filament columns directly after the skeleton's.
+``extract`` and the other ``extract_*`` (with ``instances``) are the fields of ``analysis.subtomograms.ExtractOptions``: ``"picks"``
+turns ``pick`` on, ``"filaments"`` turns ``trace`` on; oriented boxes of the tomogram (a uint8 ``data``, as ``cryovit preprocess``
+makes it) are cut at those positions while it is in HBM and written as ``subtomograms/<tomo stem>_<label_key>.mrcs``,
+``_average.mrc``, ``.star`` and ``_profiles.csv``; the table gains ``extracted`` and ``extract_skipped`` as its last columns.
 """
 
 from __future__ import annotations
@@ -44,14 +48,15 @@ from cryovit_amd import io
 from cryovit_amd.analysis.cleanup import CleanupOptions, added_rows, added_voxels, clean_mask, log_totals
 from cryovit_amd.analysis.curvature import CurvatureOptions, check_mesh_format
 from cryovit_amd.analysis.filaments import TraceOptions
-from cryovit_amd.analysis.instances import InstanceOptions, label_and_split, measure
+from cryovit_amd.analysis.instances import InstanceOptions, label_and_split, measure, merge_columns
 from cryovit_amd.analysis.picks import PickOptions
+from cryovit_amd.analysis.subtomograms import ExtractOptions, tomogram_bytes
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
 from cryovit_amd.run import writers
 from cryovit_amd.run.sharding import gather_rows, select_device, shard_records, world_info
 from cryovit_amd.types import FileData
-from cryovit_amd.utils import load_data, load_model
+from cryovit_amd.utils import load_data, load_model, mrc_voxel_size
 
 
 def _has_key(path: Path, key: str) -> bool:
@@ -111,12 +116,18 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                   open_radius: float | None = None, curvature: bool = False, curvature_radius: int = 5,
                   pick: bool = False, pick_spacing: int = 8, pick_radius: int = 5, pick_offset: float = 0.0, pick_scale: float = 1.0,
                   pick_seed: int = 0, trace: bool = False, trace_spacing: float = 8.0, trace_window: float = 4.0, trace_min_length: float = 0.0,
-                  trace_scale: float = 1.0, trace_angpix: float = 1.0) -> list[Path]:
+                  trace_scale: float = 1.0, trace_angpix: float = 1.0, extract: str | None = None, extract_box: int = 32,
+                  extract_orient: str = "aligned", extract_profile_radius: float | None = None) -> list[Path]:
     opts = InstanceOptions(connectivity=connectivity, min_size=min_size, morphology=morphology, split_radius=split_radius,
                            split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
                            thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
     cleanup = CleanupOptions(close_radius=close_radius, fill_holes=fill_holes, open_radius=open_radius)
     curve = CurvatureOptions(curvature=curvature, curvature_radius=curvature_radius)
+    extracting = ExtractOptions(extract=extract, extract_box=extract_box, extract_orient=extract_orient,
+                                extract_profile_radius=extract_profile_radius)
+    if extract is not None and not instances:
+        raise ValueError(f"extract={extract!r} needs instances=True: the subtomograms are cut at positions on the labelled instances")
+    pick, trace = pick or extract == "picks", trace or extract == "filaments"
     picking = PickOptions(pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
                           pick_seed=pick_seed)
     tracing = TraceOptions(trace=trace, trace_spacing=trace_spacing, trace_window=trace_window, trace_min_length=trace_min_length,
@@ -141,6 +152,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
     curve.validate()
     picking.validate()
     tracing.validate()
+    extracting.validate()
     check_mesh_format(curvature, mesh, mesh_format)
     rank, _, world = world_info()
     device = select_device(device)
@@ -173,10 +185,17 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 host_labels = _pinned(labels)  # on its way while the instances are measured
                 host_table = table.cpu().numpy()
                 found = measure(labels, int(table.shape[0]), component, opts, curvature=curve, picks=picking, trace=tracing)
+                cut = None
+                if extracting.extract:  # on the tables of measure, while they and the mask's device are at hand
+                    tomogram = tomogram_bytes(raw, tuple(mask.shape), str(files[i].tomo_path))
+                    cut = writers.write_subtomograms(result_dir, files[i].tomo_path.name, label_key, torch.from_numpy(tomogram).to(mask.device),
+                                                     found, int(table.shape[0]), extracting, picking, tracing, mrc_voxel_size(files[i].tomo_path))
                 if cleanup.any:
                     host_cleaned = _pinned(cleaned)
                     found.extra = added_rows(added_voxels(labels, predicted, int(table.shape[0])), found.extra)
                     log_totals(f"{files[i].tomo_path.name} '{label_key}'", totals)
+                if cut is not None:
+                    merge_columns(found.extra, cut)
                 found = found.arrays(_pinned)
             torch.cuda.current_stream(mask.device).synchronize()
             if instances:

@@ -15,6 +15,9 @@
                          membrane normals, every pick in the CSV, the oriented ones as RELION particles in the STAR file
   write_filaments        (not in the reference) <results_dir>/filaments/<tomo stem>_<label>_branches.csv (every branch of the traced
                          skeleton), <tomo stem>_<label>.csv (positions with tangents along them) and .star (helical RELION particles)
+  write_subtomograms     (not in the reference) <results_dir>/subtomograms/<tomo stem>_<label>.mrcs (oriented boxes at the picks or the
+                         filament points, a stack of float32 volumes), _average.mrc, .star (RELION particles with _rlnImageName) and
+                         _profiles.csv (the density along the box z axis per instance)
   write_mesh             (not in the reference) <results_dir>/meshes/<tomo stem>_<label>.ply or .stl, the surface of the labelled mask
   write_instance_matches (not in the reference) <results_dir>/instances/<sample>_<tomo stem>.csv of ``cryovit evaluate
                         --instance-metrics``: every annotated instance with its best predicted partner, then the unmatched predicted ones
@@ -40,6 +43,7 @@ from cryovit_amd.analysis.curvature import curvature_map
 from cryovit_amd.analysis.filaments import (TraceOptions, branch_records, filament_volume, sample_points, write_branches_csv, write_helical_star,
                                             write_points_csv)
 from cryovit_amd.analysis.picks import PickOptions, pick_records, write_picks_csv, write_star
+from cryovit_amd.analysis.subtomograms import ExtractOptions, extract_rows, extract_to_files, filament_particles, pick_particles
 from cryovit_amd.analysis.thickness import thickness_map
 
 
@@ -152,6 +156,24 @@ def write_picks(results_dir, tomo_name: str, label_key: str, table: np.ndarray, 
     records = pick_records(table, opts)
     base = Path(results_dir) / "picks" / f"{stem}_{label_key}"
     return write_picks_csv(base.with_name(base.name + ".csv"), records), write_star(base.with_name(base.name + ".star"), records, stem)
+
+
+def write_subtomograms(results_dir, tomo_name: str, label_key: str, volume, measured, k: int, extract: ExtractOptions,
+                       picks: PickOptions | None = None, trace: TraceOptions | None = None, voxel_size: float | None = None) -> list[dict]:
+    """<results_dir>/subtomograms/<tomo stem>_<label>.mrcs, _average.mrc, .star and _profiles.csv: oriented boxes of the uint8 device
+    ``volume`` at the picks (``extract.extract`` = "picks": ``measured.picks`` under ``picks``) or the filament points ("filaments":
+    ``measured.filament_voxels`` and ``measured.filament_branches`` under ``trace``) of the instances 1..k
+    (``analysis.subtomograms.extract_to_files``).  ``measure`` does not see the tomogram, so this runs after it, on its tables, while
+    they and the volume are on the device.  Returns the rows of ``analysis.subtomograms.EXTRACT_COLUMNS``, one per instance, for
+    ``measured.extra``."""
+    if extract.extract == "picks":
+        picks = picks if picks is not None else PickOptions(pick=True)
+        particles = pick_particles(pick_records(measured.picks, picks), k, picks.pick_offset, extract.extract_orient)
+    else:
+        points = sample_points(measured.filament_voxels, measured.filament_branches, trace if trace is not None else TraceOptions(trace=True))
+        particles = filament_particles(points, k, extract.extract_orient)
+    extract_to_files(volume, particles, k, extract, results_dir, tomo_name, label_key, voxel_size)
+    return extract_rows(particles, k)
 
 
 def write_filaments(results_dir, tomo_name: str, label_key: str, voxels: np.ndarray, branches: np.ndarray, opts: TraceOptions) -> tuple[Path, Path, Path]:

@@ -19,6 +19,7 @@ and refuses pickled ``.model`` files with instructions to re-export them from ``
 from __future__ import annotations
 
 import logging
+import os
 import struct
 import zlib
 from dataclasses import dataclass
@@ -115,6 +116,43 @@ def _read_mrc_array(path) -> np.ndarray:
 def read_mrc(mrc_file) -> tuple[np.ndarray, FileMetadata]:
     data = _read_mrc_array(mrc_file)
     return data, _metadata(data)
+
+
+def mrc_header(nx: int, ny: int, nz: int, *, mz: int | None = None, ispg: int = 1, voxel_size: float | None = None, dmin: float = 0.0,
+               dmax: float = 0.0, dmean: float = 0.0) -> bytes:
+    """The 1024 bytes of a little-endian MRC2014 header of mode 2 (float32): nx, ny, nz; mx = nx, my = ny, mz (default nz; the
+    sections of one volume of a stack of volumes, ``ispg`` 401); the cell = voxel size times mx, my, mz in Angstrom (1 per voxel
+    where the size is unknown), angles of 90 degrees; axes 1, 2, 3; dmin, dmax, dmean; rms -1 (not computed); no extended header;
+    NVERSION 20140; ``MAP `` and the machine stamp 0x44 0x44; no labels."""
+    mz = nz if mz is None else mz
+    size = 1.0 if voxel_size is None else float(voxel_size)
+    head = struct.pack("<10i6f3i3f2i", nx, ny, nz, 2, 0, 0, 0, nx, ny, mz, size * nx, size * ny, size * mz, 90.0, 90.0, 90.0, 1, 2, 3,
+                       dmin, dmax, dmean, ispg, 0)
+    head += bytes(8) + b"\0\0\0\0" + struct.pack("<i", 20140)  # words 25-26, EXTTYP, NVERSION
+    head = head.ljust(196, b"\0") + struct.pack("<3f", 0.0, 0.0, 0.0) + b"MAP " + bytes([0x44, 0x44, 0, 0]) + struct.pack("<fi", -1.0, 0)
+    return head.ljust(1024, b"\0")
+
+
+def write_mrc(path, data: np.ndarray, voxel_size: float | None = None) -> Path:
+    """``data`` as an MRC2014 file of mode 2: [nz, ny, nx] one volume (ISPG 1), [ny, nx] one image (ISPG 0), [P, B, ny, nx] a stack of
+    P volumes of B sections (ISPG 401, mz = B, nz = P * B).  Converted to float32; dmin, dmax and dmean (the float64 mean) are those
+    of the data; the cell is ``voxel_size`` (Angstrom; None: 1) times the grid.  Written beside its final name and moved there."""
+    data = np.ascontiguousarray(data, dtype=np.float32)
+    if data.ndim not in (2, 3, 4) or data.size == 0:
+        raise ValueError(f"write_mrc takes a non-empty image, volume or stack of volumes, got shape {data.shape}")
+    ny, nx = data.shape[-2:]
+    nz = 1 if data.ndim == 2 else int(np.prod(data.shape[:-2]))
+    mz = 1 if data.ndim == 2 else data.shape[-3]
+    head = mrc_header(nx, ny, nz, mz=mz, ispg={2: 0, 3: 1, 4: 401}[data.ndim], voxel_size=voxel_size, dmin=float(data.min()),
+                      dmax=float(data.max()), dmean=float(data.mean(dtype=np.float64)))
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    tmp = path.with_name(path.name + ".tmp")
+    with open(tmp, "wb") as f:
+        f.write(head)
+        f.write(data.astype("<f4", copy=False).tobytes())
+    os.replace(tmp, path)
+    return path
 
 
 _TIFF_TYPES = {1: "B", 2: "c", 3: "H", 4: "I", 5: "II", 6: "b", 8: "h", 9: "i", 10: "ii", 11: "f", 12: "d", 16: "Q", 17: "q"}

@@ -1057,6 +1057,44 @@ int cvx_trace_branches(int32_t* voxels, const int32_t* nbrs, const void* state, 
                        int W, long N, long B, int64_t* branches, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Oriented subtomograms (`infer --instances --extract picks|filaments`, `cryovit instances --extract`): a box of B^3 voxels around
+ * every particle, rotated so that the box axes are the columns of the particle's matrix, sampled trilinearly from the tomogram; the
+ * sums of the boxes (the average) and the density profile along the box z axis.  Fixed point throughout, integers only: the result
+ * does not depend on the launch shape or on any order, and two calls give the same bits.
+ *
+ * vol uint8 [D][H][W].  table int32 [P][CVX_SUBTOMO_COLS]: cz, cy, cx, the centre in 1/256 voxel (Q8), then m[a][j], a, j = 0..2
+ * row by row, in 1/65536 (Q16): a is the source axis z, y, x, j the box axis z, y, x.  box = B, even, 8 <= B <= 128.
+ *   Sampling   the box voxel (i_z, i_y, i_x) has the offset o = i - B/2.  Per source axis a, in 64 bits:
+ *                s16 = (c[a] << 8) + m[a][0] o_z + m[a][1] o_y + m[a][2] o_x;  s = s16 >> 9 (arithmetic: the floor, 7 fraction bits);
+ *                idx = s >> 7;  f = s & 127.
+ *              q = the sum over the 8 taps d in {0, 1}^3 of w_z w_y w_x vol[clamp(idx + d)], w = f for d = 1 and 128 - f for d = 0,
+ *              every index clamped to [0, extent - 1] (the border is replicated).  q is an int32 in units of 2^-21 grey level,
+ *              at most 255 * 2^21; the float image is float32(q) * 2^-21.
+ *   Refusal    need_a = ((15 (|m[a][0]| + |m[a][1]| + |m[a][2]|) + 65535) >> 16) + 2 bounds the source indices of axis a that a
+ *              16^3 block of the box touches.  A particle with need_z > 30, need_y > 30 or need_x > 32 (no rotation: the rows of one
+ *              have length 1 and need at most 28) is written as zeros and counted in *status.  The table may hold anything: no
+ *              access leaves the volume, the table or out.
+ *   cvx_subtomo_extract  out int32 [P][B][B][B] = q, every element written; *status int64 = the refused particles of this call.
+ *   cvx_subtomo_sum      sums int64 [G][B^3] += the boxes of the particles p with group[p] == g, element by element; particles with
+ *                        a group outside 0..G-1 (-1: left out) are skipped.  The caller zeroes sums once; the chunks of a long
+ *                        particle list accumulate.  64-bit integer atomics.
+ *   cvx_subtomo_profile  profile int64 [P][B]: entry (p, i_z) = the sum of stack[p][i_z][i_y][i_x] over o_y^2 + o_x^2 <= radius2;
+ *                        the number of voxels of the disc is the host's to derive.  Every entry written.
+ * Refused with an error before any launch: negative extents, D*H*W > CVX_COMPONENT_MAX_VOXELS, P < 0 or above
+ * CVX_SUBTOMO_MAX_PARTICLES (cut a longer list into chunks), a box that is odd or outside [8, 128], G < 1, radius2 < 0, null pointers,
+ * misaligned arrays (int32: 4 bytes, int64: 8 bytes).  P == 0, and for cvx_subtomo_extract an empty volume, succeed and touch
+ * nothing, *status included.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_SUBTOMO_COLS 12
+#define CVX_SUBTOMO_BOX_MIN 8
+#define CVX_SUBTOMO_BOX_MAX 128
+#define CVX_SUBTOMO_MAX_PARTICLES (1 << 20)
+int cvx_subtomo_extract(const uint8_t* vol, int D, int H, int W, const int32_t* table, long P, int box, int32_t* out, int64_t* status,
+                        hipStream_t stream);
+int cvx_subtomo_sum(const int32_t* stack, long P, int box, const int32_t* group, int G, int64_t* sums, hipStream_t stream);
+int cvx_subtomo_profile(const int32_t* stack, long P, int box, long radius2, int64_t* profile, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Raw tomogram -> uint8 in [0, 255] (`cryovit preprocess`, `features --normalize`): bin, moments, order statistics, quantise.
  * A volume is [D][H][W] of one of the CVX_VOL_* element types; CVX_VOL_I32 is what the bin pass makes of an integer source.
  * Everything but the two float32 moment sums is exact and bit-reproducible; those two are reproducible and bounded (below).
