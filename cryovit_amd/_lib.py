@@ -52,6 +52,7 @@ TRACE_STATE_BYTES = 20  # CVX_TRACE_STATE_BYTES
 SUBTOMO_COLS = 12  # CVX_SUBTOMO_COLS
 SUBTOMO_BOX_MIN, SUBTOMO_BOX_MAX = 8, 128  # CVX_SUBTOMO_BOX_MIN / CVX_SUBTOMO_BOX_MAX
 SUBTOMO_MAX_PARTICLES = 1 << 20  # CVX_SUBTOMO_MAX_PARTICLES
+ALIGN_SHIFT_MAX = 8  # CVX_ALIGN_SHIFT_MAX
 VOL_I8, VOL_U8, VOL_I16, VOL_U16, VOL_I32, VOL_F32 = range(6)  # CVX_VOL_* element types
 BIN_MAX = 8  # CVX_BIN_MAX
 MOMENT_GROUP, MOMENT_CHAIN, MOMENT_TREE = 4096, 16, 8  # CVX_MOMENT_*
@@ -266,6 +267,8 @@ SIGNATURES = {
     "cvx_subtomo_extract": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p]),
     "cvx_subtomo_sum": (c_int, [c_void_p, c_long, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "cvx_subtomo_profile": (c_int, [c_void_p, c_long, c_int, c_long, c_void_p, c_void_p]),
+    "cvx_align_polar": (c_int, [c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "cvx_align_correlate": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cvx_volume_bin": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_int, c_int, c_void_p, c_void_p]),
     "cvx_volume_moments": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cvx_volume_select_hist": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

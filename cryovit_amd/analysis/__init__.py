@@ -5,7 +5,8 @@ its local thickness (mean, spread, min, max), the surface mesh of the mask (PLY 
 curvature of its membrane (ball-volume integral invariant; mean, spread, min, max, convex share); evenly spaced positions on
 that membrane with its normal, the particle picks of subtomogram averaging (RELION STAR / CSV); the centreline traced into
 filaments (branches, junctions, rings; positions with tangents along them as helical STAR / CSV); oriented subtomograms cut out
-of the tomogram at either kind of position (MRC stack, average, density profile along the axis); the
+of the tomogram at either kind of position (MRC stack, average, density profile along the axis) and their alignment about that
+axis (in-plane angle and shift against the running average); the
 clean-up of the mask before all of that (close, fill holes, open); and, against annotated labels, how far the predicted boundary
 lies from the true one (HD95, surface distance, surface Dice) and how well the annotated objects are recovered one by one (detection
 F1, panoptic quality, Rand index, split / merge variation of information)."""
@@ -29,6 +30,8 @@ from cryovit_amd.analysis.filaments import (  # noqa: F401
 from cryovit_amd.analysis.subtomograms import (  # noqa: F401
     EXTRACT_COLUMNS, ExtractOptions, extract_rows, extract_to_files, filament_particles, instance_profiles, particle_frames, particle_table,
     pick_particles, write_particle_star, write_profiles_csv)
+from cryovit_amd.analysis.alignment import (  # noqa: F401
+    ALIGN_COLUMNS, ALIGNMENT_CSV_COLUMNS, ALIGNMENT_LOG_COLUMNS, AlignOptions, align_particles, align_to_files)
 from cryovit_amd.analysis.boundary import (  # noqa: F401
     BOUNDARY_COUNT_COLUMNS, BOUNDARY_DISTANCE_COLUMNS, BOUNDARY_MODES, boundary_columns, boundary_histograms, boundary_scores, check_scored,
     nsd_column)

@@ -26,6 +26,7 @@ from cryovit_amd.analysis.mesh import MESH_FORMATS, mesh_arrays, mesh_rows
 from cryovit_amd.analysis.picks import PickOptions, pick_rows, pick_table
 from cryovit_amd.analysis.shape import instance_shape
 from cryovit_amd.analysis.skeleton import skeleton_rows, skeleton_volume
+from cryovit_amd.analysis.alignment import AlignOptions
 from cryovit_amd.analysis.subtomograms import ExtractOptions, tomogram_bytes
 from cryovit_amd.analysis.thickness import thickness_rows, thickness_volume
 
@@ -277,7 +278,9 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
                pick: bool = False, pick_spacing: int = 8, pick_radius: int = 5, pick_offset: float = 0.0, pick_scale: float = 1.0,
                pick_seed: int = 0, trace: bool = False, trace_spacing: float = 8.0, trace_window: float = 4.0, trace_min_length: float = 0.0,
                trace_scale: float = 1.0, trace_angpix: float = 1.0, extract: str | None = None, extract_box: int = 32,
-               extract_orient: str = "aligned", extract_profile_radius: float | None = None) -> Path:
+               extract_orient: str = "aligned", extract_profile_radius: float | None = None, extract_align: int | None = None,
+               align_angles: int = 64, align_shift: int = 2, align_radius: int | None = None, align_height: int | None = None,
+               align_reference=None) -> Path:
     """Label ``<label>_preds`` of the prediction file ``path`` and write ``<label>_instances`` next to the file's other
     datasets (which are written back unchanged: the in-tree HDF5 writer does not append) plus the instance CSV, under
     ``result_dir`` (default: the file's folder, i.e. in place).  The measurements are those of ``InstanceOptions``.
@@ -296,6 +299,9 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     ``"filaments"`` turns ``trace`` on; oriented boxes of the file's ``data`` (a uint8 volume of the shape of the predictions, as
     ``cryovit preprocess`` makes it) are cut at those positions, ``subtomograms/<tomo stem>_<label>.mrcs``, ``_average.mrc``, ``.star``
     and ``_profiles.csv`` are written under ``result_dir`` and the CSV gains ``analysis.subtomograms.EXTRACT_COLUMNS`` as its last columns.
+    ``extract_align`` and the ``align_*`` are the fields of ``analysis.alignment.AlignOptions``: the boxes are aligned about their axis,
+    ``_aligned.mrcs``, ``_aligned_average.mrc``, ``_aligned.star``, ``_alignment.csv`` and ``_alignment_log.csv`` are written beside them and
+    the CSV gains ``analysis.alignment.ALIGN_COLUMNS`` after those.
     ``distance_to`` names another label whose mask (``<distance_to>_preds`` of the same file, else of
     ``distance_to_dir/<same stem>.hdf``) the gap and contact columns are taken against.  ``contacts_with`` names another label
     whose instances are paired with this label's: ``<contacts_with>_instances`` of the same file, else of
@@ -314,6 +320,8 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     check_mesh_format(curvature, mesh, mesh_format)
     extracting = ExtractOptions(extract=extract, extract_box=extract_box, extract_orient=extract_orient,
                                 extract_profile_radius=extract_profile_radius).validate()
+    aligning = AlignOptions(extract_align=extract_align, align_angles=align_angles, align_shift=align_shift, align_radius=align_radius,
+                            align_height=align_height, align_reference=align_reference).validate(extracting)
     pick, trace = pick or extracting.extract == "picks", trace or extracting.extract == "filaments"
     picking = PickOptions(pick=pick, pick_spacing=pick_spacing, pick_radius=pick_radius, pick_offset=pick_offset, pick_scale=pick_scale,
                           pick_seed=pick_seed).validate()
@@ -371,7 +379,7 @@ def label_file(path, label: str, *, connectivity: int = 26, min_size: int = 0, r
     result_dir = result_dir if result_dir is not None else path.parent
     if tomogram is not None:
         merge_columns(found.extra, writers.write_subtomograms(result_dir, path.name, label, torch.from_numpy(tomogram).to(device), found,
-                                                              int(table.shape[0]), extracting, picking, tracing))
+                                                              int(table.shape[0]), extracting, picking, tracing, align=aligning))
     if found.pairs is not None:
         writers.write_contacts(result_dir, path.name, label, contacts_with, found.pairs)
     return writers.write_measured(result_dir, path.name, label, datasets, labels.cpu().numpy(), table.cpu().numpy(),

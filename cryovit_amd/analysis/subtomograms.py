@@ -30,7 +30,7 @@ What the numbers mean:
   ``"aligned"`` the angles are written as 0: the images are already rotated.  With ``"none"`` they are the priors (0 where there is none).
 
 Out of scope: float or 16-bit tomograms (``cryovit preprocess`` makes the uint8 volume), boxes above 128, one file per particle, CTF or
-missing-wedge handling, alignment or classification, per-instance average volumes, thickness read off the profile, formats other
+missing-wedge handling, classification (the alignment about the axis is ``analysis.alignment``), per-instance average volumes, thickness read off the profile, formats other
 than MRC and RELION's STAR.
 """
 
@@ -129,7 +129,9 @@ def particle_table(centres, frames) -> np.ndarray:
 class Particles:
     """The particles of one extraction, in the order of their source records: ``ids`` (int64 [P], the instance), ``centres`` and ``axes``
     (float64 [P, 3], zyx; the axis is nan where there is none), ``star`` (per particle the cells of its STAR row before the image
-    name), ``columns`` (the STAR columns before it) and ``skipped`` (int64 [k + 1]: per instance id the records that were left out)."""
+    name), ``columns`` (the STAR columns before it) and ``skipped`` (int64 [k + 1]: per instance id the records that were left out).
+    ``scale`` is the factor of the written coordinates ((c + 0.5) * scale - 0.5, ``pick_scale`` or ``trace_scale``) and
+    ``alignment`` the ``analysis.alignment.Alignment`` of these particles once ``--extract-align`` has run."""
 
     ids: np.ndarray
     centres: np.ndarray
@@ -137,13 +139,15 @@ class Particles:
     star: list[list[str]]
     columns: list[str]
     skipped: np.ndarray = field(default_factory=lambda: np.zeros(1, np.int64))
+    scale: float = 1.0
+    alignment: object | None = None
 
 
 def _angles(record: dict, aligned: bool) -> list[str]:
     return [f"{0.0 if aligned or math.isnan(record[c]) else record[c]:.6f}" for c in ("rot", "tilt", "psi")]
 
 
-def _gather(records: list[dict], k: int, orient: str, centre, axis, cells, columns: list[str]) -> Particles:
+def _gather(records: list[dict], k: int, orient: str, centre, axis, cells, columns: list[str], scale: float) -> Particles:
     aligned = orient == "aligned"
     ids, centres, axes, star = [], [], [], []
     skipped = np.zeros(k + 1, np.int64)
@@ -157,24 +161,26 @@ def _gather(records: list[dict], k: int, orient: str, centre, axis, cells, colum
         axes.append(a)
         star.append([f"{r[c]:.6f}" for c in ("px", "py", "pz")] + _angles(r, aligned) + cells(r))
     return Particles(np.asarray(ids, np.int64), np.asarray(centres, np.float64).reshape(-1, 3), np.asarray(axes, np.float64).reshape(-1, 3),
-                     star, columns, skipped)
+                     star, columns, skipped, scale)
 
 
-def pick_particles(records: list[dict], k: int, pick_offset: float, orient: str) -> Particles:
+def pick_particles(records: list[dict], k: int, pick_offset: float, orient: str, scale: float = 1.0) -> Particles:
     """The particles at the picks ``records`` (``analysis.picks.pick_records``) of the instances 1..k: the centre is
-    (z, y, x) + ``pick_offset`` * n (no offset without a normal), the axis the outward normal."""
+    (z, y, x) + ``pick_offset`` * n (no offset without a normal), the axis the outward normal.  ``scale`` is the ``pick_scale`` the
+    records were made with: the alignment writes its refined coordinates under it."""
     def centre(r):
         n = (0.0, 0.0, 0.0) if math.isnan(r["nz"]) else (r["nz"], r["ny"], r["nx"])
         return tuple(c + pick_offset * d for c, d in zip((r["z"], r["y"], r["x"]), n))
 
-    return _gather(records, k, orient, centre, lambda r: (r["nz"], r["ny"], r["nx"]), lambda r: [], STAR_COLUMNS)
+    return _gather(records, k, orient, centre, lambda r: (r["nz"], r["ny"], r["nx"]), lambda r: [], STAR_COLUMNS, scale)
 
 
-def filament_particles(points: list[dict], k: int, orient: str) -> Particles:
+def filament_particles(points: list[dict], k: int, orient: str, scale: float = 1.0) -> Particles:
     """The particles at the filament points ``points`` (``analysis.filaments.sample_points``) of the instances 1..k: the centre is the
-    sampled position, the axis the tangent."""
+    sampled position, the axis the tangent.  ``scale`` is the ``trace_scale`` the points were made with: the alignment writes its
+    refined coordinates under it."""
     return _gather(points, k, orient, lambda p: (p["z"], p["y"], p["x"]), lambda p: (p["tz"], p["ty"], p["tx"]),
-                   lambda p: [str(p["branch"]), f"{p['track']:.6f}"], HELICAL_STAR_COLUMNS)
+                   lambda p: [str(p["branch"]), f"{p['track']:.6f}"], HELICAL_STAR_COLUMNS, scale)
 
 
 def tomogram_bytes(data, shape, where: str) -> np.ndarray:
@@ -198,9 +204,14 @@ def tomogram_bytes(data, shape, where: str) -> np.ndarray:
 
 
 def extract_rows(particles: Particles, k: int) -> list[dict]:
-    """Rows (``EXTRACT_COLUMNS``), one dict per instance 1..k in id order: the particles cut and the records left out."""
+    """Rows (``EXTRACT_COLUMNS``), one dict per instance 1..k in id order: the particles cut and the records left out; after an
+    alignment also ``analysis.alignment.ALIGN_COLUMNS``: the aligned particles and their mean score (nan without any)."""
     done = np.bincount(particles.ids, minlength=k + 1)
-    return [{"extracted": int(done[i]), "extract_skipped": int(particles.skipped[i])} for i in range(1, k + 1)]
+    rows = [{"extracted": int(done[i]), "extract_skipped": int(particles.skipped[i])} for i in range(1, k + 1)]
+    if particles.alignment is not None:
+        for row, more in zip(rows, particles.alignment.instance_rows(particles.ids, k)):
+            row.update(more)
+    return rows
 
 
 def instance_profiles(ids, profile, k: int, box: int, radius2: int) -> list[dict]:
@@ -246,57 +257,78 @@ def average_volume(sums, count: int) -> np.ndarray:
     return (np.asarray(sums, np.int64).astype(np.float64) * UNIT / count).astype(np.float32)
 
 
+def chunk_particles(opts: ExtractOptions, per_particle_bytes: int) -> int:
+    """The particles of one device chunk: ``extract_chunk_bytes`` over the bytes one particle takes, at least one, at most one call's."""
+    return max(1, min(CALL_MAX, opts.extract_chunk_bytes // per_particle_bytes))
+
+
+def cut_stack(volume, table: np.ndarray, box: int, per: int, stack_path: Path, voxel_size: float | None, radius2: int | None = None):
+    """Cuts the rows of ``table`` (``particle_table``; at least one) out of the uint8 device ``volume``, ``per`` particles at a time
+    through a pinned buffer, and writes them as the float32 stack ``stack_path`` (beside its final name, then moved there; a failure
+    leaves no temporary file).  Returns (the int64 [B, B, B] sums of the boxes, the int64 [P, B] profile over the disc ``radius2``
+    or None without one).  A frame that the kernel refuses raises ``RuntimeError``."""
+    import torch
+
+    from cryovit_amd.engine import ops
+    from cryovit_amd.utils import mrc_header
+
+    P = len(table)
+    profile = None if radius2 is None else np.zeros((P, box), np.int64)
+    sums = torch.zeros((1, box, box, box), dtype=torch.int64, device=volume.device)
+    pinned = torch.empty((min(per, P), box, box, box), dtype=torch.int32, pin_memory=True)
+    tmp = stack_path.with_name(stack_path.name + ".tmp")
+    low, high, refused = math.inf, -math.inf, 0
+    try:
+        with open(tmp, "wb") as fh:
+            fh.write(bytes(1024))
+            for p0 in range(0, P, per):
+                rows = torch.from_numpy(table[p0:p0 + per]).to(volume.device)
+                stack, status = ops.extract_subtomograms(volume, rows, box)
+                ops.subtomogram_sums(stack, torch.zeros(len(rows), dtype=torch.int32, device=volume.device), 1, sums)
+                part = None if radius2 is None else ops.subtomogram_profiles(stack, radius2)
+                host = pinned[:len(rows)]
+                host.copy_(stack, non_blocking=True)
+                if part is not None:
+                    profile[p0:p0 + per] = part.cpu().numpy()
+                refused += int(status.item())  # waits for the stream, the copy above included
+                images = host.numpy().astype(np.float32) * np.float32(UNIT)  # one rounding, then an exact scale
+                low, high = min(low, float(images.min())), max(high, float(images.max()))
+                fh.write(images.tobytes())
+            total = sums.cpu().numpy()[0]
+            if refused:
+                raise RuntimeError(f"{refused} particle frames were refused by the extraction kernel: they are no rotations")
+            fh.seek(0)
+            fh.write(mrc_header(box, box, P * box, mz=box, ispg=401, voxel_size=voxel_size, dmin=low, dmax=high,
+                                dmean=float(int(total.sum())) * UNIT / (P * box**3)))
+        os.replace(tmp, stack_path)
+    finally:
+        tmp.unlink(missing_ok=True)  # a failure leaves no half-written stack behind
+    return total, profile
+
+
 def extract_to_files(volume, particles: Particles, k: int, opts: ExtractOptions, results_dir, tomo_name: str, label_key: str,
-                     voxel_size: float | None = None) -> dict[str, Path]:
+                     voxel_size: float | None = None, align=None) -> dict[str, Path]:
     """Cuts ``particles`` out of the uint8 device ``volume`` under ``opts`` and writes ``subtomograms/<tomo stem>_<label>.mrcs`` (float32,
     a stack of volumes; chunk by chunk through a pinned buffer, at most ``extract_chunk_bytes`` of boxes on the device at a time),
     ``_average.mrc``, ``.star`` and ``_profiles.csv`` under ``results_dir``; every file is written beside its final name and moved
     there, and a run that fails leaves no temporary file.  Without particles the two MRC files are not written and those of an
-    earlier run are removed, so the folder never holds boxes that the STAR file does not list.  Returns the paths by suffix."""
-    import torch
-
-    from cryovit_amd.engine import ops
-    from cryovit_amd.utils import mrc_header, write_mrc
+    earlier run are removed, so the folder never holds boxes that the STAR file does not list.  ``align`` (an
+    ``analysis.alignment.AlignOptions`` with ``extract_align`` set) then refines every box about its axis and adds the files of
+    ``analysis.alignment.align_to_files``; without it no alignment call is made.  Returns the paths by suffix."""
+    from cryovit_amd.utils import write_mrc
 
     box, radius2 = opts.extract_box, opts.radius2
     stem = Path(tomo_name).stem
     base = Path(results_dir) / "subtomograms" / f"{stem}_{label_key}"
     base.parent.mkdir(parents=True, exist_ok=True)
     stack_path, average_path = base.with_name(base.name + ".mrcs"), base.with_name(base.name + "_average.mrc")
-    table = particle_table(particles.centres, particle_frames(particles.axes, opts.extract_orient))
+    frames = particle_frames(particles.axes, opts.extract_orient)
+    table = particle_table(particles.centres, frames)
     P = len(table)
-    per = max(1, min(CALL_MAX, opts.extract_chunk_bytes // (4 * box**3)))
     out = {}
     profile = np.zeros((P, box), np.int64)
     if P:
-        sums = torch.zeros((1, box, box, box), dtype=torch.int64, device=volume.device)
-        pinned = torch.empty((min(per, P), box, box, box), dtype=torch.int32, pin_memory=True)
-        tmp = stack_path.with_name(stack_path.name + ".tmp")
-        low, high, refused = math.inf, -math.inf, 0
-        try:
-            with open(tmp, "wb") as fh:
-                fh.write(bytes(1024))
-                for p0 in range(0, P, per):
-                    rows = torch.from_numpy(table[p0:p0 + per]).to(volume.device)
-                    stack, status = ops.extract_subtomograms(volume, rows, box)
-                    ops.subtomogram_sums(stack, torch.zeros(len(rows), dtype=torch.int32, device=volume.device), 1, sums)
-                    part = ops.subtomogram_profiles(stack, radius2)
-                    host = pinned[:len(rows)]
-                    host.copy_(stack, non_blocking=True)
-                    profile[p0:p0 + per] = part.cpu().numpy()  # waits for the stream, the copy above included
-                    refused += int(status.item())
-                    images = host.numpy().astype(np.float32) * np.float32(UNIT)  # one rounding, then an exact scale
-                    low, high = min(low, float(images.min())), max(high, float(images.max()))
-                    fh.write(images.tobytes())
-                total = sums.cpu().numpy()[0]
-                if refused:
-                    raise RuntimeError(f"{refused} particle frames were refused by the extraction kernel: they are no rotations")
-                fh.seek(0)
-                fh.write(mrc_header(box, box, P * box, mz=box, ispg=401, voxel_size=voxel_size, dmin=low, dmax=high,
-                                    dmean=float(int(total.sum())) * UNIT / (P * box**3)))
-            os.replace(tmp, stack_path)
-        finally:
-            tmp.unlink(missing_ok=True)  # a failure leaves no half-written stack behind
+        total, profile = cut_stack(volume, table, box, chunk_particles(opts, 4 * box**3), stack_path, voxel_size, radius2)
         out["mrcs"] = stack_path
         out["average"] = write_mrc(average_path, average_volume(total, P), voxel_size)
     else:  # an earlier run's boxes would not belong to the STAR file written below
@@ -304,4 +336,8 @@ def extract_to_files(volume, particles: Particles, k: int, opts: ExtractOptions,
         average_path.unlink(missing_ok=True)
     out["star"] = write_particle_star(base.with_name(base.name + ".star"), particles, stem, stack_path.name)
     out["profiles"] = write_profiles_csv(base.with_name(base.name + "_profiles.csv"), instance_profiles(particles.ids, profile, k, box, radius2), box)
+    if align is not None and align.extract_align is not None:
+        from cryovit_amd.analysis.alignment import align_to_files
+
+        out.update(align_to_files(volume, particles, frames, opts, align, base, stem, voxel_size))
     return out

@@ -22,7 +22,8 @@
                     [--curvature [--curvature-radius R]]
                     [--pick [--pick-spacing S] [--pick-radius R] [--pick-offset V] [--pick-scale F] [--pick-seed N]]
                     [--trace [--trace-spacing S] [--trace-window H] [--trace-min-length L] [--trace-scale F] [--trace-angpix A]]
-                    [--extract picks|filaments [--extract-box B] [--extract-orient aligned|none] [--extract-profile-radius R]]
+                    [--extract picks|filaments [--extract-box B] [--extract-orient aligned|none] [--extract-profile-radius R]
+                     [--extract-align N [--align-angles T] [--align-shift S] [--align-radius R] [--align-height Z] [--align-reference F.mrc]]]
 
 ``preprocess`` (build extension) turns raw reconstructions (int8 / uint8 / int16 / uint16 / float MRC, TIFF or HDF5, as IMOD or AreTomo
 write them) into the uint8 tomograms every other command expects, on the GPU: bin, clip, rescale to [0, 255]
@@ -44,7 +45,8 @@ the tangent, as ``filaments/<tomo>_<label>_branches.csv``, ``.csv`` and a helica
 ``--extract picks`` (it implies ``--pick``) and ``--extract filaments`` (it implies ``--trace``) cut a box of ``--extract-box`` voxels out
 of the uint8 tomogram around every such position, rotated so that its z axis is the membrane normal or the filament tangent, and write
 ``subtomograms/<tomo>_<label>.mrcs``, their average, a RELION ``.star`` and the density profile along that axis per instance
-(``analysis.subtomograms.ExtractOptions``).
+(``analysis.subtomograms.ExtractOptions``).  ``--extract-align N`` then refines every box about that axis, the in-plane angle and the
+shift along it, and writes the aligned stack, its average, a STAR file and the alignment tables (``analysis.alignment.AlignOptions``).
 ``--distance-to NAME`` adds the gap to another
 label's mask and the voxels in contact with it; ``--contacts-with NAME`` says which instance touches which: every instance gains
 ``partners_<NAME>``, and ``contacts/<tomo>_<label>_<NAME>.csv`` lists per pair (instance, nearest instance of NAME within
@@ -309,6 +311,43 @@ ExtractProfileRadius = Annotated[Optional[float], Option("--extract-profile-radi
                                                          help=_EXT + "with --extract, the radius of the disc around the axis that the density "
                                                                      "profile averages over (voxels, >= 0)",
                                                          show_default="a quarter of the box")]
+ExtractAlign = Annotated[Optional[int], Option("--extract-align", callback=_checked(lambda v: 1 <= v <= 20, "extract align must lie in 1..20 (iterations)"),
+                                               help=_EXT + "with --extract (--extract-orient aligned), refine every box about its axis on the GPU for this "
+                                                           "many iterations (1..20): the in-plane angle and the shift along the axis against the "
+                                                           "average of the boxes as aligned so far.  Writes _aligned.mrcs (every box cut again "
+                                                           "with its refined frame), _aligned_average.mrc, _aligned.star, _alignment.csv (psi, shift, "
+                                                           "score, refined centre and angles per particle) and _alignment_log.csv beside the boxes and "
+                                                           "adds aligned and align_score as the last CSV columns", show_default="off")]
+AlignAngles = Annotated[int, Option("--align-angles", callback=_checked(lambda v: v in (32, 64, 128), "align angles must be 32, 64 or 128"),
+                                    help=_EXT + "with --extract-align, the angular samples T (32, 64 or 128); the step is 360/T degrees")]
+AlignShift = Annotated[int, Option("--align-shift", callback=_checked(lambda v: 0 <= v <= 8, "align shift must lie in 0..8 (voxels)"),
+                                   help=_EXT + "with --extract-align, the search range along the axis (voxels, 0..8)")]
+AlignRadius = Annotated[Optional[int], Option("--align-radius", callback=_checked(lambda v: v >= 1, "align radius must be >= 1 (voxels)"),
+                                              help=_EXT + "with --extract-align, the rings 1..R around the axis are scored (1 <= R <= B/2 - 1)",
+                                              show_default="B/2 - 2")]
+AlignHeight = Annotated[Optional[int], Option("--align-height", callback=_checked(lambda v: v >= 0, "align height must be >= 0 (voxels)"),
+                                              help=_EXT + "with --extract-align, the slabs B/2 - Z .. B/2 + Z of the reference are scored "
+                                                          "(Z >= 0, Z + shift <= B/2 - 1)", show_default="B/2 - 1 - shift")]
+AlignReference = Annotated[Optional[str], Option("--align-reference", help=_EXT + "with --extract-align, a float32 MRC volume of B^3 voxels in grey "
+                                                                                  "levels to start from", show_default="the best particle against the plain average")]
+
+
+def _align_options(extract, extract_box, extract_orient, extract_align, align_angles, align_shift, align_radius, align_height, align_reference) -> dict:
+    """The keyword arguments of the alignment for ``run_inference`` and ``label_file``: none without --extract-align; a usage error for
+    what ``analysis.alignment.AlignOptions`` refuses."""
+    if extract_align is None:
+        return {}
+    from cryovit_amd.analysis.alignment import AlignOptions
+    from cryovit_amd.analysis.subtomograms import ExtractOptions
+
+    given = dict(extract_align=extract_align, align_angles=align_angles, align_shift=align_shift, align_radius=align_radius,
+                 align_height=align_height, align_reference=align_reference)
+    try:
+        AlignOptions(**given).validate(ExtractOptions(extract=extract, extract_box=extract_box, extract_orient=extract_orient).validate())
+    except ValueError as err:
+        raise typer.BadParameter(str(err), param_hint="--extract-align") from err
+    return given
+
 
 # infer measures nothing without --instances: asking for one of these without it is a usage error
 _NEEDS_INSTANCES = ("morphology", "shape", "skeleton", "split_radius", "thickness", "mesh", "close_radius", "fill_holes", "open_radius",
@@ -498,6 +537,12 @@ def infer(
     extract_box: ExtractBox = 32,
     extract_orient: ExtractOrient = "aligned",
     extract_profile_radius: ExtractProfileRadius = None,
+    extract_align: ExtractAlign = None,
+    align_angles: AlignAngles = 64,
+    align_shift: AlignShift = 2,
+    align_radius: AlignRadius = None,
+    align_height: AlignHeight = None,
+    align_reference: AlignReference = None,
 ):
     """Segment tomograms using a pre-trained model."""
     measurements = dict(min_size=min_size, connectivity=connectivity, morphology=morphology, split_radius=split_radius,
@@ -511,6 +556,8 @@ def infer(
                         extract=extract, extract_box=extract_box, extract_orient=extract_orient,
                         extract_profile_radius=extract_profile_radius)
     _refuse_stl_curvature(curvature, mesh, mesh_format)
+    measurements |= _align_options(extract, extract_box, extract_orient, extract_align, align_angles, align_shift, align_radius, align_height,
+                                   align_reference)
     for name in _NEEDS_INSTANCES:
         value = measurements[name]  # a flag that is off is False, a radius that is not given None; a radius of 0 is given
         if not instances and value is not False and value is not None:
@@ -572,9 +619,17 @@ def instances_cmd(
     extract_box: ExtractBox = 32,
     extract_orient: ExtractOrient = "aligned",
     extract_profile_radius: ExtractProfileRadius = None,
+    extract_align: ExtractAlign = None,
+    align_angles: AlignAngles = 64,
+    align_shift: AlignShift = 2,
+    align_radius: AlignRadius = None,
+    align_height: AlignHeight = None,
+    align_reference: AlignReference = None,
 ):
     """Label and measure the connected instances of existing predictions (build extension)."""
     _refuse_stl_curvature(curvature, mesh, mesh_format)
+    aligning = _align_options(extract, extract_box, extract_orient, extract_align, align_angles, align_shift, align_radius, align_height,
+                              align_reference)
     from cryovit_amd.analysis.instances import label_file
     from cryovit_amd.utils import load_files_from_path
 
@@ -593,7 +648,7 @@ def instances_cmd(
                          pick_seed=pick_seed, trace=trace, trace_spacing=trace_spacing, trace_window=trace_window,
                          trace_min_length=trace_min_length, trace_scale=trace_scale, trace_angpix=trace_angpix,
                          extract=extract, extract_box=extract_box, extract_orient=extract_orient,
-                         extract_profile_radius=extract_profile_radius)
+                         extract_profile_radius=extract_profile_radius, **aligning)
         logging.info("Labelled %s", out)
 
 

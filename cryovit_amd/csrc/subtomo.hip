@@ -18,7 +18,7 @@
 // SUM.  k_subtomo_sum: one thread per box voxel and segment of kSumSeg particles; the running sum of a group stays in a register
 //   and goes to the table by one 64-bit atomic add when the group changes and at the end: one per thread where all share a group.
 // PROFILE.  k_subtomo_profile: one wave per (particle, z slab), lanes over the slab's B^2 voxels inside the disc, a wave sum.
-#include "bit_rows.h"
+#include "subtomo_stack.h"
 
 namespace cvx {
 
@@ -173,19 +173,6 @@ __global__ __launch_bounds__(kCclThreads) void k_subtomo_profile(const int* __re
 }  // namespace cvx
 
 using namespace cvx;
-
-namespace {
-
-// what every entry refuses about P and the box.  nullptr: fine.  n = the voxels of a box
-const char* stack_fault(long P, int box, long& n) {
-    if (P < 0) return "P < 0";
-    if (box < kBoxMin || box > kBoxMax || box % 2) return "box must be even and lie in [8, 128]";
-    n = (long)box * box * box;
-    if (P > CVX_SUBTOMO_MAX_PARTICLES) return "P must be <= 2^20";
-    return nullptr;
-}
-
-}  // namespace
 
 extern "C" int cvx_subtomo_extract(const uint8_t* vol, int D, int H, int W, const int32_t* table, long P, int box, int32_t* out, int64_t* status,
                                    hipStream_t st) {

@@ -1842,6 +1842,68 @@ def subtomogram_profiles(stack: torch.Tensor, radius2: int) -> torch.Tensor:
     return profile
 
 
+# ---- alignment of the boxes about their axis (`--extract-align`): rings around box z, correlation with a reference (csrc/align.hip) ----
+
+ALIGN_ANGLES = (32, 64, 128)
+
+
+def _align_rings(what: str, box: int, angles, rmax) -> tuple[int, int]:
+    if not isinstance(angles, int) or isinstance(angles, bool) or angles not in ALIGN_ANGLES:
+        raise _lib.CvxError(f"{what}: angles must be 32, 64 or 128, got {angles!r}")
+    if not isinstance(rmax, int) or isinstance(rmax, bool) or not 1 <= rmax <= box // 2 - 1:
+        raise _lib.CvxError(f"{what}: rmax must be an integer in [1, {box // 2 - 1}], got {rmax!r}")
+    return angles, rmax
+
+
+def subtomogram_polar(stack: torch.Tensor, trig: torch.Tensor, rmax: int) -> torch.Tensor:
+    """int32 [P, B, rmax, T] on the device: every slab of the boxes ``stack`` (int32 [P, B, B, B], ``extract_subtomograms``) sampled
+    bilinearly on the rings r = 1..``rmax`` around the box z axis at the T steps of ``trig`` (int32 [T, 2]: sin, cos in 2^-14;
+    ``analysis.alignment.trig_table``), in the unit of the stack (the definition is in include/cryovit_hip.h).  Nobody waits."""
+    P, box = _subtomo_stack("subtomogram_polar", stack)
+    if not isinstance(trig, torch.Tensor) or trig.dtype != torch.int32 or trig.dim() != 2 or trig.shape[1] != 2:
+        got = f"{trig.dtype} {tuple(trig.shape)}" if isinstance(trig, torch.Tensor) else type(trig).__name__
+        raise _lib.CvxError(f"subtomogram_polar: trig must be int32 [T, 2], got {got}")
+    T, rmax = _align_rings("subtomogram_polar", box, int(trig.shape[0]), rmax)
+    dev = _dev_check(stack, trig)
+    polar = torch.empty((P, box, rmax, T), dtype=torch.int32, device=dev)
+    if P:
+        call(dev, "cvx_align_polar", _lib.load().cvx_align_polar, _p(stack), P, box, _p(trig), T, rmax, _p(polar))
+    return polar
+
+
+def subtomogram_correlate(polar: torch.Tensor, ref: torch.Tensor, shift: int, *, corr=None, moments=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(corr int64 [P, 2 S + 1, T], moments int64 [P, B, 2]) on the device: the ring-weighted circular correlation of the quantised
+    rings of ``polar`` (int32 [P, B, rmax, T], ``subtomogram_polar``) with ``ref`` (int16 [2 zh + 1, rmax, T]) at every step k and
+    every shift d = -S..S (S = ``shift``, 0..8, zh + S <= B/2 - 1) along the axis, and per slab the ring-weighted sums of q and
+    q^2 (the definition is in include/cryovit_hip.h).  ``corr`` and ``moments`` receive the tables when given; every element is
+    written.  Integers only, bit-reproducible.  Nobody waits."""
+    if not isinstance(polar, torch.Tensor) or polar.dtype != torch.int32 or polar.dim() != 4:
+        got = f"{polar.dtype} {tuple(polar.shape)}" if isinstance(polar, torch.Tensor) else type(polar).__name__
+        raise _lib.CvxError(f"subtomogram_correlate: polar must be int32 [P, B, rmax, T], got {got}")
+    P, box = int(polar.shape[0]), _subtomo_box("subtomogram_correlate", int(polar.shape[1]))
+    if P > _lib.SUBTOMO_MAX_PARTICLES:
+        raise _lib.CvxError(f"subtomogram_correlate: at most 2^20 particles per call, got {P}")
+    T, rmax = _align_rings("subtomogram_correlate", box, int(polar.shape[3]), int(polar.shape[2]))
+    if not isinstance(ref, torch.Tensor) or ref.dtype != torch.int16 or ref.dim() != 3 or tuple(ref.shape[1:]) != (rmax, T) or ref.shape[0] % 2 == 0:
+        got = f"{ref.dtype} {tuple(ref.shape)}" if isinstance(ref, torch.Tensor) else type(ref).__name__
+        raise _lib.CvxError(f"subtomogram_correlate: ref must be int16 [2 zh + 1, {rmax}, {T}], got {got}")
+    zh = int(ref.shape[0]) // 2
+    if not isinstance(shift, int) or isinstance(shift, bool) or not 0 <= shift <= _lib.ALIGN_SHIFT_MAX:
+        raise _lib.CvxError(f"subtomogram_correlate: shift must be an integer in [0, {_lib.ALIGN_SHIFT_MAX}], got {shift!r}")
+    if zh + shift > box // 2 - 1:
+        raise _lib.CvxError(f"subtomogram_correlate: zh + shift must be <= {box // 2 - 1}, got {zh} + {shift}")
+    for name, given, shape in (("corr", corr, (P, 2 * shift + 1, T)), ("moments", moments, (P, box, 2))):
+        if given is not None and (not isinstance(given, torch.Tensor) or given.dtype != torch.int64 or tuple(given.shape) != shape):
+            got = f"{given.dtype} {tuple(given.shape)}" if isinstance(given, torch.Tensor) else type(given).__name__
+            raise _lib.CvxError(f"subtomogram_correlate: {name} must be int64 {list(shape)}, got {got}")
+    dev = _dev_check(polar, ref, corr, moments)
+    corr = torch.empty((P, 2 * shift + 1, T), dtype=torch.int64, device=dev) if corr is None else corr
+    moments = torch.empty((P, box, 2), dtype=torch.int64, device=dev) if moments is None else moments
+    if P:
+        call(dev, "cvx_align_correlate", _lib.load().cvx_align_correlate, _p(polar), P, box, T, rmax, _p(ref), zh, shift, _p(corr), _p(moments))
+    return corr, moments
+
+
 # ---- a raw tomogram to uint8 (`cryovit preprocess`, `features --normalize`): bin, moments, order statistics, quantise ----
 
 MOMENT_GROUP = _lib.MOMENT_GROUP  # voxels of a slice under one partial of volume_moments

@@ -33,6 +33,9 @@ are written, each file also holds ``<label_key>_filaments`` and the table gains 
 turns ``pick`` on, ``"filaments"`` turns ``trace`` on; oriented boxes of the tomogram (a uint8 ``data``, as ``cryovit preprocess``
 makes it) are cut at those positions while it is in HBM and written as ``subtomograms/<tomo stem>_<label_key>.mrcs``,
 ``_average.mrc``, ``.star`` and ``_profiles.csv``; the table gains ``extracted`` and ``extract_skipped`` as its last columns.
+``extract_align`` and the ``align_*`` are the fields of ``analysis.alignment.AlignOptions``: the boxes are aligned about their axis and
+``_aligned.mrcs``, ``_aligned_average.mrc``, ``_aligned.star``, ``_alignment.csv`` and ``_alignment_log.csv`` are written beside them; the
+table gains ``aligned`` and ``align_score`` after those.
 """
 
 from __future__ import annotations
@@ -50,6 +53,7 @@ from cryovit_amd.analysis.curvature import CurvatureOptions, check_mesh_format
 from cryovit_amd.analysis.filaments import TraceOptions
 from cryovit_amd.analysis.instances import InstanceOptions, label_and_split, measure, merge_columns
 from cryovit_amd.analysis.picks import PickOptions
+from cryovit_amd.analysis.alignment import AlignOptions
 from cryovit_amd.analysis.subtomograms import ExtractOptions, tomogram_bytes
 from cryovit_amd.config import compose, instantiate
 from cryovit_amd.datasets import collate_fn
@@ -117,7 +121,9 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                   pick: bool = False, pick_spacing: int = 8, pick_radius: int = 5, pick_offset: float = 0.0, pick_scale: float = 1.0,
                   pick_seed: int = 0, trace: bool = False, trace_spacing: float = 8.0, trace_window: float = 4.0, trace_min_length: float = 0.0,
                   trace_scale: float = 1.0, trace_angpix: float = 1.0, extract: str | None = None, extract_box: int = 32,
-                  extract_orient: str = "aligned", extract_profile_radius: float | None = None) -> list[Path]:
+                  extract_orient: str = "aligned", extract_profile_radius: float | None = None, extract_align: int | None = None,
+                  align_angles: int = 64, align_shift: int = 2, align_radius: int | None = None, align_height: int | None = None,
+                  align_reference=None) -> list[Path]:
     opts = InstanceOptions(connectivity=connectivity, min_size=min_size, morphology=morphology, split_radius=split_radius,
                            split_min_core=split_min_core, shape=shape, skeleton=skeleton, skeleton_end_radius=skeleton_end_radius,
                            thickness=thickness, mesh=mesh, mesh_smooth=mesh_smooth, mesh_format=mesh_format)
@@ -125,6 +131,8 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
     curve = CurvatureOptions(curvature=curvature, curvature_radius=curvature_radius)
     extracting = ExtractOptions(extract=extract, extract_box=extract_box, extract_orient=extract_orient,
                                 extract_profile_radius=extract_profile_radius)
+    aligning = AlignOptions(extract_align=extract_align, align_angles=align_angles, align_shift=align_shift, align_radius=align_radius,
+                            align_height=align_height, align_reference=align_reference)
     if extract is not None and not instances:
         raise ValueError(f"extract={extract!r} needs instances=True: the subtomograms are cut at positions on the labelled instances")
     pick, trace = pick or extract == "picks", trace or extract == "filaments"
@@ -153,6 +161,7 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
     picking.validate()
     tracing.validate()
     extracting.validate()
+    aligning.validate(extracting)
     check_mesh_format(curvature, mesh, mesh_format)
     rank, _, world = world_info()
     device = select_device(device)
@@ -189,7 +198,8 @@ def run_inference(data_files: list[Path], model_path: Path, result_dir: Path, th
                 if extracting.extract:  # on the tables of measure, while they and the mask's device are at hand
                     tomogram = tomogram_bytes(raw, tuple(mask.shape), str(files[i].tomo_path))
                     cut = writers.write_subtomograms(result_dir, files[i].tomo_path.name, label_key, torch.from_numpy(tomogram).to(mask.device),
-                                                     found, int(table.shape[0]), extracting, picking, tracing, mrc_voxel_size(files[i].tomo_path))
+                                                     found, int(table.shape[0]), extracting, picking, tracing, mrc_voxel_size(files[i].tomo_path),
+                                                     align=aligning)
                 if cleanup.any:
                     host_cleaned = _pinned(cleaned)
                     found.extra = added_rows(added_voxels(labels, predicted, int(table.shape[0])), found.extra)

@@ -159,20 +159,24 @@ def write_picks(results_dir, tomo_name: str, label_key: str, table: np.ndarray, 
 
 
 def write_subtomograms(results_dir, tomo_name: str, label_key: str, volume, measured, k: int, extract: ExtractOptions,
-                       picks: PickOptions | None = None, trace: TraceOptions | None = None, voxel_size: float | None = None) -> list[dict]:
+                       picks: PickOptions | None = None, trace: TraceOptions | None = None, voxel_size: float | None = None,
+                       align=None) -> list[dict]:
     """<results_dir>/subtomograms/<tomo stem>_<label>.mrcs, _average.mrc, .star and _profiles.csv: oriented boxes of the uint8 device
     ``volume`` at the picks (``extract.extract`` = "picks": ``measured.picks`` under ``picks``) or the filament points ("filaments":
     ``measured.filament_voxels`` and ``measured.filament_branches`` under ``trace``) of the instances 1..k
     (``analysis.subtomograms.extract_to_files``).  ``measure`` does not see the tomogram, so this runs after it, on its tables, while
-    they and the volume are on the device.  Returns the rows of ``analysis.subtomograms.EXTRACT_COLUMNS``, one per instance, for
+    they and the volume are on the device.  ``align`` (``analysis.alignment.AlignOptions`` with ``extract_align`` set) aligns the boxes
+    about their axis and adds ``_aligned.mrcs``, ``_aligned_average.mrc``, ``_aligned.star``, ``_alignment.csv`` and ``_alignment_log.csv``.
+    Returns the rows of ``analysis.subtomograms.EXTRACT_COLUMNS`` (then ``analysis.alignment.ALIGN_COLUMNS``), one per instance, for
     ``measured.extra``."""
     if extract.extract == "picks":
         picks = picks if picks is not None else PickOptions(pick=True)
-        particles = pick_particles(pick_records(measured.picks, picks), k, picks.pick_offset, extract.extract_orient)
+        particles = pick_particles(pick_records(measured.picks, picks), k, picks.pick_offset, extract.extract_orient, picks.pick_scale)
     else:
-        points = sample_points(measured.filament_voxels, measured.filament_branches, trace if trace is not None else TraceOptions(trace=True))
-        particles = filament_particles(points, k, extract.extract_orient)
-    extract_to_files(volume, particles, k, extract, results_dir, tomo_name, label_key, voxel_size)
+        trace = trace if trace is not None else TraceOptions(trace=True)
+        particles = filament_particles(sample_points(measured.filament_voxels, measured.filament_branches, trace), k, extract.extract_orient,
+                                       trace.trace_scale)
+    extract_to_files(volume, particles, k, extract, results_dir, tomo_name, label_key, voxel_size, align)
     return extract_rows(particles, k)
 
 

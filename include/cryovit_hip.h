@@ -1095,6 +1095,38 @@ int cvx_subtomo_sum(const int32_t* stack, long P, int box, const int32_t* group,
 int cvx_subtomo_profile(const int32_t* stack, long P, int box, long radius2, int64_t* profile, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Alignment of oriented subtomograms about their axis (`--extract-align`): every box on rings around its z axis, and the circular
+ * correlation of every particle with a reference table over the in-plane angle (T steps of 360/T degrees) and the shift along the
+ * axis (-S..S voxels).  Integers only; the result does not depend on the launch shape or on any order; two calls give the same bits.
+ * The scores, the choice of the best candidate and the refinement of the frames are the host's (analysis/alignment.py).
+ *
+ * cvx_align_polar: stack int32 [P][B][B][B], the output of cvx_subtomo_extract (2^-21 grey level).  trig int32 [T][2] =
+ *   (rint(sin(2 pi t / T) * 2^14), rint(cos(2 pi t / T) * 2^14)), made by the host.  polar int32 [P][B][rmax][T], every element
+ *   written.  Per slab z, ring r = 1..rmax and step t, in 64 bits:
+ *     py7 = ((B/2) << 7) + ((r * sin_t) >> 7);  px7 = ((B/2) << 7) + ((r * cos_t) >> 7)   (arithmetic shifts: floors);
+ *     i = p7 >> 7;  f = p7 & 127;  the taps i and i + 1 are clamped to [0, B - 1] per axis;
+ *     polar = (the sum over the four taps of w_y w_x stack[p][z][y][x], w = f for the upper tap and 128 - f for the lower) >> 14.
+ *   The weights add up to 2^14: polar is at most 255 * 2^21 and has the unit of the stack.  With the trig table above and
+ *   rmax <= B/2 - 1 only an upper tap of weight 0 is clamped; with any other table the clamps keep every access inside the box.
+ * cvx_align_correlate: polar as above; ref int16 [2 zh + 1][rmax][T] (1/64 grey level, the host's to make).
+ *     q = min(255, (polar + 2^20) >> 21)   (a polar value outside [0, 255 * 2^21], which cvx_align_polar never writes, gives 0 or 255);
+ *     corr[p][d + S][k] = sum_{z' = -zh..zh} sum_{r = 1..rmax} r * sum_{t = 0..T-1} q[p][B/2 + z' + d][r][(t + k) mod T] * ref[z' + zh][r][t]
+ *   for d = -S..S, k = 0..T-1: corr int64 [P][2 S + 1][T];
+ *     moments[p][z][0] = sum_r r sum_t q[p][z][r][t],  moments[p][z][1] = sum_r r sum_t q[p][z][r][t]^2
+ *   for every slab z = 0..B-1: moments int64 [P][B][2].  Every element of both tables is written, by plain stores.
+ *   Bounds: a sum over t of one (slab, ring) is below T * 255 * 32768 <= 2^30 and is kept in 32 bits; with the ring weights and
+ *   the slabs |corr| <= 127 * 2016 * 2^30 < 2^49 (B = 128, T = 128, rmax = 63, zh = 63); a moment is below 2016 * 128 * 255^2 < 2^35.
+ * Refused with an error before any launch, in this order: P < 0, a box that is odd or outside [8, 128], P above
+ * CVX_SUBTOMO_MAX_PARTICLES, T other than 32, 64, 128, rmax outside [1, B/2 - 1], zh < 0, shift outside [0, CVX_ALIGN_SHIFT_MAX],
+ * zh + shift > B/2 - 1 (a scored slab would leave the box), then (P > 0) null pointers and misaligned arrays (int32 and ref: 4
+ * bytes, ref is read two elements at a time; int64: 8 bytes).  P == 0 succeeds and touches nothing.
+ * ------------------------------------------------------------------------------------------------- */
+#define CVX_ALIGN_SHIFT_MAX 8
+int cvx_align_polar(const int32_t* stack, long P, int box, const int32_t* trig, int T, int rmax, int32_t* polar, hipStream_t stream);
+int cvx_align_correlate(const int32_t* polar, long P, int box, int T, int rmax, const int16_t* ref, int zh, int shift, int64_t* corr,
+                          int64_t* moments, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Raw tomogram -> uint8 in [0, 255] (`cryovit preprocess`, `features --normalize`): bin, moments, order statistics, quantise.
  * A volume is [D][H][W] of one of the CVX_VOL_* element types; CVX_VOL_I32 is what the bin pass makes of an integer source.
  * Everything but the two float32 moment sums is exact and bit-reproducible; those two are reproducible and bounded (below).
